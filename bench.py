@@ -23,6 +23,7 @@ sys.path.insert(0, ROOT)
 ALG_BYTES_PER_KMER = {1: 34.0, 2: 46.0, 3: 58.0, 4: 70.0}  # SURVEY.md section 8d contract constants, by num_longs
 HBM_PEAK_GBPS = 8000.0  # MI355X_MICROARCH.md: 8.0 TB/s spec
 PROFILE = "profiles/r04_pmc_50Mreads.json"  # rocprofv3 PMC passes of this same command (scripts/pmc_profile.sh)
+DUMP_BYTES = 60 << 20  # --dump-outputs: at most this many bytes of .npy data in all (all ranks together)
 
 
 def own_alg_bytes(kernel, nl, k, read_len, results_per_raw):
@@ -58,7 +59,79 @@ def parse_args():
                     help="N>1: single-pass = a shard owns level-1 buckets (kc_shard_*), records = hash ownership "
                          "(kc_extract_partition / kc_insert_records); auto = single-pass when the shard's share of the regions holds its k-mers")
     ap.add_argument("--tune", default="", help="A/B: bucketed-path geometry overrides, e.g. slots=2048,p1=1024,p2=1024")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's results to DIR/<name>.npy (float64; beyond "
+                         "%d MB, a sample chosen by a fixed hash of the k-mer).  N > 1: one set of files on rank 0, "
+                         "the sample taken over the results of all shards together" % (DUMP_BYTES >> 20))
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return a
+
+
+def _mix64(x):
+    """splitmix64's finaliser on a uint64 array (wrapping arithmetic)."""
+    import numpy as np
+    x = (x ^ (x >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    x = (x ^ (x >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return x ^ (x >> np.uint64(31))
+
+
+def dump_outputs(kc, out_dir, world=1, dev=None):
+    """What the caller of the timed path receives from its last step (kc.results(): the purged k-mers, their counts and
+    their left / right extensions), as float64 .npy files written by rank 0.  The library returns the results in table
+    order, which depends on the build, and at N > 1 each rank holds the shard its build assigned to it; the rows are
+    therefore chosen and ordered by a fixed hash of the k-mer alone: of all ranks' results, the DUMP_BYTES budget's
+    worth of k-mers with the smallest hash, in ascending hash order, in one set of files.  Every rank sends rank 0 its
+    own smallest-hash candidates (at most the budget's rows; k-mers are owned by one rank each).  Every 64-bit word of
+    a k-mer is split into two exact 32-bit halves.  Returns what was written on rank 0, None on the other ranks."""
+    import numpy as np
+    keys, counts, left, right = kc.results()
+    n, nl = keys.shape
+    cap = DUMP_BYTES // (8 * (2 * nl + 3))
+    with np.errstate(over="ignore"):
+        h = np.zeros(n, dtype=np.uint64)
+        for j in range(nl):
+            h = _mix64(h ^ keys[:, j] ^ np.uint64(0x9E3779B97F4A7C15 * (j + 1) & (2**64 - 1)))
+    pick = np.argpartition(h, cap - 1)[:cap] if n > cap else np.arange(n)
+    keys, counts, left, right, h = keys[pick], counts[pick], left[pick], right[pick], h[pick]
+    if world > 1:
+        import torch
+        import torch.distributed as dist
+        # one int64 row per candidate: the k-mer's words, its hash, count | left << 16 | right << 24
+        rows = np.empty((len(h), nl + 2), dtype=np.int64)
+        rows[:, :nl] = keys.view(np.int64)
+        rows[:, nl] = h.view(np.int64)
+        rows[:, nl + 1] = counts.astype(np.int64) | (left.astype(np.int64) << 16) | (right.astype(np.int64) << 24)
+        sizes = torch.tensor([len(rows), n], dtype=torch.int64, device=dev)
+        all_sizes = [torch.empty_like(sizes) for _ in range(world)]
+        dist.all_gather(all_sizes, sizes)
+        all_sizes = [tuple(int(v) for v in t.tolist()) for t in all_sizes]
+        m = max(1, max(r for r, _ in all_sizes))
+        padded = torch.zeros((m, nl + 2), dtype=torch.int64, device=dev)
+        padded[:len(rows)] = torch.from_numpy(rows).to(dev)
+        gathered = [torch.empty_like(padded) for _ in range(world)]
+        dist.all_gather(gathered, padded)
+        if dist.get_rank() != 0:
+            return None
+        rows = np.concatenate([g.cpu().numpy()[:r] for g, (r, _) in zip(gathered, all_sizes)])
+        n = sum(t for _, t in all_sizes)
+        keys = np.ascontiguousarray(rows[:, :nl]).view(np.uint64)
+        h = np.ascontiguousarray(rows[:, nl]).view(np.uint64)
+        counts, left, right = rows[:, nl + 1] & 0xFFFF, (rows[:, nl + 1] >> 16) & 0xFF, (rows[:, nl + 1] >> 24) & 0xFF
+        pick = np.argpartition(h, cap - 1)[:cap] if len(h) > cap else np.arange(len(h))
+        keys, counts, left, right, h = keys[pick], counts[pick], left[pick], right[pick], h[pick]
+    order = np.lexsort([keys[:, j] for j in range(nl - 1, -1, -1)] + [h])
+    keys, counts, left, right = keys[order], counts[order], left[order], right[order]
+    arrays = {"kmer_words_hi": (keys >> np.uint64(32)).astype(np.float64), "kmer_words_lo": (keys & np.uint64(0xFFFFFFFF)).astype(np.float64),
+              "counts": counts.astype(np.float64), "left_ext": left.astype(np.float64),
+              "right_ext": right.astype(np.float64), "num_results": np.array([n], dtype=np.float64)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+    return {"dir": out_dir, "rows": int(len(keys)), "of": int(n), "files": sorted(name + ".npy" for name in arrays)}
 
 
 def pmc_traffic(nreads, k, tuned):
@@ -321,6 +394,10 @@ def main():
         dt = float(t.item())
     ktimes = kc.kernel_times()
     st = kc.stats()
+    dumped = None
+    if a.dump_outputs:
+        # before --check, which runs the stage once more
+        dumped = dump_outputs(kc, a.dump_outputs, world=world, dev=dev)
 
     checks = None
     if a.check:
@@ -400,6 +477,8 @@ def main():
         }
         if checks is not None:
             out["checks"] = checks
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
     # host-resident input (PCIe-inclusive) and the CPU baseline: rank 0 at N=1 only, outside the timed region
     if rank == 0 and world == 1 and not sharded_path and not a.no_end_to_end:
         out["end_to_end"] = end_to_end(kc, k, L, d_bases, d_quals, d_offs, nreads, dt / a.steps * 1e3)

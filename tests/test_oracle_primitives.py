@@ -1,8 +1,11 @@
 """Oracle primitives against (a) the known answers SURVEY.md section 8c recorded
 from the reference's own src/kmer.cpp + src/hash_funcs.c, and (b) oracle/_ref,
-the reference's src/hash_funcs.c compiled unmodified (present only where
-/root/reference was available at build time)."""
+the reference's src/hash_funcs.c compiled unmodified: the values it returned are
+stored in tests/golden/ref_hash_funcs.json (made by tests/golden/make_ref_vectors.py
+where oracle/_ref is built), so the comparison needs no reference checkout."""
 import ctypes as C
+import hashlib
+import json
 import os
 
 import numpy as np
@@ -11,6 +14,7 @@ import pytest
 from oracle import cpu_oracle as O
 
 REF_SO = os.path.join(os.path.dirname(O.__file__), "_ref", "libref_hash_funcs.so")
+REF_VECTORS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_hash_funcs.json")
 
 
 def test_pack_and_revcomp_k21():
@@ -102,17 +106,54 @@ def test_revcomp_is_involution_and_matches_strings():
             assert (O.revcomp(rc, k) == w).all()
 
 
-@pytest.mark.skipif(not os.path.exists(REF_SO), reason="oracle/_ref not built (needs /root/reference at build time)")
-def test_hashes_match_reference_build():
+def hash_inputs():
+    """The byte strings and words test_hashes_match_reference_build hashes (tests/golden/ref_hash_funcs.json holds what
+    the reference's hash_funcs.c returns for them)."""
+    rng = np.random.default_rng(9)
+    bufs = []
+    for n in list(range(0, 40)) + [64, 100, 255]:
+        bufs.append((n, rng.integers(0, 256, size=max(n, 1), dtype=np.uint8)))
+    words = [0, 1, 2**63, 2**64 - 1] + [int(x) for x in rng.integers(0, 2**63, size=200)]
+    return bufs, words
+
+
+def hash_inputs_sha256(bufs, words):
+    h = hashlib.sha256()
+    for n, buf in bufs:
+        h.update(bytes(buf[:n]) + b"|")
+    h.update(",".join(str(v) for v in words).encode())
+    return h.hexdigest()
+
+
+def ref_hash_lib():
     ref = C.CDLL(REF_SO)
     ref.MurmurHash3_x64_64.restype = C.c_uint64
     ref.MurmurHash3_x64_64.argtypes = [C.c_void_p, C.c_uint32]
     ref.quick_hash.restype = C.c_uint64
     ref.quick_hash.argtypes = [C.c_uint64]
+    return ref
+
+
+def test_hashes_match_reference_build():
+    """The oracle's hashes against the values oracle/_ref (the reference's src/hash_funcs.c compiled unmodified)
+    returned for the same inputs, stored in tests/golden/ref_hash_funcs.json."""
+    with open(REF_VECTORS) as f:
+        gold = json.load(f)
+    bufs, words = hash_inputs()
+    assert hash_inputs_sha256(bufs, words) == gold["inputs_sha256"], "the seeded inputs no longer match the stored vectors"
     L = O.lib()
-    rng = np.random.default_rng(9)
-    for n in list(range(0, 40)) + [64, 100, 255]:
-        buf = rng.integers(0, 256, size=max(n, 1), dtype=np.uint8)
-        assert L.orc_murmur3_x64_64(buf.ctypes.data, n) == ref.MurmurHash3_x64_64(buf.ctypes.data, n), n
-    for v in [0, 1, 2**63, 2**64 - 1] + [int(x) for x in rng.integers(0, 2**63, size=200)]:
-        assert L.orc_quick_hash(v) == ref.quick_hash(v)
+    for (n, buf), want in zip(bufs, gold["murmur3_x64_64"]):
+        assert L.orc_murmur3_x64_64(buf.ctypes.data, n) == int(want, 16), n
+    for v, want in zip(words, gold["quick_hash"]):
+        assert L.orc_quick_hash(v) == int(want, 16)
+
+
+@pytest.mark.skipif(not os.path.exists(REF_SO), reason="oracle/_ref not built (needs the reference checkout at build time)")
+def test_stored_hash_vectors_match_reference_build():
+    """Where oracle/_ref is built: the stored vectors are still what the reference's hash_funcs.c returns."""
+    with open(REF_VECTORS) as f:
+        gold = json.load(f)
+    ref = ref_hash_lib()
+    bufs, words = hash_inputs()
+    assert [hex(ref.MurmurHash3_x64_64(buf.ctypes.data, n)) for n, buf in bufs] == gold["murmur3_x64_64"]
+    assert [hex(ref.quick_hash(v)) for v in words] == gold["quick_hash"]
