@@ -15,6 +15,7 @@
 #include <algorithm>
 #include <new>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/kcount_mi355.h"
@@ -179,6 +180,41 @@ struct KernelTimer {
   ~KernelTimer();
 };
 
+// ---- compile-time dispatch ---------------------------------------------------------------------
+// The kernels are templates over the words of a k-mer (NL), the input format (FMT) and the record form (CP); these turn
+// the context's runtime values into compile-time constants for a generic lambda, e.g.
+//   with_nl(c, [&](auto nl) { return grow_table_nl<nl>(c, cap); })
+template <int N> using int_c = std::integral_constant<int, N>;
+
+template <class F>
+static auto with_nl(const kc_ctx *c, F &&f) {  // c->nl: 1, 2, 3, else 4
+  switch (c->nl) {
+    case 1: return f(int_c<1>{});
+    case 2: return f(int_c<2>{});
+    case 3: return f(int_c<3>{});
+    default: return f(int_c<4>{});
+  }
+}
+
+template <class F>
+static auto with_fmt(int fmt, F &&f) {  // FMT_READS, FMT_READS_UQ, FMT_PACKED, else FMT_SEQBLOCK
+  switch (fmt) {
+    case FMT_READS: return f(int_c<FMT_READS>{});
+    case FMT_READS_UQ: return f(int_c<FMT_READS_UQ>{});
+    case FMT_PACKED: return f(int_c<FMT_PACKED>{});
+    default: return f(int_c<FMT_SEQBLOCK>{});
+  }
+}
+
+// compact records are a property of the geometry (bk_init) and only exist for one-word k-mers
+template <int NL> static bool use_cp(const kc_ctx *c) { return NL == 1 && c->gm.cp != 0; }
+
+// f(cp) with cp = use_cp<NL>(c) as a compile-time constant: no kernel is instantiated with CP = true for NL > 1
+template <int NL, class F>
+static auto with_cp(const kc_ctx *c, F &&f) {
+  return use_cp<NL>(c) ? f(std::bool_constant<NL == 1>{}) : f(std::false_type{});
+}
+
 // ---- small helpers -----------------------------------------------------------------------------
 KernelTimer::KernelTimer(kc_ctx *ctx, int kind) : c(ctx), on(false) {
   ctx->num_gpu_calls++;
@@ -265,12 +301,7 @@ static int grow_table_nl(kc_ctx *c, uint64_t new_capacity) {
 }
 
 static int grow_table(kc_ctx *c, uint64_t new_capacity) {
-  switch (c->nl) {
-    case 1: return grow_table_nl<1>(c, new_capacity);
-    case 2: return grow_table_nl<2>(c, new_capacity);
-    case 3: return grow_table_nl<3>(c, new_capacity);
-    default: return grow_table_nl<4>(c, new_capacity);
-  }
+  return with_nl(c, [&](auto nl) { return grow_table_nl<nl>(c, new_capacity); });
 }
 
 // make sure `incoming` more distinct k-mers keep the load below 0.9 (syncs the stream)
@@ -782,11 +813,7 @@ static int bk_init(kc_ctx *c) {
   // six-byte level-1 records: wherever the kernels that write them run -- compact records whose mix fits 32 bits below the
   // level-1 bucket (k <= 21 with 1024 buckets; k = 21, MHM2's first and only one-word k of its default sweep,
   // src/options.hpp:80, has instantiations of its own)
-  // (KC_L1_ROUND16=0: the general kernels with their rounds of eight and 8-byte records, for A/B runs)
-  {
-    static const bool round16 = !(getenv("KC_L1_ROUND16") && getenv("KC_L1_ROUND16")[0] == '0');
-    g.rec6 = (c->nl == 1 && g.cp && g.k2 - g.la <= 32 && round16) ? 1u : 0u;
-  }
+  g.rec6 = (c->nl == 1 && g.cp && g.k2 - g.la <= 32) ? 1u : 0u;
   // the records flow's wire: units of four six-byte records where level 1 writes those (kc_wire6.hpp), k-mer records otherwise
   // (the owner's eight bits of the mix, 13..20, must lie below the region's: at least 21 bits of the mix that no region implies)
   c->wire6 = (c->cfg.flags & KC_FLAG_WIRE_UNITS) && g.rec6 && g.k2 - g.la - g.lb >= 21 && !(c->cfg.flags & KC_FLAG_REFERENCE_OWNER) &&
@@ -880,15 +907,6 @@ static int sync_cb(kc_ctx *c) {
   return KC_OK;
 }
 
-static int ensure_room(kc_ctx *c, uint64_t incoming);
-
-template <int NL>
-static void launch_ovf1_drain(kc_ctx *c, uint64_t n) {
-  auto kern = (NL == 1 && c->gm.cp) ? kc_ovf1_drain_kernel<NL, NL == 1> : kc_ovf1_drain_kernel<NL, false>;
-  hipLaunchKernelGGL(kern, dim3((unsigned)std::min<uint64_t>((n + TPB - 1) / TPB, 256 * 32)), dim3(TPB), 0, c->stream, c->gm, c->bb, n,
-                     c->table, c->d_ctrs);
-}
-
 // Records the level-1 overflow list can still take.  A launch over `want` k-mer positions can overflow at most that
 // many records: when the list has less room than that and holds something, its records are moved to the global table
 // first (syncs the stream).  The caller bounds its launch by the returned room.
@@ -913,12 +931,11 @@ static int bk_ovf1_room(kc_ctx *c, uint64_t want, uint64_t *room) {
     if (rc) return rc;
     {
       KernelTimer kt(c, KT_FALLBACK);
-      switch (c->nl) {
-        case 1: launch_ovf1_drain<1>(c, used); break;
-        case 2: launch_ovf1_drain<2>(c, used); break;
-        case 3: launch_ovf1_drain<3>(c, used); break;
-        default: launch_ovf1_drain<4>(c, used); break;
-      }
+      with_nl(c, [&](auto nl) {
+        auto kern = with_cp<nl>(c, [&](auto cp) { return kc_ovf1_drain_kernel<nl, cp>; });
+        hipLaunchKernelGGL(kern, dim3((unsigned)std::min<uint64_t>((used + TPB - 1) / TPB, 256 * 32)), dim3(TPB), 0, c->stream, c->gm, c->bb,
+                           used, c->table, c->d_ctrs);
+      });
     }
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemsetAsync(c->d_cb + CB_OVF1, 0, 8, c->stream));
@@ -944,9 +961,6 @@ template <int NL> static size_t lds_bin_reads() { return (sizeof(L1LDS) + 15) & 
 template <int NL> static size_t lds_l1_records() { return ((sizeof(L1RLDS) + 15) & ~size_t(15)) + Rnd<NL>::STAGE; }
 template <int NL> static size_t lds_l2() { return ((sizeof(L2LDS) + 15) & ~size_t(15)) + Rnd<NL>::STAGE; }
 
-// compact records are a property of the geometry (bk_init) and only exist for one-word k-mers
-template <int NL> static bool use_cp(const kc_ctx *c) { return NL == 1 && c->gm.cp != 0; }
-
 template <int NL, int FMT>
 static int launch_l1_reads_t(kc_ctx *c, const ExtractArgs &a, uint64_t nsuper) {
   const bool sh = c->cfg.rank_n > 1 && !c->sh.extracting;  // the shard flow ships whole buckets instead of testing k-mers
@@ -958,17 +972,8 @@ static int launch_l1_reads_t(kc_ctx *c, const ExtractArgs &a, uint64_t nsuper) {
     c->gm.own_lo = shard_first_bucket((uint32_t)c->cfg.rank_me, c->gm.P1, (uint32_t)c->cfg.rank_n);
     c->gm.own_hi = shard_first_bucket((uint32_t)c->cfg.rank_me + 1, c->gm.P1, (uint32_t)c->cfg.rank_n);
   }
-  // compact records at k = 21 (MHM2's first and only one-word k of its default sweep, src/options.hpp:80): the
-  // instantiation made for that k; any other k takes the general one
-  constexpr int K21 = NL == 1 ? 21 : 0;
-  const bool k21 = NL == 1 && c->k == 21 && c->gm.k2 - c->gm.la <= 32;  // its registers hold the 32 bits below the bucket
-  auto kern = use_cp<NL>(c) ? (k21 ? (sh ? kc_l1_reads_kernel<NL, FMT, NL == 1, true, K21> : kc_l1_reads_kernel<NL, FMT, NL == 1, false, K21>)
-                                   : (sh ? kc_l1_reads_kernel<NL, FMT, NL == 1, true, 0> : kc_l1_reads_kernel<NL, FMT, NL == 1, false, 0>))
-                            : (sh ? kc_l1_reads_kernel<NL, FMT, false, true, 0> : kc_l1_reads_kernel<NL, FMT, false, false, 0>);
+  auto kern = with_cp<NL>(c, [&](auto cp) { return sh ? kc_l1_reads_kernel<NL, FMT, cp, true> : kc_l1_reads_kernel<NL, FMT, cp, false>; });
   const unsigned grid = (unsigned)std::min<uint64_t>(c->gm.G, nsuper);
-#ifdef KC_ABLATE
-  c->gm.abl = getenv("KC_ABL_L1") ? (uint32_t)atoi(getenv("KC_ABL_L1")) : 0u;
-#endif
   if constexpr (NL == 1) {
     // ... and its rounds of sixteen k-mers per thread, six-byte records (kc_l1_reads16_kernel; Geom::rec6)
     if (c->gm.rec6) {
@@ -993,36 +998,7 @@ static int launch_l1_reads_t(kc_ctx *c, const ExtractArgs &a, uint64_t nsuper) {
 }
 
 static int launch_l1_reads(kc_ctx *c, const ExtractArgs &a, uint64_t ntiles, int fmt) {
-  if (fmt == FMT_READS) {
-    switch (c->nl) {
-      case 1: return launch_l1_reads_t<1, FMT_READS>(c, a, ntiles);
-      case 2: return launch_l1_reads_t<2, FMT_READS>(c, a, ntiles);
-      case 3: return launch_l1_reads_t<3, FMT_READS>(c, a, ntiles);
-      default: return launch_l1_reads_t<4, FMT_READS>(c, a, ntiles);
-    }
-  }
-  if (fmt == FMT_READS_UQ) {
-    switch (c->nl) {
-      case 1: return launch_l1_reads_t<1, FMT_READS_UQ>(c, a, ntiles);
-      case 2: return launch_l1_reads_t<2, FMT_READS_UQ>(c, a, ntiles);
-      case 3: return launch_l1_reads_t<3, FMT_READS_UQ>(c, a, ntiles);
-      default: return launch_l1_reads_t<4, FMT_READS_UQ>(c, a, ntiles);
-    }
-  }
-  if (fmt == FMT_PACKED) {
-    switch (c->nl) {
-      case 1: return launch_l1_reads_t<1, FMT_PACKED>(c, a, ntiles);
-      case 2: return launch_l1_reads_t<2, FMT_PACKED>(c, a, ntiles);
-      case 3: return launch_l1_reads_t<3, FMT_PACKED>(c, a, ntiles);
-      default: return launch_l1_reads_t<4, FMT_PACKED>(c, a, ntiles);
-    }
-  }
-  switch (c->nl) {
-    case 1: return launch_l1_reads_t<1, FMT_SEQBLOCK>(c, a, ntiles);
-    case 2: return launch_l1_reads_t<2, FMT_SEQBLOCK>(c, a, ntiles);
-    case 3: return launch_l1_reads_t<3, FMT_SEQBLOCK>(c, a, ntiles);
-    default: return launch_l1_reads_t<4, FMT_SEQBLOCK>(c, a, ntiles);
-  }
+  return with_fmt(fmt, [&](auto f) { return with_nl(c, [&](auto nl) { return launch_l1_reads_t<nl, f>(c, a, ntiles); }); });
 }
 
 template <int NL, int FMT>
@@ -1037,12 +1013,7 @@ static int launch_bin_reads_t(kc_ctx *c, const ExtractArgs &a, uint64_t nsuper) 
 }
 
 // pieces per destination of the wire units (kc_wire6.hpp)
-static uint32_t bin_lg_pieces(const kc_ctx *c) {
-  if (!c->wire6) return 0;
-  uint32_t lg = wire6_lg_pieces((uint32_t)c->cfg.rank_n);
-  if (const char *e = getenv("KC_WIRE6_LG_PIECES")) lg = std::min<uint32_t>(lg, (uint32_t)atoi(e));  // (A/B runs)
-  return lg;
-}
+static uint32_t bin_lg_pieces(const kc_ctx *c) { return c->wire6 ? wire6_lg_pieces((uint32_t)c->cfg.rank_n) : 0; }
 static uint32_t bin_pieces(const kc_ctx *c) { return 1u << bin_lg_pieces(c); }
 
 template <int FMT>
@@ -1057,47 +1028,15 @@ static int launch_bin16_t(kc_ctx *c, const ExtractArgs &a, uint64_t nsuper) {
 }
 
 static int launch_bin_reads(kc_ctx *c, const ExtractArgs &a, uint64_t ntiles, int fmt) {
-  if (c->wire6) {  // six-byte wire records (kc_wire6.hpp)
-    if (fmt == FMT_READS) return launch_bin16_t<FMT_READS>(c, a, ntiles);
-    if (fmt == FMT_READS_UQ) return launch_bin16_t<FMT_READS_UQ>(c, a, ntiles);
-    if (fmt == FMT_PACKED) return launch_bin16_t<FMT_PACKED>(c, a, ntiles);
-    return launch_bin16_t<FMT_SEQBLOCK>(c, a, ntiles);
-  }
-  if (fmt == FMT_READS) {
-    switch (c->nl) {
-      case 1: return launch_bin_reads_t<1, FMT_READS>(c, a, ntiles);
-      case 2: return launch_bin_reads_t<2, FMT_READS>(c, a, ntiles);
-      case 3: return launch_bin_reads_t<3, FMT_READS>(c, a, ntiles);
-      default: return launch_bin_reads_t<4, FMT_READS>(c, a, ntiles);
-    }
-  }
-  if (fmt == FMT_READS_UQ) {
-    switch (c->nl) {
-      case 1: return launch_bin_reads_t<1, FMT_READS_UQ>(c, a, ntiles);
-      case 2: return launch_bin_reads_t<2, FMT_READS_UQ>(c, a, ntiles);
-      case 3: return launch_bin_reads_t<3, FMT_READS_UQ>(c, a, ntiles);
-      default: return launch_bin_reads_t<4, FMT_READS_UQ>(c, a, ntiles);
-    }
-  }
-  if (fmt == FMT_PACKED) {
-    switch (c->nl) {
-      case 1: return launch_bin_reads_t<1, FMT_PACKED>(c, a, ntiles);
-      case 2: return launch_bin_reads_t<2, FMT_PACKED>(c, a, ntiles);
-      case 3: return launch_bin_reads_t<3, FMT_PACKED>(c, a, ntiles);
-      default: return launch_bin_reads_t<4, FMT_PACKED>(c, a, ntiles);
-    }
-  }
-  switch (c->nl) {
-    case 1: return launch_bin_reads_t<1, FMT_SEQBLOCK>(c, a, ntiles);
-    case 2: return launch_bin_reads_t<2, FMT_SEQBLOCK>(c, a, ntiles);
-    case 3: return launch_bin_reads_t<3, FMT_SEQBLOCK>(c, a, ntiles);
-    default: return launch_bin_reads_t<4, FMT_SEQBLOCK>(c, a, ntiles);
-  }
+  return with_fmt(fmt, [&](auto f) {
+    if (c->wire6) return launch_bin16_t<f>(c, a, ntiles);  // six-byte wire records (kc_wire6.hpp)
+    return with_nl(c, [&](auto nl) { return launch_bin_reads_t<nl, f>(c, a, ntiles); });
+  });
 }
 
 template <int NL>
 static int launch_l1_records_t(kc_ctx *c, const uint64_t *recs, uint64_t n) {
-  auto kern = use_cp<NL>(c) ? kc_l1_records_kernel<NL, NL == 1> : kc_l1_records_kernel<NL, false>;
+  auto kern = with_cp<NL>(c, [](auto cp) { return kc_l1_records_kernel<NL, cp>; });
   c->gm.own_lo = 0;
   c->gm.own_hi = PMAX;
   const uint64_t per_round = (uint64_t)WGB * Rnd<NL>::RPOS;
@@ -1151,7 +1090,7 @@ template <int NL>
 static int bk_drain_t(kc_ctx *c) {
   {
     KernelTimer kt(c, KT_FALLBACK);
-    auto kern = use_cp<NL>(c) ? kc_l1_to_table_kernel<NL, NL == 1> : kc_l1_to_table_kernel<NL, false>;
+    auto kern = with_cp<NL>(c, [](auto cp) { return kc_l1_to_table_kernel<NL, cp>; });
     hipLaunchKernelGGL(kern, dim3((unsigned)std::min<size_t>((size_t)c->gm.G * c->gm.P1, 65536)), dim3(TPB), 0, c->stream,
                        c->gm, c->bb, c->table, c->d_ctrs);
   }
@@ -1182,12 +1121,7 @@ static int bk_drain_to_table(kc_ctx *c) {
   }
   rc = ensure_room(c, c->h_ctrs[CTR_INSERTED]);
   if (rc) return rc;
-  switch (c->nl) {
-    case 1: rc = bk_drain_t<1>(c); break;
-    case 2: rc = bk_drain_t<2>(c); break;
-    case 3: rc = bk_drain_t<3>(c); break;
-    default: rc = bk_drain_t<4>(c); break;
-  }
+  rc = with_nl(c, [&](auto nl) { return bk_drain_t<nl>(c); });
   if (rc) return rc;
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemsetAsync(c->bb.cnt1, 0, (size_t)c->gm.G * c->gm.P1 * 4, c->stream));
@@ -1200,7 +1134,6 @@ static int bk_drain_to_table(kc_ctx *c) {
 }
 
 static bool bk_active(const kc_ctx *c) { return c->tuning.mode != 1 && !c->table_mode; }
-static int bk_spill_pass(kc_ctx *c);
 static int bk_light_spill(kc_ctx *c, uint64_t buffered);
 static int bk_level2_instalment(kc_ctx *c);
 // A shard of several that has started the shard flow owns level-1 buckets, not hash values: the entry points that test
@@ -1208,28 +1141,12 @@ static int bk_level2_instalment(kc_ctx *c);
 static bool shard_flow_only(const kc_ctx *c) { return c->sh.flow && c->cfg.rank_n > 1; }
 
 // ---- extraction launches -----------------------------------------------------------------------
-template <int NL, int FMT>
-static void launch_extract_t(kc_ctx *c, const ExtractArgs &a, unsigned ntiles) {
-  hipLaunchKernelGGL((kc_extract_kernel<NL, FMT>), dim3(ntiles), dim3(TPB), 0, c->stream, a, c->table, c->d_ctrs);
-}
-
-template <int FMT>
-static void launch_extract_m(kc_ctx *c, const ExtractArgs &a, unsigned ntiles) {
-  switch (c->nl) {
-    case 1: launch_extract_t<1, FMT>(c, a, ntiles); break;
-    case 2: launch_extract_t<2, FMT>(c, a, ntiles); break;
-    case 3: launch_extract_t<3, FMT>(c, a, ntiles); break;
-    default: launch_extract_t<4, FMT>(c, a, ntiles); break;
-  }
-}
-
 // global-table path: extract and insert in one kernel
 static void launch_extract(kc_ctx *c, const ExtractArgs &a, unsigned ntiles, int fmt) {
   KernelTimer kt(c, KT_EXTRACT_INSERT);
-  if (fmt == FMT_READS) launch_extract_m<FMT_READS>(c, a, ntiles);
-  else if (fmt == FMT_READS_UQ) launch_extract_m<FMT_READS_UQ>(c, a, ntiles);
-  else if (fmt == FMT_PACKED) launch_extract_m<FMT_PACKED>(c, a, ntiles);
-  else launch_extract_m<FMT_SEQBLOCK>(c, a, ntiles);
+  with_fmt(fmt, [&](auto f) {
+    with_nl(c, [&](auto nl) { hipLaunchKernelGGL((kc_extract_kernel<nl, f>), dim3(ntiles), dim3(TPB), 0, c->stream, a, c->table, c->d_ctrs); });
+  });
 }
 
 // One block of device-resident input through extraction, in chunks of tiles.  mode MODE_INSERT feeds this
@@ -1922,12 +1839,6 @@ extern "C" int kc_extract_partition_seq_block(kc_ctx *c, const char *seqs, uint6
   return bin_end(c, d_records, seg_capacity, h_counts);
 }
 
-template <int NL>
-static void launch_insert_records(kc_ctx *c, const uint64_t *recs, uint64_t n, uint32_t count_inserted) {
-  unsigned nblk = (unsigned)std::min<uint64_t>((n + TPB - 1) / TPB, 256 * 32);
-  hipLaunchKernelGGL(kc_insert_records_kernel<NL>, dim3(nblk), dim3(TPB), 0, c->stream, recs, n, c->table, c->d_ctrs, count_inserted);
-}
-
 // records straight into the global table, growing it as needed
 static int table_insert_records(kc_ctx *c, const uint64_t *d_records, uint64_t n, uint32_t count_inserted) {
   uint64_t done = 0;
@@ -1938,12 +1849,10 @@ static int table_insert_records(kc_ctx *c, const uint64_t *d_records, uint64_t n
     const uint64_t *p = d_records + done * c->nl;
     {
       KernelTimer kt(c, KT_INSERT_RECORDS);
-      switch (c->nl) {
-        case 1: launch_insert_records<1>(c, p, m, count_inserted); break;
-        case 2: launch_insert_records<2>(c, p, m, count_inserted); break;
-        case 3: launch_insert_records<3>(c, p, m, count_inserted); break;
-        default: launch_insert_records<4>(c, p, m, count_inserted); break;
-      }
+      const unsigned nblk = (unsigned)std::min<uint64_t>((m + TPB - 1) / TPB, 256 * 32);
+      with_nl(c, [&](auto nl) {
+        hipLaunchKernelGGL(kc_insert_records_kernel<nl>, dim3(nblk), dim3(TPB), 0, c->stream, p, m, c->table, c->d_ctrs, count_inserted);
+      });
     }
     HIPCHK(hipGetLastError());
     done += m;
@@ -2007,12 +1916,7 @@ extern "C" int kc_insert_records(kc_ctx *c, const uint64_t *d_records, uint64_t 
           continue;
         }
         const uint64_t *p = d_records + done * c->nl;
-        switch (c->nl) {
-          case 1: rc = launch_l1_records_t<1>(c, p, m); break;
-          case 2: rc = launch_l1_records_t<2>(c, p, m); break;
-          case 3: rc = launch_l1_records_t<3>(c, p, m); break;
-          default: rc = launch_l1_records_t<4>(c, p, m); break;
-        }
+        rc = with_nl(c, [&](auto nl) { return launch_l1_records_t<nl>(c, p, m); });
         if (rc) return rc;
         HIPCHK(hipGetLastError());
         done += m;
@@ -2142,31 +2046,6 @@ static int shard_init(kc_ctx *c) {
   return KC_OK;
 }
 
-template <int NL>
-static void launch_shard_pack(kc_ctx *c, uint64_t *segs, uint64_t seg_words, const uint64_t *off, const uint64_t *flags) {
-  const uint32_t Q = 4;  // workgroups per bucket
-  KernelTimer kt(c, KT_SHARD_PACK);
-  auto kern = (NL == 1 && shard_wire_of(c->gm) == SHARD_WIRE_COMPACT) ? kc_shard_pack_kernel<NL, NL == 1> : kc_shard_pack_kernel<NL, false>;
-  hipLaunchKernelGGL(kern, dim3(c->gm.P1 * Q), dim3(WGB), 0, c->stream, c->gm, c->bb, (uint32_t)c->cfg.rank_me, (uint32_t)c->cfg.rank_n, segs,
-                     seg_words, off, flags, Q);
-}
-
-template <int NL>
-static void launch_shard_route(kc_ctx *c, uint64_t n1, uint64_t *segs, uint64_t seg_words, const uint64_t *wtotals, uint64_t *loose, uint64_t *flags) {
-  auto kern = use_cp<NL>(c) ? kc_shard_route_ovf1_kernel<NL, NL == 1> : kc_shard_route_ovf1_kernel<NL, false>;
-  KernelTimer kt(c, KT_FALLBACK);
-  hipLaunchKernelGGL(kern, dim3((unsigned)std::min<uint64_t>((n1 + TPB - 1) / TPB, 256 * 32)), dim3(TPB), 0, c->stream, c->gm, c->bb, n1,
-                     (uint32_t)c->cfg.rank_me, (uint32_t)c->cfg.rank_n, segs, seg_words, wtotals, loose, flags, c->table, c->d_ctrs);
-}
-
-template <int NL>
-static void launch_shard_loose(kc_ctx *c, const uint64_t *recs, uint64_t n) {
-  auto kern = use_cp<NL>(c) ? kc_shard_loose_kernel<NL, NL == 1> : kc_shard_loose_kernel<NL, false>;
-  KernelTimer kt(c, KT_FALLBACK);
-  hipLaunchKernelGGL(kern, dim3((unsigned)std::min<uint64_t>((n + TPB - 1) / TPB, 256 * 32)), dim3(TPB), 0, c->stream, c->gm, c->bb, recs, n,
-                     c->table, c->d_ctrs);
-}
-
 // checks and set-up shared by the two forms of kc_shard_extract
 static int shard_extract_begin(kc_ctx *c, uint64_t *d_segments, uint64_t seg_words, uint64_t *h_words) {
   if (!c || !h_words) return KC_ERR_INVALID_ARG;
@@ -2203,11 +2082,14 @@ static int shard_extract_pack(kc_ctx *c, bool anything, uint64_t *d_segments, ui
   HIPCHK(hipMemsetAsync(loose, 0, SHARD_MAX * 8, c->stream));
   hipLaunchKernelGGL(kc_shard_plan_kernel, dim3(1), dim3(WGB), 0, c->stream, c->gm, c->bb, me, n, d_segments, seg_words, shard_signature(c),
                      (uint32_t)c->nl, off, totals, flags, wtotals);
-  switch (c->nl) {
-    case 1: launch_shard_pack<1>(c, d_segments, seg_words, off, flags); break;
-    case 2: launch_shard_pack<2>(c, d_segments, seg_words, off, flags); break;
-    case 3: launch_shard_pack<3>(c, d_segments, seg_words, off, flags); break;
-    default: launch_shard_pack<4>(c, d_segments, seg_words, off, flags); break;
+  {
+    const uint32_t Q = 4;  // workgroups per bucket
+    KernelTimer kt(c, KT_SHARD_PACK);
+    const bool compact = shard_wire_of(c->gm) == SHARD_WIRE_COMPACT;
+    with_nl(c, [&](auto nl) {
+      auto kern = (nl == 1 && compact) ? kc_shard_pack_kernel<nl, nl == 1> : kc_shard_pack_kernel<nl, false>;
+      hipLaunchKernelGGL(kern, dim3(c->gm.P1 * Q), dim3(WGB), 0, c->stream, c->gm, c->bb, me, n, d_segments, seg_words, off, flags, Q);
+    });
   }
   c->num_gpu_calls += 2;
   HIPCHK(hipGetLastError());
@@ -2222,12 +2104,12 @@ static int shard_extract_pack(kc_ctx *c, bool anything, uint64_t *d_segments, ui
   if (n1) {
     rc = ensure_room(c, n1);
     if (rc) return rc;
-    switch (c->nl) {
-      case 1: launch_shard_route<1>(c, n1, d_segments, seg_words, wtotals, loose, flags); break;
-      case 2: launch_shard_route<2>(c, n1, d_segments, seg_words, wtotals, loose, flags); break;
-      case 3: launch_shard_route<3>(c, n1, d_segments, seg_words, wtotals, loose, flags); break;
-      default: launch_shard_route<4>(c, n1, d_segments, seg_words, wtotals, loose, flags); break;
-    }
+    with_nl(c, [&](auto nl) {
+      auto kern = with_cp<nl>(c, [&](auto cp) { return kc_shard_route_ovf1_kernel<nl, cp>; });
+      KernelTimer kt(c, KT_FALLBACK);
+      hipLaunchKernelGGL(kern, dim3((unsigned)std::min<uint64_t>((n1 + TPB - 1) / TPB, 256 * 32)), dim3(TPB), 0, c->stream, c->gm, c->bb, n1,
+                         me, n, d_segments, seg_words, wtotals, loose, flags, c->table, c->d_ctrs);
+    });
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemsetAsync(c->d_cb + CB_OVF1, 0, 8, c->stream));
   }
@@ -2392,12 +2274,12 @@ extern "C" int kc_shard_commit(kc_ctx *c, const uint64_t *d_segment, uint64_t nw
     rc = ensure_room(c, loose);
     if (rc) return rc;
     const uint64_t *lp = d_segment + shard_header_words(nb) + rec_words;
-    switch (c->nl) {
-      case 1: launch_shard_loose<1>(c, lp, loose); break;
-      case 2: launch_shard_loose<2>(c, lp, loose); break;
-      case 3: launch_shard_loose<3>(c, lp, loose); break;
-      default: launch_shard_loose<4>(c, lp, loose); break;
-    }
+    with_nl(c, [&](auto nl) {
+      auto kern = with_cp<nl>(c, [&](auto cp) { return kc_shard_loose_kernel<nl, cp>; });
+      KernelTimer kt(c, KT_FALLBACK);
+      hipLaunchKernelGGL(kern, dim3((unsigned)std::min<uint64_t>((loose + TPB - 1) / TPB, 256 * 32)), dim3(TPB), 0, c->stream, c->gm, c->bb, lp,
+                         loose, c->table, c->d_ctrs);
+    });
     HIPCHK(hipGetLastError());
   }
   c->sh.received += nrec + loose;
@@ -2430,13 +2312,11 @@ extern "C" int kc_shard_owner(kc_ctx *c, const uint64_t *kmer, int *owner) {
     const uint64_t mix = kc_feistel_fwd(a[0] >> (64u - c->gm.k2), c->k);
     b1 = (uint32_t)(mix >> (c->gm.k2 - c->gm.la));
   } else {
-    uint64_t h;
-    switch (c->nl) {
-      case 1: { uint64_t x[1] = {a[0]}; h = kc_hash<1>(x); break; }
-      case 2: { uint64_t x[2] = {a[0], a[1]}; h = kc_hash<2>(x); break; }
-      case 3: { uint64_t x[3] = {a[0], a[1], a[2]}; h = kc_hash<3>(x); break; }
-      default: h = kc_hash<4>(a); break;
-    }
+    const uint64_t h = with_nl(c, [&](auto nl) {
+      uint64_t x[nl];
+      std::copy(a, a + nl, x);
+      return kc_hash<nl>(x);
+    });
     b1 = (uint32_t)((((uint32_t)h & 0xFFFFu) * c->gm.P1) >> 16);
   }
   *owner = (int)shard_of_bucket(b1, c->gm.P1, (uint32_t)c->cfg.rank_n);
@@ -2453,13 +2333,6 @@ extern "C" int kc_flush(kc_ctx *c) {
 }
 
 // ---- finalize ----------------------------------------------------------------------------------
-template <int NL>
-static void launch_finalize(kc_ctx *c) {
-  unsigned nblk = (unsigned)std::min<uint64_t>((c->capacity + TPB - 1) / TPB, 256 * 16);
-  hipLaunchKernelGGL(kc_finalize_kernel<NL>, dim3(nblk), dim3(TPB), 0, c->stream, c->table, c->capacity, c->cfg.dmin_thres,
-                     c->d_out_keys, c->d_out_counts, c->d_out_left, c->d_out_right, c->d_ctrs);
-}
-
 static int alloc_results(kc_ctx *c, uint64_t cap) {
   if (!cap) cap = 1;
   if (c->d_out_keys && c->out_cap >= cap) {  // the arrays of an earlier run are big enough: keep them
@@ -2510,12 +2383,11 @@ static int table_finalize_append(kc_ctx *c) {
   if (rc) return rc;
   {
     KernelTimer kt(c, KT_FINALIZE);
-    switch (c->nl) {
-      case 1: launch_finalize<1>(c); break;
-      case 2: launch_finalize<2>(c); break;
-      case 3: launch_finalize<3>(c); break;
-      default: launch_finalize<4>(c); break;
-    }
+    const unsigned nblk = (unsigned)std::min<uint64_t>((c->capacity + TPB - 1) / TPB, 256 * 16);
+    with_nl(c, [&](auto nl) {
+      hipLaunchKernelGGL(kc_finalize_kernel<nl>, dim3(nblk), dim3(TPB), 0, c->stream, c->table, c->capacity, c->cfg.dmin_thres, c->d_out_keys,
+                         c->d_out_counts, c->d_out_left, c->d_out_right, c->d_ctrs);
+    });
   }
   HIPCHK(hipGetLastError());
   return KC_OK;
@@ -2531,11 +2403,11 @@ static int bk_level2_launch(kc_ctx *c, bool inc) {
   const bool cr = use_cp<NL>(c) && c->gm.k2 - c->gm.la <= 32;
   const bool fl = shard_flow_only(c);  // only this shard's buckets, their flat sources behind their chains
   if (inc && fl) return KC_ERR_STATE;
-  auto kern = inc ? (use_cp<NL>(c) ? (cr ? kc_l2_split_kernel<NL, NL == 1, NL == 1, false, true> : kc_l2_split_kernel<NL, NL == 1, false, false, true>)
-                                   : kc_l2_split_kernel<NL, false, false, false, true>)
-              : use_cp<NL>(c) ? (cr ? (fl ? kc_l2_split_kernel<NL, NL == 1, NL == 1, true> : kc_l2_split_kernel<NL, NL == 1, NL == 1, false>)
-                                    : (fl ? kc_l2_split_kernel<NL, NL == 1, false, true> : kc_l2_split_kernel<NL, NL == 1, false, false>))
-                              : (fl ? kc_l2_split_kernel<NL, false, false, true> : kc_l2_split_kernel<NL, false, false, false>);
+  auto kern = with_cp<NL>(c, [&](auto cp) {  // (cr implies cp)
+    if (inc) return cr ? kc_l2_split_kernel<NL, cp, cp, false, true> : kc_l2_split_kernel<NL, cp, false, false, true>;
+    if (cr) return fl ? kc_l2_split_kernel<NL, cp, cp, true> : kc_l2_split_kernel<NL, cp, cp, false>;
+    return fl ? kc_l2_split_kernel<NL, cp, false, true> : kc_l2_split_kernel<NL, cp, false, false>;
+  });
   // six-byte level-1 records have a level 2 of their own (kc_l2_rec6_kernel)
   const bool r6 = NL == 1 && c->gm.rec6 != 0;
   auto kern6 = inc ? kc_l2_rec6_kernel<false, true> : (fl ? kc_l2_rec6_kernel<true, false> : kc_l2_rec6_kernel<false, false>);
@@ -2564,9 +2436,6 @@ static int bk_level2_launch(kc_ctx *c, bool inc) {
       c->inc_on = true;
     }
   }
-#ifdef KC_ABLATE
-  c->gm.abl = getenv("KC_ABL_L2") ? (uint32_t)atoi(getenv("KC_ABL_L2")) : 0u;
-#endif
   if (fs.b_hi > fs.b_lo) {
     KernelTimer kt(c, r6 ? KT_L2_REC6 : KT_L2_SPLIT);
     const dim3 grid(std::min<unsigned>(fs.b_hi - fs.b_lo, (unsigned)c->num_cus));
@@ -2580,12 +2449,7 @@ static int bk_level2_launch(kc_ctx *c, bool inc) {
 // an instalment of level 2 over what has been buffered since the last one (the host pipe, between two blocks)
 static int bk_level2_instalment(kc_ctx *c) {
   if (!bk_active(c) || !c->bk_ready || c->bk_level2 || c->sh.flow) return KC_OK;
-  switch (c->nl) {
-    case 1: return bk_level2_launch<1>(c, true);
-    case 2: return bk_level2_launch<2>(c, true);
-    case 3: return bk_level2_launch<3>(c, true);
-    default: return bk_level2_launch<4>(c, true);
-  }
+  return with_nl(c, [&](auto nl) { return bk_level2_launch<nl>(c, true); });
 }
 
 // Room in the level-2 arena for `need` compact records in all while level 2 runs in instalments: every bucket's part is
@@ -2781,7 +2645,7 @@ static int bk_level2_t(kc_ctx *c) {
 #endif
   const uint64_t n1 = std::min<uint64_t>(c->h_cb[CB_OVF1], c->bb.ovf1_cap);
   if (n1) {
-    auto okern = use_cp<NL>(c) ? kc_ovf1_to_regions_kernel<NL, NL == 1> : kc_ovf1_to_regions_kernel<NL, false>;
+    auto okern = with_cp<NL>(c, [](auto cp) { return kc_ovf1_to_regions_kernel<NL, cp>; });
     hipLaunchKernelGGL(okern, dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, c->stream, c->gm, c->bb, n1, c->d_cb);
     c->num_gpu_calls++;
     HIPCHK(hipGetLastError());
@@ -2816,12 +2680,7 @@ static int bk_build_regions(kc_ctx *c) {
     if (rc) return rc;
   }
   for (int attempt = 0;; attempt++) {
-    switch (c->nl) {
-      case 1: rc = bk_level2_t<1>(c); break;
-      case 2: rc = bk_level2_t<2>(c); break;
-      case 3: rc = bk_level2_t<3>(c); break;
-      default: rc = bk_level2_t<4>(c); break;
-    }
+    rc = with_nl(c, [&](auto nl) { return bk_level2_t<nl>(c); });
     if (rc) return rc;
     rc = sync_cb(c);
     if (rc) return rc;
@@ -2857,7 +2716,7 @@ static int bk_build_regions(kc_ctx *c) {
 
 template <int NL, bool DUMP>
 static int bk_count_t(kc_ctx *c, const OutBufs &ob) {
-  auto kern = use_cp<NL>(c) ? kc_count_kernel<NL, DUMP, NL == 1> : kc_count_kernel<NL, DUMP, false>;
+  auto kern = with_cp<NL>(c, [](auto cp) { return kc_count_kernel<NL, DUMP, cp>; });
   const size_t lds = CountLDS<NL>::bytes(c->gm.S, use_cp<NL>(c));
   int rc = set_dyn_lds(kern, lds);
   if (rc) return rc;
@@ -2865,9 +2724,6 @@ static int bk_count_t(kc_ctx *c, const OutBufs &ob) {
   // as many workgroups per CU as the LDS admits (at most 2: 1024 threads each), so that one region's barriers
   // and scans overlap another's inserts
   const unsigned per_cu = lds * 2 <= 160 * 1024 ? 2u : 1u;
-#ifdef KC_ABLATE
-  c->gm.abl = getenv("KC_ABL_COUNT") ? (uint32_t)atoi(getenv("KC_ABL_COUNT")) : 0u;
-#endif
   KernelTimer kt(c, KT_COUNT_REGIONS);
   hipLaunchKernelGGL(kern, dim3((unsigned)std::min<uint64_t>(R, (uint64_t)c->num_cus * per_cu)), dim3(WGB), lds, c->stream, c->gm, c->bb,
                      ob, c->cfg.dmin_thres, c->d_ctrs, c->d_cb);
@@ -2875,34 +2731,10 @@ static int bk_count_t(kc_ctx *c, const OutBufs &ob) {
 }
 
 static int bk_count(kc_ctx *c, const OutBufs &ob, bool dump) {
-  int rc;
-  if (dump) {
-    switch (c->nl) {
-      case 1: rc = bk_count_t<1, true>(c, ob); break;
-      case 2: rc = bk_count_t<2, true>(c, ob); break;
-      case 3: rc = bk_count_t<3, true>(c, ob); break;
-      default: rc = bk_count_t<4, true>(c, ob); break;
-    }
-  } else {
-    switch (c->nl) {
-      case 1: rc = bk_count_t<1, false>(c, ob); break;
-      case 2: rc = bk_count_t<2, false>(c, ob); break;
-      case 3: rc = bk_count_t<3, false>(c, ob); break;
-      default: rc = bk_count_t<4, false>(c, ob); break;
-    }
-  }
+  int rc = with_nl(c, [&](auto nl) { return dump ? bk_count_t<nl, true>(c, ob) : bk_count_t<nl, false>(c, ob); });
   if (rc) return rc;
   HIPCHK(hipGetLastError());
   return KC_OK;
-}
-
-template <int NL>
-static void launch_flagged_to_table(kc_ctx *c) {
-  const uint64_t R = (uint64_t)c->gm.P1 * c->gm.P2;
-  KernelTimer kt(c, KT_FALLBACK);
-  auto kern = use_cp<NL>(c) ? kc_flagged_to_table_kernel<NL, NL == 1> : kc_flagged_to_table_kernel<NL, false>;
-  hipLaunchKernelGGL(kern, dim3((unsigned)std::min<uint64_t>(R, 65536)), dim3(TPB), 0, c->stream, c->gm, c->bb,
-                     c->table, c->d_ctrs);
 }
 
 // after a count pass: regions that did not fit, and the overflow records, go to the global table (once)
@@ -2923,12 +2755,11 @@ static int bk_move_flagged(kc_ctx *c) {
   if (nflag) {
     rc = ensure_room(c, nflag + n2);
     if (rc) return rc;
-    switch (c->nl) {
-      case 1: launch_flagged_to_table<1>(c); break;
-      case 2: launch_flagged_to_table<2>(c); break;
-      case 3: launch_flagged_to_table<3>(c); break;
-      default: launch_flagged_to_table<4>(c); break;
-    }
+    with_nl(c, [&](auto nl) {
+      KernelTimer kt(c, KT_FALLBACK);
+      auto kern = with_cp<nl>(c, [&](auto cp) { return kc_flagged_to_table_kernel<nl, cp>; });
+      hipLaunchKernelGGL(kern, dim3((unsigned)std::min<uint64_t>(R, 65536)), dim3(TPB), 0, c->stream, c->gm, c->bb, c->table, c->d_ctrs);
+    });
     HIPCHK(hipGetLastError());
   }
   if (n2) {
@@ -2985,12 +2816,7 @@ static int bk_finalize(kc_ctx *c) {
       hipLaunchKernelGGL(kc_out_plan_kernel, dim3(1), dim3(WGB), 0, c->stream, ob.tails, 2 * max_wg, ob.cursor, c->d_cb + CB_OUT_RESERVED,
                          c->d_out_plan);
       const unsigned mgrid = (unsigned)std::min<uint64_t>((slack + 255) / 256, 4096);
-      switch (c->nl) {
-        case 1: hipLaunchKernelGGL(kc_out_move_kernel<1>, dim3(mgrid), dim3(256), 0, c->stream, c->d_out_plan, ob); break;
-        case 2: hipLaunchKernelGGL(kc_out_move_kernel<2>, dim3(mgrid), dim3(256), 0, c->stream, c->d_out_plan, ob); break;
-        case 3: hipLaunchKernelGGL(kc_out_move_kernel<3>, dim3(mgrid), dim3(256), 0, c->stream, c->d_out_plan, ob); break;
-        default: hipLaunchKernelGGL(kc_out_move_kernel<4>, dim3(mgrid), dim3(256), 0, c->stream, c->d_out_plan, ob); break;
-      }
+      with_nl(c, [&](auto nl) { hipLaunchKernelGGL(kc_out_move_kernel<nl>, dim3(mgrid), dim3(256), 0, c->stream, c->d_out_plan, ob); });
       c->num_gpu_calls += 2;
       HIPCHK(hipGetLastError());
     }
@@ -3165,13 +2991,6 @@ static int bk_dump(kc_ctx *c, uint64_t **dk, uint16_t **dc, uint16_t **de, uint6
 // like kc_dump_table), add every counted k-mer to the global table in ONE table operation (not one per occurrence:
 // about a seventh of the operations at the benchmark's depth), and start the buffer again empty.  The table is where
 // the passes meet; kc_finalize then runs one last pass and the table's own finalize.
-template <int NL>
-static void launch_merge_entries(kc_ctx *c, const uint64_t *dk, const uint16_t *dc, const uint16_t *de, uint64_t n) {
-  KernelTimer kt(c, KT_INSERT_RECORDS);
-  hipLaunchKernelGGL(kc_merge_entries_kernel<NL>, dim3((unsigned)std::min<uint64_t>((n + TPB - 1) / TPB, 256 * 32)), dim3(TPB), 0, c->stream, dk,
-                     dc, de, n, c->table, c->d_ctrs);
-}
-
 static int bk_spill_pass(kc_ctx *c) {
   uint64_t *dk = nullptr;
   uint16_t *dc = nullptr, *de = nullptr;
@@ -3180,12 +2999,11 @@ static int bk_spill_pass(kc_ctx *c) {
   if (!rc && n) {
     rc = ensure_room(c, n);
     if (!rc) {
-      switch (c->nl) {
-        case 1: launch_merge_entries<1>(c, dk, dc, de, n); break;
-        case 2: launch_merge_entries<2>(c, dk, dc, de, n); break;
-        case 3: launch_merge_entries<3>(c, dk, dc, de, n); break;
-        default: launch_merge_entries<4>(c, dk, dc, de, n); break;
-      }
+      with_nl(c, [&](auto nl) {
+        KernelTimer kt(c, KT_INSERT_RECORDS);
+        hipLaunchKernelGGL(kc_merge_entries_kernel<nl>, dim3((unsigned)std::min<uint64_t>((n + TPB - 1) / TPB, 256 * 32)), dim3(TPB), 0, c->stream,
+                           dk, dc, de, n, c->table, c->d_ctrs);
+      });
       if (hipGetLastError() != hipSuccess) rc = KC_ERR_HIP;
     }
   }
@@ -3273,12 +3091,9 @@ extern "C" int kc_dump_table(kc_ctx *c, uint64_t *keys, uint16_t *counts, uint16
     HIPCHK(hipMalloc((void **)&dcur, 8));
     HIPCHK(hipMemsetAsync(dcur, 0, 8, c->stream));
     const unsigned nblk = (unsigned)((c->capacity + 255) / 256);
-    switch (c->nl) {
-      case 1: hipLaunchKernelGGL(kc_dump_kernel<1>, dim3(nblk), dim3(256), 0, c->stream, c->table, c->capacity, dk, dc, de, dcur); break;
-      case 2: hipLaunchKernelGGL(kc_dump_kernel<2>, dim3(nblk), dim3(256), 0, c->stream, c->table, c->capacity, dk, dc, de, dcur); break;
-      case 3: hipLaunchKernelGGL(kc_dump_kernel<3>, dim3(nblk), dim3(256), 0, c->stream, c->table, c->capacity, dk, dc, de, dcur); break;
-      default: hipLaunchKernelGGL(kc_dump_kernel<4>, dim3(nblk), dim3(256), 0, c->stream, c->table, c->capacity, dk, dc, de, dcur); break;
-    }
+    with_nl(c, [&](auto nl) {
+      hipLaunchKernelGGL(kc_dump_kernel<nl>, dim3(nblk), dim3(256), 0, c->stream, c->table, c->capacity, dk, dc, de, dcur);
+    });
     c->num_gpu_calls++;
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -3387,13 +3202,7 @@ extern "C" int kc_lookup(kc_ctx *c, const uint64_t *queries, uint64_t nq, int on
     HIPCHK(hipGetLastError());
     dq = wq;
   }
-  int rc;
-  switch (c->nl) {
-    case 1: rc = lookup_t<1>(c, dq, nq, dc, dl, dr); break;
-    case 2: rc = lookup_t<2>(c, dq, nq, dc, dl, dr); break;
-    case 3: rc = lookup_t<3>(c, dq, nq, dc, dl, dr); break;
-    default: rc = lookup_t<4>(c, dq, nq, dc, dl, dr); break;
-  }
+  int rc = with_nl(c, [&](auto nl) { return lookup_t<nl>(c, dq, nq, dc, dl, dr); });
   if (!rc && !on_device && nq) {
     HIPCHK(hipStreamSynchronize(c->stream));
     HIPCHK(hipMemcpy(counts, dc, nq * 2, hipMemcpyDeviceToHost));
@@ -3475,12 +3284,10 @@ extern "C" int kc_submit_ctg_block(kc_ctx *c, const char *seqs, const uint16_t *
     }
     const uint64_t p1 = std::min<uint64_t>(len, p0 + (limit - st[1]));
     const unsigned nblk = (unsigned)((p1 - p0 + 255) / 256);
-    switch (c->nl) {
-      case 1: hipLaunchKernelGGL(kc_ctg_insert_kernel<1>, dim3(nblk), dim3(256), 0, c->stream, d_seqs, d_depths, p0, p1, len, c->k, c->ctg_table, c->d_ctg_status, own); break;
-      case 2: hipLaunchKernelGGL(kc_ctg_insert_kernel<2>, dim3(nblk), dim3(256), 0, c->stream, d_seqs, d_depths, p0, p1, len, c->k, c->ctg_table, c->d_ctg_status, own); break;
-      case 3: hipLaunchKernelGGL(kc_ctg_insert_kernel<3>, dim3(nblk), dim3(256), 0, c->stream, d_seqs, d_depths, p0, p1, len, c->k, c->ctg_table, c->d_ctg_status, own); break;
-      default: hipLaunchKernelGGL(kc_ctg_insert_kernel<4>, dim3(nblk), dim3(256), 0, c->stream, d_seqs, d_depths, p0, p1, len, c->k, c->ctg_table, c->d_ctg_status, own); break;
-    }
+    with_nl(c, [&](auto nl) {
+      hipLaunchKernelGGL(kc_ctg_insert_kernel<nl>, dim3(nblk), dim3(256), 0, c->stream, d_seqs, d_depths, p0, p1, len, c->k, c->ctg_table,
+                         c->d_ctg_status, own);
+    });
     c->num_gpu_calls++;
     e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(st, c->d_ctg_status, 16, hipMemcpyDeviceToHost, c->stream);
@@ -3547,14 +3354,7 @@ static int ctg_merge_t(kc_ctx *c) {
   return KC_OK;
 }
 
-static int ctg_merge(kc_ctx *c) {
-  switch (c->nl) {
-    case 1: return ctg_merge_t<1>(c);
-    case 2: return ctg_merge_t<2>(c);
-    case 3: return ctg_merge_t<3>(c);
-    default: return ctg_merge_t<4>(c);
-  }
-}
+static int ctg_merge(kc_ctx *c) { return with_nl(c, [&](auto nl) { return ctg_merge_t<nl>(c); }); }
 
 extern "C" int kc_get_kernel_times(kc_ctx *c, kc_kernel_time *out, int max, int *n) {
   if (!c || !n) return KC_ERR_INVALID_ARG;

@@ -74,15 +74,7 @@ struct Geom {
   // records are one 12-byte store for the writer and one aligned 12-byte load for level 2 (kc_l2_rec6_kernel): a third more
   // records per second than 8-byte ones on either side (scripts/ubench_rec6.hip, profiles/r04_ubench_rec6.txt).
   uint32_t rec6;
-#ifdef KC_ABLATE
-  uint32_t abl;                // experiment builds (-DKC_ABLATE): which part of a kernel to leave out (scripts/ablate.py)
-#endif
 };
-#ifdef KC_ABLATE
-#define KC_ABL(x, k) ((x).abl == (k))
-#else
-#define KC_ABL(x, k) false
-#endif
 
 struct BucketBufs {
   uint64_t *rec1;      // [G][A1] chunks of CH1 records
@@ -280,10 +272,6 @@ struct ChainDest {
   // top, and giving the top back whole (kc_shard_release_kernel) recycles their chunks, the partly filled last ones
   // included -- a bump allocator that only grew lost about half a chunk per foreign chain and block.
   uint32_t own_lo, own_hi;
-#ifdef KC_ABLATE
-  uint32_t abl;         // experiment builds: see Geom::abl
-  uint32_t abl_a;       // experiment builds: records per 64 bytes of this destination
-#endif
 };
 
 // state of destination `tid`, kept in thread tid's registers (only that thread ever touches it)
@@ -367,25 +355,23 @@ __device__ __forceinline__ uint32_t split_stage(SplitLDS &L, uint64_t *sorted, u
   lds_barrier();
   KC_SPLIT_STAMP(2)  // scan + reserve
   const uint32_t total = L.scan.total;
-  if (!KC_ABL(D, 3)) {
-    // all the run starts first, then all the writes (eight records at a time: sixteen starts in flight cost the level-2
-    // kernel registers it does not have); a position without a record goes to a slot of its lane's behind the staging
-    constexpr int H = R < 8 ? R : 8;
+  // all the run starts first, then all the writes (eight records at a time: sixteen starts in flight cost the level-2
+  // kernel registers it does not have); a position without a record goes to a slot of its lane's behind the staging
+  constexpr int H = R < 8 ? R : 8;
 #pragma unroll
-    for (int j0 = 0; j0 < R; j0 += H) {
-      uint32_t pos[H];
+  for (int j0 = 0; j0 < R; j0 += H) {
+    uint32_t pos[H];
 #pragma unroll
-      for (int j = 0; j < H; j++) pos[j] = L.hist[buf][br[j0 + j] & (PMAX - 1)];
+    for (int j = 0; j < H; j++) pos[j] = L.hist[buf][br[j0 + j] & (PMAX - 1)];
 #pragma unroll
-      for (int j = 0; j < H; j++) {
-        const uint32_t bj = br[j0 + j];
-        const uint32_t p = bj != ~0u ? pos[j] + (bj >> RS) : (uint32_t)(R * WGB) + lane_id();
-        uint64_t r[NL];
-        rec_of(j0 + j, r);
+    for (int j = 0; j < H; j++) {
+      const uint32_t bj = br[j0 + j];
+      const uint32_t p = bj != ~0u ? pos[j] + (bj >> RS) : (uint32_t)(R * WGB) + lane_id();
+      uint64_t r[NL];
+      rec_of(j0 + j, r);
 #pragma unroll
-        for (int w = 0; w < NL; w++) sorted[(size_t)p * NL + w] = r[w];
-        if (sbucket) sbucket[p] = (uint16_t)(bj & (PMAX - 1));
-      }
+      for (int w = 0; w < NL; w++) sorted[(size_t)p * NL + w] = r[w];
+      if (sbucket) sbucket[p] = (uint16_t)(bj & (PMAX - 1));
     }
   }
   lds_barrier();
@@ -400,7 +386,6 @@ __device__ __forceinline__ void split_copy_out(SplitLDS &L, const uint64_t *sort
   // copy out, U elements per thread and trip: first all their records, then all their destinations, then the stores
   constexpr int U = NL == 1 ? 4 : 2;
   const size_t arena0 = (size_t)D.arena_base << D.log2CH;
-  if (KC_ABL(D, 2) || KC_ABL(D, 3)) return;
   for (uint32_t i0 = tid; i0 < total; i0 += U * WGB) {
     uint64_t r[U][NL];
     uint32_t b[U];
@@ -427,14 +412,7 @@ __device__ __forceinline__ void split_copy_out(SplitLDS &L, const uint64_t *sort
       const bool live = i < total, fits = j < (d[u].z >> 16);
       // x and y are "index minus staging position" modulo 2^32: the sum must wrap in 32 bits before it is widened
       const uint32_t at = (j < d[u].w ? d[u].x : d[u].y) + i;
-#ifdef KC_ABLATE
-      if (KC_ABL(D, 4)) {  // timing only (wrong results): every run starts on a 64-byte boundary and is whole 64-byte blocks long
-        const uint32_t am = D.abl_a - 1u, nfit = ((d[u].z >> 16) + (D.abl_a >> 1)) & ~am;
-        const uint32_t at2 = at - ((at - j) & am);
-        if (live && j < nfit) store(arena0 + at2, r[u]);
-      } else
-#endif
-      if (live && fits && !KC_ABL(D, 1)) store(arena0 + at, r[u]);
+      if (live && fits) store(arena0 + at, r[u]);
       spill |= live && !fits;
     }
     if (__any(spill)) {  // rare: a chain or the arena is full
@@ -519,10 +497,6 @@ __device__ __forceinline__ ChainDest l1_dest(const Geom &gm, const BucketBufs &b
   D.arena_base = 0;
   D.own_lo = gm.own_lo;
   D.own_hi = gm.own_hi;
-#ifdef KC_ABLATE
-  D.abl = gm.abl;
-  D.abl_a = 8 / NL;
-#endif
   return D;
 }
 
@@ -648,8 +622,7 @@ __device__ __forceinline__ uint32_t cut_run_fixed(const TL &L, int lp0, bool act
 
 // SH: the context is one shard of several and keeps only the k-mers it owns (kc_submit_reads with rank_n > 1); the
 // single-shard instantiation carries none of the ownership code.
-// KK: k when the instantiation is made for one k (compact records only: cp_run_fixed), 0 = any k
-template <int NL, int FMT, bool CP, bool SH, int KK>
+template <int NL, int FMT, bool CP, bool SH>
 __global__ __launch_bounds__(WGB) void kc_l1_reads_kernel(ExtractArgs a, Geom gm, BucketBufs bb, uint64_t nsuper, uint32_t rot,
                                                           uint64_t *ctrs, uint64_t *cb) {
   extern __shared__ __align__(16) uint8_t smem[];
@@ -688,9 +661,7 @@ __global__ __launch_bounds__(WGB) void kc_l1_reads_kernel(ExtractArgs a, Geom gm
     if (work && st >= nsuper) break;
 #pragma unroll 1
     for (int round = 0; round < NROUND; round++) {
-      constexpr bool SHORT = KK != 0;  // records in the short register form
-      uint64_t rec[SHORT ? 1 : RPOS][NL];
-      uint32_t lo[SHORT ? RPOS : 1];
+      uint64_t rec[RPOS][NL];
       uint32_t br[RPOS];
       uint32_t total = 0;
       if (work) {
@@ -698,31 +669,26 @@ __global__ __launch_bounds__(WGB) void kc_l1_reads_kernel(ExtractArgs a, Geom gm
       const int run_id = round * WGB + tid;
       const bool active = run_id < RUNS;
       const int lp0 = PRE + (active ? run_id : 0) * RPOS;
-      if constexpr (KK != 0) {
-        static_assert(NL == 1 && CP, "a fixed k goes with compact records");
-        cp_run_fixed<KK, RPOS, SH>(L.tile, lp0, active, gm, a, lo, br);
-      } else {
-        KmerRun<NL> run;
-        run_begin<NL>(run, L.tile, lp0, a.k);
+      KmerRun<NL> run;
+      run_begin<NL>(run, L.tile, lp0, a.k);
 #pragma unroll
-        for (int j = 0; j < RPOS; j++) {
-          uint64_t h = 0;
-          uint32_t owner = 0;
-          bool valid = run_kmer<NL, !CP>(run, j, lp0, a.k, rec[j], h, SH ? a.rank_n : 1u, SH ? a.reference_owner : 0u, SH ? &owner : nullptr) && active;
-          if (SH) {
-            if (CP && !a.reference_owner) {
-              uint64_t key[NL];
+      for (int j = 0; j < RPOS; j++) {
+        uint64_t h = 0;
+        uint32_t owner = 0;
+        bool valid = run_kmer<NL, !CP>(run, j, lp0, a.k, rec[j], h, SH ? a.rank_n : 1u, SH ? a.reference_owner : 0u, SH ? &owner : nullptr) && active;
+        if (SH) {
+          if (CP && !a.reference_owner) {
+            uint64_t key[NL];
 #pragma unroll
-              for (int w = 0; w < NL; w++) key[w] = rec[j][w];
-              key[NL - 1] &= ~KC_EXT_MASK;
-              owner = kc_owner_of_hash(kc_hash<NL>(key), a.rank_n);
-            }
-            valid = valid && owner == a.rank_me;
+            for (int w = 0; w < NL; w++) key[w] = rec[j][w];
+            key[NL - 1] &= ~KC_EXT_MASK;
+            owner = kc_owner_of_hash(kc_hash<NL>(key), a.rank_n);
           }
-          if (CP) rec[j][0] = cp_mix_rec(rec[j][0], gm);
-          br[j] = valid ? (CP ? cp_b1(rec[j][0], gm) : hash_b1(h, gm)) : ~0u;
-          if (j + 1 < RPOS) run_advance<NL>(run, j, lp0, a.k);
+          valid = valid && owner == a.rank_me;
         }
+        if (CP) rec[j][0] = cp_mix_rec(rec[j][0], gm);
+        br[j] = valid ? (CP ? cp_b1(rec[j][0], gm) : hash_b1(h, gm)) : ~0u;
+        if (j + 1 < RPOS) run_advance<NL>(run, j, lp0, a.k);
       }
       // the ranks: one LDS add per record, all of a thread's adds in flight together (no branch around them: a
       // position without a k-mer bumps a word of its own lane's instead)
@@ -730,20 +696,16 @@ __global__ __launch_bounds__(WGB) void kc_l1_reads_kernel(ExtractArgs a, Geom gm
       for (int j = 0; j < RPOS; j++) {
         const bool valid = br[j] != ~0u;
         const uint32_t rank = hist_rank(L.sp, buf, br[j] & (PMAX - 1), valid);
-        br[j] = valid ? (br[j] | (rank << (SHORT ? 16 : 10))) : ~0u;
+        br[j] = valid ? (br[j] | (rank << 10)) : ~0u;
         n_ins += valid ? 1u : 0u;
       }
       KC_SPLIT_STAMP(0)  // cut the k-mers out of the super-tile, histogram
       lds_barrier();
-      total = split_stage<NL, RPOS, SHORT ? 16 : 10>(
+      total = split_stage<NL, RPOS>(
           L.sp, sorted, sbucket, buf, P1,
           [&](int j, uint64_t (&o)[NL]) {
-            if constexpr (SHORT) {
-              o[0] = ((uint64_t)(br[j] & (PMAX - 1)) << (64u - gm.la)) | ((uint64_t)lo[j] << (64u - gm.k2)) | (uint64_t)((br[j] >> 10) & 63u);
-            } else {
 #pragma unroll
-              for (int w = 0; w < NL; w++) o[w] = rec[j][w];
-            }
+            for (int w = 0; w < NL; w++) o[w] = rec[j][w];
           },
           br, D, cst);
       }
@@ -884,10 +846,7 @@ template <class OvfFn>
 __device__ __forceinline__ void split_copy_out_pairs(SplitLDS &L, const uint32_t *slo, const uint16_t *sbk, uint32_t total, const ChainDest &D,
                                                      const Geom &gm, OvfFn overflow) {
   const int tid = fresh_tid();
-#ifndef KC_COPY_U
-#define KC_COPY_U 2
-#endif
-  constexpr int U = KC_COPY_U;  // pairs per thread and trip: first all their records, then all their destinations, then the stores
+  constexpr int U = 2;  // pairs per thread and trip: first all their records, then all their destinations, then the stores
   // (D.arena: the owner's part of the level-1 arena in six-byte records, l1_dest6)
   uint8_t *const arena0 = reinterpret_cast<uint8_t *>(D.arena) + ((size_t)D.arena_base << D.log2CH) * 6;
   const uint32_t shb = 64u - gm.la, shl = 64u - gm.k2;  // (the record as a 64-bit mixed one, for the overflow list only)
@@ -1461,10 +1420,6 @@ __global__ __launch_bounds__(WGB) void kc_l2_split_kernel(Geom gm, BucketBufs bb
     D.arena_cap = bb.base2[b1 + 1] - bb.base2[b1];
     D.own_lo = 0;
     D.own_hi = PMAX;
-#ifdef KC_ABLATE
-    D.abl = gm.abl;
-    D.abl_a = CP ? 16 : 8 / NL;
-#endif
 #ifdef KC_STAMPS
     unsigned long long tprev_ = __builtin_amdgcn_s_memtime();
     D.stamps = cb + 8;
@@ -1674,10 +1629,6 @@ __global__ __launch_bounds__(WGB) void kc_l2_rec6_kernel(Geom gm, BucketBufs bb,
     D.arena_cap = bb.base2[b1 + 1] - bb.base2[b1];
     D.own_lo = 0;
     D.own_hi = PMAX;
-#ifdef KC_ABLATE
-    D.abl = gm.abl;
-    D.abl_a = 16;
-#endif
 #ifdef KC_STAMPS
     unsigned long long tprev_ = __builtin_amdgcn_s_memtime();
     D.stamps = cb + 8;
@@ -2290,11 +2241,7 @@ __global__ __launch_bounds__(WGB, 8) void kc_count_kernel(Geom gm, BucketBufs bb
       // several independent loads in flight per thread before the dependent LDS work starts
       // (two: with the next region's lines touched into the L2 a region ahead the loads need no depth, and eight records
       // in registers cost spilled registers -- 19.1 -> 18.6 ms, profiles/r03_ab_count_batch.txt)
-#ifndef KC_BATCH
-#define KC_BATCH 2
-#endif
-      constexpr int BATCH = NL == 1 ? KC_BATCH : NL == 2 ? 4 : 2;
-#ifndef KC_COUNT_NO_PAIRS
+      constexpr int BATCH = NL == 2 ? 4 : 2;
       if constexpr (NL == 1 && CP) {
         // Compact records: a lane takes TWO neighbouring records with one 8-byte load (the order in which a region's
         // records are counted is free): one chunk id, one address, one load instruction for two records.  A chunk holds an
@@ -2306,7 +2253,7 @@ __global__ __launch_bounds__(WGB, 8) void kc_count_kernel(Geom gm, BucketBufs bb
           i = v0 ? i : 0u;
           const size_t at = ((size_t)T.chain[buf][i >> gm.log2CH2] << gm.log2CH2) + (i & CHm);
           const uint2 rr = *reinterpret_cast<const uint2 *>(reinterpret_cast<const uint32_t *>(bb.rec2) + at);
-          if (__builtin_amdgcn_ballot_w64(v0) == 0 || KC_ABL(gm, 2)) continue;  // past the end of the region for the whole wave
+          if (__builtin_amdgcn_ballot_w64(v0) == 0) continue;  // past the end of the region for the whole wave
 #pragma unroll
           for (int j = 0; j < 2; j++) {
             const bool v = j ? v1 : v0;
@@ -2314,15 +2261,13 @@ __global__ __launch_bounds__(WGB, 8) void kc_count_kernel(Geom gm, BucketBufs bb
             const uint32_t s = lds_probe32(keys32, S - 1u, key, key & (S - 1u), ((key >> tb.lgS) << 1) | 1u, v, failed);
             const uint32_t le = r0 & 7u, re = (r0 >> 3) & 7u;
             // only lanes that hold a record touch the counters: 64 atomic adds of zero to one LDS word are serialised
-            if (v && !KC_ABL(gm, 1)) ext_count<EW>(tb, s, le, re);
+            if (v) ext_count<EW>(tb, s, le, re);
           }
         }
         if (failed) T.fail[buf] = 1;
       } else
-#endif
-      for (uint32_t i0 = 0; i0 < n; i0 += WGB * BATCH) {
+      for (uint32_t i0 = 0; i0 < n; i0 += WGB * BATCH) {  // (wide records: CP only exists for NL == 1)
         uint64_t rec[BATCH][NL];
-        uint32_t rec32[BATCH];
         // no branches around the loads (an out-of-range lane re-reads record 0): the compiler can then issue
         // all of them before the first wait instead of fencing each one off in its own basic block
         size_t at[BATCH];
@@ -2336,28 +2281,10 @@ __global__ __launch_bounds__(WGB, 8) void kc_count_kernel(Geom gm, BucketBufs bb
         }
 #pragma unroll
         for (int j = 0; j < BATCH; j++) {
-          if (CP) {
-            rec32[j] = reinterpret_cast<const uint32_t *>(bb.rec2)[at[j]];
-          } else {
 #pragma unroll
-            for (int w = 0; w < NL; w++) rec[j][w] = bb.rec2[at[j] * NL + w];
-          }
+          for (int w = 0; w < NL; w++) rec[j][w] = bb.rec2[at[j] * NL + w];
         }
-        if constexpr (NL == 1 && CP) {
-          uint32_t failed = 0;
-#pragma unroll
-          for (int j = 0; j < BATCH; j++) {
-            const bool v = (i0 + (uint32_t)j * WGB + tid) < n;
-            const uint32_t r0 = rec32[j], key = r0 >> 6;
-            if (__builtin_amdgcn_ballot_w64(v) == 0 || KC_ABL(gm, 2)) continue;  // past the end of the region for the whole wave
-            const uint32_t s = lds_probe32(keys32, S - 1u, key, key & (S - 1u), ((key >> tb.lgS) << 1) | 1u, v, failed);
-            const uint32_t le = r0 & 7u, re = (r0 >> 3) & 7u;
-            // only lanes that hold a record touch the counters: the idle lanes of a wave all re-read record 0, and 64
-            // atomic adds of zero to one LDS word are serialised
-            if (v && !KC_ABL(gm, 1)) ext_count<EW>(tb, s, le, re);
-          }
-          if (failed) T.fail[buf] = 1;
-        } else if constexpr (NL == 1) {
+        if constexpr (NL == 1) {
           uint32_t failed = 0;
 #pragma unroll
           for (int j = 0; j < BATCH; j++) {
@@ -2437,7 +2364,7 @@ __global__ __launch_bounds__(WGB, 8) void kc_count_kernel(Geom gm, BucketBufs bb
 #pragma unroll
         for (int u = 0; u < 2; u++) {
           cand[u] = false;
-          if (taken[u] && !failed && !KC_ABL(gm, 3)) {
+          if (taken[u] && !failed) {
             // the k-mer's count: every occurrence bumped exactly one of the left side's counters (<= 65535: n is)
             const uint32_t count = (w[u][0] & 0xFFFFu) + (w[u][0] >> 16) + (w[u][1] & 0xFFFFu) + (w[u][1] >> 16) + (w[u][2] & 0xFFFFu);
             cand[u] = DUMP || count >= 2;
