@@ -137,14 +137,12 @@ struct kc_ctx {
   uint64_t h_w6cur[WIRE6_MAX_SHARDS << WIRE6_MAX_LG_PIECES];
   bool l1_dropped;       // earlier buffer-fulls of this pass went through level 2 and left level 1 (bk_light_spill): level 2 holds them
   uint64_t l2_held;      // ... that many records (an upper bound)
-  uint8_t *d_l2snap;     // level 2's state before an instalment that cannot be run again as a whole pass (l2_snapshot)
+  uint8_t *d_l2snap;     // level 2's state before a launch that cannot be run again as a whole pass (l2_snapshot)
   size_t l2snap_bytes;
-  bool l2snap_fresh;     // the snapshot is of a level 2 that had not begun (inc_on was false)
   uint64_t l2_per_bucket;  // records every bucket's part of the level-2 arena has room for while level 2 runs in instalments
   uint64_t expect_base;  // CTR_EXPECT when the buffer was last emptied: what is buffered now is CTR_EXPECT - expect_base
   uint64_t expect_prev;  // CTR_EXPECT after the previous block
   uint64_t bk_capacity;  // records the level-1 segments are sized for
-  uint64_t bk_buffered;  // upper bound of records buffered so far (positions submitted)
   uint32_t bk_rot;       // first writer of the next level-1 launch
   size_t bk_bytes;
   int num_cus;
@@ -323,6 +321,27 @@ static int ensure_tile_first(kc_ctx *c, size_t ntiles) {
   c->tile_first_cap = 0;
   HIPCHK(hipMalloc((void **)&c->d_tile_first, ntiles * 8));
   c->tile_first_cap = ntiles;
+  return KC_OK;
+}
+
+// records straight into the global table, growing it as needed
+static int table_insert_records(kc_ctx *c, const uint64_t *d_records, uint64_t n, uint32_t count_inserted) {
+  uint64_t done = 0;
+  while (done < n) {
+    uint64_t m = std::min<uint64_t>(n - done, std::max<uint64_t>(c->capacity / 4, 1u << 18));
+    int rc = ensure_room(c, m);
+    if (rc) return rc;
+    const uint64_t *p = d_records + done * c->nl;
+    {
+      KernelTimer kt(c, KT_INSERT_RECORDS);
+      const unsigned nblk = (unsigned)std::min<uint64_t>((m + TPB - 1) / TPB, 256 * 32);
+      with_nl(c, [&](auto nl) {
+        hipLaunchKernelGGL(kc_insert_records_kernel<nl>, dim3(nblk), dim3(TPB), 0, c->stream, p, m, c->table, c->d_ctrs, count_inserted);
+      });
+    }
+    HIPCHK(hipGetLastError());
+    done += m;
+  }
   return KC_OK;
 }
 
@@ -544,6 +563,34 @@ static void shard_free(kc_ctx *c) {
   c->sh.d_plan = c->sh.h_plan = nullptr;
 }
 
+// Level 1 empty: every chain, every writer's arena whole, nothing on its overflow list (whose counter, CB_OVF1, is
+// among the counters bk_empty_level2 clears).  The arrays exist while the context has a geometry (bk_ready).
+static int bk_empty_level1(kc_ctx *c) {
+  if (c->bk_ready) {
+    HIPCHK(hipMemsetAsync(c->bb.cnt1, 0, (size_t)c->gm.G * c->gm.P1 * 4, c->stream));
+    HIPCHK(hipMemsetAsync(c->bb.used1, 0, (size_t)c->gm.G * 2 * 4, c->stream));
+  }
+  c->ovf1_ub = 0;
+  return KC_OK;
+}
+
+// Level 2 empty: no region holds a record or is flagged, every counter of the bucketed path is zero, and nothing of an
+// instalment, a light spill or a finished pass is left
+static int bk_empty_level2(kc_ctx *c) {
+  if (c->bk_ready) {
+    const size_t R = (size_t)c->gm.P1 * c->gm.P2;
+    HIPCHK(hipMemsetAsync(c->bb.cnt2, 0, R * 4, c->stream));
+    HIPCHK(hipMemsetAsync(c->bb.flag, 0, R * 4, c->stream));
+  }
+  HIPCHK(hipMemsetAsync(c->d_cb, 0, CB_COUNT * 8, c->stream));
+  c->inc_on = false;
+  c->l2_per_bucket = 0;
+  c->l1_dropped = false;
+  c->l2_held = 0;
+  c->bk_level2 = c->bk_flagged = false;
+  return KC_OK;
+}
+
 extern "C" int kc_reset(kc_ctx *c, int new_k) {
   if (!c) return KC_ERR_INVALID_ARG;
   if (new_k == 0) new_k = c->k;
@@ -574,29 +621,17 @@ extern "C" int kc_reset(kc_ctx *c, int new_k) {
   c->purged = c->sum_counts = c->unique_at_finalize = 0;
   // bucketed path: keep the arrays when the record width is unchanged, else choose the geometry again (so does a
   // new k among the one-word ones: whether the records are compact, and how, depends on k)
-  if (c->bk_ready) {
-    if (c->nl != old_nl || (c->nl == 1 && new_k != old_k)) {
-      bk_free(c, true);  // the next geometry takes the arrays over where they are large enough
-    } else {
-      const size_t R = (size_t)c->gm.P1 * c->gm.P2;
-      HIPCHK(hipMemsetAsync(c->bb.cnt1, 0, (size_t)c->gm.G * c->gm.P1 * 4, c->stream));
-      HIPCHK(hipMemsetAsync(c->bb.used1, 0, (size_t)c->gm.G * 2 * 4, c->stream));
-      HIPCHK(hipMemsetAsync(c->bb.cnt2, 0, R * 4, c->stream));
-      HIPCHK(hipMemsetAsync(c->bb.flag, 0, R * 4, c->stream));
-    }
-  }
-  c->inc_on = false;
-  c->l2_per_bucket = 0;
-  HIPCHK(hipMemsetAsync(c->d_cb, 0, CB_COUNT * 8, c->stream));
-  c->bk_level2 = c->bk_flagged = c->table_mode = c->started = false;
+  const bool new_geometry = c->nl != old_nl || (c->nl == 1 && new_k != old_k);
+  if (c->bk_ready && new_geometry) bk_free(c, true);  // the next geometry takes the arrays over where they are large enough
+  st = bk_empty_level1(c);
+  if (!st) st = bk_empty_level2(c);
+  if (st) return st;
+  c->table_mode = c->started = false;
   c->bk_spilled = false;
-  c->l1_dropped = false;
-  c->l2_held = 0;
   c->expect_base = c->expect_prev = 0;
   c->expect_host = 0;
   c->expect_host_ok = true;
-  c->ovf1_ub = 0;
-  shard_reset(c, c->nl != old_nl || (c->nl == 1 && new_k != old_k));
+  shard_reset(c, new_geometry);
   HIPCHK(hipStreamSynchronize(c->stream));
   return KC_OK;
 }
@@ -848,7 +883,7 @@ static int bk_init(kc_ctx *c) {
   // Overflow lists.  Neither can lose a record: every level-1 launch is bounded by the free room of the first
   // (bk_ovf1_room) -- a quarter (one-word records) or an eighth of the buffer, so that a block of reads goes through in
   // a few launches -- and level 2 is run again with a second list of the size it asked for when that one was too small
-  // (bk_build_regions): the second starts at an eighth of the first (1.7 GB instead of 13 at 50 M reads).
+  // (bk_level2_pass): the second starts at an eighth of the first (1.7 GB instead of 13 at 50 M reads).
   // (at least one super-tile of positions, whatever the buffer: a level-1 launch covers whole tiles)
   b.ovf1_cap = t.ovf_capacity ? t.ovf_capacity : std::max<uint64_t>(bcap / (c->nl == 1 ? 4 : 8) + 4096, 2 * (uint64_t)SUPER_SPAN);
   b.ovf2_cap = t.ovf_capacity ? t.ovf_capacity : std::max<uint64_t>(bcap / (c->nl == 1 ? 32 : 64) + 4096, 2 * (uint64_t)SUPER_SPAN);
@@ -883,22 +918,16 @@ static int bk_init(kc_ctx *c) {
     if (!rc) rc = bk_take(c, 12, (void **)&b.used2, (size_t)g.P1 * 4);
     if (rc) return rc;
   }
-  c->inc_on = false;
-  c->l2_per_bucket = 0;
-  HIPCHK(hipMemsetAsync(b.cnt1, 0, nseg * 4, c->stream));
-  HIPCHK(hipMemsetAsync(b.used1, 0, (size_t)g.G * 2 * 4, c->stream));
-  HIPCHK(hipMemsetAsync(b.cnt2, 0, (size_t)R * 4, c->stream));
-  HIPCHK(hipMemsetAsync(b.flag, 0, (size_t)R * 4, c->stream));
-  HIPCHK(hipMemsetAsync(c->d_cb, 0, CB_COUNT * 8, c->stream));
   if (getenv("KC_DEBUG_ADDR"))
     fprintf(stderr, "kc arenas: rec1 %p (%zu MB) chain1 %p cnt1 %p rec2 %p chain2 %p ovf1 %p ovf2 %p\n", (void *)b.rec1, rec1_bytes >> 20,
             (void *)b.chain1, (void *)b.cnt1, (void *)b.rec2, (void *)b.chain2, (void *)b.ovf1, (void *)b.ovf2);
   c->bk_bytes = rec1_bytes + rec2_bytes + (b.ovf1_cap + b.ovf2_cap) * w + nseg * (g.L1MAX + 1) * 4 + (size_t)R * (g.L2MAX + 2) * 4;
   c->bk_capacity = bcap;
   c->bk_ready = true;
-  c->bk_level2 = c->bk_flagged = false;
   c->bk_rot = 0;
-  return KC_OK;
+  int rc = bk_empty_level1(c);
+  if (!rc) rc = bk_empty_level2(c);
+  return rc;
 }
 
 static int sync_cb(kc_ctx *c) {
@@ -919,7 +948,7 @@ static int bk_ovf1_room(kc_ctx *c, uint64_t want, uint64_t *room) {
   }
   int rc = sync_cb(c);
   if (rc) return rc;
-  if (c->h_cb[CB_FATAL] & ~(c->inc_on ? (uint64_t)FATAL_OVF2 : 0ULL)) {  // (an instalment's full second list is bk_build_regions' business)
+  if (c->h_cb[CB_FATAL] & ~(c->inc_on ? (uint64_t)FATAL_OVF2 : 0ULL)) {  // (an instalment's full second list is bk_level2_pass' business)
     snprintf(g_last_error, sizeof(g_last_error), "k-mer buffer: records were lost (fatal bits %llu)", (unsigned long long)c->h_cb[CB_FATAL]);
     return KC_ERR_CAPACITY;
   }
@@ -1086,6 +1115,414 @@ static int launch_l1_wire6(kc_ctx *c, const uint8_t *base, uint64_t stride, uint
   return KC_OK;
 }
 
+static bool bk_active(const kc_ctx *c) { return c->tuning.mode != 1 && !c->table_mode; }
+// A shard of several that has started the shard flow owns level-1 buckets, not hash values: the entry points that test
+// ownership per k-mer (kc_submit_*, kc_insert_records) would put records where its level 2 never looks.
+static bool shard_flow_only(const kc_ctx *c) { return c->sh.flow && c->cfg.rank_n > 1; }
+
+// ---- bucketed path: level 2, counting, and what happens when the buffer is full ------------------
+// The kernels of level 2, no host wait.  inc: an instalment (kc_l2_split_kernel<..., INC>) -- the first one fixes the
+// buckets' parts of the level-2 arena (the buffer's capacity over the fan-out each) and clears the state the
+// instalments carry; inc with c->inc_on already set: the next one.  !inc && c->inc_on never happens (bk_level2_pass).
+template <int NL>
+static int bk_level2_launch(kc_ctx *c, bool inc) {
+  // short register form: compact records whose mix fits 32 bits below the level-1 bucket
+  const bool cr = use_cp<NL>(c) && c->gm.k2 - c->gm.la <= 32;
+  const bool fl = shard_flow_only(c);  // only this shard's buckets, their flat sources behind their chains
+  if (inc && fl) return KC_ERR_STATE;
+  auto kern = with_cp<NL>(c, [&](auto cp) {  // (cr implies cp)
+    if (inc) return cr ? kc_l2_split_kernel<NL, cp, cp, false, true> : kc_l2_split_kernel<NL, cp, false, false, true>;
+    if (cr) return fl ? kc_l2_split_kernel<NL, cp, cp, true> : kc_l2_split_kernel<NL, cp, cp, false>;
+    return fl ? kc_l2_split_kernel<NL, cp, false, true> : kc_l2_split_kernel<NL, cp, false, false>;
+  });
+  // six-byte level-1 records have a level 2 of their own (kc_l2_rec6_kernel)
+  const bool r6 = NL == 1 && c->gm.rec6 != 0;
+  auto kern6 = inc ? kc_l2_rec6_kernel<false, true> : (fl ? kc_l2_rec6_kernel<true, false> : kc_l2_rec6_kernel<false, false>);
+  int rc = r6 ? set_dyn_lds(kern6, l2r6_lds_bytes()) : set_dyn_lds(kern, lds_l2<NL>());
+  if (rc) return rc;
+  FlatSrc fs;
+  memset(&fs, 0, sizeof(fs));
+  fs.b_hi = c->gm.P1;
+  if (fl) {
+    fs.cnt = c->sh.d_cnt;
+    fs.at = c->sh.d_at;
+    fs.F = c->sh.F;
+    fs.b_lo = shard_first_bucket((uint32_t)c->cfg.rank_me, c->gm.P1, (uint32_t)c->cfg.rank_n);
+    fs.b_hi = shard_first_bucket((uint32_t)c->cfg.rank_me + 1, c->gm.P1, (uint32_t)c->cfg.rank_n);
+    fs.nbo = fs.b_hi - fs.b_lo;
+  }
+  if (!inc || !c->inc_on) {
+    if (inc && !c->l2_per_bucket) c->l2_per_bucket = (c->bk_capacity + c->gm.P1 - 1) / c->gm.P1;
+    const uint64_t per_bucket = inc ? c->l2_per_bucket : 0;
+    hipLaunchKernelGGL(kc_bucket_prefix_kernel, dim3(1), dim3(WGB), 0, c->stream, c->gm, c->bb, fs, c->d_cb, per_bucket);
+    c->num_gpu_calls++;
+    if (inc) {
+      HIPCHK(hipMemsetAsync(c->bb.cnt2, 0, (size_t)c->gm.P1 * c->gm.P2 * 4, c->stream));
+      HIPCHK(hipMemsetAsync(c->bb.done1, 0, (size_t)c->gm.G * c->gm.P1 * 4, c->stream));
+      HIPCHK(hipMemsetAsync(c->bb.used2, 0, (size_t)c->gm.P1 * 4, c->stream));
+      c->inc_on = true;
+    }
+  }
+  if (fs.b_hi > fs.b_lo) {
+    KernelTimer kt(c, r6 ? KT_L2_REC6 : KT_L2_SPLIT);
+    const dim3 grid(std::min<unsigned>(fs.b_hi - fs.b_lo, (unsigned)c->num_cus));
+    if (r6) hipLaunchKernelGGL(kern6, grid, dim3(WGB), l2r6_lds_bytes(), c->stream, c->gm, c->bb, fs, c->d_cb);
+    else hipLaunchKernelGGL(kern, grid, dim3(WGB), lds_l2<NL>(), c->stream, c->gm, c->bb, fs, c->d_cb);
+  }
+  HIPCHK(hipGetLastError());
+  return KC_OK;
+}
+
+// An instalment of level 2 over what has been buffered since the last one (the host pipe, between two blocks).  It is
+// not checked: an unchecked launch of level 2 may run only while level 1 holds every record it was given, so that a
+// region overflow list it fills can be answered by running the whole pass again (bk_level2_pass).  Once level 1 has been
+// emptied behind an instalment (l1_dropped), what it holds waits for the next light spill or the last pass.
+static int bk_level2_instalment(kc_ctx *c) {
+  if (!bk_active(c) || !c->bk_ready || c->bk_level2 || c->sh.flow || c->l1_dropped) return KC_OK;
+  return with_nl(c, [&](auto nl) { return bk_level2_launch<nl>(c, true); });
+}
+
+// Room in the level-2 arena for `need` compact records in all while level 2 runs in instalments: every bucket's part is
+// fixed up front (kc_bucket_prefix_kernel with per_bucket), so more records than planned mean a larger arena and, once
+// instalments have begun, the parts moved into it (kc_l2_grow_kernel).  KC_ERR_OUT_OF_MEMORY when the device has no room.
+static int bk_l2_reserve(kc_ctx *c, uint64_t need) {
+  const Geom &g = c->gm;
+  const uint64_t CH2 = 1ULL << g.log2CH2;
+  const uint64_t pb_need = (uint64_t)((double)need * 1.08 / (double)g.P1) + 2 * CH2;  // (buckets differ by a few per cent)
+  const uint64_t pb_now = c->inc_on ? c->l2_per_bucket : (c->bk_capacity + g.P1 - 1) / g.P1;
+  if (pb_need <= pb_now) {
+    if (!c->inc_on) c->l2_per_bucket = pb_now;
+    return KC_OK;
+  }
+  const uint64_t pb = c->inc_on ? std::max<uint64_t>(2 * pb_now, pb_need) : pb_need;
+  const uint64_t a2 = (uint64_t)g.P1 * ((pb + CH2 - 1) / CH2 + g.P2) + 16;
+  if (a2 >= (1ULL << 32)) return KC_ERR_OUT_OF_MEMORY;
+  uint64_t *bigger = nullptr;
+  const size_t bytes = (size_t)a2 * CH2 * 4;
+  size_t free_b = 0, total_b = 0;
+  if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b < bytes + ((size_t)4 << 30) || hipMalloc((void **)&bigger, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    return KC_ERR_OUT_OF_MEMORY;
+  }
+  if (c->inc_on) {
+    uint32_t *nb = nullptr;
+    if (hipMalloc((void **)&nb, ((size_t)g.P1 + 1) * 4) != hipSuccess) {
+      (void)hipGetLastError();
+      (void)hipFree(bigger);
+      return KC_ERR_OUT_OF_MEMORY;
+    }
+    BucketBufs tmp = c->bb;
+    tmp.base2 = nb;
+    FlatSrc fs;
+    memset(&fs, 0, sizeof(fs));
+    hipLaunchKernelGGL(kc_bucket_prefix_kernel, dim3(1), dim3(WGB), 0, c->stream, c->gm, tmp, fs, c->d_cb, pb);
+    hipLaunchKernelGGL(kc_l2_grow_kernel, dim3(g.P1), dim3(WGB), 0, c->stream, c->gm, reinterpret_cast<const uint32_t *>(c->bb.rec2),
+                       reinterpret_cast<uint32_t *>(bigger), c->bb.base2, nb, c->bb.used2, c->bb.chain2, c->bb.cnt2);
+    c->num_gpu_calls += 2;
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(c->bb.base2, nb, ((size_t)g.P1 + 1) * 4, hipMemcpyDeviceToDevice, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    (void)hipFree(nb);
+    if (e != hipSuccess) {
+      (void)hipFree(bigger);
+      return hip_fail(e, "bk_l2_reserve", __LINE__);
+    }
+  }
+  HIPCHK(hipFree(c->bb.rec2));
+  c->bk_bytes += bytes - c->bk_held[4];
+  c->bb.rec2 = bigger;
+  c->bk_held[4] = bytes;
+  c->gm.A2 = (uint32_t)a2;
+  c->l2_per_bucket = pb;
+  return KC_OK;
+}
+
+// A region overflow list of at least `records` records, the first `keep` entries of the current one kept
+static int grow_ovf2(kc_ctx *c, uint64_t records, uint64_t keep) {
+  if (records <= c->bb.ovf2_cap) return KC_OK;
+  const size_t w = (size_t)c->nl * 8;
+  uint64_t *bigger = nullptr;
+  if (hipMalloc((void **)&bigger, records * w) != hipSuccess) {
+    (void)hipGetLastError();
+    snprintf(g_last_error, sizeof(g_last_error), "no memory for a region overflow list of %llu records", (unsigned long long)records);
+    return KC_ERR_OUT_OF_MEMORY;
+  }
+  if (keep) HIPCHK(hipMemcpyAsync(bigger, c->bb.ovf2, keep * w, hipMemcpyDeviceToDevice, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipFree(c->bb.ovf2));
+  c->bk_bytes += (records - c->bb.ovf2_cap) * w;
+  c->bb.ovf2 = bigger;
+  c->bb.ovf2_cap = records;
+  c->bk_held[10] = records * w;
+  return KC_OK;
+}
+
+// Level 2's state -- the regions' lengths, the buckets' arena marks, how far every level-1 chain has been read, the region
+// overflow list's length: a few MB -- saved to d_l2snap, or (restore) put back from it with the list's fatal bit cleared
+static int l2_snapshot(kc_ctx *c, bool restore) {
+  const Geom &g = c->gm;
+  void *const part[4] = {c->bb.cnt2, c->bb.used2, c->bb.done1, c->d_cb + CB_OVF2};
+  const size_t bytes[4] = {(size_t)g.P1 * g.P2 * 4, (size_t)g.P1 * 4, (size_t)g.G * g.P1 * 4, 8};
+  const size_t need = bytes[0] + bytes[1] + bytes[2] + bytes[3];
+  if (!restore && c->l2snap_bytes < need) {
+    if (c->d_l2snap) HIPCHK(hipFree(c->d_l2snap));
+    c->d_l2snap = nullptr;
+    c->l2snap_bytes = 0;
+    HIPCHK(hipMalloc((void **)&c->d_l2snap, need));
+    c->l2snap_bytes = need;
+  }
+  uint8_t *s = c->d_l2snap;
+  for (int i = 0; i < 4; s += bytes[i], i++)
+    HIPCHK(hipMemcpyAsync(restore ? part[i] : s, restore ? s : part[i], bytes[i], hipMemcpyDeviceToDevice, c->stream));
+  if (restore) HIPCHK(hipMemsetAsync(c->d_cb + CB_FATAL, 0, 8, c->stream));
+  return KC_OK;
+}
+
+// One launch of level 2, then what found no room at level 1 (n1 records) onto the regions' list; no host wait
+template <int NL>
+static int bk_level2_t(kc_ctx *c, bool inc, uint64_t n1) {
+  int rc = bk_level2_launch<NL>(c, inc);
+  if (rc) return rc;
+#ifdef KC_STAMPS
+  (void)sync_cb(c);
+  fprintf(stderr, "l2 kernel cycles (thread 0, summed over workgroups): hist %llu barrierA %llu scan+reserve %llu scatter %llu copyout %llu take-over+loads %llu\n",
+          (unsigned long long)c->h_cb[8], (unsigned long long)c->h_cb[9], (unsigned long long)c->h_cb[10],
+          (unsigned long long)c->h_cb[11], (unsigned long long)c->h_cb[12], (unsigned long long)c->h_cb[13]);
+  HIPCHK(hipMemsetAsync(c->d_cb + 8, 0, 8 * 8, c->stream));
+#endif
+  if (n1) {
+    auto okern = with_cp<NL>(c, [](auto cp) { return kc_ovf1_to_regions_kernel<NL, cp>; });
+    hipLaunchKernelGGL(okern, dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, c->stream, c->gm, c->bb, n1, c->d_cb);
+    c->num_gpu_calls++;
+    HIPCHK(hipGetLastError());
+  }
+  return KC_OK;
+}
+
+// One checked pass of level 2: an instalment behind which level 1 is emptied (bk_light_spill), or the last pass
+// (bk_build_regions; after instalments one more, over the rest).  When the region overflow list fills up -- regions that
+// outgrew their chains, heavy hitters -- its counter keeps counting past the end and says how much room the launch needs:
+// * level 1 still holds every record it was given (!l1_dropped): the list grows and the whole pass runs again;
+// * it does not: the launch cannot be run again from level 1, so level 2's state is saved before it and put back, the
+//   list grows (its entries from before the launch kept), and the same launch is repeated once.
+// A list left full by an unchecked instalment (bk_level2_instalment) is the first case: none runs once l1_dropped is set.
+static int bk_level2_pass(kc_ctx *c, bool instalment) {
+  int rc = sync_cb(c);
+  if (rc) return rc;
+  const uint64_t fatal0 = c->h_cb[CB_FATAL];
+  if ((fatal0 & ~(uint64_t)FATAL_OVF2) || (fatal0 && c->l1_dropped)) {  // (never a snapshot of a counter larger than its list)
+    snprintf(g_last_error, sizeof(g_last_error), "k-mer buffer: records were lost (fatal bits %llu)", (unsigned long long)fatal0);
+    return KC_ERR_CAPACITY;
+  }
+  // the list takes what an instalment's heavy regions spill: at least half of it free, or it grows
+  if (instalment && c->h_cb[CB_OVF2] * 2 > c->bb.ovf2_cap) {
+    rc = grow_ovf2(c, 2 * c->bb.ovf2_cap, std::min<uint64_t>(c->h_cb[CB_OVF2], c->bb.ovf2_cap));
+    if (rc) return rc;
+  }
+  const uint64_t listed = std::min<uint64_t>(c->h_cb[CB_OVF2], c->bb.ovf2_cap);  // on the list before this pass
+  const uint64_t n1 = std::min<uint64_t>(c->h_cb[CB_OVF1], c->bb.ovf1_cap);
+  if (c->l1_dropped) {  // (l1_dropped implies inc_on: the launch goes on from the state of the instalments before it)
+    rc = l2_snapshot(c, false);
+    if (rc) return rc;
+  }
+  for (int attempt = 0;; attempt++) {
+    rc = with_nl(c, [&](auto nl) { return bk_level2_t<nl>(c, instalment || c->inc_on, n1); });
+    if (rc) return rc;
+    rc = sync_cb(c);
+    if (rc) return rc;
+    const uint64_t fatal = c->h_cb[CB_FATAL], asked = c->h_cb[CB_OVF2];
+    if (!fatal) return KC_OK;
+    if (fatal != FATAL_OVF2 || attempt > 0) {
+      snprintf(g_last_error, sizeof(g_last_error), "k-mer buffer: records were lost %s (fatal bits %llu)",
+               instalment ? "in an instalment of level 2" : "building the regions", (unsigned long long)fatal);
+      return KC_ERR_CAPACITY;
+    }
+    if (c->l1_dropped) {
+      rc = grow_ovf2(c, asked + asked / 16 + 4096, listed);
+      if (!rc) rc = l2_snapshot(c, true);
+      if (rc) return rc;
+    } else {
+      c->inc_on = false;  // (the next launch starts level 2 from zero)
+      rc = grow_ovf2(c, asked + asked / 64 + 4096, 0);
+      if (rc) return rc;
+      HIPCHK(hipMemsetAsync(c->d_cb + CB_OVF2, 0, 2 * 8, c->stream));  // OVF2, FATAL
+    }
+  }
+}
+
+// The buffer is full and more reads are coming (compact records): level 1's records go through level 2 now, level 1
+// starts again empty, level 2 keeps what it has until the regions are counted.  buffered: records level 1 holds (an upper
+// bound).  KC_ERR_UNSUPPORTED_K: not a geometry this works for (the caller takes the other way).
+static int bk_light_spill(kc_ctx *c, uint64_t buffered) {
+  if (!c->gm.cp || c->nl != 1 || !bk_active(c) || !c->bk_ready || c->bk_level2 || c->sh.flow) return KC_ERR_UNSUPPORTED_K;
+  const char *e = getenv("KC_LIGHT_SPILL");
+  if (e && e[0] == '0') return KC_ERR_UNSUPPORTED_K;  // (A/B runs: the counted buffer merged into the global table, as for longer k-mers)
+  int rc = bk_l2_reserve(c, c->l2_held + buffered);
+  if (!rc) rc = bk_level2_pass(c, true);
+  if (!rc) rc = bk_empty_level1(c);
+  if (rc) return rc;
+  // (level 1's overflow records are on the regions' list now, and level 2 reads the new chains from their start)
+  HIPCHK(hipMemsetAsync(c->d_cb + CB_OVF1, 0, 8, c->stream));
+  HIPCHK(hipMemsetAsync(c->bb.done1, 0, (size_t)c->gm.G * c->gm.P1 * 4, c->stream));
+  c->l2_held += buffered;
+  c->l1_dropped = true;
+  return KC_OK;
+}
+
+// build the regions from everything buffered (once per reset)
+static int bk_build_regions(kc_ctx *c) {
+  if (c->bk_level2) return KC_OK;
+#ifdef KC_STAMPS
+  (void)sync_cb(c);
+  fprintf(stderr, "l1 kernel cycles (thread 0, summed over workgroups): extract+hist %llu barrierA %llu scan+reserve %llu scatter %llu copyout %llu stage %llu\n",
+          (unsigned long long)c->h_cb[8], (unsigned long long)c->h_cb[9], (unsigned long long)c->h_cb[10],
+          (unsigned long long)c->h_cb[11], (unsigned long long)c->h_cb[12], (unsigned long long)c->h_cb[13]);
+  (void)sync_ctrs(c);
+  fprintf(stderr, "   encode: first barrier %llu groups %llu offsets %llu last barrier %llu\n", (unsigned long long)c->h_ctrs[CTR_BIN0 + 40],
+          (unsigned long long)c->h_ctrs[CTR_BIN0 + 41], (unsigned long long)c->h_ctrs[CTR_BIN0 + 42], (unsigned long long)c->h_ctrs[CTR_BIN0 + 43]);
+  HIPCHK(hipMemsetAsync(c->d_cb + 8, 0, 8 * 8, c->stream));
+#endif
+  int rc = KC_OK;
+  if (c->l1_dropped) {  // level 1 holds what came after the last light spill: the buckets' parts of level 2 take that too
+    rc = sync_ctrs(c);
+    if (!rc) rc = bk_l2_reserve(c, c->l2_held + (c->h_ctrs[CTR_EXPECT] - c->expect_base));
+    if (rc) return rc;
+  }
+  rc = bk_level2_pass(c, false);
+  if (rc) return rc;
+  c->bk_level2 = true;
+  return KC_OK;
+}
+
+template <int NL, bool DUMP>
+static int bk_count_t(kc_ctx *c, const OutBufs &ob) {
+  auto kern = with_cp<NL>(c, [](auto cp) { return kc_count_kernel<NL, DUMP, cp>; });
+  const size_t lds = CountLDS<NL>::bytes(c->gm.S, use_cp<NL>(c));
+  int rc = set_dyn_lds(kern, lds);
+  if (rc) return rc;
+  const uint64_t R = (uint64_t)c->gm.P1 * c->gm.P2;
+  // as many workgroups per CU as the LDS admits (at most 2: 1024 threads each), so that one region's barriers
+  // and scans overlap another's inserts
+  const unsigned per_cu = lds * 2 <= 160 * 1024 ? 2u : 1u;
+  KernelTimer kt(c, KT_COUNT_REGIONS);
+  hipLaunchKernelGGL(kern, dim3((unsigned)std::min<uint64_t>(R, (uint64_t)c->num_cus * per_cu)), dim3(WGB), lds, c->stream, c->gm, c->bb,
+                     ob, c->cfg.dmin_thres, c->d_ctrs, c->d_cb);
+  return KC_OK;
+}
+
+static int bk_count(kc_ctx *c, const OutBufs &ob, bool dump) {
+  int rc = with_nl(c, [&](auto nl) { return dump ? bk_count_t<nl, true>(c, ob) : bk_count_t<nl, false>(c, ob); });
+  if (rc) return rc;
+  HIPCHK(hipGetLastError());
+  return KC_OK;
+}
+
+// after a count pass: regions that did not fit, and the overflow records, go to the global table (once)
+static int bk_move_flagged(kc_ctx *c) {
+  if (c->bk_flagged) return KC_OK;
+  const uint64_t R = (uint64_t)c->gm.P1 * c->gm.P2;
+  HIPCHK(hipMemsetAsync(c->d_cb + CB_FLAGGED_RECS, 0, 8, c->stream));
+  hipLaunchKernelGGL(kc_sum_flagged_kernel, dim3((unsigned)std::min<uint64_t>((R + 255) / 256, 1024)), dim3(256), 0, c->stream, c->gm, c->bb,
+                     c->d_cb);
+  c->num_gpu_calls++;
+  int rc = sync_cb(c);
+  if (rc) return rc;
+  if (c->h_cb[CB_FATAL]) {
+    snprintf(g_last_error, sizeof(g_last_error), "region overflow list exhausted: raise max_kmers_buffered");
+    return KC_ERR_CAPACITY;
+  }
+  const uint64_t nflag = c->h_cb[CB_FLAGGED_RECS], n2 = std::min<uint64_t>(c->h_cb[CB_OVF2], c->bb.ovf2_cap);
+  if (nflag) {
+    rc = ensure_room(c, nflag + n2);
+    if (rc) return rc;
+    with_nl(c, [&](auto nl) {
+      KernelTimer kt(c, KT_FALLBACK);
+      auto kern = with_cp<nl>(c, [&](auto cp) { return kc_flagged_to_table_kernel<nl, cp>; });
+      hipLaunchKernelGGL(kern, dim3((unsigned)std::min<uint64_t>(R, 65536)), dim3(TPB), 0, c->stream, c->gm, c->bb, c->table, c->d_ctrs);
+    });
+    HIPCHK(hipGetLastError());
+  }
+  if (n2) {
+    rc = table_insert_records(c, c->bb.ovf2, n2, 0u);
+    if (rc) return rc;
+  }
+  c->bk_flagged = true;
+  return KC_OK;
+}
+
+// entries of the LDS-counted regions, unfiltered: two passes (size, then write)
+static int bk_dump(kc_ctx *c, uint64_t **dk, uint16_t **dc, uint16_t **de, uint64_t *n_regions) {
+  int rc = bk_build_regions(c);
+  if (rc) return rc;
+  uint64_t cap = 0;
+  *dk = nullptr;
+  *dc = nullptr;
+  *de = nullptr;
+  for (int pass = 0; pass < 2; pass++) {
+    HIPCHK(hipMemsetAsync(c->d_cb + CB_DUMP, 0, 8, c->stream));
+    OutBufs ob;
+    memset(&ob, 0, sizeof(ob));
+    ob.keys = *dk;
+    ob.counts = *dc;
+    ob.exts = *de;
+    ob.cap = cap;
+    ob.cursor = c->d_cb + CB_DUMP;
+    rc = bk_count(c, ob, true);
+    if (rc) return rc;
+    rc = sync_cb(c);
+    if (rc) return rc;
+    if (pass == 0) {
+      cap = c->h_cb[CB_DUMP];
+      if (!cap) break;
+      HIPCHK(hipMalloc((void **)dk, cap * c->nl * 8));
+      HIPCHK(hipMalloc((void **)dc, cap * 2));
+      HIPCHK(hipMalloc((void **)de, cap * 16));
+    }
+  }
+  *n_regions = cap;
+  return bk_move_flagged(c);
+}
+
+// The buffer is full and more reads are coming: count what it holds (the regions' entries with their raw counters,
+// like kc_dump_table), add every counted k-mer to the global table in ONE table operation (not one per occurrence:
+// about a seventh of the operations at the benchmark's depth), and start the buffer again empty.  The table is where
+// the passes meet; kc_finalize then runs one last pass and the table's own finalize.
+static int bk_spill_pass(kc_ctx *c) {
+  uint64_t *dk = nullptr;
+  uint16_t *dc = nullptr, *de = nullptr;
+  uint64_t n = 0;
+  int rc = bk_dump(c, &dk, &dc, &de, &n);  // regions built, entries listed, flagged regions and overflow records to the table
+  if (!rc && n) {
+    rc = ensure_room(c, n);
+    if (!rc) {
+      with_nl(c, [&](auto nl) {
+        KernelTimer kt(c, KT_INSERT_RECORDS);
+        hipLaunchKernelGGL(kc_merge_entries_kernel<nl>, dim3((unsigned)std::min<uint64_t>((n + TPB - 1) / TPB, 256 * 32)), dim3(TPB), 0, c->stream,
+                           dk, dc, de, n, c->table, c->d_ctrs);
+      });
+      if (hipGetLastError() != hipSuccess) rc = KC_ERR_HIP;
+    }
+  }
+  if (hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = KC_ERR_HIP;
+  if (dk) (void)hipFree(dk);
+  if (dc) (void)hipFree(dc);
+  if (de) (void)hipFree(de);
+  if (!rc) rc = bk_empty_level1(c);
+  if (!rc) rc = bk_empty_level2(c);
+  if (rc) return rc;
+  c->bk_spilled = true;
+  return KC_OK;
+}
+
+// The buffer cannot take what comes next on top of the `buffered` records it holds (an upper bound): compact records hand
+// them on to level 2 (bk_light_spill); where that cannot be done -- longer k-mers, no room for level 2 to grow -- they are
+// counted and merged into the global table (bk_spill_pass).  Either way level 1 is empty afterwards.
+static int bk_make_room(kc_ctx *c, uint64_t buffered) {
+  int rc = bk_light_spill(c, buffered);
+  if (rc == KC_ERR_OUT_OF_MEMORY || rc == KC_ERR_UNSUPPORTED_K) rc = bk_spill_pass(c);
+  return rc;
+}
+
 template <int NL>
 static int bk_drain_t(kc_ctx *c) {
   {
@@ -1104,7 +1541,6 @@ static int bk_drain_t(kc_ctx *c) {
 }
 
 // The buffer is full: move everything buffered into the global table and stay on the table path.
-static int bk_spill_pass(kc_ctx *c);
 static int bk_drain_to_table(kc_ctx *c) {
   int rc;
   if (c->l1_dropped) {  // level 2 holds records that level 1 no longer has: count them and merge them into the table first
@@ -1124,21 +1560,14 @@ static int bk_drain_to_table(kc_ctx *c) {
   rc = with_nl(c, [&](auto nl) { return bk_drain_t<nl>(c); });
   if (rc) return rc;
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemsetAsync(c->bb.cnt1, 0, (size_t)c->gm.G * c->gm.P1 * 4, c->stream));
-  HIPCHK(hipMemsetAsync(c->bb.used1, 0, (size_t)c->gm.G * 2 * 4, c->stream));
-  HIPCHK(hipMemsetAsync(c->d_cb, 0, CB_COUNT * 8, c->stream));
-  c->inc_on = false;  // (what instalments of level 2 had taken is still in the level-1 chains, which went to the table whole)
-  c->l2_per_bucket = 0;
+  // (what instalments of level 2 had taken is still in the level-1 chains, which went to the table whole; the bucketed
+  // path is not used again before kc_reset, which empties both levels once more)
+  rc = bk_empty_level1(c);
+  if (!rc) rc = bk_empty_level2(c);
+  if (rc) return rc;
   c->table_mode = true;
   return KC_OK;
 }
-
-static bool bk_active(const kc_ctx *c) { return c->tuning.mode != 1 && !c->table_mode; }
-static int bk_light_spill(kc_ctx *c, uint64_t buffered);
-static int bk_level2_instalment(kc_ctx *c);
-// A shard of several that has started the shard flow owns level-1 buckets, not hash values: the entry points that test
-// ownership per k-mer (kc_submit_*, kc_insert_records) would put records where its level 2 never looks.
-static bool shard_flow_only(const kc_ctx *c) { return c->sh.flow && c->cfg.rank_n > 1; }
 
 // ---- extraction launches -----------------------------------------------------------------------
 // global-table path: extract and insert in one kernel
@@ -1207,8 +1636,7 @@ static int run_extract_device(kc_ctx *c, const uint8_t *bases, const uint8_t *qu
         // 2 stay until the regions are counted, once, at the end.  Nothing is counted twice, nothing merged: a buffer for
         // 30 % of the input costs what one pass costs (scripts/spill_probe.py).  KC_ERR_OUT_OF_MEMORY: no room for level
         // 2 to grow -- then, as for longer k-mers, the counted buffer is merged into the global table.
-        rc = bk_light_spill(c, c->expect_prev - c->expect_base);
-        if (rc == KC_ERR_OUT_OF_MEMORY || rc == KC_ERR_UNSUPPORTED_K) rc = bk_spill_pass(c);
+        rc = bk_make_room(c, c->expect_prev - c->expect_base);
         if (rc) return rc;
         c->expect_base = c->expect_prev;
         over_capacity = false;
@@ -1839,27 +2267,6 @@ extern "C" int kc_extract_partition_seq_block(kc_ctx *c, const char *seqs, uint6
   return bin_end(c, d_records, seg_capacity, h_counts);
 }
 
-// records straight into the global table, growing it as needed
-static int table_insert_records(kc_ctx *c, const uint64_t *d_records, uint64_t n, uint32_t count_inserted) {
-  uint64_t done = 0;
-  while (done < n) {
-    uint64_t m = std::min<uint64_t>(n - done, std::max<uint64_t>(c->capacity / 4, 1u << 18));
-    int rc = ensure_room(c, m);
-    if (rc) return rc;
-    const uint64_t *p = d_records + done * c->nl;
-    {
-      KernelTimer kt(c, KT_INSERT_RECORDS);
-      const unsigned nblk = (unsigned)std::min<uint64_t>((m + TPB - 1) / TPB, 256 * 32);
-      with_nl(c, [&](auto nl) {
-        hipLaunchKernelGGL(kc_insert_records_kernel<nl>, dim3(nblk), dim3(TPB), 0, c->stream, p, m, c->table, c->d_ctrs, count_inserted);
-      });
-    }
-    HIPCHK(hipGetLastError());
-    done += m;
-  }
-  return KC_OK;
-}
-
 extern "C" int kc_insert_records(kc_ctx *c, const uint64_t *d_records, uint64_t n) {
   if (!c || (n && !d_records)) return KC_ERR_INVALID_ARG;
   if (c->finalized || c->bk_level2 || shard_flow_only(c)) return KC_ERR_STATE;
@@ -1879,8 +2286,7 @@ extern "C" int kc_insert_records(kc_ctx *c, const uint64_t *d_records, uint64_t 
     const uint64_t buffered = c->h_ctrs[CTR_EXPECT] - c->expect_base;
     bool fits = buffered + n <= c->bk_capacity;
     if (!fits && buffered && n <= c->bk_capacity) {  // hand what is buffered on to level 2 (compact records), or count it and merge it into the table; go on empty
-      rc = bk_light_spill(c, buffered);
-      if (rc == KC_ERR_OUT_OF_MEMORY || rc == KC_ERR_UNSUPPORTED_K) rc = bk_spill_pass(c);
+      rc = bk_make_room(c, buffered);
       if (rc) return rc;
       c->expect_base = c->h_ctrs[CTR_EXPECT];
       fits = true;
@@ -2393,383 +2799,6 @@ static int table_finalize_append(kc_ctx *c) {
   return KC_OK;
 }
 
-// ---- bucketed path: regions, counting, flagged regions ------------------------------------------
-// The kernels of level 2, no host wait.  inc: an instalment (kc_l2_split_kernel<..., INC>) -- the first one fixes the
-// buckets' parts of the level-2 arena (the buffer's capacity over the fan-out each) and clears the state the
-// instalments carry; inc with c->inc_on already set: the next one.  !inc && c->inc_on never happens (bk_level2_t).
-template <int NL>
-static int bk_level2_launch(kc_ctx *c, bool inc) {
-  // short register form: compact records whose mix fits 32 bits below the level-1 bucket
-  const bool cr = use_cp<NL>(c) && c->gm.k2 - c->gm.la <= 32;
-  const bool fl = shard_flow_only(c);  // only this shard's buckets, their flat sources behind their chains
-  if (inc && fl) return KC_ERR_STATE;
-  auto kern = with_cp<NL>(c, [&](auto cp) {  // (cr implies cp)
-    if (inc) return cr ? kc_l2_split_kernel<NL, cp, cp, false, true> : kc_l2_split_kernel<NL, cp, false, false, true>;
-    if (cr) return fl ? kc_l2_split_kernel<NL, cp, cp, true> : kc_l2_split_kernel<NL, cp, cp, false>;
-    return fl ? kc_l2_split_kernel<NL, cp, false, true> : kc_l2_split_kernel<NL, cp, false, false>;
-  });
-  // six-byte level-1 records have a level 2 of their own (kc_l2_rec6_kernel)
-  const bool r6 = NL == 1 && c->gm.rec6 != 0;
-  auto kern6 = inc ? kc_l2_rec6_kernel<false, true> : (fl ? kc_l2_rec6_kernel<true, false> : kc_l2_rec6_kernel<false, false>);
-  int rc = r6 ? set_dyn_lds(kern6, l2r6_lds_bytes()) : set_dyn_lds(kern, lds_l2<NL>());
-  if (rc) return rc;
-  FlatSrc fs;
-  memset(&fs, 0, sizeof(fs));
-  fs.b_hi = c->gm.P1;
-  if (fl) {
-    fs.cnt = c->sh.d_cnt;
-    fs.at = c->sh.d_at;
-    fs.F = c->sh.F;
-    fs.b_lo = shard_first_bucket((uint32_t)c->cfg.rank_me, c->gm.P1, (uint32_t)c->cfg.rank_n);
-    fs.b_hi = shard_first_bucket((uint32_t)c->cfg.rank_me + 1, c->gm.P1, (uint32_t)c->cfg.rank_n);
-    fs.nbo = fs.b_hi - fs.b_lo;
-  }
-  if (!inc || !c->inc_on) {
-    if (inc && !c->l2_per_bucket) c->l2_per_bucket = (c->bk_capacity + c->gm.P1 - 1) / c->gm.P1;
-    const uint64_t per_bucket = inc ? c->l2_per_bucket : 0;
-    hipLaunchKernelGGL(kc_bucket_prefix_kernel, dim3(1), dim3(WGB), 0, c->stream, c->gm, c->bb, fs, c->d_cb, per_bucket);
-    c->num_gpu_calls++;
-    if (inc) {
-      HIPCHK(hipMemsetAsync(c->bb.cnt2, 0, (size_t)c->gm.P1 * c->gm.P2 * 4, c->stream));
-      HIPCHK(hipMemsetAsync(c->bb.done1, 0, (size_t)c->gm.G * c->gm.P1 * 4, c->stream));
-      HIPCHK(hipMemsetAsync(c->bb.used2, 0, (size_t)c->gm.P1 * 4, c->stream));
-      c->inc_on = true;
-    }
-  }
-  if (fs.b_hi > fs.b_lo) {
-    KernelTimer kt(c, r6 ? KT_L2_REC6 : KT_L2_SPLIT);
-    const dim3 grid(std::min<unsigned>(fs.b_hi - fs.b_lo, (unsigned)c->num_cus));
-    if (r6) hipLaunchKernelGGL(kern6, grid, dim3(WGB), l2r6_lds_bytes(), c->stream, c->gm, c->bb, fs, c->d_cb);
-    else hipLaunchKernelGGL(kern, grid, dim3(WGB), lds_l2<NL>(), c->stream, c->gm, c->bb, fs, c->d_cb);
-  }
-  HIPCHK(hipGetLastError());
-  return KC_OK;
-}
-
-// an instalment of level 2 over what has been buffered since the last one (the host pipe, between two blocks)
-static int bk_level2_instalment(kc_ctx *c) {
-  if (!bk_active(c) || !c->bk_ready || c->bk_level2 || c->sh.flow) return KC_OK;
-  return with_nl(c, [&](auto nl) { return bk_level2_launch<nl>(c, true); });
-}
-
-// Room in the level-2 arena for `need` compact records in all while level 2 runs in instalments: every bucket's part is
-// fixed up front (kc_bucket_prefix_kernel with per_bucket), so more records than planned mean a larger arena and, once
-// instalments have begun, the parts moved into it (kc_l2_grow_kernel).  KC_ERR_OUT_OF_MEMORY when the device has no room.
-static int bk_l2_reserve(kc_ctx *c, uint64_t need) {
-  const Geom &g = c->gm;
-  const uint64_t CH2 = 1ULL << g.log2CH2;
-  const uint64_t pb_need = (uint64_t)((double)need * 1.08 / (double)g.P1) + 2 * CH2;  // (buckets differ by a few per cent)
-  const uint64_t pb_now = c->inc_on ? c->l2_per_bucket : (c->bk_capacity + g.P1 - 1) / g.P1;
-  if (pb_need <= pb_now) {
-    if (!c->inc_on) c->l2_per_bucket = pb_now;
-    return KC_OK;
-  }
-  const uint64_t pb = c->inc_on ? std::max<uint64_t>(2 * pb_now, pb_need) : pb_need;
-  const uint64_t a2 = (uint64_t)g.P1 * ((pb + CH2 - 1) / CH2 + g.P2) + 16;
-  if (a2 >= (1ULL << 32)) return KC_ERR_OUT_OF_MEMORY;
-  uint64_t *bigger = nullptr;
-  const size_t bytes = (size_t)a2 * CH2 * 4;
-  size_t free_b = 0, total_b = 0;
-  if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b < bytes + ((size_t)4 << 30) || hipMalloc((void **)&bigger, bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    return KC_ERR_OUT_OF_MEMORY;
-  }
-  if (c->inc_on) {
-    uint32_t *nb = nullptr;
-    if (hipMalloc((void **)&nb, ((size_t)g.P1 + 1) * 4) != hipSuccess) {
-      (void)hipGetLastError();
-      (void)hipFree(bigger);
-      return KC_ERR_OUT_OF_MEMORY;
-    }
-    BucketBufs tmp = c->bb;
-    tmp.base2 = nb;
-    FlatSrc fs;
-    memset(&fs, 0, sizeof(fs));
-    hipLaunchKernelGGL(kc_bucket_prefix_kernel, dim3(1), dim3(WGB), 0, c->stream, c->gm, tmp, fs, c->d_cb, pb);
-    hipLaunchKernelGGL(kc_l2_grow_kernel, dim3(g.P1), dim3(WGB), 0, c->stream, c->gm, reinterpret_cast<const uint32_t *>(c->bb.rec2),
-                       reinterpret_cast<uint32_t *>(bigger), c->bb.base2, nb, c->bb.used2, c->bb.chain2, c->bb.cnt2);
-    c->num_gpu_calls += 2;
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(c->bb.base2, nb, ((size_t)g.P1 + 1) * 4, hipMemcpyDeviceToDevice, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(nb);
-    if (e != hipSuccess) {
-      (void)hipFree(bigger);
-      return hip_fail(e, "bk_l2_reserve", __LINE__);
-    }
-  }
-  HIPCHK(hipFree(c->bb.rec2));
-  c->bk_bytes += bytes - c->bk_held[4];
-  c->bb.rec2 = bigger;
-  c->bk_held[4] = bytes;
-  c->gm.A2 = (uint32_t)a2;
-  c->l2_per_bucket = pb;
-  return KC_OK;
-}
-
-// An instalment of level 2 behind which level 1 is emptied (bk_light_spill), and the last pass of a context that has done
-// that, cannot be answered by "run the whole pass again" when the region overflow list fills up: level 1 no longer holds
-// every record.  So level 2's state -- the regions' lengths, the buckets' arena marks, how far every level-1 chain has been
-// read, the list's length -- is saved before such a launch (a few MB), and when the launch reports a full list the state
-// is put back, the list grown to what the launch asked for, and the same launch repeated.
-static int l2_snapshot(kc_ctx *c) {
-  const Geom &g = c->gm;
-  const size_t b_cnt2 = (size_t)g.P1 * g.P2 * 4, b_used2 = (size_t)g.P1 * 4, b_done1 = (size_t)g.G * g.P1 * 4, need = b_cnt2 + b_used2 + b_done1 + 8;
-  c->l2snap_fresh = !c->inc_on;
-  if (c->l2snap_fresh) return KC_OK;  // nothing to save: the launch itself starts level 2 from zero
-  if (c->l2snap_bytes < need) {
-    if (c->d_l2snap) HIPCHK(hipFree(c->d_l2snap));
-    c->d_l2snap = nullptr;
-    c->l2snap_bytes = 0;
-    HIPCHK(hipMalloc((void **)&c->d_l2snap, need));
-    c->l2snap_bytes = need;
-  }
-  HIPCHK(hipMemcpyAsync(c->d_l2snap, c->bb.cnt2, b_cnt2, hipMemcpyDeviceToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(c->d_l2snap + b_cnt2, c->bb.used2, b_used2, hipMemcpyDeviceToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(c->d_l2snap + b_cnt2 + b_used2, c->bb.done1, b_done1, hipMemcpyDeviceToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(c->d_l2snap + b_cnt2 + b_used2 + b_done1, c->d_cb + CB_OVF2, 8, hipMemcpyDeviceToDevice, c->stream));
-  return KC_OK;
-}
-// back to the snapshot with a list of at least `need` records (its entries from before the launch kept)
-static int l2_restore_and_grow(kc_ctx *c, uint64_t need, uint64_t kept) {
-  const Geom &g = c->gm;
-  const size_t b_cnt2 = (size_t)g.P1 * g.P2 * 4, b_used2 = (size_t)g.P1 * 4, b_done1 = (size_t)g.G * g.P1 * 4;
-  if (need > c->bb.ovf2_cap) {
-    uint64_t *bigger = nullptr;
-    if (hipMalloc((void **)&bigger, need * (size_t)c->nl * 8) != hipSuccess) {
-      (void)hipGetLastError();
-      snprintf(g_last_error, sizeof(g_last_error), "no memory for a region overflow list of %llu records", (unsigned long long)need);
-      return KC_ERR_OUT_OF_MEMORY;
-    }
-    if (kept) HIPCHK(hipMemcpyAsync(bigger, c->bb.ovf2, kept * (size_t)c->nl * 8, hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    HIPCHK(hipFree(c->bb.ovf2));
-    c->bk_bytes += (need - c->bb.ovf2_cap) * (size_t)c->nl * 8;
-    c->bb.ovf2 = bigger;
-    c->bb.ovf2_cap = need;
-    c->bk_held[10] = need * (size_t)c->nl * 8;
-  }
-  if (c->l2snap_fresh) {
-    c->inc_on = false;  // the launch starts level 2 from zero again
-    HIPCHK(hipMemsetAsync(c->d_cb + CB_OVF2, 0, 2 * 8, c->stream));  // OVF2, FATAL (nothing was on the list before level 2 began)
-  } else {
-    HIPCHK(hipMemcpyAsync(c->bb.cnt2, c->d_l2snap, b_cnt2, hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->bb.used2, c->d_l2snap + b_cnt2, b_used2, hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->bb.done1, c->d_l2snap + b_cnt2 + b_used2, b_done1, hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->d_cb + CB_OVF2, c->d_l2snap + b_cnt2 + b_used2 + b_done1, 8, hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(hipMemsetAsync(c->d_cb + CB_FATAL, 0, 8, c->stream));
-  }
-  return KC_OK;
-}
-
-// The buffer is full and more reads are coming (compact records): level 1's records go through level 2 now, level 1
-// starts again empty, level 2 keeps what it has until the regions are counted.  buffered: records level 1 holds (an upper
-// bound).  KC_ERR_UNSUPPORTED_K: not a geometry this works for (the caller takes the other way).
-static int bk_light_spill(kc_ctx *c, uint64_t buffered) {
-  if (!c->gm.cp || c->nl != 1 || !bk_active(c) || !c->bk_ready || c->bk_level2 || c->sh.flow) return KC_ERR_UNSUPPORTED_K;
-  const char *e = getenv("KC_LIGHT_SPILL");
-  if (e && e[0] == '0') return KC_ERR_UNSUPPORTED_K;  // (A/B runs: the counted buffer merged into the global table, as for longer k-mers)
-  int rc = sync_cb(c);
-  if (rc) return rc;
-  if (c->h_cb[CB_FATAL]) {
-    snprintf(g_last_error, sizeof(g_last_error), "k-mer buffer: records were lost (fatal bits %llu)", (unsigned long long)c->h_cb[CB_FATAL]);
-    return KC_ERR_CAPACITY;
-  }
-  rc = bk_l2_reserve(c, c->l2_held + buffered);
-  if (rc) return rc;
-  // the region overflow list takes what this instalment's heavy regions spill: at least half of it free, or it grows
-  const uint64_t used2 = std::min<uint64_t>(c->h_cb[CB_OVF2], c->bb.ovf2_cap);
-  if (used2 * 2 > c->bb.ovf2_cap) {
-    const uint64_t cap = 2 * c->bb.ovf2_cap;
-    uint64_t *bigger = nullptr;
-    if (hipMalloc((void **)&bigger, cap * 8) != hipSuccess) {
-      (void)hipGetLastError();
-      return KC_ERR_OUT_OF_MEMORY;
-    }
-    HIPCHK(hipMemcpyAsync(bigger, c->bb.ovf2, used2 * 8, hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    HIPCHK(hipFree(c->bb.ovf2));
-    c->bk_bytes += (cap - c->bb.ovf2_cap) * 8;
-    c->bb.ovf2 = bigger;
-    c->bb.ovf2_cap = cap;
-    c->bk_held[10] = cap * 8;
-  }
-  const uint64_t listed = std::min<uint64_t>(c->h_cb[CB_OVF2], c->bb.ovf2_cap);  // on the list before this instalment
-  rc = l2_snapshot(c);
-  if (rc) return rc;
-  for (int attempt = 0;; attempt++) {
-    rc = bk_level2_launch<1>(c, true);
-    if (rc) return rc;
-    rc = sync_cb(c);
-    if (rc) return rc;
-    const uint64_t fatal = c->h_cb[CB_FATAL];
-    if (!fatal) break;
-    if (fatal != FATAL_OVF2 || attempt > 0) {
-      snprintf(g_last_error, sizeof(g_last_error), "k-mer buffer: records were lost in an instalment of level 2 (fatal bits %llu)", (unsigned long long)fatal);
-      return KC_ERR_CAPACITY;
-    }
-    // the list was too small for what this instalment's heavy regions spill: the counter kept counting past its end
-    rc = l2_restore_and_grow(c, c->h_cb[CB_OVF2] + c->h_cb[CB_OVF2] / 16 + 4096, c->l2snap_fresh ? 0 : listed);
-    if (rc) return rc;
-  }
-  // what found no room at level 1 joins the flagged regions' list (as bk_level2_t does at the end of a pass)
-  const uint64_t n1 = std::min<uint64_t>(c->h_cb[CB_OVF1], c->bb.ovf1_cap);
-  if (n1) {
-    hipLaunchKernelGGL((kc_ovf1_to_regions_kernel<1, true>), dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, c->stream, c->gm, c->bb, n1, c->d_cb);
-    c->num_gpu_calls++;
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemsetAsync(c->d_cb + CB_OVF1, 0, 8, c->stream));
-  }
-  // level 1 starts again: every chain empty, every writer's arena whole
-  HIPCHK(hipMemsetAsync(c->bb.cnt1, 0, (size_t)c->gm.G * c->gm.P1 * 4, c->stream));
-  HIPCHK(hipMemsetAsync(c->bb.done1, 0, (size_t)c->gm.G * c->gm.P1 * 4, c->stream));
-  HIPCHK(hipMemsetAsync(c->bb.used1, 0, (size_t)c->gm.G * 2 * 4, c->stream));
-  c->ovf1_ub = 0;
-  c->l2_held += buffered;
-  c->l1_dropped = true;
-  return KC_OK;
-}
-
-template <int NL>
-static int bk_level2_t(kc_ctx *c) {
-  int rc = bk_level2_launch<NL>(c, c->inc_on);  // (after instalments: one more, over the rest)
-  if (rc) return rc;
-  HIPCHK(hipGetLastError());
-  rc = sync_cb(c);
-  if (rc) return rc;
-#ifdef KC_STAMPS
-  fprintf(stderr, "l2 kernel cycles (thread 0, summed over workgroups): hist %llu barrierA %llu scan+reserve %llu scatter %llu copyout %llu take-over+loads %llu\n",
-          (unsigned long long)c->h_cb[8], (unsigned long long)c->h_cb[9], (unsigned long long)c->h_cb[10],
-          (unsigned long long)c->h_cb[11], (unsigned long long)c->h_cb[12], (unsigned long long)c->h_cb[13]);
-  HIPCHK(hipMemsetAsync(c->d_cb + 8, 0, 8 * 8, c->stream));
-#endif
-  const uint64_t n1 = std::min<uint64_t>(c->h_cb[CB_OVF1], c->bb.ovf1_cap);
-  if (n1) {
-    auto okern = with_cp<NL>(c, [](auto cp) { return kc_ovf1_to_regions_kernel<NL, cp>; });
-    hipLaunchKernelGGL(okern, dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, c->stream, c->gm, c->bb, n1, c->d_cb);
-    c->num_gpu_calls++;
-    HIPCHK(hipGetLastError());
-  }
-  return KC_OK;
-}
-
-// build the regions from everything buffered (once per reset)
-static int bk_build_regions(kc_ctx *c) {
-  if (c->bk_level2) return KC_OK;
-  int rc = sync_cb(c);
-  if (rc) return rc;
-  // (an instalment of level 2 may have filled the second overflow list already: the loop below deals with that)
-  if (c->h_cb[CB_FATAL] & ~(c->inc_on ? (uint64_t)FATAL_OVF2 : 0ULL)) {
-    snprintf(g_last_error, sizeof(g_last_error), "k-mer buffer: records were lost at level 1 (fatal bits %llu)", (unsigned long long)c->h_cb[CB_FATAL]);
-    return KC_ERR_CAPACITY;
-  }
-#ifdef KC_STAMPS
-  (void)sync_cb(c);
-  fprintf(stderr, "l1 kernel cycles (thread 0, summed over workgroups): extract+hist %llu barrierA %llu scan+reserve %llu scatter %llu copyout %llu stage %llu\n",
-          (unsigned long long)c->h_cb[8], (unsigned long long)c->h_cb[9], (unsigned long long)c->h_cb[10],
-          (unsigned long long)c->h_cb[11], (unsigned long long)c->h_cb[12], (unsigned long long)c->h_cb[13]);
-  (void)sync_ctrs(c);
-  fprintf(stderr, "   encode: first barrier %llu groups %llu offsets %llu last barrier %llu\n", (unsigned long long)c->h_ctrs[CTR_BIN0 + 40],
-          (unsigned long long)c->h_ctrs[CTR_BIN0 + 41], (unsigned long long)c->h_ctrs[CTR_BIN0 + 42], (unsigned long long)c->h_ctrs[CTR_BIN0 + 43]);
-  HIPCHK(hipMemsetAsync(c->d_cb + 8, 0, 8 * 8, c->stream));
-#endif
-  uint64_t listed = 0;
-  if (c->l1_dropped) {  // (the last pass of a context whose level 1 has been emptied behind earlier instalments)
-    listed = std::min<uint64_t>(c->h_cb[CB_OVF2], c->bb.ovf2_cap);
-    rc = l2_snapshot(c);
-    if (rc) return rc;
-  }
-  for (int attempt = 0;; attempt++) {
-    rc = with_nl(c, [&](auto nl) { return bk_level2_t<nl>(c); });
-    if (rc) return rc;
-    rc = sync_cb(c);
-    if (rc) return rc;
-    const uint64_t fatal = c->h_cb[CB_FATAL];
-    if (!fatal) break;
-    if (fatal != FATAL_OVF2 || attempt > 0) {
-      snprintf(g_last_error, sizeof(g_last_error), "k-mer buffer: records were lost building the regions (fatal bits %llu)", (unsigned long long)fatal);
-      return KC_ERR_CAPACITY;
-    }
-    if (c->l1_dropped) {  // level 1 no longer holds every record: back to where this pass began, with a larger list
-      rc = l2_restore_and_grow(c, c->h_cb[CB_OVF2] + c->h_cb[CB_OVF2] / 16 + 4096, c->l2snap_fresh ? 0 : listed);
-      if (rc) return rc;
-      continue;
-    }
-    // The second overflow list was too small for the regions that outgrew their chains (heavy hitters).  Level 1 is
-    // untouched and the counter kept counting past the end, so it says exactly how much room the same pass needs.
-    // (After instalments the pass is run whole: the level-1 chains still hold every record.)
-    c->inc_on = false;
-  c->l2_per_bucket = 0;
-    const uint64_t need = c->h_cb[CB_OVF2] + c->h_cb[CB_OVF2] / 64 + 4096;
-    uint64_t *bigger = nullptr;
-    HIPCHK(hipMalloc((void **)&bigger, need * (size_t)c->nl * 8));
-    HIPCHK(hipFree(c->bb.ovf2));
-    c->bk_bytes += (need - c->bb.ovf2_cap) * (size_t)c->nl * 8;
-    c->bb.ovf2 = bigger;
-    c->bb.ovf2_cap = need;
-    c->bk_held[10] = need * (size_t)c->nl * 8;
-    HIPCHK(hipMemsetAsync(c->d_cb + CB_OVF2, 0, 2 * 8, c->stream));  // OVF2, FATAL
-  }
-  c->bk_level2 = true;
-  return KC_OK;
-}
-
-template <int NL, bool DUMP>
-static int bk_count_t(kc_ctx *c, const OutBufs &ob) {
-  auto kern = with_cp<NL>(c, [](auto cp) { return kc_count_kernel<NL, DUMP, cp>; });
-  const size_t lds = CountLDS<NL>::bytes(c->gm.S, use_cp<NL>(c));
-  int rc = set_dyn_lds(kern, lds);
-  if (rc) return rc;
-  const uint64_t R = (uint64_t)c->gm.P1 * c->gm.P2;
-  // as many workgroups per CU as the LDS admits (at most 2: 1024 threads each), so that one region's barriers
-  // and scans overlap another's inserts
-  const unsigned per_cu = lds * 2 <= 160 * 1024 ? 2u : 1u;
-  KernelTimer kt(c, KT_COUNT_REGIONS);
-  hipLaunchKernelGGL(kern, dim3((unsigned)std::min<uint64_t>(R, (uint64_t)c->num_cus * per_cu)), dim3(WGB), lds, c->stream, c->gm, c->bb,
-                     ob, c->cfg.dmin_thres, c->d_ctrs, c->d_cb);
-  return KC_OK;
-}
-
-static int bk_count(kc_ctx *c, const OutBufs &ob, bool dump) {
-  int rc = with_nl(c, [&](auto nl) { return dump ? bk_count_t<nl, true>(c, ob) : bk_count_t<nl, false>(c, ob); });
-  if (rc) return rc;
-  HIPCHK(hipGetLastError());
-  return KC_OK;
-}
-
-// after a count pass: regions that did not fit, and the overflow records, go to the global table (once)
-static int bk_move_flagged(kc_ctx *c) {
-  if (c->bk_flagged) return KC_OK;
-  const uint64_t R = (uint64_t)c->gm.P1 * c->gm.P2;
-  HIPCHK(hipMemsetAsync(c->d_cb + CB_FLAGGED_RECS, 0, 8, c->stream));
-  hipLaunchKernelGGL(kc_sum_flagged_kernel, dim3((unsigned)std::min<uint64_t>((R + 255) / 256, 1024)), dim3(256), 0, c->stream, c->gm, c->bb,
-                     c->d_cb);
-  c->num_gpu_calls++;
-  int rc = sync_cb(c);
-  if (rc) return rc;
-  if (c->h_cb[CB_FATAL]) {
-    snprintf(g_last_error, sizeof(g_last_error), "region overflow list exhausted: raise max_kmers_buffered");
-    return KC_ERR_CAPACITY;
-  }
-  const uint64_t nflag = c->h_cb[CB_FLAGGED_RECS], n2 = std::min<uint64_t>(c->h_cb[CB_OVF2], c->bb.ovf2_cap);
-  if (nflag) {
-    rc = ensure_room(c, nflag + n2);
-    if (rc) return rc;
-    with_nl(c, [&](auto nl) {
-      KernelTimer kt(c, KT_FALLBACK);
-      auto kern = with_cp<nl>(c, [&](auto cp) { return kc_flagged_to_table_kernel<nl, cp>; });
-      hipLaunchKernelGGL(kern, dim3((unsigned)std::min<uint64_t>(R, 65536)), dim3(TPB), 0, c->stream, c->gm, c->bb, c->table, c->d_ctrs);
-    });
-    HIPCHK(hipGetLastError());
-  }
-  if (n2) {
-    rc = table_insert_records(c, c->bb.ovf2, n2, 0u);
-    if (rc) return rc;
-  }
-  c->bk_flagged = true;
-  return KC_OK;
-}
-
 static int bk_finalize(kc_ctx *c) {
   int rc = bk_build_regions(c);
   if (rc) return rc;
@@ -2951,79 +2980,6 @@ extern "C" int kc_copy_results_entries(kc_ctx *c, uint64_t *keys, kc_count_exts 
     (void)hipFree(d_vals);
     if (e != hipSuccess) return hip_fail(e, "kc_copy_results_entries", __LINE__);
   }
-  return KC_OK;
-}
-
-// entries of the LDS-counted regions, unfiltered: two passes (size, then write)
-static int bk_dump(kc_ctx *c, uint64_t **dk, uint16_t **dc, uint16_t **de, uint64_t *n_regions) {
-  int rc = bk_build_regions(c);
-  if (rc) return rc;
-  uint64_t cap = 0;
-  *dk = nullptr;
-  *dc = nullptr;
-  *de = nullptr;
-  for (int pass = 0; pass < 2; pass++) {
-    HIPCHK(hipMemsetAsync(c->d_cb + CB_DUMP, 0, 8, c->stream));
-    OutBufs ob;
-    memset(&ob, 0, sizeof(ob));
-    ob.keys = *dk;
-    ob.counts = *dc;
-    ob.exts = *de;
-    ob.cap = cap;
-    ob.cursor = c->d_cb + CB_DUMP;
-    rc = bk_count(c, ob, true);
-    if (rc) return rc;
-    rc = sync_cb(c);
-    if (rc) return rc;
-    if (pass == 0) {
-      cap = c->h_cb[CB_DUMP];
-      if (!cap) break;
-      HIPCHK(hipMalloc((void **)dk, cap * c->nl * 8));
-      HIPCHK(hipMalloc((void **)dc, cap * 2));
-      HIPCHK(hipMalloc((void **)de, cap * 16));
-    }
-  }
-  *n_regions = cap;
-  return bk_move_flagged(c);
-}
-
-// The buffer is full and more reads are coming: count what it holds (the regions' entries with their raw counters,
-// like kc_dump_table), add every counted k-mer to the global table in ONE table operation (not one per occurrence:
-// about a seventh of the operations at the benchmark's depth), and start the buffer again empty.  The table is where
-// the passes meet; kc_finalize then runs one last pass and the table's own finalize.
-static int bk_spill_pass(kc_ctx *c) {
-  uint64_t *dk = nullptr;
-  uint16_t *dc = nullptr, *de = nullptr;
-  uint64_t n = 0;
-  int rc = bk_dump(c, &dk, &dc, &de, &n);  // regions built, entries listed, flagged regions and overflow records to the table
-  if (!rc && n) {
-    rc = ensure_room(c, n);
-    if (!rc) {
-      with_nl(c, [&](auto nl) {
-        KernelTimer kt(c, KT_INSERT_RECORDS);
-        hipLaunchKernelGGL(kc_merge_entries_kernel<nl>, dim3((unsigned)std::min<uint64_t>((n + TPB - 1) / TPB, 256 * 32)), dim3(TPB), 0, c->stream,
-                           dk, dc, de, n, c->table, c->d_ctrs);
-      });
-      if (hipGetLastError() != hipSuccess) rc = KC_ERR_HIP;
-    }
-  }
-  if (hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = KC_ERR_HIP;
-  if (dk) (void)hipFree(dk);
-  if (dc) (void)hipFree(dc);
-  if (de) (void)hipFree(de);
-  if (rc) return rc;
-  const size_t R = (size_t)c->gm.P1 * c->gm.P2;
-  HIPCHK(hipMemsetAsync(c->bb.cnt1, 0, (size_t)c->gm.G * c->gm.P1 * 4, c->stream));
-  HIPCHK(hipMemsetAsync(c->bb.used1, 0, (size_t)c->gm.G * 2 * 4, c->stream));
-  HIPCHK(hipMemsetAsync(c->bb.cnt2, 0, R * 4, c->stream));
-  HIPCHK(hipMemsetAsync(c->bb.flag, 0, R * 4, c->stream));
-  HIPCHK(hipMemsetAsync(c->d_cb, 0, CB_COUNT * 8, c->stream));
-  c->bk_level2 = c->bk_flagged = false;
-  c->inc_on = false;
-  c->l2_per_bucket = 0;
-  c->l1_dropped = false;
-  c->l2_held = 0;
-  c->bk_spilled = true;
   return KC_OK;
 }
 
