@@ -280,6 +280,59 @@ struct ChainState {
   uint32_t last;  // id of its last chunk (valid when cur is not chunk-aligned)
 };
 
+// Thread tid reserves room for the v records destination tid has in this round, at the end of its chain; the run starts at
+// position `excl` of the round's order.  x, y as in SplitLDS::dst; fit: how many found room; w: how many of those still go
+// into the old last chunk.
+struct RunPlace {
+  uint32_t x, y, fit, w;
+};
+__device__ __forceinline__ RunPlace split_reserve(SplitLDS &L, uint32_t tid, uint32_t v, uint32_t excl, const ChainDest &D, ChainState &st) {
+  const uint32_t CHm = (1u << D.log2CH) - 1u;
+  const uint32_t base = st.cur;
+  uint32_t fit = v;
+  const uint64_t room = ((uint64_t)D.LMAX << D.log2CH) - base;  // the chain holds at most LMAX chunks
+  if ((uint64_t)fit > room) fit = (uint32_t)room;
+  const uint32_t have = (base + CHm) >> D.log2CH;
+  uint32_t k = ((base + fit + CHm) >> D.log2CH) - have, a = 0;
+  if (k) {
+    const bool own = tid >= D.own_lo && tid < D.own_hi;
+    if (own) {
+      a = atomicAdd(&L.arena_used, k);
+      const uint32_t left = D.arena_cap - min(D.arena_cap, L.arena_top);  // (the top only moves between launches of a shard's blocks)
+      if (a + k > left) {  // arena exhausted: use what is left of it, the rest overflows
+        k = a < left ? left - a : 0;
+        const uint64_t cap = ((uint64_t)(have + k) << D.log2CH) - base;
+        if ((uint64_t)fit > cap) fit = (uint32_t)cap;
+      }
+    } else {
+      // k consecutive chunks below what the top has taken so far; the bottom is whatever the launch started with
+      // plus what it takes meanwhile: the two ends may only meet in a launch that is about to overflow anyway, and
+      // then both sides stop at the other's starting point of this launch
+      const uint32_t t = atomicAdd(&L.arena_top, k);
+      const uint32_t left = D.arena_cap - min(D.arena_cap, L.arena_used);
+      if (t + k > left) {
+        k = 0;
+        const uint64_t cap = ((uint64_t)have << D.log2CH) - base;
+        if ((uint64_t)fit > cap) fit = (uint32_t)cap;
+      } else {
+        a = D.arena_cap - t - k;
+      }
+    }
+    uint32_t *ch = D.chain + (size_t)tid * D.LMAX + have;
+    for (uint32_t i = 0; i < k; i++) ch[i] = D.arena_base + a + i;
+  }
+  // element j of the run sits at chain position base + j: in the old last chunk (id st.last) while that has room,
+  // then in the new chunks a, a+1, ... whose first one holds chain positions have << log2CH onwards
+  RunPlace q;
+  q.x = ((st.last - D.arena_base - (base >> D.log2CH)) << D.log2CH) + base - excl;
+  q.y = ((a - have) << D.log2CH) + base - excl;
+  q.fit = fit;
+  q.w = (base & CHm) ? min(fit, (CHm + 1u) - (base & CHm)) : 0u;
+  if (k) st.last = D.arena_base + a + k - 1;
+  st.cur = base + fit;
+  return q;
+}
+
 // A round has two halves.  split_stage: scan, reserve, scatter to LDS; the caller has already bumped hist[buf] with LDS
 // atomics (bucket | rank<<10 in br[], ~0 for "no record") and hit a barrier; returns the number of staged records.
 // split_copy_out: the staged records go to HBM.
@@ -302,51 +355,9 @@ __device__ __forceinline__ uint32_t split_stage(SplitLDS &L, uint64_t *sorted, u
   KC_SPLIT_STAMP(1)  // barrier after the histogram
   const uint32_t v = ((uint32_t)tid < P) ? L.hist[buf][tid] : 0u;
   const uint32_t excl = block_excl_scan(v, L.scan);
-  const uint32_t CHm = (1u << D.log2CH) - 1u;
   if ((uint32_t)tid < P) {
-    const uint32_t base = st.cur;
-    uint32_t fit = v;
-    const uint64_t room = ((uint64_t)D.LMAX << D.log2CH) - base;  // the chain holds at most LMAX chunks
-    if ((uint64_t)fit > room) fit = (uint32_t)room;
-    const uint32_t have = (base + CHm) >> D.log2CH;
-    uint32_t k = ((base + fit + CHm) >> D.log2CH) - have, a = 0;
-    if (k) {
-      const bool own = (uint32_t)tid >= D.own_lo && (uint32_t)tid < D.own_hi;
-      if (own) {
-        a = atomicAdd(&L.arena_used, k);
-        const uint32_t left = D.arena_cap - min(D.arena_cap, L.arena_top);  // (the top only moves between launches of a shard's blocks)
-        if (a + k > left) {  // arena exhausted: use what is left of it, the rest overflows
-          k = a < left ? left - a : 0;
-          const uint64_t cap = ((uint64_t)(have + k) << D.log2CH) - base;
-          if ((uint64_t)fit > cap) fit = (uint32_t)cap;
-        }
-      } else {
-        // k consecutive chunks below what the top has taken so far; the bottom is whatever the launch started with
-        // plus what it takes meanwhile: the two ends may only meet in a launch that is about to overflow anyway, and
-        // then both sides stop at the other's starting point of this launch
-        const uint32_t t = atomicAdd(&L.arena_top, k);
-        const uint32_t left = D.arena_cap - min(D.arena_cap, L.arena_used);
-        if (t + k > left) {
-          k = 0;
-          const uint64_t cap = ((uint64_t)have << D.log2CH) - base;
-          if ((uint64_t)fit > cap) fit = (uint32_t)cap;
-        } else {
-          a = D.arena_cap - t - k;
-        }
-      }
-      uint32_t *ch = D.chain + (size_t)tid * D.LMAX + have;
-      for (uint32_t i = 0; i < k; i++) ch[i] = D.arena_base + a + i;
-    }
-    // element j of the run sits at chain position base + j: in the old last chunk (id st.last) while that has room,
-    // then in the new chunks a, a+1, ... whose first one holds chain positions have << log2CH onwards
-    uint4 d;
-    d.x = ((st.last - D.arena_base - (base >> D.log2CH)) << D.log2CH) + base - excl;
-    d.y = ((a - have) << D.log2CH) + base - excl;
-    d.z = excl | (fit << 16);
-    d.w = (base & CHm) ? min(fit, (CHm + 1u) - (base & CHm)) : 0u;
-    L.dst[tid] = d;
-    if (k) st.last = D.arena_base + a + k - 1;
-    st.cur = base + fit;
+    const RunPlace q = split_reserve(L, (uint32_t)tid, v, excl, D, st);
+    L.dst[tid] = make_uint4(q.x, q.y, excl | (q.fit << 16), q.w);
     // the scatter takes a run's start from the histogram's word, which has served its purpose: a dense array of words
     // spreads over all the banks, the .z of 16-byte entries over a quarter of them
     L.hist[buf][tid] = excl;
@@ -1559,16 +1570,29 @@ __global__ __launch_bounds__(WGB) void kc_l2_split_kernel(Geom gm, BucketBufs bb
 }
 
 // ---- level 2 over six-byte level-1 records (Geom::rec6) -----------------------------------------------------------------
-// The walk, the rounds, the staging and the copy-out of kc_l2_split_kernel<1, true, true, ...>; what differs is how a round's
-// records arrive.  A thread takes them two at a time: a bucket's segments (its G chains, then its flat sources) are laid
+// The walk and the split of kc_l2_split_kernel<1, true, true, ...>; what differs is how the records arrive and how a round
+// is staged.  A thread takes them two at a time: a bucket's segments (its G chains, then its flat sources) are laid
 // end to end with every segment starting at an EVEN in-chain index and padded to an even length, so that a pair of slots
 // never straddles two segments or two chunks and a pair of a chain is ONE aligned 12-byte load (a third more records per
 // second than 8-byte records one per lane, scripts/ubench_rec6.hip); a slot that holds no record of this pass -- the pad
 // behind an odd segment; with instalments the record in front of an odd start, which an earlier instalment took -- is a
 // bit in the thread's mask.  A pair of a flat source is the 10 bytes of two wire records (kc_shard.hpp) in one unaligned
 // 12-byte load.
+//
+// A round is 32 records per thread, taken in two halves of sixteen, so that a region's run of a round is ~128 bytes
+// (two lines of HBM) instead of two runs of ~64 bytes that start anywhere (1.43 lines each), and a thread never holds
+// more than one half:
+//   half A: rank into the round's histogram, scan it, scatter A sorted by region into the front of the staging;
+//   half B: rank into the SAME histogram (its ranks go on behind A's), scan, reserve the whole round, scatter B sorted by
+//           region behind A;
+//   copy-out in region order: output position o of region b (run start S_b, rank j = o - S_b) is staged at start1_b + j
+//           in A while j < c1_b, at total1 + (o - start1_b - c1_b) in B after that.
+// The staging holds only the 32-bit word level 2 writes (cp_pack32): where it goes follows from its position.  Wave w
+// copies out the runs of its own 64 regions, [S_64w, S_64w+64) (of P2 / 16 regions with fewer than 1024): lane l holds
+// S_64w+l, and the region of a position is found with two ballots and a scalar walk over the run starts that fall inside
+// the wave's window.
 struct L2R6LDS {
-  SplitLDS sp;
+  SplitLDS sp;             // sp.dst[b] = {x, y, fit | w << 16, c1 | start1 << 16} (x, y, fit, w: split_reserve)
   uint32_t pre[GMAX + 1];  // prefix of the segments' padded lengths, in slots
   uint32_t end[GMAX];      // a segment's true end: records in the chain (in the flat source)
   union {
@@ -1576,8 +1600,11 @@ struct L2R6LDS {
     uint32_t skip[GMAX];     // INC: records at the head of each chain that an earlier instalment has taken
   };
 };
-constexpr size_t l2r6_lds_bytes() { return ((sizeof(L2R6LDS) + 15) & ~size_t(15)) + Rnd<1>::STAGE; }
+constexpr int L2R6_RPOS = 16;                            // records a thread holds: one half-round
+constexpr uint32_t L2R6_ROUND = 2u * WGB * L2R6_RPOS;    // records of a round, staged at once (+ a slot per lane for the non-records)
+constexpr size_t l2r6_lds_bytes() { return ((sizeof(L2R6LDS) + 15) & ~size_t(15)) + ((size_t)L2R6_ROUND + 64) * 4; }
 static_assert(l2r6_lds_bytes() <= 160 * 1024, "level 2's working set fits the LDS");
+static_assert(L2R6_ROUND <= 32768, "run starts, counts and the ranks of a round fit 16 bits");
 struct __attribute__((packed, aligned(2))) Load12 {
   uint32_t a, b, c;
 };
@@ -1587,8 +1614,8 @@ __global__ __launch_bounds__(WGB) void kc_l2_rec6_kernel(Geom gm, BucketBufs bb,
   static_assert(!(INC && FL), "instalments are for a context that is not in the shard flow");
   extern __shared__ __align__(16) uint8_t smem[];
   L2R6LDS &L = *reinterpret_cast<L2R6LDS *>(smem);
-  uint64_t *sorted = reinterpret_cast<uint64_t *>(smem + ((sizeof(L2R6LDS) + 15) & ~size_t(15)));
-  constexpr int RPOS = 16, NPAIR = 8;
+  uint32_t *staged = reinterpret_cast<uint32_t *>(smem + ((sizeof(L2R6LDS) + 15) & ~size_t(15)));
+  constexpr int RPOS = L2R6_RPOS, NPAIR = RPOS / 2;
   const int tid = threadIdx.x;
   const uint32_t P1 = gm.P1, P2 = gm.P2, G = gm.G;
   const uint32_t GT = FL ? G + fs.F : G;  // segments of a bucket
@@ -1625,8 +1652,10 @@ __global__ __launch_bounds__(WGB) void kc_l2_rec6_kernel(Geom gm, BucketBufs bb,
     D.chain = bb.chain2 + (size_t)b1 * P2 * gm.L2MAX;
     D.log2CH = gm.log2CH2;
     D.LMAX = gm.L2MAX;
-    D.arena_base = bb.base2[b1];
-    D.arena_cap = bb.base2[b1 + 1] - bb.base2[b1];
+    // (the bucket's arena bounds are one value for the workgroup: in scalar registers, not in two vector registers that
+    // were spilled)
+    D.arena_base = (uint32_t)__builtin_amdgcn_readfirstlane((int)bb.base2[b1]);
+    D.arena_cap = (uint32_t)__builtin_amdgcn_readfirstlane((int)(bb.base2[b1 + 1] - bb.base2[b1]));
     D.own_lo = 0;
     D.own_hi = PMAX;
 #ifdef KC_STAMPS
@@ -1637,16 +1666,18 @@ __global__ __launch_bounds__(WGB) void kc_l2_rec6_kernel(Geom gm, BucketBufs bb,
     ChainState cst = split_load_state(L.sp, P2, INC ? bb.cnt2 + (size_t)b1 * P2 : nullptr, D.chain, D.LMAX, D.log2CH, INC ? bb.used2[b1] : 0u);
     __syncthreads();
     const uint32_t n = L.pre[GT];  // slots of the bucket (even)
-    const uint32_t per_round = WGB * RPOS;
+    const uint32_t half = WGB * RPOS;
     uint32_t p_ids = 0, p_rec = 0;  // segment cursors of this thread, one per pass (their indices only grow)
-    Load12 nxt[NPAIR];
+    uint32_t nxa[NPAIR], nxb[NPAIR], nxc[NPAIR];  // the next half's pairs, a word per array (a Load12 array was kept in scratch)
     uint32_t nxt_valid = 0, nxt_flat = 0;  // bit s: slot s of the thread holds a record; bit j: pair j came from a flat source
     // no branches around the loads (a lane past the end re-reads the bucket's last pair)
-    auto load_round = [&](uint32_t v0) {  // n > 0
+    // (the thread's offsets are recomputed at every call: hoisted out of the loop, sixteen of them were spilled)
+    auto load_half = [&](uint32_t v0) __attribute__((always_inline)) {  // n > 0
+      const uint32_t t = (uint32_t)fresh_tid();
       uint32_t ids[NPAIR];
 #pragma unroll
       for (int j = 0; j < NPAIR; j++) {
-        const uint32_t e = min(v0 + 2u * ((uint32_t)j * WGB + tid), n - 2u);
+        const uint32_t e = min(v0 + 2u * ((uint32_t)j * WGB + t), n - 2u);
         while (e >= L.pre[p_ids + 1]) p_ids++;
         // (a pair of a flat source needs no chunk id: it re-reads the table's first word, no branch)
         const uint32_t i0 = e - L.pre[p_ids] + (INC ? (L.skip[p_ids] & ~1u) : 0u);
@@ -1656,7 +1687,7 @@ __global__ __launch_bounds__(WGB) void kc_l2_rec6_kernel(Geom gm, BucketBufs bb,
       nxt_valid = 0;
 #pragma unroll
       for (int j = 0; j < NPAIR; j++) {
-        const uint32_t ev = v0 + 2u * ((uint32_t)j * WGB + tid), e = min(ev, n - 2u);
+        const uint32_t ev = v0 + 2u * ((uint32_t)j * WGB + t), e = min(ev, n - 2u);
         while (e >= L.pre[p_rec + 1]) p_rec++;
         const bool flat = FL && p_rec >= G;
         const uint32_t first = (INC && !flat) ? L.skip[p_rec] : 0u;
@@ -1670,17 +1701,25 @@ __global__ __launch_bounds__(WGB) void kc_l2_rec6_kernel(Geom gm, BucketBufs bb,
         const bool in = ev < n;
         nxt_valid |= (in && i0 >= first && i0 < end ? 1u : 0u) << (2 * j);
         nxt_valid |= (in && i0 + 1u < end ? 2u : 0u) << (2 * j);  // (i0 + 1 >= first always: first <= i0 + 1)
-        nxt[j] = *reinterpret_cast<const Load12 *>(src);
+        const Load12 w = *reinterpret_cast<const Load12 *>(src);
+        nxa[j] = w.a;
+        nxb[j] = w.b;
+        nxc[j] = w.c;
       }
     };
-    // lo + br: this round's records in the short form; nxt: the next round's, taken over in the middle of the round
+    // the next half-round's records are requested when there are any (else it is taken over as empty)
+    auto request = [&](uint64_t v0) __attribute__((always_inline)) {
+      if (v0 < n) load_half((uint32_t)v0);
+      else nxt_valid = 0;
+    };
+    // lo + br: this half-round's records in the short form; nxt: the next half's, taken over in the middle of the round
     uint32_t lo[RPOS], br[RPOS];
     uint32_t cur_valid = 0;
     const uint32_t sh_b2 = gm.k2 - gm.la - gm.lb;  // where the region's index starts in the mix
-    auto take_over = [&]() {
+    auto take_over = [&]() __attribute__((always_inline)) {
 #pragma unroll
       for (int j = 0; j < NPAIR; j++) {
-        const Load12 w = nxt[j];
+        const Load12 w = {nxa[j], nxb[j], nxc[j]};
         uint32_t e0, e1;
         if (FL && ((nxt_flat >> j) & 1u)) {  // two wire records: 4 + 1 bytes each
           lo[2 * j] = w.a;
@@ -1698,38 +1737,152 @@ __global__ __launch_bounds__(WGB) void kc_l2_rec6_kernel(Geom gm, BucketBufs bb,
       }
       cur_valid = nxt_valid;
     };
-    if (n) load_round(0);
-    take_over();
-    if (per_round < n) load_round(per_round);
-    int buf = 0;
-    for (uint32_t v0 = 0; v0 < n; v0 += per_round) {
+    // br = region | extension codes << 10 | rank in the region's run of the round << 16, or ~0 for a slot without a record
+    auto rank_half = [&](int buf) __attribute__((always_inline)) {
 #pragma unroll
       for (int j = 0; j < RPOS; j++) {
         const bool valid = (cur_valid >> j) & 1u;
         const uint32_t rank = hist_rank(L.sp, buf, br[j] & (PMAX - 1), valid);
         br[j] = valid ? (br[j] | (rank << 16)) : ~0u;
       }
+    };
+    // the half's records to the staging at at[region] + rank (the run starts first, eight at a time, then the writes, as in
+    // split_stage); a slot without a record goes to a word of its lane's behind the round
+    const uint32_t rb_mask = (1u << sh_b2) - 1u;
+    auto scatter_half = [&](const uint32_t *at) __attribute__((always_inline)) {
+#pragma unroll
+      for (int j0 = 0; j0 < RPOS; j0 += 8) {
+        uint32_t pos[8];
+#pragma unroll
+        for (int j = 0; j < 8; j++) pos[j] = at[br[j0 + j] & (PMAX - 1)];
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+          const uint32_t bj = br[j0 + j];
+          const uint32_t p = bj != ~0u ? pos[j] + (bj >> 16) : L2R6_ROUND + lane_id();
+          staged[p] = ((lo[j0 + j] & rb_mask) << 6) | ((bj >> 10) & 63u);
+        }
+      }
+    };
+    uint32_t *const arena32 = reinterpret_cast<uint32_t *>(D.arena);
+    const size_t arena0 = (size_t)D.arena_base << D.log2CH;
+    if (n) load_half(0);
+    take_over();
+    request(half);
+    // One half-round per trip (one load site and one take-over in the loop: the loads' bookkeeping is not kept live
+    // twice).  A round is an A trip and a B trip; a last A trip is always followed by a B trip, empty if need be.
+    int buf = 0;
+    bool second = false;            // this trip is half B
+    uint32_t a1 = 0, total1 = 0;    // from half A: c1 | start1 << 16 of the region of this thread; records of half A
+    for (uint32_t v0 = 0; v0 < n || second; v0 += half) {
+      rank_half(buf);  // (half B: behind A's ranks, in the same histogram)
       KC_SPLIT_STAMP(0)  // histogram
       lds_barrier();
-      const uint32_t total = split_stage<1, RPOS, 16>(
-          L.sp, sorted, nullptr, buf, P2,
-          [&](int j, uint64_t (&o)[1]) {
-            o[0] = ((uint64_t)b1 << (64u - gm.la)) | ((uint64_t)lo[j] << (64u - gm.k2)) | (uint64_t)((br[j] >> 10) & 63u);
-          },
-          br, D, cst);
+      uint32_t S = 0, o_hi = 0;  // half B: where the region's run starts in the round's (region) order; where the wave's runs end
+      {
+        const int tid = fresh_tid();
+        KC_SPLIT_STAMP(1)  // barrier after the histogram
+        const uint32_t c = (uint32_t)tid < P2 ? L.sp.hist[buf][tid] : 0u;
+        const uint32_t e = block_excl_scan(c, L.sp.scan);
+        if (!second) {  // A: scan of A's counts, A's run starts for the scatter (the next round's histogram is free until B's scan)
+          if ((uint32_t)tid < P2) L.sp.hist[buf ^ 1][tid] = e;
+          a1 = c | (e << 16);
+        } else {  // B: scan of the round's counts, reserve
+          S = e;
+          o_hi = (uint32_t)__builtin_amdgcn_readlane((int)(e + c), 63);
+          if ((uint32_t)tid < P2) {
+            const RunPlace q = split_reserve(L.sp, (uint32_t)tid, c, S, D, cst);
+            L.sp.dst[tid] = make_uint4(q.x, q.y, q.fit | (q.w << 16), a1);
+            L.sp.hist[buf][tid] = total1 + S - (a1 >> 16) - (a1 & 0xFFFFu);  // B's records of the region: at this + rank (>= c1)
+            L.sp.hist[buf ^ 1][tid] = 0;                                     // next round's histogram
+          }
+        }
+        lds_barrier();
+        if (!second) total1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)L.sp.scan.total);
+        KC_SPLIT_STAMP(2)  // scan (+ reserve)
+      }
+      scatter_half(second ? L.sp.hist[buf] : L.sp.hist[buf ^ 1]);
+      if (second) lds_barrier();
+      KC_SPLIT_STAMP(3)  // scatter to LDS
       take_over();
-      if (v0 + 2 * (uint64_t)per_round < n) load_round(v0 + 2 * per_round);
-      KC_SPLIT_STAMP(5)  // take over the next round's records, request the one after
-      split_copy_out<1>(
-          L.sp, sorted, nullptr, total, D, [&](const uint64_t (&r)[1]) { return cp_b2(r[0], gm); },
-          [&](uint32_t b, const uint64_t (&r)[1]) {
-            bb.flag[(size_t)b1 * P2 + b] = 1;
-            const uint64_t o = atomicAdd((unsigned long long *)&cb[CB_OVF2], 1ULL);
-            if (o < bb.ovf2_cap) bb.ovf2[o] = cp_unmix_rec(r[0], gm);
-            else atomicOr((unsigned long long *)&cb[CB_FATAL], (unsigned long long)FATAL_OVF2);
-          },
-          [&](size_t i, const uint64_t (&r)[1]) { reinterpret_cast<uint32_t *>(D.arena)[i] = cp_pack32(r[0], gm); });
-      buf ^= 1;
+      request(v0 + 2 * (uint64_t)half);
+      KC_SPLIT_STAMP(5)  // take over the next half, request the one after
+      if (second) {
+        // ---- copy-out: every wave writes the runs of its regions, four windows of 64 positions per trip
+        const int tid = fresh_tid();
+        const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane(tid >> 6), lane = lane_id();
+        // the wave's regions r0 .. r0 + 63 and their run starts, one per lane: its own threads' with 1024 regions; with
+        // fewer, P2 / 16 regions per wave through the histogram's words (free now), so that every wave has a share --
+        // a lane past the wave's regions holds ~0, which no window's ballot picks (and a wave without regions: o_lo > o_hi)
+        uint32_t r0 = wave * 64u, Sl = S;
+        if (P2 < (uint32_t)WGB) {
+          if ((uint32_t)tid < P2) L.sp.hist[buf][tid] = S;
+          lds_barrier();
+          const uint32_t G = (P2 + 15u) >> 4, total = L.sp.scan.total;
+          r0 = min(wave * G, P2);
+          const uint32_t r1 = min(r0 + G, P2), r = min(r0 + lane, r1);
+          Sl = r < r1 ? L.sp.hist[buf][r] : ~0u;
+          o_hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(r1 < P2 ? L.sp.hist[buf][r1] : total));
+        }
+        const uint32_t o_lo = (uint32_t)__builtin_amdgcn_readlane((int)Sl, 0);
+        constexpr int U = 4;
+        for (uint32_t o0 = o_lo; o0 < o_hi; o0 += U * 64) {
+          uint32_t oc[U], r[U], s[U], word[U];
+          uint4 d[U];
+#pragma unroll
+          for (int u = 0; u < U; u++) {
+            // (a lane past the end takes the last position: every read stays inside the round)
+            const uint32_t ou = min(o0 + 64u * u, o_hi - 1u);
+            oc[u] = min(ou + lane, o_hi - 1u);
+            // the region of oc: the last of the wave's regions that starts at or before it (an empty run starts where
+            // the next one does, and the next one wins)
+            const uint64_t le = __ballot(Sl <= ou);  // lane 0: Sl == o_lo <= ou
+            uint32_t l = 63u - (uint32_t)__clzll((long long)le);
+            r[u] = l;
+            s[u] = (uint32_t)__builtin_amdgcn_readlane((int)Sl, (int)l);
+            for (uint64_t m = __ballot(Sl > ou && Sl - ou < 64u); m; m &= m - 1u) {  // runs that start inside the window
+              l = (uint32_t)__builtin_ctzll(m);
+              const uint32_t sl = (uint32_t)__builtin_amdgcn_readlane((int)Sl, (int)l);
+              if (oc[u] >= sl) {
+                r[u] = l;
+                s[u] = sl;
+              }
+            }
+          }
+#pragma unroll
+          for (int u = 0; u < U; u++) d[u] = L.sp.dst[r0 + r[u]];
+#pragma unroll
+          for (int u = 0; u < U; u++) {
+            const uint32_t j = oc[u] - s[u], n1 = d[u].w & 0xFFFFu, st1 = d[u].w >> 16;
+            word[u] = staged[j < n1 ? st1 + j : total1 + oc[u] - st1 - n1];
+          }
+          bool spill = false;
+#pragma unroll
+          for (int u = 0; u < U; u++) {
+            const uint32_t j = oc[u] - s[u];
+            const bool live = o0 + 64u * u + lane < o_hi, fits = j < (d[u].z & 0xFFFFu);
+            // x and y are "index minus position" modulo 2^32: the sum must wrap in 32 bits before it is widened
+            const uint32_t at = (j < (d[u].z >> 16) ? d[u].x : d[u].y) + oc[u];
+            if (live && fits) arena32[arena0 + at] = word[u];
+            spill |= live && !fits;
+          }
+          if (__any(spill)) {  // rare: a chain or the arena is full
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+              if (o0 + 64u * u + lane < o_hi && oc[u] - s[u] >= (d[u].z & 0xFFFFu)) {
+                const size_t reg = (size_t)b1 * P2 + r0 + r[u];
+                bb.flag[reg] = 1;
+                const uint64_t o = atomicAdd((unsigned long long *)&cb[CB_OVF2], 1ULL);
+                if (o < bb.ovf2_cap) bb.ovf2[o] = cp_unpack_rec(word[u], reg, gm);
+                else atomicOr((unsigned long long *)&cb[CB_FATAL], (unsigned long long)FATAL_OVF2);
+              }
+            }
+          }
+        }
+        KC_SPLIT_STAMP(4)  // copy-out
+        // no barrier here: until its first barrier the next round only touches registers and the other histogram
+        buf ^= 1;
+      }
+      second = !second;
     }
     {
       const int tid = fresh_tid();
