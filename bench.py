@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- k-mers/s of the kcount stage on MI355X (BASELINE.json's metric).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One step = the whole kcount stage over one batch of synthetic ArcticSynth-shaped reads that is
@@ -10,6 +10,10 @@ exchange over RCCL, insert), vote/purge/compaction to dense result arrays in HBM
 workload is BASELINE.json configs[1] (50 M reads of 150 bp, k=21); for N>1 every GPU gets the same
 number of reads (weak scaling).  value = raw k-mers (sum of len-k+1, kcount.cpp:86) of all ranks
 per second of the slowest rank.  Prints ONE JSON line on rank 0.
+
+A plain run does only what that line needs: set-up, warm-up, the timed steps, --dump-outputs and the line itself (its
+`roofline` comes from the timed steps' kernel times and a committed profile).  --full adds, at N=1 after the timed
+steps, the host-resident legs (`end_to_end`) and the CPU baseline (`cpu_baseline`, null when not measured).
 """
 import argparse
 import json
@@ -50,8 +54,12 @@ def parse_args():
     ap.add_argument("--reads", type=int, default=50_000_000, help="reads per GPU (150 bp each)")
     ap.add_argument("--k", type=int, default=21)
     ap.add_argument("--block-reads", type=int, default=8_000_000, help="N>1: reads per exchange block")
-    ap.add_argument("--cpu-sample-reads", type=int, default=4_000_000, help="reads timed through the CPU oracle (0 = skip)")
-    ap.add_argument("--no-end-to-end", action="store_true", help="skip the host-resident (PCIe-inclusive) leg at N=1")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need, after the timed steps: at N=1 the host-resident "
+                         "(PCIe-inclusive) legs and the CPU baseline.  Without it a run sets up, warms up, times the steps, "
+                         "writes --dump-outputs and prints the result line")
+    ap.add_argument("--cpu-sample-reads", type=int, default=4_000_000, help="--full: reads timed through the CPU oracle (0 = skip)")
+    ap.add_argument("--no-end-to-end", action="store_true", help="--full: skip the host-resident (PCIe-inclusive) leg at N=1")
     ap.add_argument("--check", action="store_true", help="size-independent result checks after the timed region")
     ap.add_argument("--table-path", action="store_true", help="A/B: force the global-table insert path instead of the bucketed one")
     ap.add_argument("--force-sharded", action="store_true", help="run the N>1 code path (extract per block, exchange, receive) even at N=1")
@@ -479,10 +487,10 @@ def main():
             out["checks"] = checks
         if dumped is not None:
             out["dumped_outputs"] = dumped
-    # host-resident input (PCIe-inclusive) and the CPU baseline: rank 0 at N=1 only, outside the timed region
-    if rank == 0 and world == 1 and not sharded_path and not a.no_end_to_end:
+    # host-resident input (PCIe-inclusive) and the CPU baseline: --full, rank 0 at N=1 only, outside the timed region
+    if a.full and rank == 0 and world == 1 and not sharded_path and not a.no_end_to_end:
         out["end_to_end"] = end_to_end(kc, k, L, d_bases, d_quals, d_offs, nreads, dt / a.steps * 1e3)
-    if rank == 0 and world == 1 and a.cpu_sample_reads > 0:
+    if a.full and rank == 0 and world == 1 and a.cpu_sample_reads > 0:
         kc.close()
         del d_bases, d_quals, d_offs
         out["cpu_baseline"] = cpu_baseline(k, min(a.cpu_sample_reads, nreads), nreads, params)

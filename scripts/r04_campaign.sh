@@ -5,7 +5,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/r4/final
 mkdir -p $O
 cd $R
-python3 bench.py > $O/bench_default.json 2> $O/bench_default.err || exit 1
+python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err || exit 1
 echo "bench default done"; tail -c 200 $O/bench_default.json
 bash scripts/profile_bench.sh > $O/profile_bench.txt 2>&1
 cp gpurun_out/prof_bench/*/*_kernel_stats.csv $O/bench_default_kernel_stats.csv 2>/dev/null
