@@ -186,6 +186,52 @@ int kc_fastq_to_packed(const char *text, uint64_t len, int qual_offset, uint8_t 
                        uint64_t reads_capacity, uint64_t *nreads, uint64_t *nbytes);
 
 /*
+ * Paired FASTQ text -> interleaved ASCII reads, on the host (no context, no GPU): the input of kc_merge_pairs.
+ * text2 == NULL: text1 holds the pairs interleaved (mate 1, mate 2, mate 1, ...); else text1 holds the mates 1 and
+ * text2 the mates 2, record by record.  bases / quals (capacity bytes each) receive the sequences and the quality
+ * bytes as they are, offsets (reads_capacity + 1 entries) the read boundaries; read 2p is mate 1 of pair p and read
+ * 2p+1 its mate 2.  Validation and the size query are those of kc_fastq_to_packed (NULL arrays: only *nreads /
+ * *nbytes; KC_ERR_CAPACITY: call again with that much room).  Two files with different record counts, or an
+ * interleaved file with an odd count, are KC_ERR_INVALID_ARG.  Record names are not checked (the reference's name
+ * repair, src/merge_reads.cpp:386-467, is not part of this stage).
+ */
+int kc_fastq_pairs(const char *text1, uint64_t len1, const char *text2, uint64_t len2, uint8_t *bases, uint8_t *quals,
+                   uint64_t capacity, uint64_t *offsets, uint64_t reads_capacity, uint64_t *nreads, uint64_t *nbytes);
+
+/* Counters of kc_merge_pairs, the reference's merge_reads counters (src/merge_reads.cpp:469-648) */
+typedef struct kc_merge_stats {
+  uint64_t pairs;       /* pairs submitted */
+  uint64_t merged;      /* num_merged */
+  uint64_t ambiguous;   /* num_ambiguous: every increment the reference makes */
+  uint64_t dropped;     /* both mates shorter than min_kmer_len (:473) */
+  uint64_t overlap_len; /* sum of the merged pairs' overlaps */
+  uint64_t merged_len;  /* sum of the merged reads' lengths */
+  uint64_t out_reads;   /* reads written: 2 * pairs - merged - 2 * dropped */
+  uint64_t out_bases;
+} kc_merge_stats;
+
+/*
+ * Overlap merge of read pairs on the device: the pair loop of merge_reads (src/merge_reads.cpp:469-648) with no
+ * adapter file, writing the read cache's packed bytes (code | min(q - qual_offset, 31) << 3, as kc_fastq_to_packed)
+ * ready for kc_submit_packed_reads(..., on_device = 1).  The exact rules are in csrc/kc_merge.hpp's header comment.
+ * Input: interleaved mates (kc_fastq_pairs' layout, the one kc_submit_reads takes): 2 * npairs reads, ASCII bases
+ * and qualities, offsets of 2 * npairs + 1 entries; device memory (on_device = 1) or host memory, which is staged.
+ * min_kmer_len: a pair whose mates are both shorter is dropped (0 = the context's k).  The context's qual_offset is
+ * used; nothing else of the context changes.
+ * Output, always device memory, in pair order: one read for a merged pair, both mates as they came (mate 2 not
+ * reverse-complemented) for an unmerged pair, nothing for a dropped pair; d_out_offsets gets *nreads + 1 entries.
+ * The reference's one-base dummy mate after a merged pair holds no k-mer and is not produced.  Output bytes never
+ * exceed the input's bases and output reads never exceed 2 * npairs.
+ * KC_ERR_CAPACITY: the arrays are too small (or NULL); *nreads, *nbytes and *stats hold the totals.
+ * KC_ERR_BAD_BASE: a byte outside kc_fastq_to_packed's table.  KC_ERR_INVALID_ARG: a quality outside
+ * [qual_offset, qual_offset + 80] or a mate longer than 32767 -- stricter than the reference, which asserts or DIEs
+ * only where its loop meets one.
+ */
+int kc_merge_pairs(kc_ctx *ctx, const uint8_t *bases, const uint8_t *quals, const uint64_t *offsets, uint64_t npairs, int on_device,
+                   int min_kmer_len, uint8_t *d_packed, uint64_t packed_capacity, uint64_t *d_out_offsets, uint64_t reads_capacity,
+                   uint64_t *nreads, uint64_t *nbytes, kc_merge_stats *stats);
+
+/*
  * ParseAndPackGPUDriver::process_seq_block input format
  * (src/kcount/kcount_gpu.cpp:167-180, parse_and_pack.cpp:281-319): reads already
  * case-masked (lowercase = low quality) and joined by '_'.

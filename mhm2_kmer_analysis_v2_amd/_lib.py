@@ -6,6 +6,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
 
 KC_OK = 0
+KC_ERR_INVALID_ARG = -1
 KC_ERR_CAPACITY = -6
 KC_ERR_BAD_BASE = -7
 KC_FLAG_TIME_KERNELS = 1
@@ -56,6 +57,11 @@ class kc_synth_params(C.Structure):
                 ("n_rate", C.c_double), ("abundance_sigma", C.c_double)]
 
 
+class kc_merge_stats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("pairs", "merged", "ambiguous", "dropped", "overlap_len", "merged_len", "out_reads",
+                                           "out_bases")]
+
+
 # every symbol include/kcount_mi355.h declares: (restype, argtypes)
 SYMBOLS = {
     "kc_abi_version": (C.c_int, []),
@@ -74,6 +80,10 @@ SYMBOLS = {
     "kc_submit_packed_reads": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int]),
     "kc_fastq_to_packed": (C.c_int, [C.c_char_p, C.c_uint64, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),
                                       C.POINTER(C.c_uint64)]),
+    "kc_fastq_pairs": (C.c_int, [C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
+                                  C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "kc_merge_pairs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_uint64,
+                                  C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(kc_merge_stats)]),
     "kc_submit_seq_block": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int]),
     "kc_extract_partition": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p,
                                        C.c_uint64, C.c_void_p]),

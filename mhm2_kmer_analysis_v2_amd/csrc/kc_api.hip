@@ -24,6 +24,7 @@
 #include "kc_wire6.hpp"
 #include "kc_supermer.hpp"
 #include "kc_ctg.hpp"
+#include "kc_merge.hpp"
 
 using namespace kc;
 
@@ -41,12 +42,15 @@ static int hip_fail(hipError_t e, const char *what, int line) {
   } while (0)
 
 enum { KT_EXTRACT_INSERT = 0, KT_EXTRACT_BIN, KT_INSERT_RECORDS, KT_FINALIZE, KT_TILE_FIRST, KT_REHASH, KT_L1_READS, KT_L1_RECORDS,
-       KT_L2_SPLIT, KT_COUNT_REGIONS, KT_FALLBACK, KT_SHARD_PACK, KT_L1_READS_UQ, KT_L1_READS16, KT_L2_REC6, KT_BIN16, KT_L1_WIRE6, KT_COUNT };
+       KT_L2_SPLIT, KT_COUNT_REGIONS, KT_FALLBACK, KT_SHARD_PACK, KT_L1_READS_UQ, KT_L1_READS16, KT_L2_REC6, KT_BIN16, KT_L1_WIRE6,
+       KT_MERGE_DECIDE, KT_MERGE_DECIDE_LONG, KT_MERGE_SCAN, KT_MERGE_WRITE, KT_MERGE_WRITE_LONG, KT_COUNT };
 static const char *const kt_names[KT_COUNT] = {"kc_extract_kernel<insert>", "kc_bin_reads_kernel", "kc_insert_records_kernel",
                                                "kc_finalize_kernel", "kc_tile_first_kernel", "kc_rehash_kernel",
                                                "kc_l1_reads_kernel", "kc_l1_records_kernel", "kc_l2_split_kernel",
                                                "kc_count_kernel", "kc_flagged_to_table_kernel", "kc_shard_pack_kernel",
-                                               "kc_l1_reads_kernel<byte-loaded qualities>", "kc_l1_reads16_kernel", "kc_l2_rec6_kernel", "kc_bin16_kernel", "kc_l1_wire6_kernel"};
+                                               "kc_l1_reads_kernel<byte-loaded qualities>", "kc_l1_reads16_kernel", "kc_l2_rec6_kernel", "kc_bin16_kernel", "kc_l1_wire6_kernel",
+                                               "kc_merge_decide_kernel", "kc_merge_decide_kernel<long>", "kc_merge_scan_kernel",
+                                               "kc_merge_write_kernel", "kc_merge_write_kernel<long>"};
 struct kt_pending {
   hipEvent_t start, stop;
   int kind;
@@ -108,6 +112,9 @@ struct kc_ctx {
   SupermerInfo *d_sm_out;
   uint32_t *d_sm_ctr;     // n_out, n_kmers, too_long, + a u64 "bad character" flag behind them
   size_t sm_bytes_cap, sm_packed_cap, sm_targets_cap, sm_out_cap;
+  // scratch of kc_merge_pairs: per-pair decisions and sizes, the long-pair list, per-tile sums, statistics
+  uint8_t *d_mg;
+  size_t mg_cap;
   // host-side stats
   uint64_t num_reads, num_bases, num_gpu_calls;
   uint64_t purged, sum_counts, unique_at_finalize;
@@ -521,6 +528,7 @@ extern "C" void kc_destroy(kc_ctx *c) {
   if (c->d_sm_targets) (void)hipFree(c->d_sm_targets);
   if (c->d_sm_out) (void)hipFree(c->d_sm_out);
   if (c->d_sm_ctr) (void)hipFree(c->d_sm_ctr);
+  if (c->d_mg) (void)hipFree(c->d_mg);
   host_pipe_free(c);
   free_ctg(c);
   bk_free(c, false);
@@ -2018,57 +2026,81 @@ extern "C" int kc_submit_packed_reads(kc_ctx *c, const uint8_t *packed, const ui
 }
 
 // ---- FASTQ front end (host only) -----------------------------------------------------------------------------------
-extern "C" int kc_fastq_to_packed(const char *text, uint64_t len, int qual_offset, uint8_t *packed, uint64_t packed_capacity,
-                                  uint64_t *offsets, uint64_t reads_capacity, uint64_t *nreads, uint64_t *nbytes) {
-  if ((len && !text) || !nreads || !nbytes) return KC_ERR_INVALID_ARG;
-  // base codes of PackedRead (packed_reads.cpp:99-124): 255 = the reference DIEs
-  uint8_t code[256];
-  memset(code, 255, sizeof(code));
+// base codes of PackedRead (packed_reads.cpp:99-124): 255 = the reference DIEs
+static void fq_code_table(uint8_t code[256]) {
+  memset(code, 255, 256);
   const char *acgt = "ACGT";
   for (int i = 0; i < 4; i++) code[(uint8_t)acgt[i]] = code[(uint8_t)(acgt[i] | 0x20)] = (uint8_t)i;
   code[(uint8_t)'N'] = code[(uint8_t)'n'] = 4;
   for (const char *p = "URYKMSWBDHV"; *p; p++) code[(uint8_t)*p] = 4;
-  uint64_t nr = 0, nb = 0, pos = 0, line_no = 0;
-  bool fits = true;
+}
+
+// one FASTQ record of text[pos, len): 1 with [sb, sb + *sl) the sequence and [qb, qb + *sl) the qualities, 0 at the end,
+// KC_ERR_INVALID_ARG for a malformed record (kc_last_error names the line)
+struct FqCursor {
+  const char *text;
+  uint64_t len, pos, line_no;
+};
+
+static int fq_next(FqCursor &f, uint64_t *sb, uint64_t *qb, uint64_t *sl) {
   auto next_line = [&](uint64_t &b, uint64_t &e) -> bool {  // [b, e): the line without its end and trailing white space
-    if (pos >= len) return false;
-    b = pos;
-    while (pos < len && text[pos] != '\n') pos++;
-    e = pos;
-    if (pos < len) pos++;
-    while (e > b && (text[e - 1] == '\r' || text[e - 1] == ' ' || text[e - 1] == '\t')) e--;
-    line_no++;
+    if (f.pos >= f.len) return false;
+    b = f.pos;
+    while (f.pos < f.len && f.text[f.pos] != '\n') f.pos++;
+    e = f.pos;
+    if (f.pos < f.len) f.pos++;
+    while (e > b && (f.text[e - 1] == '\r' || f.text[e - 1] == ' ' || f.text[e - 1] == '\t')) e--;
+    f.line_no++;
     return true;
   };
+  const char *text = f.text;
+  const uint64_t len = f.len;
+  uint64_t b0, e0, b1, e1, b2, e2, b3, e3;
+  if (!next_line(b0, e0)) return 0;
+  if (e0 == b0 && f.pos >= len) return 0;  // a final empty line
+  if (!next_line(b1, e1) || !next_line(b2, e2) || !next_line(b3, e3)) {
+    snprintf(g_last_error, sizeof(g_last_error), "FASTQ ends inside the record that starts at line %llu", (unsigned long long)(f.line_no - (f.line_no - 1) % 4));
+    return KC_ERR_INVALID_ARG;
+  }
+  if (e0 == b0 || text[b0] != '@') {
+    snprintf(g_last_error, sizeof(g_last_error), "Invalid FASTQ: expected read name (@) at line %llu", (unsigned long long)(f.line_no - 3));
+    return KC_ERR_INVALID_ARG;
+  }
+  if (e2 == b2 || text[b2] != '+') {
+    snprintf(g_last_error, sizeof(g_last_error), "Invalid FASTQ: expected '+' at line %llu", (unsigned long long)(f.line_no - 1));
+    return KC_ERR_INVALID_ARG;
+  }
+  if (e1 - b1 != e3 - b3) {
+    snprintf(g_last_error, sizeof(g_last_error), "Invalid FASTQ: sequence length %llu != %llu quals length at line %llu",
+             (unsigned long long)(e1 - b1), (unsigned long long)(e3 - b3), (unsigned long long)(f.line_no - 2));
+    return KC_ERR_INVALID_ARG;
+  }
+  *sb = b1;
+  *qb = b3;
+  *sl = e1 - b1;
+  return 1;
+}
+
+extern "C" int kc_fastq_to_packed(const char *text, uint64_t len, int qual_offset, uint8_t *packed, uint64_t packed_capacity,
+                                  uint64_t *offsets, uint64_t reads_capacity, uint64_t *nreads, uint64_t *nbytes) {
+  if ((len && !text) || !nreads || !nbytes) return KC_ERR_INVALID_ARG;
+  uint8_t code[256];
+  fq_code_table(code);
+  uint64_t nr = 0, nb = 0;
+  bool fits = true;
+  FqCursor f{text, len, 0, 0};
   if (offsets && reads_capacity + 1 > 0) offsets[0] = 0;
   for (;;) {
-    uint64_t b0, e0, b1, e1, b2, e2, b3, e3;
-    if (!next_line(b0, e0)) break;
-    if (e0 == b0 && pos >= len) break;  // a final empty line
-    if (!next_line(b1, e1) || !next_line(b2, e2) || !next_line(b3, e3)) {
-      snprintf(g_last_error, sizeof(g_last_error), "FASTQ ends inside the record that starts at line %llu", (unsigned long long)(line_no - (line_no - 1) % 4));
-      return KC_ERR_INVALID_ARG;
-    }
-    if (e0 == b0 || text[b0] != '@') {
-      snprintf(g_last_error, sizeof(g_last_error), "Invalid FASTQ: expected read name (@) at line %llu", (unsigned long long)(line_no - 3));
-      return KC_ERR_INVALID_ARG;
-    }
-    if (e2 == b2 || text[b2] != '+') {
-      snprintf(g_last_error, sizeof(g_last_error), "Invalid FASTQ: expected '+' at line %llu", (unsigned long long)(line_no - 1));
-      return KC_ERR_INVALID_ARG;
-    }
-    const uint64_t sl = e1 - b1;
-    if (sl != e3 - b3) {
-      snprintf(g_last_error, sizeof(g_last_error), "Invalid FASTQ: sequence length %llu != %llu quals length at line %llu",
-               (unsigned long long)sl, (unsigned long long)(e3 - b3), (unsigned long long)(line_no - 2));
-      return KC_ERR_INVALID_ARG;
-    }
+    uint64_t b1, b3, sl;
+    const int r = fq_next(f, &b1, &b3, &sl);
+    if (r < 0) return r;
+    if (r == 0) break;
     const bool room = fits && packed && offsets && nr < reads_capacity && nb + sl <= packed_capacity;
     for (uint64_t i = 0; i < sl; i++) {
       const uint8_t cb = code[(uint8_t)text[b1 + i]];
       if (cb == 255) {
         snprintf(g_last_error, sizeof(g_last_error), "Illegal char in comp nucleotide (int=%d) at line %llu", (int)(uint8_t)text[b1 + i],
-                 (unsigned long long)(line_no - 2));
+                 (unsigned long long)(f.line_no - 2));
         return KC_ERR_BAD_BASE;
       }
       if (room) {
@@ -2088,6 +2120,209 @@ extern "C" int kc_fastq_to_packed(const char *text, uint64_t len, int qual_offse
     snprintf(g_last_error, sizeof(g_last_error), "%llu reads with %llu bases do not fit the arrays", (unsigned long long)nr, (unsigned long long)nb);
     return KC_ERR_CAPACITY;
   }
+  return KC_OK;
+}
+
+extern "C" int kc_fastq_pairs(const char *text1, uint64_t len1, const char *text2, uint64_t len2, uint8_t *bases, uint8_t *quals,
+                              uint64_t capacity, uint64_t *offsets, uint64_t reads_capacity, uint64_t *nreads, uint64_t *nbytes) {
+  if ((len1 && !text1) || (len2 && !text2) || !nreads || !nbytes) return KC_ERR_INVALID_ARG;
+  uint8_t code[256];
+  fq_code_table(code);
+  FqCursor f[2] = {{text1, len1, 0, 0}, {text2, len2, 0, 0}};
+  const bool two = text2 != nullptr;
+  uint64_t nr = 0, nb = 0;
+  bool fits = true;
+  if (offsets && reads_capacity + 1 > 0) offsets[0] = 0;
+  for (;;) {
+    FqCursor &fc = f[two ? (nr & 1) : 0];
+    uint64_t b1, b3, sl;
+    const int r = fq_next(fc, &b1, &b3, &sl);
+    if (r < 0) return r;
+    if (r == 0) {
+      if (two && (nr & 1)) {
+        snprintf(g_last_error, sizeof(g_last_error), "the second file ends after %llu records, the first has more", (unsigned long long)(nr / 2));
+        return KC_ERR_INVALID_ARG;
+      }
+      if (two) {  // the first file ended: the second must end too
+        uint64_t x, y, z;
+        const int r2 = fq_next(f[1], &x, &y, &z);
+        if (r2 < 0) return r2;
+        if (r2 > 0) {
+          snprintf(g_last_error, sizeof(g_last_error), "the first file ends after %llu records, the second has more", (unsigned long long)(nr / 2));
+          return KC_ERR_INVALID_ARG;
+        }
+      }
+      break;
+    }
+    const bool room = fits && bases && quals && offsets && nr < reads_capacity && nb + sl <= capacity;
+    for (uint64_t i = 0; i < sl; i++) {
+      if (code[(uint8_t)fc.text[b1 + i]] == 255) {
+        snprintf(g_last_error, sizeof(g_last_error), "Illegal char in comp nucleotide (int=%d) at line %llu of file %d",
+                 (int)(uint8_t)fc.text[b1 + i], (unsigned long long)(fc.line_no - 2), two ? (int)(nr & 1) + 1 : 1);
+        return KC_ERR_BAD_BASE;
+      }
+    }
+    if (room) {
+      memcpy(bases + nb, fc.text + b1, sl);
+      memcpy(quals + nb, fc.text + b3, sl);
+    } else {
+      fits = false;
+    }
+    nb += sl;
+    nr++;
+    if (room) offsets[nr] = nb;
+  }
+  if (nr & 1) {
+    snprintf(g_last_error, sizeof(g_last_error), "an interleaved file of %llu records: pairs need an even count", (unsigned long long)nr);
+    return KC_ERR_INVALID_ARG;
+  }
+  *nreads = nr;
+  *nbytes = nb;
+  if (!fits && (nr || nb)) {
+    snprintf(g_last_error, sizeof(g_last_error), "%llu reads with %llu bases do not fit the arrays", (unsigned long long)nr, (unsigned long long)nb);
+    return KC_ERR_CAPACITY;
+  }
+  return KC_OK;
+}
+
+// ---- overlap merge of read pairs (kc_merge.hpp) --------------------------------------------------------------------
+extern "C" int kc_merge_pairs(kc_ctx *c, const uint8_t *bases, const uint8_t *quals, const uint64_t *offsets, uint64_t npairs,
+                              int on_device, int min_kmer_len, uint8_t *d_packed, uint64_t packed_capacity, uint64_t *d_out_offsets,
+                              uint64_t reads_capacity, uint64_t *nreads, uint64_t *nbytes, kc_merge_stats *stats) {
+  if (!c || !nreads || !nbytes || min_kmer_len < 0 || (npairs && (!bases || !quals || !offsets))) return KC_ERR_INVALID_ARG;
+  HIPCHK(hipSetDevice(c->cfg.device));
+  kc_merge_stats ms;
+  memset(&ms, 0, sizeof(ms));
+  ms.pairs = npairs;
+  *nreads = *nbytes = 0;
+  if (stats) *stats = ms;
+  if (d_out_offsets && reads_capacity + 1 > 0) HIPCHK(hipMemsetAsync(d_out_offsets, 0, 8, c->stream));
+  if (!npairs) {
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return KC_OK;
+  }
+  if (npairs > 0xFFFFFFFFull) return KC_ERR_INVALID_ARG;  // pair indices of the long-pair list are 32-bit
+  const uint64_t nr_in = 2 * npairs;
+  if (!on_device) {  // staged the way kc_submit_seq_block stages a host block
+    const uint64_t first = offsets[0], last = offsets[nr_in];
+    if (last < first) return KC_ERR_INVALID_ARG;
+    int rc = ensure_stage(c, (size_t)(last - first), (size_t)nr_in, true);
+    if (rc) return rc;
+    std::vector<uint64_t> rel(nr_in + 1);
+    for (uint64_t r = 0; r <= nr_in; r++) {
+      if (offsets[r] < first || offsets[r] > last) return KC_ERR_INVALID_ARG;
+      rel[r] = offsets[r] - first;
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemcpyAsync(c->d_stage_bases, bases + first, last - first, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->d_stage_quals, quals + first, last - first, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->d_stage_offsets, rel.data(), (nr_in + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));  // rel goes out of scope
+    bases = c->d_stage_bases;
+    quals = c->d_stage_quals;
+    offsets = c->d_stage_offsets;
+  }
+  const uint64_t ntiles = (npairs + MG_TILE - 1) / MG_TILE;
+  auto up = [](size_t x) { return (x + 255) & ~size_t(255); };
+  const size_t sz_pair = up(npairs * 4), sz_tile = up(ntiles * 8), sz_stats = up(MG_SLOTS * MGS_N * 8), sz_ctl = 256;
+  const size_t need = 3 * sz_pair + 2 * sz_tile + sz_stats + sz_ctl;
+  if (need > c->mg_cap) {
+    if (c->d_mg) HIPCHK(hipFree(c->d_mg));
+    c->d_mg = nullptr;
+    c->mg_cap = 0;
+    HIPCHK(hipMalloc((void **)&c->d_mg, need));
+    c->mg_cap = need;
+  }
+  MergeArgs a;
+  memset(&a, 0, sizeof(a));
+  a.bases = bases;
+  a.quals = quals;
+  a.offsets = offsets;
+  a.npairs = npairs;
+  a.qoff = c->cfg.qual_offset;
+  a.min_len = min_kmer_len ? min_kmer_len : c->k;
+  uint8_t *m = c->d_mg;
+  a.pair_dec = (uint32_t *)m;
+  a.pair_out = (uint32_t *)(m + sz_pair);
+  a.long_list = (uint32_t *)(m + 2 * sz_pair);
+  a.tile_bytes = (uint64_t *)(m + 3 * sz_pair);
+  a.tile_reads = (uint64_t *)(m + 3 * sz_pair + sz_tile);
+  a.stats = (uint64_t *)(m + 3 * sz_pair + 2 * sz_tile);
+  a.ctl = (uint32_t *)(m + 3 * sz_pair + 2 * sz_tile + sz_stats);
+  a.totals = (uint64_t *)(a.ctl + 16);
+  a.out = d_packed;
+  a.out_offsets = d_out_offsets;
+  HIPCHK(hipMemsetAsync(a.stats, 0, sz_stats + sz_ctl, c->stream));
+  {
+    KernelTimer kt(c, KT_MERGE_DECIDE);
+    hipLaunchKernelGGL(kc_merge_decide_kernel, dim3((unsigned)ntiles), dim3(64 * MG_WAVES), 0, c->stream, a);
+  }
+  HIPCHK(hipGetLastError());
+  uint32_t ctl[MG_CTL_N];
+  HIPCHK(hipMemcpyAsync(ctl, a.ctl, sizeof(ctl), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  const uint32_t nlong = ctl[MG_CTL_NLONG];
+  const int lcap = (int)((ctl[MG_CTL_LONGMAX] + 3) & ~3u);
+  const size_t lbytes = 4 * ((size_t)lcap + MG_PAD);
+  if (nlong && !ctl[MG_CTL_ERR]) {
+    int rc = set_dyn_lds(kc_merge_decide_long_kernel, lbytes);
+    if (!rc) rc = set_dyn_lds(kc_merge_write_long_kernel, lbytes);
+    if (rc) return rc;
+    {
+      KernelTimer kt(c, KT_MERGE_DECIDE_LONG);
+      hipLaunchKernelGGL(kc_merge_decide_long_kernel, dim3(nlong), dim3(64), lbytes, c->stream, a, lcap);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(ctl, a.ctl, sizeof(ctl), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+  }
+  if (ctl[MG_CTL_ERR] & MG_ERR_BASE) {
+    snprintf(g_last_error, sizeof(g_last_error), "kc_merge_pairs: a read holds a byte outside ACGTN/acgtn/IUPAC");
+    return KC_ERR_BAD_BASE;
+  }
+  if (ctl[MG_CTL_ERR]) {
+    snprintf(g_last_error, sizeof(g_last_error), "kc_merge_pairs: a quality outside [qual_offset, qual_offset + 80] or a mate longer than %d",
+             MG_MAX_LEN);
+    return KC_ERR_INVALID_ARG;
+  }
+  {
+    KernelTimer kt(c, KT_MERGE_SCAN);
+    hipLaunchKernelGGL(kc_merge_scan_kernel, dim3(1), dim3(MG_SCAN_TPB), 0, c->stream, a, ntiles);
+  }
+  HIPCHK(hipGetLastError());
+  uint64_t tot[2], hs[MG_SLOTS * MGS_N];
+  HIPCHK(hipMemcpyAsync(tot, a.totals, sizeof(tot), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(hs, a.stats, sizeof(hs), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  for (int s = 0; s < MG_SLOTS; s++) {
+    ms.merged += hs[s * MGS_N + MGS_MERGED];
+    ms.ambiguous += hs[s * MGS_N + MGS_AMBIG];
+    ms.dropped += hs[s * MGS_N + MGS_DROPPED];
+    ms.overlap_len += hs[s * MGS_N + MGS_OVERLAP];
+    ms.merged_len += hs[s * MGS_N + MGS_MERGED_LEN];
+  }
+  ms.out_bases = tot[0];
+  ms.out_reads = tot[1];
+  *nbytes = tot[0];
+  *nreads = tot[1];
+  if (stats) *stats = ms;
+  if (!d_packed || !d_out_offsets || tot[0] > packed_capacity || tot[1] > reads_capacity) {
+    if (!tot[0] && !tot[1]) return KC_OK;
+    snprintf(g_last_error, sizeof(g_last_error), "%llu merged reads with %llu bases do not fit the arrays", (unsigned long long)tot[1],
+             (unsigned long long)tot[0]);
+    return KC_ERR_CAPACITY;
+  }
+  {
+    KernelTimer kt(c, KT_MERGE_WRITE);
+    hipLaunchKernelGGL(kc_merge_write_kernel, dim3((unsigned)ntiles), dim3(64 * MG_WAVES), 0, c->stream, a);
+  }
+  HIPCHK(hipGetLastError());
+  if (nlong) {
+    KernelTimer kt(c, KT_MERGE_WRITE_LONG);
+    hipLaunchKernelGGL(kc_merge_write_long_kernel, dim3(nlong), dim3(64), lbytes, c->stream, a, lcap);
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(c->stream));
   return KC_OK;
 }
 

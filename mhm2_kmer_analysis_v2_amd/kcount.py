@@ -2,6 +2,7 @@
 
   reference (src/kcount/kcount.cpp:142-161)          here
   -------------------------------------------        --------------------------------
+  merge_reads' pair loop (merge_reads.cpp:469-648)   .merge_pairs(...)        kc_merge_pairs
   KmerDHT ctor -> HashTableInserter::init             KmerCounter(k, ...)      kc_create
   count_kmers: per read quality-mask + process_seq    .submit_reads(...)       kc_submit_reads
   kmer_dht->flush_updates()                           .flush()                 kc_flush
@@ -14,7 +15,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import check, kc_config, kc_kernel_time, kc_result, kc_stats, kc_synth_params, kc_tuning, lib
+from ._lib import check, kc_config, kc_kernel_time, kc_merge_stats, kc_result, kc_stats, kc_synth_params, kc_tuning, lib
 
 
 def _ptr(a):
@@ -138,6 +139,27 @@ class KmerCounter:
         po, _ = _ptr(offsets)
         n = (len(offsets) - 1) if nreads is None else nreads
         check(lib().kc_submit_packed_reads(self._h, pp, po, n, 1 if dev else 0), "kc_submit_packed_reads")
+
+    def merge_pairs(self, bases, quals, offsets, npairs=None, min_kmer_len=0):
+        """Overlap merge of interleaved pairs on the device (kc_merge_pairs): returns (packed u8, offsets int64) as device
+        tensors holding exactly the output, ready for submit_packed_reads, and the counters as a dict.  Host arrays are
+        staged; min_kmer_len 0 = this counter's k."""
+        import torch
+        pb, dev = _ptr(bases)
+        pq, _ = _ptr(quals)
+        po, _ = _ptr(offsets)
+        n = (len(offsets) - 1) // 2 if npairs is None else npairs
+        if dev:
+            total = int(offsets[2 * n].item()) - int(offsets[0].item()) if n else 0
+        else:
+            total = int(offsets[2 * n]) - int(offsets[0]) if n else 0
+        d = "cuda:%d" % self.device
+        packed = torch.empty(max(total, 1), dtype=torch.uint8, device=d)
+        outo = torch.empty(2 * n + 1, dtype=torch.int64, device=d)
+        nr, nb, st = C.c_uint64(0), C.c_uint64(0), kc_merge_stats()
+        check(lib().kc_merge_pairs(self._h, pb, pq, po, n, 1 if dev else 0, min_kmer_len, packed.data_ptr(), total, outo.data_ptr(),
+                                   2 * n, C.byref(nr), C.byref(nb), C.byref(st)), "kc_merge_pairs")
+        return packed[:nb.value], outo[:nr.value + 1], {f: int(getattr(st, f)) for f, _ in kc_merge_stats._fields_}
 
     def submit_seq_block(self, seqs, length=None):
         if isinstance(seqs, (bytes, bytearray)):
@@ -389,6 +411,37 @@ def fastq_to_packed(text, qual_offset=33):
     check(lib().kc_fastq_to_packed(data, len(data), qual_offset, packed.ctypes.data, nb.value, offs.ctypes.data, n.value, C.byref(n),
                                    C.byref(nb)), "kc_fastq_to_packed")
     return packed[:nb.value], offs
+
+
+def fastq_pairs(text1, text2=None):
+    """Paired FASTQ text (bytes; text2 None = text1 interleaved) -> interleaved ASCII (bases u8, quals u8, offsets u64), the
+    input of KmerCounter.merge_pairs (kc_fastq_pairs, host only)."""
+    t1 = text1.encode() if isinstance(text1, str) else bytes(text1)
+    t2 = None if text2 is None else (text2.encode() if isinstance(text2, str) else bytes(text2))
+    l2 = 0 if t2 is None else len(t2)
+    n, nb = C.c_uint64(0), C.c_uint64(0)
+    st = lib().kc_fastq_pairs(t1, len(t1), t2, l2, None, None, 0, None, 0, C.byref(n), C.byref(nb))
+    if st not in (_lib.KC_OK, _lib.KC_ERR_CAPACITY):
+        check(st, "kc_fastq_pairs")
+    bases = np.zeros(max(nb.value, 1), dtype=np.uint8)
+    quals = np.zeros(max(nb.value, 1), dtype=np.uint8)
+    offs = np.zeros(n.value + 1, dtype=np.uint64)
+    check(lib().kc_fastq_pairs(t1, len(t1), t2, l2, bases.ctypes.data, quals.ctypes.data, nb.value, offs.ctypes.data, n.value,
+                               C.byref(n), C.byref(nb)), "kc_fastq_pairs")
+    return bases[:nb.value], quals[:nb.value], offs
+
+
+def analyze_kmers_paired(kmer_len, qual_offset, bases, quals, offsets, dmin_thres=2, device=0, max_elems=0, tuning=None,
+                         min_kmer_len=0):
+    """merge_reads' pair loop then analyze_kmers for one shard: interleaved pairs are merged on the device
+    (kc_merge_pairs), the merged read cache is counted (kc_submit_packed_reads).  Returns sorted results, the counter's
+    stats and the merge's counters."""
+    with KmerCounter(kmer_len, qual_offset, dmin_thres, device=device, max_elems=max_elems, tuning=tuning) as kc:
+        packed, offs, mst = kc.merge_pairs(bases, quals, offsets, min_kmer_len=min_kmer_len)
+        kc.submit_packed_reads(packed, offs, nreads=mst["out_reads"])
+        kc.flush()
+        res = kc.sorted_results()
+        return res, kc.stats(), mst
 
 
 def analyze_kmers(kmer_len, qual_offset, bases, quals, offsets, dmin_thres=2, device=0, max_elems=0, tuning=None):
