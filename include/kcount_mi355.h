@@ -198,6 +198,41 @@ int kc_fastq_to_packed(const char *text, uint64_t len, int qual_offset, uint8_t 
 int kc_fastq_pairs(const char *text1, uint64_t len1, const char *text2, uint64_t len2, uint8_t *bases, uint8_t *quals,
                    uint64_t capacity, uint64_t *offsets, uint64_t reads_capacity, uint64_t *nreads, uint64_t *nbytes);
 
+#define KC_FASTQ_PARTIAL 1u /* the text is a prefix of a longer input: parse only its whole records */
+
+/*
+ * FASTQ text -> the read cache's packed bytes, parsed on the device: the reference's FastqReader::get_next_fq_record
+ * (src/fastq.cpp:1028-1140) and PackedRead (src/packed_reads.cpp:99-126), in parallel over the text
+ * (csrc/kc_fastq.hpp).  The device twin of kc_fastq_to_packed with the context's qual_offset: for every input, well
+ * formed or not, the same status, *nreads, *nbytes, output bytes, offsets and kc_last_error() text.  NULL arrays are
+ * a size query; KC_ERR_CAPACITY fills in the totals; a format error wins over KC_ERR_CAPACITY.
+ * text: device memory read in place (on_device = 1), or host memory copied to the device first.  Any length, 2^32
+ * bytes and more.  Output is device memory: d_packed (packed_capacity bytes) and d_offsets (reads_capacity + 1 entries,
+ * d_offsets[0] = 0).
+ * flags KC_FASTQ_PARTIAL: only whole records count, those whose four lines all end in '\n' inside the text; an
+ * unfinished tail is neither parsed nor an error.  *consumed receives the byte just past the last whole record, and
+ * the call equals the flag-free call on text[0, *consumed): a caller streams a file by carrying the tail into the
+ * next call and making the last call without the flag.  Without the flag *consumed = len.  consumed may be NULL.
+ * The context's table and state are not touched, so this may be called in any state.  The call runs on the context's
+ * stream (kc_set_stream) and returns when its work there is done; device text written on another stream must be
+ * complete before the call.
+ */
+int kc_fastq_to_packed_device(kc_ctx *ctx, const char *text, uint64_t len, int on_device, uint32_t flags, uint8_t *d_packed,
+                              uint64_t packed_capacity, uint64_t *d_offsets, uint64_t reads_capacity, uint64_t *nreads,
+                              uint64_t *nbytes, uint64_t *consumed);
+
+/*
+ * Paired FASTQ text -> interleaved ASCII reads, parsed on the device: FastqReader::get_next_fq_record
+ * (src/fastq.cpp:1028-1140) for the input of kc_merge_pairs.  The device twin of kc_fastq_pairs (text2 == NULL:
+ * text1 holds the pairs interleaved), identical to it as kc_fastq_to_packed_device is to kc_fastq_to_packed.
+ * Input residence, output memory and the context as for kc_fastq_to_packed_device.  KC_FASTQ_PARTIAL: an interleaved
+ * file is consumed up to its last whole pair; two files are each consumed up to the same record count, the smaller of
+ * their whole-record counts (*consumed1, *consumed2).
+ */
+int kc_fastq_pairs_device(kc_ctx *ctx, const char *text1, uint64_t len1, const char *text2, uint64_t len2, int on_device,
+                          uint32_t flags, uint8_t *d_bases, uint8_t *d_quals, uint64_t capacity, uint64_t *d_offsets,
+                          uint64_t reads_capacity, uint64_t *nreads, uint64_t *nbytes, uint64_t *consumed1, uint64_t *consumed2);
+
 /* Counters of kc_merge_pairs, the reference's merge_reads counters (src/merge_reads.cpp:469-648) */
 typedef struct kc_merge_stats {
   uint64_t pairs;       /* pairs submitted */

@@ -10,6 +10,7 @@ KC_ERR_INVALID_ARG = -1
 KC_ERR_CAPACITY = -6
 KC_ERR_BAD_BASE = -7
 KC_FLAG_TIME_KERNELS = 1
+KC_FASTQ_PARTIAL = 1
 KC_FLAG_REFERENCE_OWNER = 2
 KC_FLAG_SHARD_BUCKETS = 4
 KC_FLAG_WIRE_UNITS = 8
@@ -82,6 +83,11 @@ SYMBOLS = {
                                       C.POINTER(C.c_uint64)]),
     "kc_fastq_pairs": (C.c_int, [C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
                                   C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "kc_fastq_to_packed_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p,
+                                             C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "kc_fastq_pairs_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.c_uint32, C.c_void_p,
+                                         C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                         C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "kc_merge_pairs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_uint64,
                                   C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(kc_merge_stats)]),
     "kc_submit_seq_block": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int]),

@@ -25,6 +25,7 @@
 #include "kc_supermer.hpp"
 #include "kc_ctg.hpp"
 #include "kc_merge.hpp"
+#include "kc_fastq.hpp"
 
 using namespace kc;
 
@@ -43,14 +44,18 @@ static int hip_fail(hipError_t e, const char *what, int line) {
 
 enum { KT_EXTRACT_INSERT = 0, KT_EXTRACT_BIN, KT_INSERT_RECORDS, KT_FINALIZE, KT_TILE_FIRST, KT_REHASH, KT_L1_READS, KT_L1_RECORDS,
        KT_L2_SPLIT, KT_COUNT_REGIONS, KT_FALLBACK, KT_SHARD_PACK, KT_L1_READS_UQ, KT_L1_READS16, KT_L2_REC6, KT_BIN16, KT_L1_WIRE6,
-       KT_MERGE_DECIDE, KT_MERGE_DECIDE_LONG, KT_MERGE_SCAN, KT_MERGE_WRITE, KT_MERGE_WRITE_LONG, KT_COUNT };
+       KT_MERGE_DECIDE, KT_MERGE_DECIDE_LONG, KT_MERGE_SCAN, KT_MERGE_WRITE, KT_MERGE_WRITE_LONG, KT_FQ_COUNT, KT_FQ_SCAN,
+       KT_FQ_INDEX, KT_FQ_CHECK, KT_FQ_DETAIL, KT_FQ_SUMS, KT_FQ_WRITE_PACKED, KT_FQ_WRITE_PAIRS, KT_COUNT };
 static const char *const kt_names[KT_COUNT] = {"kc_extract_kernel<insert>", "kc_bin_reads_kernel", "kc_insert_records_kernel",
                                                "kc_finalize_kernel", "kc_tile_first_kernel", "kc_rehash_kernel",
                                                "kc_l1_reads_kernel", "kc_l1_records_kernel", "kc_l2_split_kernel",
                                                "kc_count_kernel", "kc_flagged_to_table_kernel", "kc_shard_pack_kernel",
                                                "kc_l1_reads_kernel<byte-loaded qualities>", "kc_l1_reads16_kernel", "kc_l2_rec6_kernel", "kc_bin16_kernel", "kc_l1_wire6_kernel",
                                                "kc_merge_decide_kernel", "kc_merge_decide_kernel<long>", "kc_merge_scan_kernel",
-                                               "kc_merge_write_kernel", "kc_merge_write_kernel<long>"};
+                                               "kc_merge_write_kernel", "kc_merge_write_kernel<long>", "kc_fq_count_kernel",
+                                               "kc_fq_scan_kernel", "kc_fq_index_kernel", "kc_fq_check_kernel",
+                                               "kc_fq_detail_kernel", "kc_fq_sums_kernel", "kc_fq_write_kernel<packed>",
+                                               "kc_fq_write_kernel<pairs>"};
 struct kt_pending {
   hipEvent_t start, stop;
   int kind;
@@ -115,6 +120,9 @@ struct kc_ctx {
   // scratch of kc_merge_pairs: per-pair decisions and sizes, the long-pair list, per-tile sums, statistics
   uint8_t *d_mg;
   size_t mg_cap;
+  // kc_fastq_*_device scratch: the staged text, the tile counts and control words, the line and record tables
+  uint8_t *d_fq_text, *d_fq_tiles, *d_fq_recs;
+  size_t fq_text_cap, fq_tiles_cap, fq_recs_cap;
   // host-side stats
   uint64_t num_reads, num_bases, num_gpu_calls;
   uint64_t purged, sum_counts, unique_at_finalize;
@@ -529,6 +537,9 @@ extern "C" void kc_destroy(kc_ctx *c) {
   if (c->d_sm_out) (void)hipFree(c->d_sm_out);
   if (c->d_sm_ctr) (void)hipFree(c->d_sm_ctr);
   if (c->d_mg) (void)hipFree(c->d_mg);
+  if (c->d_fq_text) (void)hipFree(c->d_fq_text);
+  if (c->d_fq_tiles) (void)hipFree(c->d_fq_tiles);
+  if (c->d_fq_recs) (void)hipFree(c->d_fq_recs);
   host_pipe_free(c);
   free_ctg(c);
   bk_free(c, false);
@@ -2183,6 +2194,274 @@ extern "C" int kc_fastq_pairs(const char *text1, uint64_t len1, const char *text
     return KC_ERR_CAPACITY;
   }
   return KC_OK;
+}
+
+// ---- FASTQ front end on the device (kc_fastq.hpp) ------------------------------------------------------------------
+static int fq_grow(uint8_t **buf, size_t *cap, size_t need) {
+  if (need <= *cap) return KC_OK;
+  if (*buf) HIPCHK(hipFree(*buf));
+  *buf = nullptr;
+  *cap = 0;
+  HIPCHK(hipMalloc((void **)buf, need));
+  *cap = need;
+  return KC_OK;
+}
+
+// kc_fastq_to_packed_device (two = -1: one file, packed output) and kc_fastq_pairs_device (two = 0: one interleaved
+// file, 1: two files).  The kernels find each file's first structural and first base error; this rebuilds the host
+// parser's walk from them (fq_next's order, and the pairs' alternation), its status and its kc_last_error text.
+static int fq_device(kc_ctx *c, const char *const text_in[2], const uint64_t len_in[2], int two, int on_device, uint32_t flags,
+                     uint8_t *d_packed, uint8_t *d_bases, uint8_t *d_quals, uint64_t capacity, uint64_t *d_offsets,
+                     uint64_t reads_capacity, uint64_t *nreads, uint64_t *nbytes, uint64_t *consumed[2]) {
+  const bool packed = two < 0;
+  const int nf = two > 0 ? 2 : 1;
+  if (!c || !nreads || !nbytes || (flags & ~KC_FASTQ_PARTIAL)) return KC_ERR_INVALID_ARG;
+  for (int i = 0; i < nf; i++)
+    if (len_in[i] && !text_in[i]) return KC_ERR_INVALID_ARG;
+  const bool partial = (flags & KC_FASTQ_PARTIAL) != 0;
+  HIPCHK(hipSetDevice(c->cfg.device));
+  auto up = [](uint64_t x) { return (x + 255) & ~uint64_t(255); };
+  const uint8_t *text[2] = {(const uint8_t *)text_in[0], nf > 1 ? (const uint8_t *)text_in[1] : nullptr};
+  const uint64_t len[2] = {len_in[0], nf > 1 ? len_in[1] : 0};
+  if (!on_device) {  // one copy into context scratch
+    int rc = fq_grow(&c->d_fq_text, &c->fq_text_cap, up(len[0]) + up(len[1]) + 256);
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    for (int i = 0; i < nf; i++) {
+      uint8_t *dst = c->d_fq_text + (i ? up(len[0]) : 0);
+      if (len[i]) HIPCHK(hipMemcpyAsync(dst, text[i], len[i], hipMemcpyHostToDevice, c->stream));
+      text[i] = dst;
+    }
+  }
+  FqFile f[2];
+  memset(f, 0, sizeof(f));
+  uint64_t ntiles_all = 0;
+  for (int i = 0; i < nf; i++) {
+    f[i].text = text[i];
+    f[i].len = len[i];
+    f[i].head = len[i] ? (uint64_t)((uintptr_t)text[i] & 15u) : 0;
+    f[i].ntiles = (f[i].head + len[i] + FQ_TILE - 1) / FQ_TILE;
+    ntiles_all += f[i].ntiles;
+  }
+  int rc = fq_grow(&c->d_fq_tiles, &c->fq_tiles_cap, 2 * FQC_N * 8 + up(ntiles_all * 8));
+  if (rc) return rc;
+  for (int i = 0; i < nf; i++) {
+    f[i].ctl = (uint64_t *)c->d_fq_tiles + i * FQC_N;
+    f[i].tile = (uint64_t *)c->d_fq_tiles + 2 * FQC_N + (i ? f[0].ntiles : 0);
+  }
+  f[1].ctl = (uint64_t *)c->d_fq_tiles + FQC_N;  // (unused with one file, read back all the same)
+  HIPCHK(hipMemsetAsync(c->d_fq_tiles, 0xFF, 2 * FQC_N * 8, c->stream));
+  auto grid = [](uint64_t n) { return dim3((unsigned)std::max<uint64_t>(1, std::min<uint64_t>(n, FQ_MAX_GRID))); };
+  uint8_t last[2] = {'\n', '\n'};
+  for (int i = 0; i < nf; i++) {
+    if (f[i].ntiles) {
+      KernelTimer kt(c, KT_FQ_COUNT);
+      hipLaunchKernelGGL(kc_fq_count_kernel, grid(f[i].ntiles), dim3(FQ_TPB), 0, c->stream, f[i]);
+    }
+    HIPCHK(hipGetLastError());
+    {
+      KernelTimer kt(c, KT_FQ_SCAN);
+      hipLaunchKernelGGL(kc_fq_scan_kernel, dim3(1), dim3(FQ_SCAN_TPB), 0, c->stream, f[i].tile, f[i].ntiles, f[i].ctl + FQC_NNL);
+    }
+    HIPCHK(hipGetLastError());
+    if (len[i]) HIPCHK(hipMemcpyAsync(&last[i], text[i] + len[i] - 1, 1, hipMemcpyDeviceToHost, c->stream));
+  }
+  uint64_t h_ctl[2][FQC_N];
+  HIPCHK(hipMemcpyAsync(h_ctl, c->d_fq_tiles, sizeof(h_ctl), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  for (int i = 0; i < nf; i++) {
+    f[i].nnl = h_ctl[i][FQC_NNL];
+    f[i].nl = f[i].nnl + (len[i] && last[i] != '\n' ? 1 : 0);
+  }
+  if (partial) {  // whole records only: all four lines end in '\n' inside the text
+    uint64_t w = f[0].nnl / 4;
+    if (two == 0) w &= ~uint64_t(1);  // an interleaved file: whole pairs
+    if (two > 0) w = std::min(w, f[1].nnl / 4);
+    for (int i = 0; i < nf; i++) f[i].nl = 4 * w;
+  }
+  uint64_t recs_bytes = 0;
+  for (int i = 0; i < nf; i++) {
+    f[i].nrec = (f[i].nl + 3) / 4;
+    recs_bytes += up(f[i].nnl * 8) + up(f[i].nrec * 8);
+  }
+  const uint64_t nout = two > 0 ? 2 * std::max(f[0].nrec, f[1].nrec) : f[0].nrec;
+  const uint64_t nblk = (nout + FQ_TPB - 1) / FQ_TPB;
+  rc = fq_grow(&c->d_fq_recs, &c->fq_recs_cap, recs_bytes + up(nblk * 8) + 256);
+  if (rc) return rc;
+  {
+    uint8_t *m = c->d_fq_recs;
+    for (int i = 0; i < nf; i++) {
+      f[i].ends = (uint64_t *)m;
+      m += up(f[i].nnl * 8);
+      f[i].slen = (uint64_t *)m;
+      m += up(f[i].nrec * 8);
+    }
+    if (nf == 1) f[1] = f[0];  // the kernels' second file is never read
+    f[1].ctl = (uint64_t *)c->d_fq_tiles + FQC_N;
+  }
+  uint64_t *bsum = (uint64_t *)(c->d_fq_recs + recs_bytes);
+  for (int i = 0; i < nf; i++) {
+    if (f[i].ntiles && f[i].nnl) {
+      KernelTimer kt(c, KT_FQ_INDEX);
+      hipLaunchKernelGGL(kc_fq_index_kernel, grid(f[i].ntiles), dim3(FQ_TPB), 0, c->stream, f[i]);
+    }
+    HIPCHK(hipGetLastError());
+    if (f[i].nrec) {
+      KernelTimer kt(c, KT_FQ_CHECK);
+      hipLaunchKernelGGL(kc_fq_check_kernel, grid((f[i].nrec + FQ_TPB - 1) / FQ_TPB), dim3(FQ_TPB), 0, c->stream, f[i]);
+    }
+    HIPCHK(hipGetLastError());
+    {
+      KernelTimer kt(c, KT_FQ_DETAIL);
+      hipLaunchKernelGGL(kc_fq_detail_kernel, dim3(1), dim3(64), 0, c->stream, f[i]);
+    }
+    HIPCHK(hipGetLastError());
+  }
+  if (nout) {
+    KernelTimer kt(c, KT_FQ_SUMS);
+    hipLaunchKernelGGL(kc_fq_sums_kernel, grid(nblk), dim3(FQ_TPB), 0, c->stream, f[0], f[1], two > 0 ? 1 : 0, nout, bsum);
+  }
+  HIPCHK(hipGetLastError());
+  {
+    KernelTimer kt(c, KT_FQ_SCAN);
+    hipLaunchKernelGGL(kc_fq_scan_kernel, dim3(1), dim3(FQ_SCAN_TPB), 0, c->stream, bsum, nblk, f[0].ctl + FQC_TOTAL);
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(h_ctl, c->d_fq_tiles, sizeof(h_ctl), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+
+  // the host parser's walk.  Per file: t = the record where fq_next stops (its structural error, or the end after the
+  // sound records), bb = its first record with a bad base if that comes before t.
+  uint64_t t[2] = {0, 0}, bb[2] = {FQ_NONE, FQ_NONE};
+  bool serr[2] = {false, false};
+  for (int i = 0; i < nf; i++) {
+    const uint64_t *k = h_ctl[i];
+    const uint64_t valid = f[i].nrec - (f[i].nrec && k[FQC_END] == 1 ? 1 : 0);
+    serr[i] = k[FQC_STRUCT] != FQ_NONE;
+    t[i] = serr[i] ? k[FQC_STRUCT] : valid;
+    if (k[FQC_BASE] < t[i]) bb[i] = k[FQC_BASE];
+    if (consumed[i]) *consumed[i] = partial ? k[FQC_CONSUMED] : len[i];
+  }
+  enum { EV_BASE, EV_STRUCT, EV_END } ev = EV_END;
+  int evf = 0;     // the file the walk stops in
+  uint64_t g = 0;  // output records written before it stops
+  if (two > 0) {
+    // record j of file 1 is step 2j of the walk, of file 2 step 2j + 1
+    uint64_t best = FQ_NONE;
+    auto take = [&](uint64_t step, int e, int fi) {
+      if (step < best) {
+        best = step;
+        ev = (decltype(ev))e;
+        evf = fi;
+      }
+    };
+    for (int i = 0; i < 2; i++) {
+      if (bb[i] != FQ_NONE) take(2 * bb[i] + i, EV_BASE, i);
+      take(2 * t[i] + i, serr[i] ? EV_STRUCT : EV_END, i);
+    }
+    g = best;
+  } else {
+    ev = bb[0] != FQ_NONE ? EV_BASE : serr[0] ? EV_STRUCT : EV_END;
+    g = ev == EV_BASE ? bb[0] : t[0];
+  }
+  int status = KC_OK;
+  uint64_t part_rec = FQ_NONE, part_len = 0;
+  const uint64_t *k = h_ctl[evf];
+  const uint64_t r = two > 0 ? g >> 1 : g;  // the record of file evf
+  if (ev == EV_BASE) {
+    status = KC_ERR_BAD_BASE;
+    if (packed) {
+      snprintf(g_last_error, sizeof(g_last_error), "Illegal char in comp nucleotide (int=%d) at line %llu", (int)k[FQC_BYTE],
+               (unsigned long long)(4 * r + 2));
+      part_rec = g;
+      part_len = k[FQC_POS];
+    } else {
+      snprintf(g_last_error, sizeof(g_last_error), "Illegal char in comp nucleotide (int=%d) at line %llu of file %d", (int)k[FQC_BYTE],
+               (unsigned long long)(4 * r + 2), evf + 1);
+    }
+  } else if (ev == EV_END && two > 0 && evf == 1) {
+    status = KC_ERR_INVALID_ARG;
+    snprintf(g_last_error, sizeof(g_last_error), "the second file ends after %llu records, the first has more", (unsigned long long)t[1]);
+  } else if (ev == EV_END && two > 0 && t[1] > t[0]) {  // file 1 ended; file 2's next record is sound
+    status = KC_ERR_INVALID_ARG;
+    snprintf(g_last_error, sizeof(g_last_error), "the first file ends after %llu records, the second has more", (unsigned long long)t[0]);
+  } else if (ev == EV_STRUCT || (ev == EV_END && two > 0 && serr[1] && t[1] == t[0])) {
+    int fi = ev == EV_STRUCT ? evf : 1;  // (or file 2's record after file 1's end is malformed)
+    const uint64_t *kk = h_ctl[fi];
+    const unsigned long long rr = (unsigned long long)t[fi];
+    status = KC_ERR_INVALID_ARG;
+    switch ((int)kk[FQC_KIND]) {
+      case FQK_TRUNCATED: snprintf(g_last_error, sizeof(g_last_error), "FASTQ ends inside the record that starts at line %llu", 4 * rr + 1); break;
+      case FQK_NAME: snprintf(g_last_error, sizeof(g_last_error), "Invalid FASTQ: expected read name (@) at line %llu", 4 * rr + 1); break;
+      case FQK_PLUS: snprintf(g_last_error, sizeof(g_last_error), "Invalid FASTQ: expected '+' at line %llu", 4 * rr + 3); break;
+      default:
+        snprintf(g_last_error, sizeof(g_last_error), "Invalid FASTQ: sequence length %llu != %llu quals length at line %llu",
+                 (unsigned long long)kk[FQC_A], (unsigned long long)kk[FQC_B], 4 * rr + 2);
+    }
+  } else if (two == 0 && (g & 1)) {
+    status = KC_ERR_INVALID_ARG;
+    snprintf(g_last_error, sizeof(g_last_error), "an interleaved file of %llu records: pairs need an even count", (unsigned long long)g);
+  }
+  const uint64_t nr = g, nb = h_ctl[0][FQC_TOTAL];
+  const bool arrays = d_offsets && (packed ? d_packed != nullptr : (d_bases && d_quals));
+  if (d_offsets && reads_capacity + 1 > 0) HIPCHK(hipMemsetAsync(d_offsets, 0, 8, c->stream));
+  if (arrays && (g || part_rec != FQ_NONE) && g <= nout && (part_rec == FQ_NONE || part_rec < nout)) {  // (always, by construction)
+    FqOut o;
+    memset(&o, 0, sizeof(o));
+    o.packed = d_packed;
+    o.bases = d_bases;
+    o.quals = d_quals;
+    o.offsets = d_offsets;
+    o.cap = capacity;
+    o.reads_cap = reads_capacity;
+    o.nout = nout;
+    o.lim = g;
+    o.part_rec = part_rec;
+    o.part_len = part_len;
+    o.bsum = bsum;
+    o.qoff = c->cfg.qual_offset;
+    const uint64_t nw = part_rec != FQ_NONE ? part_rec + 1 : g;
+    if (packed) {
+      KernelTimer kt(c, KT_FQ_WRITE_PACKED);
+      hipLaunchKernelGGL(kc_fq_write_kernel<true>, grid((nw + FQ_TPB - 1) / FQ_TPB), dim3(FQ_TPB), 0, c->stream, f[0], f[1], 0, o);
+    } else {
+      KernelTimer kt(c, KT_FQ_WRITE_PAIRS);
+      hipLaunchKernelGGL(kc_fq_write_kernel<false>, grid((nw + FQ_TPB - 1) / FQ_TPB), dim3(FQ_TPB), 0, c->stream, f[0], f[1],
+                         two > 0 ? 1 : 0, o);
+    }
+    HIPCHK(hipGetLastError());
+  }
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (status) return status;
+  *nreads = nr;
+  *nbytes = nb;
+  const bool fits = arrays && nr <= reads_capacity && nb <= capacity;
+  if (!fits && (nr || nb)) {
+    snprintf(g_last_error, sizeof(g_last_error), "%llu reads with %llu bases do not fit the arrays", (unsigned long long)nr, (unsigned long long)nb);
+    return KC_ERR_CAPACITY;
+  }
+  return KC_OK;
+}
+
+extern "C" int kc_fastq_to_packed_device(kc_ctx *c, const char *text, uint64_t len, int on_device, uint32_t flags, uint8_t *d_packed,
+                                         uint64_t packed_capacity, uint64_t *d_offsets, uint64_t reads_capacity, uint64_t *nreads,
+                                         uint64_t *nbytes, uint64_t *consumed) {
+  const char *t[2] = {text, nullptr};
+  const uint64_t l[2] = {len, 0};
+  uint64_t *cons[2] = {consumed, nullptr};
+  return fq_device(c, t, l, -1, on_device, flags, d_packed, nullptr, nullptr, packed_capacity, d_offsets, reads_capacity, nreads, nbytes,
+                   cons);
+}
+
+extern "C" int kc_fastq_pairs_device(kc_ctx *c, const char *text1, uint64_t len1, const char *text2, uint64_t len2, int on_device,
+                                     uint32_t flags, uint8_t *d_bases, uint8_t *d_quals, uint64_t capacity, uint64_t *d_offsets,
+                                     uint64_t reads_capacity, uint64_t *nreads, uint64_t *nbytes, uint64_t *consumed1,
+                                     uint64_t *consumed2) {
+  const char *t[2] = {text1, text2};
+  const uint64_t l[2] = {len1, len2};
+  uint64_t *cons[2] = {consumed1, consumed2};
+  return fq_device(c, t, l, text2 ? 1 : 0, on_device, flags, nullptr, d_bases, d_quals, capacity, d_offsets, reads_capacity, nreads,
+                   nbytes, cons);
 }
 
 // ---- overlap merge of read pairs (kc_merge.hpp) --------------------------------------------------------------------

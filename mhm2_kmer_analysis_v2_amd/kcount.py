@@ -2,6 +2,7 @@
 
   reference (src/kcount/kcount.cpp:142-161)          here
   -------------------------------------------        --------------------------------
+  FastqReader + PackedRead (fastq.cpp:1028-1140)    .fastq_to_packed(...)    kc_fastq_to_packed_device
   merge_reads' pair loop (merge_reads.cpp:469-648)   .merge_pairs(...)        kc_merge_pairs
   KmerDHT ctor -> HashTableInserter::init             KmerCounter(k, ...)      kc_create
   count_kmers: per read quality-mask + process_seq    .submit_reads(...)       kc_submit_reads
@@ -27,6 +28,28 @@ def _ptr(a):
     if hasattr(a, "data_ptr"):  # torch tensor
         return a.data_ptr(), bool(a.is_cuda)
     return a.ctypes.data, False
+
+
+def _text_on_device(t):
+    return hasattr(t, "data_ptr") and bool(t.is_cuda)
+
+
+def _text(t):
+    """FASTQ text -> (address, length, on_device, keep-alive): bytes-like and numpy uint8 arrays are host memory, a
+    uint8 torch tensor on the GPU is read in place."""
+    if hasattr(t, "data_ptr"):
+        if t.dtype.itemsize != 1 or not t.is_contiguous():
+            raise ValueError("FASTQ text tensors must be contiguous uint8")
+        if not t.is_cuda:
+            a = t.numpy()
+            return (a.ctypes.data if a.size else None), a.size, False, a
+        return t.data_ptr(), t.numel(), True, t
+    if isinstance(t, str):
+        t = t.encode()
+    a = np.ascontiguousarray(t if isinstance(t, np.ndarray) else np.frombuffer(t, dtype=np.uint8))
+    if a.dtype != np.uint8:
+        raise ValueError("FASTQ text arrays must be uint8")
+    return (a.ctypes.data if a.size else None), a.size, False, a
 
 
 class _DeviceWords:
@@ -160,6 +183,78 @@ class KmerCounter:
         check(lib().kc_merge_pairs(self._h, pb, pq, po, n, 1 if dev else 0, min_kmer_len, packed.data_ptr(), total, outo.data_ptr(),
                                    2 * n, C.byref(nr), C.byref(nb), C.byref(st)), "kc_merge_pairs")
         return packed[:nb.value], outo[:nr.value + 1], {f: int(getattr(st, f)) for f, _ in kc_merge_stats._fields_}
+
+    def fastq_to_packed(self, text, partial=False):
+        """FASTQ text parsed on the device (kc_fastq_to_packed_device): returns (packed u8, offsets int64) as device
+        tensors holding exactly kc_fastq_to_packed's output, ready for submit_packed_reads, and with partial=True also
+        `consumed`, the byte past the last whole record (only whole records are parsed; the caller carries the tail).
+        text: bytes, a numpy uint8 array (copied to the device) or a uint8 device tensor (read in place)."""
+        import torch
+        pt, n, dev, keep = _text(text)
+        d = "cuda:%d" % self.device
+        packed = torch.empty(max(n, 1), dtype=torch.uint8, device=d)
+        offs = torch.empty(n // 4 + 2, dtype=torch.int64, device=d)
+        nr, nb, cons = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        torch.cuda.current_stream(self.device).synchronize()  # the text and the fresh arrays are torch's until now
+        check(lib().kc_fastq_to_packed_device(self._h, pt, n, 1 if dev else 0, _lib.KC_FASTQ_PARTIAL if partial else 0,
+                                              packed.data_ptr(), n, offs.data_ptr(), n // 4 + 1, C.byref(nr), C.byref(nb),
+                                              C.byref(cons)), "kc_fastq_to_packed_device")
+        del keep
+        out = (packed[:nb.value], offs[:nr.value + 1])
+        return out + (cons.value,) if partial else out
+
+    def fastq_pairs(self, text1, text2=None, partial=False):
+        """Paired FASTQ text parsed on the device (kc_fastq_pairs_device; text2 None = text1 interleaved): returns
+        (bases u8, quals u8, offsets int64) device tensors holding exactly kc_fastq_pairs' output, ready for merge_pairs,
+        and with partial=True also (consumed1, consumed2), the bytes of each text taken (consumed2 None for one text)."""
+        import torch
+        p1, n1, dev, keep1 = _text(text1)
+        p2, n2, _, keep2 = _text(text2) if text2 is not None else (None, 0, dev, None)
+        if text2 is not None and _text_on_device(text2) != dev:
+            raise ValueError("text1 and text2 must both be host or both be device memory")
+        d = "cuda:%d" % self.device
+        if text2 is not None and not p2:  # an empty second file is still a second file: NULL text2 would mean interleaved
+            keep2 = torch.zeros(1, dtype=torch.uint8, device=d) if dev else np.zeros(1, dtype=np.uint8)
+            p2 = keep2.data_ptr() if dev else keep2.ctypes.data
+        n = n1 + n2
+        bases = torch.empty(max(n, 1), dtype=torch.uint8, device=d)
+        quals = torch.empty(max(n, 1), dtype=torch.uint8, device=d)
+        offs = torch.empty(n // 4 + 2, dtype=torch.int64, device=d)
+        nr, nb, c1, c2 = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        torch.cuda.current_stream(self.device).synchronize()  # the texts and the fresh arrays are torch's until now
+        check(lib().kc_fastq_pairs_device(self._h, p1, n1, p2, n2, 1 if dev else 0, _lib.KC_FASTQ_PARTIAL if partial else 0,
+                                          bases.data_ptr(), quals.data_ptr(), n, offs.data_ptr(), n // 4 + 1, C.byref(nr),
+                                          C.byref(nb), C.byref(c1), C.byref(c2)), "kc_fastq_pairs_device")
+        del keep1, keep2
+        out = (bases[:nb.value], quals[:nb.value], offs[:nr.value + 1])
+        return out + ((c1.value, None if text2 is None else c2.value),) if partial else out
+
+    def submit_fastq(self, path_or_fileobj, block_bytes=1 << 30):
+        """Stream a FASTQ file into the counter: block by block through fastq_to_packed(partial=True) and
+        submit_packed_reads, the unfinished tail carried into the next block, the last call without the flag.
+        Returns the number of reads submitted."""
+        own = not hasattr(path_or_fileobj, "read")
+        f = open(path_or_fileobj, "rb") if own else path_or_fileobj
+        total, tail = 0, b""
+        try:
+            while True:
+                chunk = f.read(block_bytes)
+                buf = tail + chunk if tail else chunk
+                if not chunk:  # end of file: the rest must be whole records
+                    packed, offs = self.fastq_to_packed(buf)
+                    tail = b""
+                else:
+                    packed, offs, consumed = self.fastq_to_packed(buf, partial=True)
+                    tail = buf[consumed:]
+                nr = offs.numel() - 1
+                if nr:
+                    self.submit_packed_reads(packed, offs, nreads=nr)
+                    total += nr
+                if not chunk:
+                    return total
+        finally:
+            if own:
+                f.close()
 
     def submit_seq_block(self, seqs, length=None):
         if isinstance(seqs, (bytes, bytearray)):
@@ -439,6 +534,30 @@ def analyze_kmers_paired(kmer_len, qual_offset, bases, quals, offsets, dmin_thre
     with KmerCounter(kmer_len, qual_offset, dmin_thres, device=device, max_elems=max_elems, tuning=tuning) as kc:
         packed, offs, mst = kc.merge_pairs(bases, quals, offsets, min_kmer_len=min_kmer_len)
         kc.submit_packed_reads(packed, offs, nreads=mst["out_reads"])
+        kc.flush()
+        res = kc.sorted_results()
+        return res, kc.stats(), mst
+
+
+def analyze_kmers_fastq(kmer_len, qual_offset, text, dmin_thres=2, device=0, max_elems=0, tuning=None):
+    """analyze_kmers from FASTQ text: parsed on the device (kc_fastq_to_packed_device), then counted.  Returns sorted
+    results and stats."""
+    with KmerCounter(kmer_len, qual_offset, dmin_thres, device=device, max_elems=max_elems, tuning=tuning) as kc:
+        packed, offs = kc.fastq_to_packed(text)
+        kc.submit_packed_reads(packed, offs, nreads=offs.numel() - 1)
+        kc.flush()
+        res = kc.sorted_results()
+        return res, kc.stats()
+
+
+def analyze_kmers_fastq_paired(kmer_len, qual_offset, text1, text2=None, dmin_thres=2, device=0, max_elems=0, tuning=None,
+                               min_kmer_len=0):
+    """analyze_kmers_paired from paired FASTQ text (text2 None = text1 interleaved): parsed on the device
+    (kc_fastq_pairs_device), merged (kc_merge_pairs), counted.  Returns sorted results, stats and the merge's counters."""
+    with KmerCounter(kmer_len, qual_offset, dmin_thres, device=device, max_elems=max_elems, tuning=tuning) as kc:
+        bases, quals, offs = kc.fastq_pairs(text1, text2)
+        packed, moffs, mst = kc.merge_pairs(bases, quals, offs, min_kmer_len=min_kmer_len)
+        kc.submit_packed_reads(packed, moffs, nreads=mst["out_reads"])
         kc.flush()
         res = kc.sorted_results()
         return res, kc.stats(), mst
