@@ -247,7 +247,7 @@ typedef struct kc_merge_stats {
 
 /*
  * Overlap merge of read pairs on the device: the pair loop of merge_reads (src/merge_reads.cpp:469-648) with no
- * adapter file, writing the read cache's packed bytes (code | min(q - qual_offset, 31) << 3, as kc_fastq_to_packed)
+ * adapter file (Adapters::trim_pair, the step in front of it, is kc_trim_adapters), writing the read cache's packed bytes (code | min(q - qual_offset, 31) << 3, as kc_fastq_to_packed)
  * ready for kc_submit_packed_reads(..., on_device = 1).  The exact rules are in csrc/kc_merge.hpp's header comment.
  * Input: interleaved mates (kc_fastq_pairs' layout, the one kc_submit_reads takes): 2 * npairs reads, ASCII bases
  * and qualities, offsets of 2 * npairs + 1 entries; device memory (on_device = 1) or host memory, which is staged.
@@ -265,6 +265,65 @@ typedef struct kc_merge_stats {
 int kc_merge_pairs(kc_ctx *ctx, const uint8_t *bases, const uint8_t *quals, const uint64_t *offsets, uint64_t npairs, int on_device,
                    int min_kmer_len, uint8_t *d_packed, uint64_t packed_capacity, uint64_t *d_out_offsets, uint64_t reads_capacity,
                    uint64_t *nreads, uint64_t *nbytes, kc_merge_stats *stats);
+
+/*
+ * Adapter FASTA text -> the adapter index, on the host (no context, no GPU): the first half of kc_adapters_load, on
+ * its own so that the loading rules can be checked without a device.  Replaces Adapters::load_adapter_seqs
+ * (src/adapters.cpp:48-146): lines as getline yields them, '>' lines are names, a sequence shorter than adapter_k (an
+ * empty line too) is ignored and counted in *n_short, a trailing CR is not stripped; every kept sequence s gives the
+ * entries s and revcomp(s) (src/utils.cpp:98-129; a byte it DIEs on is KC_ERR_BAD_BASE), and every k-mer of every
+ * entry is indexed with Kmer<32>::get_kmers' 2-bit code (N counts as G, nothing is canonicalised).
+ * *n_adapters = kept sequences, *n_entries = 2 * *n_adapters, *n_kmers = distinct k-mers (what the reference logs at
+ * :132).  adapter_k > 32 is KC_ERR_UNSUPPORTED_K (MAX_ADAPTER_K, src/adapters.hpp:56); a sequence longer than 1024
+ * bytes or more than 32768 kept sequences are KC_ERR_INVALID_ARG.  Any output pointer may be NULL.
+ */
+int kc_adapters_index(const char *text, uint64_t len, int adapter_k, uint64_t *n_adapters, uint64_t *n_short, uint64_t *n_entries,
+                      uint64_t *n_kmers);
+
+#define KC_ADAPTERS_BLASTN_SCORES 1u /* align with 2/3/5/2/1 (BLASTN_ALN_SCORES) instead of 1/1/1/1/1: the reference's
+                                      * use_blastn_scores, optimize_for == "contiguity" (src/main.cpp:214) */
+
+/*
+ * Load an adapter set into the context: the Adapters constructor plus load_adapter_seqs (src/adapters.cpp:48-156).
+ * The entries, the k-mer index and the record lists are built on the host as kc_adapters_index builds them (same
+ * statuses and counts) and placed in device memory the context owns.  adapter_k = 0: the context's k.  Loading again
+ * replaces the set, kc_adapters_clear drops it, kc_reset keeps it (a multi-k sweep trims with the same adapters),
+ * kc_destroy frees it.  The set is independent of the table's state: both calls are allowed in any state.
+ */
+int kc_adapters_load(kc_ctx *ctx, const char *text, uint64_t len, int adapter_k, uint32_t flags, uint64_t *n_adapters,
+                     uint64_t *n_short, uint64_t *n_entries, uint64_t *n_kmers);
+int kc_adapters_clear(kc_ctx *ctx);
+
+/* Counters of kc_trim_adapters, the reference's (Adapters::done, src/adapters.cpp:158-169) */
+typedef struct kc_trim_stats {
+  uint64_t reads;         /* reads submitted */
+  uint64_t trimmed;       /* reads for which Adapters::trim returned true (a cut of no base included) */
+  uint64_t bases_trimmed; /* bases_trimmed: bases cut by trim itself (not by the pair rule) */
+  uint64_t reads_removed; /* reads_removed: reads cut to nothing */
+  uint64_t alignments;    /* aligner calls (the population of trim_timer_ssw) */
+  uint64_t out_bases;     /* bases written */
+} kc_trim_stats;
+
+#define KC_TRIM_PAIRED 1u /* reads 2p and 2p+1 are mates: Adapters::trim_pair; without it Adapters::trim per read */
+
+/*
+ * Adapter trimming on the device: Adapters::trim_pair (src/adapters.cpp:260-273), the first step of merge_reads' pair
+ * loop (src/merge_reads.cpp:469), or with flags = 0 Adapters::trim per read (src/packed_reads.cpp:390), in the build
+ * the reference ships (MERGE_READS_TRIM_WITH_SSW).  The exact rules are in csrc/kc_trim.hpp's header comment.
+ * Input: interleaved ASCII reads in kc_fastq_pairs' layout (nreads reads, offsets of nreads + 1 entries); device
+ * memory (on_device = 1) or host memory, which is staged.  KC_TRIM_PAIRED with an odd nreads is KC_ERR_INVALID_ARG.
+ * Output, always device memory, in the same layout with the same number of reads, ready for kc_merge_pairs or
+ * kc_submit_reads: a read cut to nothing stays as an empty read.  d_out_bases and d_out_quals hold capacity bytes
+ * each, d_out_offsets nreads + 1 entries.  Output bytes never exceed input bytes.
+ * KC_ERR_CAPACITY: the arrays are too small (or NULL); *nbytes and *stats hold the totals.  KC_ERR_STATE: no adapter
+ * set is loaded (the call is never a silent copy).  KC_ERR_INVALID_ARG: a read longer than 32767.  Base and quality
+ * bytes are not validated: the reference's trim looks at no quality, and any byte has a k-mer code and an aligner code.
+ * The context's table and state are not touched.  The call runs on the context's stream and returns when its work
+ * there is done.
+ */
+int kc_trim_adapters(kc_ctx *ctx, const uint8_t *bases, const uint8_t *quals, const uint64_t *offsets, uint64_t nreads, int on_device,
+                     uint32_t flags, uint8_t *d_out_bases, uint8_t *d_out_quals, uint64_t capacity, uint64_t *d_out_offsets,
+                     uint64_t *nbytes, kc_trim_stats *stats);
 
 /*
  * ParseAndPackGPUDriver::process_seq_block input format

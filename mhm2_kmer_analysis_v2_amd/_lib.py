@@ -8,9 +8,13 @@ _LIB = None
 KC_OK = 0
 KC_ERR_INVALID_ARG = -1
 KC_ERR_CAPACITY = -6
+KC_ERR_UNSUPPORTED_K = -2
 KC_ERR_BAD_BASE = -7
+KC_ERR_STATE = -8
 KC_FLAG_TIME_KERNELS = 1
 KC_FASTQ_PARTIAL = 1
+KC_ADAPTERS_BLASTN_SCORES = 1
+KC_TRIM_PAIRED = 1
 KC_FLAG_REFERENCE_OWNER = 2
 KC_FLAG_SHARD_BUCKETS = 4
 KC_FLAG_WIRE_UNITS = 8
@@ -63,6 +67,10 @@ class kc_merge_stats(C.Structure):
                                            "out_bases")]
 
 
+class kc_trim_stats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("reads", "trimmed", "bases_trimmed", "reads_removed", "alignments", "out_bases")]
+
+
 # every symbol include/kcount_mi355.h declares: (restype, argtypes)
 SYMBOLS = {
     "kc_abi_version": (C.c_int, []),
@@ -90,6 +98,13 @@ SYMBOLS = {
                                          C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "kc_merge_pairs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_uint64,
                                   C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(kc_merge_stats)]),
+    "kc_adapters_index": (C.c_int, [C.c_char_p, C.c_uint64, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                     C.POINTER(C.c_uint64)]),
+    "kc_adapters_load": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                    C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "kc_adapters_clear": (C.c_int, [C.c_void_p]),
+    "kc_trim_adapters": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p,
+                                    C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(kc_trim_stats)]),
     "kc_submit_seq_block": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int]),
     "kc_extract_partition": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p,
                                        C.c_uint64, C.c_void_p]),

@@ -15,7 +15,9 @@
 #include <algorithm>
 #include <new>
 #include <thread>
+#include <string>
 #include <type_traits>
+#include <unordered_map>
 #include <vector>
 
 #include "../../include/kcount_mi355.h"
@@ -25,6 +27,7 @@
 #include "kc_supermer.hpp"
 #include "kc_ctg.hpp"
 #include "kc_merge.hpp"
+#include "kc_trim.hpp"
 #include "kc_fastq.hpp"
 
 using namespace kc;
@@ -45,7 +48,8 @@ static int hip_fail(hipError_t e, const char *what, int line) {
 enum { KT_EXTRACT_INSERT = 0, KT_EXTRACT_BIN, KT_INSERT_RECORDS, KT_FINALIZE, KT_TILE_FIRST, KT_REHASH, KT_L1_READS, KT_L1_RECORDS,
        KT_L2_SPLIT, KT_COUNT_REGIONS, KT_FALLBACK, KT_SHARD_PACK, KT_L1_READS_UQ, KT_L1_READS16, KT_L2_REC6, KT_BIN16, KT_L1_WIRE6,
        KT_MERGE_DECIDE, KT_MERGE_DECIDE_LONG, KT_MERGE_SCAN, KT_MERGE_WRITE, KT_MERGE_WRITE_LONG, KT_FQ_COUNT, KT_FQ_SCAN,
-       KT_FQ_INDEX, KT_FQ_CHECK, KT_FQ_DETAIL, KT_FQ_SUMS, KT_FQ_WRITE_PACKED, KT_FQ_WRITE_PAIRS, KT_COUNT };
+       KT_FQ_INDEX, KT_FQ_CHECK, KT_FQ_DETAIL, KT_FQ_SUMS, KT_FQ_WRITE_PACKED, KT_FQ_WRITE_PAIRS, KT_TRIM_SEED, KT_TRIM_ALIGN,
+       KT_TRIM_SIZES, KT_TRIM_SCAN, KT_TRIM_WRITE, KT_COUNT };
 static const char *const kt_names[KT_COUNT] = {"kc_extract_kernel<insert>", "kc_bin_reads_kernel", "kc_insert_records_kernel",
                                                "kc_finalize_kernel", "kc_tile_first_kernel", "kc_rehash_kernel",
                                                "kc_l1_reads_kernel", "kc_l1_records_kernel", "kc_l2_split_kernel",
@@ -55,7 +59,8 @@ static const char *const kt_names[KT_COUNT] = {"kc_extract_kernel<insert>", "kc_
                                                "kc_merge_write_kernel", "kc_merge_write_kernel<long>", "kc_fq_count_kernel",
                                                "kc_fq_scan_kernel", "kc_fq_index_kernel", "kc_fq_check_kernel",
                                                "kc_fq_detail_kernel", "kc_fq_sums_kernel", "kc_fq_write_kernel<packed>",
-                                               "kc_fq_write_kernel<pairs>"};
+                                               "kc_fq_write_kernel<pairs>", "kc_trim_seed_kernel", "kc_trim_align_kernel",
+                                               "kc_trim_sizes_kernel", "kc_merge_scan_kernel<trim>", "kc_trim_write_kernel"};
 struct kt_pending {
   hipEvent_t start, stop;
   int kind;
@@ -120,6 +125,16 @@ struct kc_ctx {
   // scratch of kc_merge_pairs: per-pair decisions and sizes, the long-pair list, per-tile sums, statistics
   uint8_t *d_mg;
   size_t mg_cap;
+  // the adapter set (kc_adapters_load, kc_trim.hpp): slots, records, entry offsets and entry bytes in one allocation;
+  // it belongs to the context, not to a pass (kc_reset keeps it)
+  uint8_t *d_ad;
+  bool ad_loaded;
+  int ad_k, ad_blastn;
+  uint32_t ad_entries, ad_lg_slots;
+  size_t ad_off_recs, ad_off_ent, ad_off_bytes;
+  // scratch of kc_trim_adapters: per-read results, final lengths, the hit list, per-tile sums, statistics
+  uint8_t *d_tr;
+  size_t tr_cap;
   // kc_fastq_*_device scratch: the staged text, the tile counts and control words, the line and record tables
   uint8_t *d_fq_text, *d_fq_tiles, *d_fq_recs;
   size_t fq_text_cap, fq_tiles_cap, fq_recs_cap;
@@ -537,6 +552,8 @@ extern "C" void kc_destroy(kc_ctx *c) {
   if (c->d_sm_out) (void)hipFree(c->d_sm_out);
   if (c->d_sm_ctr) (void)hipFree(c->d_sm_ctr);
   if (c->d_mg) (void)hipFree(c->d_mg);
+  if (c->d_ad) (void)hipFree(c->d_ad);
+  if (c->d_tr) (void)hipFree(c->d_tr);
   if (c->d_fq_text) (void)hipFree(c->d_fq_text);
   if (c->d_fq_tiles) (void)hipFree(c->d_fq_tiles);
   if (c->d_fq_recs) (void)hipFree(c->d_fq_recs);
@@ -2599,6 +2616,322 @@ extern "C" int kc_merge_pairs(kc_ctx *c, const uint8_t *bases, const uint8_t *qu
   if (nlong) {
     KernelTimer kt(c, KT_MERGE_WRITE_LONG);
     hipLaunchKernelGGL(kc_merge_write_long_kernel, dim3(nlong), dim3(64), lbytes, c->stream, a, lcap);
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return KC_OK;
+}
+
+// ---- adapter trimming (kc_trim.hpp) ---------------------------------------------------------------------------------
+namespace {
+struct HostAdapters {
+  std::vector<std::string> entries;  // s at 2n, revcomp(s) at 2n+1
+  uint64_t n_short = 0;
+  std::vector<uint64_t> keys;                 // distinct k-mers in order of first insertion
+  std::vector<std::vector<uint32_t>> records; // per k-mer: entry << TR_REC_OFF_BITS | offset, in insertion order
+};
+}  // namespace
+
+// revcomp, src/utils.cpp:98-129; false for a byte the reference DIEs on
+static bool adapters_revcomp(const std::string &s, std::string &rc) {
+  rc.clear();
+  rc.reserve(s.size());
+  for (size_t i = s.size(); i-- > 0;) {
+    switch (s[i]) {
+      case 'A': case 'a': rc += 'T'; break;
+      case 'C': case 'c': rc += 'G'; break;
+      case 'G': case 'g': rc += 'C'; break;
+      case 'T': case 't': rc += 'A'; break;
+      case 'N': case 'n':
+      case 'U': case 'R': case 'Y': case 'K': case 'M': case 'S': case 'W': case 'B': case 'D': case 'H': case 'V': rc += 'N'; break;
+      default: return false;
+    }
+  }
+  return true;
+}
+
+// Adapters::load_adapter_seqs (src/adapters.cpp:48-146) on a text in memory
+static int adapters_build(const char *text, uint64_t len, int k, HostAdapters &h) {
+  if (k < 1 || (len && !text)) return KC_ERR_INVALID_ARG;
+  if (k > TR_MAX_K) {
+    snprintf(g_last_error, sizeof(g_last_error), "adapter_k %d is above MAX_ADAPTER_K = %d", k, TR_MAX_K);
+    return KC_ERR_UNSUPPORTED_K;
+  }
+  uint64_t lineno = 0;
+  for (uint64_t p = 0; p < len;) {  // getline: a last line without '\n' counts, nothing after the last '\n' does not
+    const char *nl = (const char *)memchr(text + p, '\n', len - p);
+    const uint64_t e = nl ? (uint64_t)(nl - text) : len;
+    const uint64_t n = e - p;
+    lineno++;
+    if (!(n && text[p] == '>')) {
+      if (n < (uint64_t)k) {
+        h.n_short++;
+      } else {
+        if (n > (uint64_t)TR_MAX_ENTRY_LEN) {
+          snprintf(g_last_error, sizeof(g_last_error), "adapter of %llu bases in line %llu: at most %d", (unsigned long long)n,
+                   (unsigned long long)lineno, TR_MAX_ENTRY_LEN);
+          return KC_ERR_INVALID_ARG;
+        }
+        if (h.entries.size() + 2 > (size_t)TR_MAX_ENTRIES) {
+          snprintf(g_last_error, sizeof(g_last_error), "more than %d adapter sequences", TR_MAX_ENTRIES / 2);
+          return KC_ERR_INVALID_ARG;
+        }
+        std::string s(text + p, (size_t)n), rc;
+        if (!adapters_revcomp(s, rc)) {
+          snprintf(g_last_error, sizeof(g_last_error), "adapter in line %llu holds a byte revcomp does not take", (unsigned long long)lineno);
+          return KC_ERR_BAD_BASE;
+        }
+        h.entries.push_back(std::move(s));
+        h.entries.push_back(std::move(rc));
+      }
+    }
+    p = e + 1;
+  }
+  std::unordered_map<uint64_t, uint32_t> ids;
+  const uint64_t mask = k >= 32 ? ~0ull : (1ull << (2 * k)) - 1ull;
+  for (size_t e = 0; e < h.entries.size(); e++) {
+    const std::string &s = h.entries[e];
+    uint64_t key = 0;
+    for (size_t j = 0; j < s.size(); j++) {  // base p of a k-mer in bits 2p, 2p+1 (tr_seed_keys)
+      key = (key >> 2) | ((uint64_t)tr_kcode((uint8_t)s[j]) << (2 * (k - 1)));
+      if (j + 1 < (size_t)k) continue;
+      const uint64_t kk = key & mask;
+      auto it = ids.find(kk);
+      uint32_t id;
+      if (it == ids.end()) {
+        id = (uint32_t)h.keys.size();
+        ids.emplace(kk, id);
+        h.keys.push_back(kk);
+        h.records.emplace_back();
+      } else {
+        id = it->second;
+      }
+      h.records[id].push_back((uint32_t)(e << TR_REC_OFF_BITS) | (uint32_t)(j + 1 - k));
+    }
+  }
+  return KC_OK;
+}
+
+static void adapters_counts(const HostAdapters &h, uint64_t *n_adapters, uint64_t *n_short, uint64_t *n_entries, uint64_t *n_kmers) {
+  if (n_adapters) *n_adapters = h.entries.size() / 2;
+  if (n_short) *n_short = h.n_short;
+  if (n_entries) *n_entries = h.entries.size();
+  if (n_kmers) *n_kmers = h.keys.size();
+}
+
+extern "C" int kc_adapters_index(const char *text, uint64_t len, int adapter_k, uint64_t *n_adapters, uint64_t *n_short,
+                                 uint64_t *n_entries, uint64_t *n_kmers) {
+  HostAdapters h;
+  const int rc = adapters_build(text, len, adapter_k, h);
+  if (rc) return rc;
+  adapters_counts(h, n_adapters, n_short, n_entries, n_kmers);
+  return KC_OK;
+}
+
+extern "C" int kc_adapters_clear(kc_ctx *c) {
+  if (!c) return KC_ERR_INVALID_ARG;
+  HIPCHK(hipSetDevice(c->cfg.device));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (c->d_ad) HIPCHK(hipFree(c->d_ad));
+  c->d_ad = nullptr;
+  c->ad_loaded = false;
+  c->ad_entries = 0;
+  return KC_OK;
+}
+
+extern "C" int kc_adapters_load(kc_ctx *c, const char *text, uint64_t len, int adapter_k, uint32_t flags, uint64_t *n_adapters,
+                                uint64_t *n_short, uint64_t *n_entries, uint64_t *n_kmers) {
+  if (!c || adapter_k < 0 || (flags & ~KC_ADAPTERS_BLASTN_SCORES)) return KC_ERR_INVALID_ARG;
+  const int k = adapter_k ? adapter_k : c->k;
+  HostAdapters h;
+  int rc = adapters_build(text, len, k, h);
+  if (rc) return rc;
+  // the device image: the k-mer table at most half full, the records, the entries' offsets and bytes
+  uint32_t lg = 4;
+  while ((1ull << lg) < 2 * h.keys.size()) lg++;
+  std::vector<TrSlot> slots((size_t)1 << lg);
+  memset(slots.data(), 0, slots.size() * sizeof(TrSlot));
+  std::vector<uint32_t> recs;
+  for (size_t i = 0; i < h.keys.size(); i++) {
+    uint32_t s = tr_hash(h.keys[i], lg);
+    while (slots[s].rec_count) s = (s + 1) & ((1u << lg) - 1u);
+    slots[s].key = h.keys[i];
+    slots[s].rec_start = (uint32_t)recs.size();
+    slots[s].rec_count = (uint32_t)h.records[i].size();
+    recs.insert(recs.end(), h.records[i].begin(), h.records[i].end());
+  }
+  std::vector<uint32_t> ent_off(h.entries.size() + 1, 0);
+  std::string bytes;
+  for (size_t e = 0; e < h.entries.size(); e++) {
+    ent_off[e] = (uint32_t)bytes.size();
+    bytes += h.entries[e];
+  }
+  ent_off[h.entries.size()] = (uint32_t)bytes.size();
+  auto up = [](size_t x) { return (x + 255) & ~size_t(255); };
+  const size_t sz_slots = up(slots.size() * sizeof(TrSlot)), sz_recs = up(recs.size() * 4 + 4), sz_ent = up(ent_off.size() * 4);
+  const size_t total = sz_slots + sz_recs + sz_ent + up(bytes.size() + 1);
+  rc = kc_adapters_clear(c);  // loading again replaces the set
+  if (rc) return rc;
+  HIPCHK(hipMalloc((void **)&c->d_ad, total));
+  HIPCHK(hipMemcpy(c->d_ad, slots.data(), slots.size() * sizeof(TrSlot), hipMemcpyHostToDevice));
+  if (!recs.empty()) HIPCHK(hipMemcpy(c->d_ad + sz_slots, recs.data(), recs.size() * 4, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(c->d_ad + sz_slots + sz_recs, ent_off.data(), ent_off.size() * 4, hipMemcpyHostToDevice));
+  if (!bytes.empty()) HIPCHK(hipMemcpy(c->d_ad + sz_slots + sz_recs + sz_ent, bytes.data(), bytes.size(), hipMemcpyHostToDevice));
+  c->ad_off_recs = sz_slots;
+  c->ad_off_ent = sz_slots + sz_recs;
+  c->ad_off_bytes = sz_slots + sz_recs + sz_ent;
+  c->ad_lg_slots = lg;
+  c->ad_entries = (uint32_t)h.entries.size();
+  c->ad_k = k;
+  c->ad_blastn = (flags & KC_ADAPTERS_BLASTN_SCORES) ? 1 : 0;
+  c->ad_loaded = true;
+  adapters_counts(h, n_adapters, n_short, n_entries, n_kmers);
+  return KC_OK;
+}
+
+extern "C" int kc_trim_adapters(kc_ctx *c, const uint8_t *bases, const uint8_t *quals, const uint64_t *offsets, uint64_t nreads,
+                                int on_device, uint32_t flags, uint8_t *d_out_bases, uint8_t *d_out_quals, uint64_t capacity,
+                                uint64_t *d_out_offsets, uint64_t *nbytes, kc_trim_stats *stats) {
+  if (!c || !nbytes || (flags & ~KC_TRIM_PAIRED) || (nreads && (!bases || !quals || !offsets))) return KC_ERR_INVALID_ARG;
+  const int paired = (flags & KC_TRIM_PAIRED) ? 1 : 0;
+  if (paired && (nreads & 1)) {
+    snprintf(g_last_error, sizeof(g_last_error), "kc_trim_adapters: KC_TRIM_PAIRED with an odd number of reads");
+    return KC_ERR_INVALID_ARG;
+  }
+  if (!c->ad_loaded) {
+    snprintf(g_last_error, sizeof(g_last_error), "kc_trim_adapters: no adapter set is loaded (kc_adapters_load)");
+    return KC_ERR_STATE;
+  }
+  HIPCHK(hipSetDevice(c->cfg.device));
+  kc_trim_stats ts;
+  memset(&ts, 0, sizeof(ts));
+  ts.reads = nreads;
+  *nbytes = 0;
+  if (stats) *stats = ts;
+  if (d_out_offsets) HIPCHK(hipMemsetAsync(d_out_offsets, 0, 8, c->stream));
+  if (!nreads) {
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return KC_OK;
+  }
+  if (nreads > 0xFFFFFFFFull) return KC_ERR_INVALID_ARG;  // read indices of the hit list are 32-bit
+  if (!on_device) {  // staged as kc_merge_pairs stages a host block
+    const uint64_t first = offsets[0], last = offsets[nreads];
+    if (last < first) return KC_ERR_INVALID_ARG;
+    int rc = ensure_stage(c, (size_t)(last - first), (size_t)nreads, true);
+    if (rc) return rc;
+    std::vector<uint64_t> rel(nreads + 1);
+    for (uint64_t r = 0; r <= nreads; r++) {
+      if (offsets[r] < first || offsets[r] > last) return KC_ERR_INVALID_ARG;
+      rel[r] = offsets[r] - first;
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemcpyAsync(c->d_stage_bases, bases + first, last - first, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->d_stage_quals, quals + first, last - first, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->d_stage_offsets, rel.data(), (nreads + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));  // rel goes out of scope
+    bases = c->d_stage_bases;
+    quals = c->d_stage_quals;
+    offsets = c->d_stage_offsets;
+  }
+  const uint64_t ntiles = (nreads + TR_TILE - 1) / TR_TILE;
+  auto up = [](size_t x) { return (x + 255) & ~size_t(255); };
+  const size_t sz_read = up(nreads * 4), sz_tile = up(ntiles * 8), sz_ctl = 256;
+  const size_t need = 3 * sz_read + 2 * sz_tile + sz_ctl;
+  if (need > c->tr_cap) {
+    if (c->d_tr) HIPCHK(hipFree(c->d_tr));
+    c->d_tr = nullptr;
+    c->tr_cap = 0;
+    HIPCHK(hipMalloc((void **)&c->d_tr, need));
+    c->tr_cap = need;
+  }
+  TrimArgs a;
+  memset(&a, 0, sizeof(a));
+  a.bases = bases;
+  a.quals = quals;
+  a.offsets = offsets;
+  a.nreads = nreads;
+  a.k = c->ad_k;
+  a.paired = paired;
+  a.match = c->ad_blastn ? 2 : 1;  // BLASTN_ALN_SCORES 23521 / ALTERNATE_ALN_SCORES 11111
+  a.mismatch = c->ad_blastn ? 3 : 1;
+  a.gap_open = c->ad_blastn ? 5 : 1;
+  a.gap_ext = c->ad_blastn ? 2 : 1;
+  a.amb = 1;
+  a.slots = (const TrSlot *)c->d_ad;
+  a.lg_slots = c->ad_lg_slots;
+  a.slot_mask = (1u << c->ad_lg_slots) - 1u;
+  a.recs = (const uint32_t *)(c->d_ad + c->ad_off_recs);
+  a.ent_off = (const uint32_t *)(c->d_ad + c->ad_off_ent);
+  a.ent_bytes = c->d_ad + c->ad_off_bytes;
+  a.n_entries = c->ad_entries;
+  uint8_t *m = c->d_tr;
+  a.res = (uint32_t *)m;
+  a.flen = (uint32_t *)(m + sz_read);
+  a.list = (uint32_t *)(m + 2 * sz_read);
+  a.tile_bytes = (uint64_t *)(m + 3 * sz_read);
+  uint64_t *tile_reads = (uint64_t *)(m + 3 * sz_read + sz_tile);  // kc_merge_scan_kernel scans two arrays
+  a.ctl = (uint32_t *)(m + 3 * sz_read + 2 * sz_tile);
+  a.stats = (unsigned long long *)(a.ctl + 8);
+  uint64_t *totals = (uint64_t *)(a.ctl + 24);
+  a.out_bases = d_out_bases;
+  a.out_quals = d_out_quals;
+  a.out_offsets = d_out_offsets;
+  HIPCHK(hipMemsetAsync(tile_reads, 0, sz_tile + sz_ctl, c->stream));
+  {
+    KernelTimer kt(c, KT_TRIM_SEED);
+    const uint64_t per = (uint64_t)TR_SEED_WAVES * TR_RPW;
+    hipLaunchKernelGGL(kc_trim_seed_kernel, dim3((unsigned)((nreads + per - 1) / per)), dim3(64 * TR_SEED_WAVES), 0, c->stream, a);
+  }
+  HIPCHK(hipGetLastError());
+  uint32_t ctl[TR_CTL_N];
+  HIPCHK(hipMemcpyAsync(ctl, a.ctl, sizeof(ctl), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (ctl[TR_CTL_ERR]) {
+    snprintf(g_last_error, sizeof(g_last_error), "kc_trim_adapters: a read longer than %d, or offsets that decrease", MG_MAX_LEN);
+    return KC_ERR_INVALID_ARG;
+  }
+  if (ctl[TR_CTL_NLIST]) {
+    KernelTimer kt(c, KT_TRIM_ALIGN);
+    const uint32_t nlist = ctl[TR_CTL_NLIST];
+    const unsigned grid = (unsigned)std::min<uint64_t>(nlist, (uint64_t)c->num_cus * 32);
+    hipLaunchKernelGGL(kc_trim_align_kernel, dim3(grid), dim3(64), 0, c->stream, a, nlist);
+  }
+  HIPCHK(hipGetLastError());
+  {
+    KernelTimer kt(c, KT_TRIM_SIZES);
+    hipLaunchKernelGGL(kc_trim_sizes_kernel, dim3((unsigned)ntiles), dim3(TR_TILE), 0, c->stream, a);
+  }
+  HIPCHK(hipGetLastError());
+  {
+    MergeArgs sa;
+    memset(&sa, 0, sizeof(sa));
+    sa.tile_bytes = a.tile_bytes;
+    sa.tile_reads = tile_reads;
+    sa.totals = totals;
+    KernelTimer kt(c, KT_TRIM_SCAN);
+    hipLaunchKernelGGL(kc_merge_scan_kernel, dim3(1), dim3(MG_SCAN_TPB), 0, c->stream, sa, ntiles);
+  }
+  HIPCHK(hipGetLastError());
+  uint64_t tot[2];
+  unsigned long long hs[TRS_N];
+  HIPCHK(hipMemcpyAsync(tot, totals, sizeof(tot), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(hs, a.stats, sizeof(hs), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  ts.trimmed = hs[TRS_TRIMMED];
+  ts.bases_trimmed = hs[TRS_BASES];
+  ts.reads_removed = hs[TRS_REMOVED];
+  ts.alignments = hs[TRS_ALIGN];
+  ts.out_bases = tot[0];
+  *nbytes = tot[0];
+  if (stats) *stats = ts;
+  if (!d_out_bases || !d_out_quals || !d_out_offsets || tot[0] > capacity) {
+    snprintf(g_last_error, sizeof(g_last_error), "%llu trimmed reads with %llu bases do not fit the arrays", (unsigned long long)nreads,
+             (unsigned long long)tot[0]);
+    return KC_ERR_CAPACITY;
+  }
+  {
+    KernelTimer kt(c, KT_TRIM_WRITE);
+    hipLaunchKernelGGL(kc_trim_write_kernel, dim3((unsigned)ntiles), dim3(TR_TILE), 0, c->stream, a);
   }
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(c->stream));

@@ -1,6 +1,7 @@
 // kc_merge.hpp -- overlap merge of read pairs on the device (kc_merge_pairs): the pair loop of the reference's
 // merge_reads (src/merge_reads.cpp:469-648) with no adapter file (Adapters::trim_pair returns at once when
 // adapter_seqs is empty, src/adapters.cpp:260-261), producing the read cache's packed bytes.
+// With an adapter file that step is kc_trim_adapters (kc_trim.hpp), run in front of this one.
 //
 // Rules (the contract of the kernels below and of tests/merge_model.py):
 //  * Input: interleaved mates in one set of arrays, ASCII bases and qualities, offsets of 2*npairs+1 entries; read 2p

@@ -3,6 +3,8 @@
   reference (src/kcount/kcount.cpp:142-161)          here
   -------------------------------------------        --------------------------------
   FastqReader + PackedRead (fastq.cpp:1028-1140)    .fastq_to_packed(...)    kc_fastq_to_packed_device
+  Adapters ctor + load_adapter_seqs (adapters.cpp)   .load_adapters(...)      kc_adapters_load
+  Adapters::trim_pair / trim (adapters.cpp:171-273)  .trim_adapters(...)      kc_trim_adapters
   merge_reads' pair loop (merge_reads.cpp:469-648)   .merge_pairs(...)        kc_merge_pairs
   KmerDHT ctor -> HashTableInserter::init             KmerCounter(k, ...)      kc_create
   count_kmers: per read quality-mask + process_seq    .submit_reads(...)       kc_submit_reads
@@ -16,7 +18,8 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import check, kc_config, kc_kernel_time, kc_merge_stats, kc_result, kc_stats, kc_synth_params, kc_tuning, lib
+from ._lib import (check, kc_config, kc_kernel_time, kc_merge_stats, kc_result, kc_stats, kc_synth_params, kc_trim_stats, kc_tuning,
+                   lib)
 
 
 def _ptr(a):
@@ -183,6 +186,43 @@ class KmerCounter:
         check(lib().kc_merge_pairs(self._h, pb, pq, po, n, 1 if dev else 0, min_kmer_len, packed.data_ptr(), total, outo.data_ptr(),
                                    2 * n, C.byref(nr), C.byref(nb), C.byref(st)), "kc_merge_pairs")
         return packed[:nb.value], outo[:nr.value + 1], {f: int(getattr(st, f)) for f, _ in kc_merge_stats._fields_}
+
+    def load_adapters(self, text_or_path, adapter_k=0, blastn_scores=False):
+        """Load an adapter set into this counter (kc_adapters_load): FASTA text as bytes, or the path of a FASTA file as
+        str.  adapter_k 0 = this counter's k; blastn_scores: align with 2/3/5/2/1 instead of 1/1/1/1/1.  The set stays
+        over reset(); loading again replaces it.  Returns the loader's counts."""
+        data = _adapter_text(text_or_path)
+        v = [C.c_uint64(0) for _ in range(4)]
+        check(lib().kc_adapters_load(self._h, data, len(data), adapter_k, _lib.KC_ADAPTERS_BLASTN_SCORES if blastn_scores else 0,
+                                     *[C.byref(x) for x in v]), "kc_adapters_load")
+        return dict(zip(("n_adapters", "n_short", "n_entries", "n_kmers"), (x.value for x in v)))
+
+    def clear_adapters(self):
+        check(lib().kc_adapters_clear(self._h), "kc_adapters_clear")
+
+    def trim_adapters(self, bases, quals, offsets, paired=True, nreads=None):
+        """Adapter trimming of interleaved reads on the device (kc_trim_adapters): Adapters::trim_pair over reads
+        (2p, 2p+1), or with paired=False Adapters::trim per read.  Returns (bases u8, quals u8, offsets int64) as device
+        tensors in the input's layout, ready for merge_pairs or submit_reads, and the counters as a dict.  Host arrays
+        are staged."""
+        import torch
+        pb, dev = _ptr(bases)
+        pq, _ = _ptr(quals)
+        po, _ = _ptr(offsets)
+        n = (len(offsets) - 1) if nreads is None else nreads
+        if dev:
+            total = int(offsets[n].item()) - int(offsets[0].item()) if n else 0
+        else:
+            total = int(offsets[n]) - int(offsets[0]) if n else 0
+        d = "cuda:%d" % self.device
+        ob = torch.empty(max(total, 1), dtype=torch.uint8, device=d)
+        oq = torch.empty(max(total, 1), dtype=torch.uint8, device=d)
+        oo = torch.empty(n + 1, dtype=torch.int64, device=d)
+        nb, st = C.c_uint64(0), kc_trim_stats()
+        torch.cuda.current_stream(self.device).synchronize()  # the input and the fresh arrays are torch's until now
+        check(lib().kc_trim_adapters(self._h, pb, pq, po, n, 1 if dev else 0, _lib.KC_TRIM_PAIRED if paired else 0, ob.data_ptr(),
+                                     oq.data_ptr(), total, oo.data_ptr(), C.byref(nb), C.byref(st)), "kc_trim_adapters")
+        return ob[:nb.value], oq[:nb.value], oo, {f: int(getattr(st, f)) for f, _ in kc_trim_stats._fields_}
 
     def fastq_to_packed(self, text, partial=False):
         """FASTQ text parsed on the device (kc_fastq_to_packed_device): returns (packed u8, offsets int64) as device
@@ -508,6 +548,22 @@ def fastq_to_packed(text, qual_offset=33):
     return packed[:nb.value], offs
 
 
+def _adapter_text(text_or_path):
+    if isinstance(text_or_path, str):
+        with open(text_or_path, "rb") as f:
+            return f.read()
+    return bytes(text_or_path)
+
+
+def adapters_index(text, adapter_k):
+    """Adapter FASTA text (bytes) -> the loader's counts (kc_adapters_index, host only): kept sequences, sequences
+    shorter than adapter_k, entries (both orientations) and distinct k-mers."""
+    data = _adapter_text(text)
+    v = [C.c_uint64(0) for _ in range(4)]
+    check(lib().kc_adapters_index(data, len(data), adapter_k, *[C.byref(x) for x in v]), "kc_adapters_index")
+    return dict(zip(("n_adapters", "n_short", "n_entries", "n_kmers"), (x.value for x in v)))
+
+
 def fastq_pairs(text1, text2=None):
     """Paired FASTQ text (bytes; text2 None = text1 interleaved) -> interleaved ASCII (bases u8, quals u8, offsets u64), the
     input of KmerCounter.merge_pairs (kc_fastq_pairs, host only)."""
@@ -527,12 +583,20 @@ def fastq_pairs(text1, text2=None):
 
 
 def analyze_kmers_paired(kmer_len, qual_offset, bases, quals, offsets, dmin_thres=2, device=0, max_elems=0, tuning=None,
-                         min_kmer_len=0):
+                         min_kmer_len=0, adapters=None, blastn_scores=False, adapter_k=0):
     """merge_reads' pair loop then analyze_kmers for one shard: interleaved pairs are merged on the device
     (kc_merge_pairs), the merged read cache is counted (kc_submit_packed_reads).  Returns sorted results, the counter's
-    stats and the merge's counters."""
+    stats and the merge's counters.  adapters (FASTA bytes, or a path as str): the pairs are adapter-trimmed on the
+    device first (kc_trim_adapters) with k-mers of adapter_k (0: min_kmer_len, else kmer_len), and the merge's
+    counters carry the trim's under "trim"."""
     with KmerCounter(kmer_len, qual_offset, dmin_thres, device=device, max_elems=max_elems, tuning=tuning) as kc:
+        tst = None
+        if adapters is not None:
+            kc.load_adapters(adapters, adapter_k or min_kmer_len, blastn_scores)
+            bases, quals, offsets, tst = kc.trim_adapters(bases, quals, offsets, paired=True)
         packed, offs, mst = kc.merge_pairs(bases, quals, offsets, min_kmer_len=min_kmer_len)
+        if tst is not None:
+            mst["trim"] = tst
         kc.submit_packed_reads(packed, offs, nreads=mst["out_reads"])
         kc.flush()
         res = kc.sorted_results()
@@ -551,12 +615,19 @@ def analyze_kmers_fastq(kmer_len, qual_offset, text, dmin_thres=2, device=0, max
 
 
 def analyze_kmers_fastq_paired(kmer_len, qual_offset, text1, text2=None, dmin_thres=2, device=0, max_elems=0, tuning=None,
-                               min_kmer_len=0):
+                               min_kmer_len=0, adapters=None, blastn_scores=False, adapter_k=0):
     """analyze_kmers_paired from paired FASTQ text (text2 None = text1 interleaved): parsed on the device
-    (kc_fastq_pairs_device), merged (kc_merge_pairs), counted.  Returns sorted results, stats and the merge's counters."""
+    (kc_fastq_pairs_device), merged (kc_merge_pairs), counted.  Returns sorted results, stats and the merge's counters.
+    adapters: as for analyze_kmers_paired -- parse, trim (kc_trim_adapters), merge and count, all in device memory."""
     with KmerCounter(kmer_len, qual_offset, dmin_thres, device=device, max_elems=max_elems, tuning=tuning) as kc:
         bases, quals, offs = kc.fastq_pairs(text1, text2)
+        tst = None
+        if adapters is not None:
+            kc.load_adapters(adapters, adapter_k or min_kmer_len, blastn_scores)
+            bases, quals, offs, tst = kc.trim_adapters(bases, quals, offs, paired=True)
         packed, moffs, mst = kc.merge_pairs(bases, quals, offs, min_kmer_len=min_kmer_len)
+        if tst is not None:
+            mst["trim"] = tst
         kc.submit_packed_reads(packed, moffs, nreads=mst["out_reads"])
         kc.flush()
         res = kc.sorted_results()
