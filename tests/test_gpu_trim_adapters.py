@@ -301,3 +301,105 @@ def test_mates_of_length_0_and_1_through_the_merge():
         packed, offs, mst = kc.merge_pairs(gb, gq, go, min_kmer_len=21)
     assert {s: mst[s] for s in want if s in mst} == {s: want[s] for s in want if s in mst}
     assert np.array_equal(packed.cpu().numpy(), want_p) and np.array_equal(offs.cpu().numpy().view(np.uint64), want_o)
+
+
+# ---- the seed kernel's own edges -----------------------------------------------------------------------------------------
+LONG_AD = [s for s in FA_SEQS if len(s) >= 60][0]
+
+
+@pytest.mark.parametrize("k", [1, 16, 27, 28, 29, 31, 32])
+def test_seed_k(k):
+    """k = 1 is the smallest the loader takes (there every fourth base is a seed, so the random reads are kept short for
+    the model's sake); 29..32 need the eighth gathered byte, 32 the whole key.  Each k also gets hand-built reads whose
+    only indexed k-mer differs from one that is not indexed in a single base."""
+    kw = dict(read_len=40, frag_lo=20, frag_hi=80) if k == 1 else {}
+    b, q, o = M.random_pairs(300 + k, 2000, FA_SEQS, **kw)
+    st = check_same(FA, k, k % 2 == 0, b, q, o, what="adapter_k %d, 2000 pairs" % k)
+    assert st["trimmed"] > 200 and st["alignments"] >= st["trimmed"]
+    if k == 1:
+        # the adapter "A" indexes A and its complement T.  The reads hold C or G at every stride position and anything in
+        # between, so nothing is found, until one stride position gets the A (or T) that differs from the C there in
+        # that one base; a neighbour of the stride changed the same way stays unseen
+        rng = np.random.default_rng(1)
+        text = b">one\nA\n"
+        ads = M.AdapterSet(text, 1)
+        reads = []
+        for ln in (1, 4, 5, 9, 40, 225, 229):
+            r = list(M._rand_seq(rng, ln))
+            r[0::4] = M._rand_seq(rng, len(r[0::4]), "CG")
+            reads.append("".join(r))
+            for pos in (0, 4, 8, 224, 228, 1, 5, 223):
+                if pos < ln:
+                    v = list(r)
+                    v[pos] = "AT"[pos % 8 == 4]
+                    reads.append("".join(v))
+        reads += reads[:len(reads) % 2]
+        b, q, o = M.reads_to_arrays(reads, seed=1)
+        per = M.trim_per_read(ads, b, o)
+        nal = {r: x[2] for r, x in zip(reads, per)}
+        assert all((nal[r] > 0) == any(c in "AT" for c in r[0::4]) for r in reads) and 10 < sum(1 for v in nal.values() if v) < len(nal) - 10
+        check_same(text, 1, False, b, q, o, modes=(False, True), what="adapter_k 1, one base")
+        return
+    # one adapter of exactly k bases; a read holding it, and reads holding it with one base changed: the last one (which a
+    # short mask would not see), the first, and the base behind it (which a long mask would see)
+    rng = np.random.default_rng(k)
+    while True:
+        ad = M._rand_seq(rng, k)
+        if ad != M.revcomp(ad.encode()).decode():
+            break
+    text = (">one\n%s\n" % ad).encode()
+    ads = M.AdapterSet(text, k)
+    oth = lambda c: "ACGT"[("ACGT".index(c) + 1) % 4]
+    reads = []
+    for tail in "ACGT":
+        fill = tail + M._no_seed_filler(rng, ads, 60)
+        reads += [ad + fill, ad[:-1] + oth(ad[-1]) + fill, oth(ad[0]) + ad[1:] + fill, ad[:-1] + oth(oth(ad[-1])) + fill]
+    reads += [M._no_seed_filler(rng, ads, 8) + r for r in reads[:8]]
+    b, q, o = M.reads_to_arrays(reads, seed=k)
+    per = M.trim_per_read(ads, b, o)
+    assert [x[2] for x in per[:4]] == [1, 0, 0, 0] and sum(x[2] for x in per) == 6
+    check_same(text, k, False, b, q, o, modes=(False, True), what="adapter_k %d, one k-mer" % k)
+
+
+@pytest.mark.parametrize("k", [21, 29, 32])
+def test_seed_positions(k):
+    ads = M.AdapterSet(FA, k)
+    fam = M.seed_position_reads(ads, LONG_AD, seed=60 + k)
+    reads = [r for r, _, _ in fam]
+    b, q, o = M.reads_to_arrays(reads + reads[:len(reads) % 2], seed=k)
+    st = check_same(FA, k, False, b, q, o, what="seed positions, k %d" % k)
+    assert st["alignments"] >= sum(1 for _, _, hit in fam if hit) > 30
+
+
+@pytest.mark.parametrize("k", [29, 30, 31, 21])
+def test_last_read_ends_the_input(k):
+    """device arrays sized exactly: the last read's last word has 1-3 bytes (k = 21: a read of 4m + 1 whose last k-mer
+    starts on the stride), and its only seed is its last k-mer"""
+    ads = M.AdapterSet(FA, k)
+    rng = np.random.default_rng(k)
+    for m in (0, 1, 13, 56, 57):
+        ln = 4 * m + k
+        assert ln % 4 in (1, 2, 3)
+        last = M._no_seed_filler(rng, ads, 4 * m) + LONG_AD[:k]
+        reads = [M._no_seed_filler(rng, ads, 50), last]
+        b, q, o = M.reads_to_arrays(reads, seed=m)
+        assert M.trim_per_read(ads, b, o)[1][2] == 1
+        check_same(FA, k, False, b, q, o, what="last read of %d" % ln)
+        # and unpaired with the odd read alone
+        b, q, o = M.reads_to_arrays([last], seed=m)
+        check_same(FA, k, True, b, q, o, modes=(False,), what="only read of %d" % ln)
+
+
+def test_any_byte_is_legal():
+    b, q, o = M.random_pairs(77, 3000, FA_SEQS)
+    rng = np.random.default_rng(78)
+    q = rng.integers(0, 256, len(q)).astype(np.uint8)
+    odd = np.frombuffer(b"acgtnNRYKMSWBDHVUu0123456789.-*@ \x00\xff", dtype=np.uint8)
+    at = rng.integers(0, len(b), len(b) // 25)
+    b[at] = rng.choice(odd, len(at))
+    lo = rng.integers(0, len(o) - 1, 300)  # whole reads in lower case
+    for r in lo:
+        b[int(o[r]):int(o[r + 1])] |= 0x20
+    st = check_same(FA, 21, False, b, q, o, what="any byte")
+    assert st["trimmed"] > 500
+    check_same(FA, 31, True, b, q, o, modes=(True,), device_input=False, what="any byte, k 31, 2/3 scores")

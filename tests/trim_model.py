@@ -416,3 +416,94 @@ def random_pairs(seed, npairs, adapters, read_len=150, frag_lo=60, frag_hi=400, 
     bases = np.frombuffer("".join(bs).encode(), dtype=np.uint8).copy()
     quals = np.frombuffer(b"".join(qs), dtype=np.uint8).copy()
     return bases, quals, np.array(offs, dtype=np.uint64)
+
+
+# ---- per-read results and composed batches -----------------------------------------------------------------------------
+def trim_per_read(ads, bases, offsets):
+    """trim()'s answer for every read: [(new length, trimmed, alignments)], the per_read list of trim_reads"""
+    bases = np.asarray(bases, dtype=np.uint8)
+    offsets = [int(o) for o in offsets]
+    return [trim(ads, bases[offsets[r]:offsets[r + 1]].tobytes()) for r in range(len(offsets) - 1)]
+
+
+class TrimItems:
+    """The model's output read by read for a base set of reads.  Trimming is independent per pair when paired and per
+    read when not, so the expected output of any arrangement of the base set's pairs (or reads) is a gather."""
+
+    def __init__(self, ads, bases, quals, offsets, per_read=None):
+        self.bases = np.asarray(bases, dtype=np.uint8)
+        self.quals = np.asarray(quals, dtype=np.uint8)
+        o = np.asarray(offsets).astype(np.int64)
+        self.start, self.len = o[:-1], np.diff(o)
+        self.per_read = per_read if per_read is not None else trim_per_read(ads, self.bases, o)
+        self.cut = np.array([x[0] for x in self.per_read], dtype=np.int64)
+        self.trimmed = np.array([x[1] for x in self.per_read], dtype=bool)
+        self.naligns = np.array([x[2] for x in self.per_read], dtype=np.int64)
+        n = len(self.len) // 2 * 2
+        self.pair_len = self.cut.copy()  # final lengths under trim_pair's rule (an odd last read keeps its own)
+        a, b = self.cut[0:n:2], self.cut[1:n:2]
+        both = (self.trimmed[0:n:2] | self.trimmed[1:n:2]) & (a > 1) & (b > 1)
+        self.pair_len[0:n:2] = np.where(both, np.minimum(a, b), a)
+        self.pair_len[1:n:2] = np.where(both, np.minimum(a, b), b)
+
+    def compose(self, order, paired):
+        """order: pair indices when paired, read indices when not.  Returns (bases, quals, offsets u64, expected bases,
+        expected quals, expected offsets int64, stats)."""
+        from merge_model import gather_segments
+        order = np.asarray(order, dtype=np.int64)
+        reads = np.stack([2 * order, 2 * order + 1], axis=1).reshape(-1) if paired else order
+        ln = self.len[reads]
+        offs = np.zeros(len(reads) + 1, dtype=np.uint64)
+        offs[1:] = np.cumsum(ln)
+        bases = gather_segments(self.bases, self.start[reads], ln)
+        quals = gather_segments(self.quals, self.start[reads], ln)
+        fl = (self.pair_len if paired else self.cut)[reads]
+        oo = np.zeros(len(reads) + 1, dtype=np.int64)
+        oo[1:] = np.cumsum(fl)
+        t = self.trimmed[reads]
+        st = dict(reads=len(reads), trimmed=int(t.sum()), bases_trimmed=int((ln - self.cut[reads])[t].sum()),
+                  reads_removed=int((t & (self.cut[reads] == 0)).sum()), alignments=int(self.naligns[reads].sum()), out_bases=int(oo[-1]))
+        return bases, quals, offs, gather_segments(self.bases, self.start[reads], fl), gather_segments(self.quals, self.start[reads], fl), oo, st
+
+
+# ---- seeded families aimed at the seed kernel's own structure ------------------------------------------------------------
+def reads_to_arrays(reads, quals=None, seed=0):
+    """[bytes / str] -> bases, quals (seeded 35..73 unless given), offsets u64"""
+    reads = [r.encode() if isinstance(r, str) else bytes(r) for r in reads]
+    b = np.frombuffer(b"".join(reads), dtype=np.uint8).copy()
+    q = np.random.default_rng(seed).integers(35, 74, len(b)).astype(np.uint8) if quals is None else np.asarray(quals, dtype=np.uint8)
+    return b, q, np.cumsum([0] + [len(r) for r in reads]).astype(np.uint64)
+
+
+def _no_seed_filler(rng, ads, n):
+    """n random bases none of whose k-mers is in the index (a fresh draw until that holds)"""
+    while True:
+        s = _rand_seq(rng, n)
+        codes = KCODE[np.frombuffer(s.encode(), dtype=np.uint8)].tobytes()
+        if all(codes[i:i + ads.k] not in ads.index for i in range(max(0, n - ads.k + 1))):
+            return s
+
+
+def seed_position_reads(ads, adapter, seed=61):
+    """Reads holding exactly one k-mer of the index, the first k bases of `adapter`, at chosen positions: multiples of 4
+    around the seed kernel's rounds of 224 bases, and their neighbours, which the stride of 4 never visits.  Returns
+    [(read, position, position % 4 == 0)]."""
+    rng = np.random.default_rng(seed)
+    k = ads.k
+    kmer = adapter[:k]
+    out = []
+    for ln in (k - 1, k, k + 1, 223 + k, 224 + k, 225 + k, 448 + k, 449 + k, 450 + k, 451 + k):
+        if ln < k:
+            out.append((_no_seed_filler(rng, ads, ln), -1, False))
+            continue
+        cand = [0, 4, 216, 220, 224, 228, 444, 448, ln - k]
+        cand += [1, 2, 3, 5, 215, 217, 221, 222, 223, 225, 226, 227, 443, 445, 447, 449, ln - k - 1]
+        for pos in sorted(set(c for c in cand if 0 <= c <= ln - k)):
+            while True:
+                s = _no_seed_filler(rng, ads, pos) + kmer + _no_seed_filler(rng, ads, ln - k - pos)
+                codes = KCODE[np.frombuffer(s.encode(), dtype=np.uint8)].tobytes()
+                hits = [i for i in range(ln - k + 1) if codes[i:i + k] in ads.index]
+                if hits == [pos]:
+                    break
+            out.append((s, pos, pos % 4 == 0))
+    return out
