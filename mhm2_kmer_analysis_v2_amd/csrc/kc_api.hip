@@ -45,11 +45,53 @@ static int hip_fail(hipError_t e, const char *what, int line) {
     if (e_ != hipSuccess) return hip_fail(e_, #call, __LINE__); \
   } while (0)
 
+// ---- small host helpers the context itself needs ------------------------------------------------
+// a device scratch buffer that only ever grows: reserve() frees and allocates again when it is too small (the contents
+// are lost then) and leaves {nullptr, 0} behind when the allocation fails
+struct DevBuf {
+  uint8_t *p;
+  size_t cap;  // bytes
+  hipError_t release() {
+    const hipError_t e = p ? hipFree(p) : hipSuccess;
+    if (e == hipSuccess) p = nullptr, cap = 0;
+    return e;
+  }
+  int reserve(size_t bytes) {
+    if (bytes <= cap) return KC_OK;
+    HIPCHK(release());
+    HIPCHK(hipMalloc((void **)&p, bytes));
+    cap = bytes;
+    return KC_OK;
+  }
+  template <class T> T *as() const { return (T *)p; }
+};
+
+// Bump carver over one scratch allocation, every piece aligned to 256 bytes.  A layout is a few lines that name its
+// pieces; they run twice, on Carver{nullptr} for the size (`used`) and on Carver{base} for the pointers.
+struct Carver {
+  uint8_t *base;
+  size_t used;
+  template <class T> T *take(size_t n) {
+    T *p = (T *)((uintptr_t)base + used);
+    used += (n * sizeof(T) + 255) & ~size_t(255);
+    return p;
+  }
+};
+
+#define KCTRY(call)           \
+  do {                        \
+    const int rc_ = (call);   \
+    if (rc_) return rc_;      \
+  } while (0)
+
+// ---- kernel timing kinds and their reported names -------------------------------------------------
 enum { KT_EXTRACT_INSERT = 0, KT_EXTRACT_BIN, KT_INSERT_RECORDS, KT_FINALIZE, KT_TILE_FIRST, KT_REHASH, KT_L1_READS, KT_L1_RECORDS,
        KT_L2_SPLIT, KT_COUNT_REGIONS, KT_FALLBACK, KT_SHARD_PACK, KT_L1_READS_UQ, KT_L1_READS16, KT_L2_REC6, KT_BIN16, KT_L1_WIRE6,
        KT_MERGE_DECIDE, KT_MERGE_DECIDE_LONG, KT_MERGE_SCAN, KT_MERGE_WRITE, KT_MERGE_WRITE_LONG, KT_FQ_COUNT, KT_FQ_SCAN,
        KT_FQ_INDEX, KT_FQ_CHECK, KT_FQ_DETAIL, KT_FQ_SUMS, KT_FQ_WRITE_PACKED, KT_FQ_WRITE_PAIRS, KT_TRIM_SEED, KT_TRIM_ALIGN,
        KT_TRIM_SIZES, KT_TRIM_SCAN, KT_TRIM_WRITE, KT_COUNT };
+// KT_FQ_SCAN, KT_MERGE_SCAN and KT_TRIM_SCAN label the three uses of the one shared kc_scan_kernel (kc_scan.hpp); their
+// strings keep the names the uses were first reported under
 static const char *const kt_names[KT_COUNT] = {"kc_extract_kernel<insert>", "kc_bin_reads_kernel", "kc_insert_records_kernel",
                                                "kc_finalize_kernel", "kc_tile_first_kernel", "kc_rehash_kernel",
                                                "kc_l1_reads_kernel", "kc_l1_records_kernel", "kc_l2_split_kernel",
@@ -85,9 +127,7 @@ struct kc_ctx {
   uint64_t *d_out_plan;  // hole-closing plan + per-workgroup tails of the block-wise result output
   size_t tile_first_cap;
   // staging for host-resident input (single slot: the '_'-joined blocks of kc_submit_seq_block)
-  uint8_t *d_stage_bases, *d_stage_quals;
-  uint64_t *d_stage_offsets;
-  size_t stage_bytes, stage_reads;
+  DevBuf stage_bases, stage_quals, stage_offsets;
   // host-resident reads: two device slots and two pinned host slots, copies on a stream of their own (host_pipe_*)
   struct {
     uint8_t *d_bases[2], *d_quals[2], *h_bases[2], *h_quals[2];
@@ -116,28 +156,25 @@ struct kc_ctx {
   double arena_probe_tbps;  // rate of level 1's write pattern on the arena pick_fast_arena chose (0: no probe ran)
   kc_synth_table *d_synth;
   // scratch of the reference-wire entry points (kc_build_supermers, kc_submit_packed_supermers)
-  uint8_t *d_sm_bytes;    // block / unpacked block
-  uint8_t *d_sm_packed;   // packed block / packed supermers
-  int32_t *d_sm_targets;
-  SupermerInfo *d_sm_out;
+  DevBuf sm_bytes;        // block / unpacked block
+  DevBuf sm_packed;       // packed block / packed supermers
+  DevBuf sm_targets;      // int32_t
+  DevBuf sm_out;          // SupermerInfo
   uint32_t *d_sm_ctr;     // n_out, n_kmers, too_long, + a u64 "bad character" flag behind them
-  size_t sm_bytes_cap, sm_packed_cap, sm_targets_cap, sm_out_cap;
   // scratch of kc_merge_pairs: per-pair decisions and sizes, the long-pair list, per-tile sums, statistics
-  uint8_t *d_mg;
-  size_t mg_cap;
+  DevBuf mg;
   // the adapter set (kc_adapters_load, kc_trim.hpp): slots, records, entry offsets and entry bytes in one allocation;
   // it belongs to the context, not to a pass (kc_reset keeps it)
   uint8_t *d_ad;
   bool ad_loaded;
   int ad_k, ad_blastn;
   uint32_t ad_entries, ad_lg_slots;
-  size_t ad_off_recs, ad_off_ent, ad_off_bytes;
+  const uint32_t *ad_recs, *ad_ent_off;  // inside d_ad, like ad_bytes
+  const uint8_t *ad_bytes;
   // scratch of kc_trim_adapters: per-read results, final lengths, the hit list, per-tile sums, statistics
-  uint8_t *d_tr;
-  size_t tr_cap;
+  DevBuf tr;
   // kc_fastq_*_device scratch: the staged text, the tile counts and control words, the line and record tables
-  uint8_t *d_fq_text, *d_fq_tiles, *d_fq_recs;
-  size_t fq_text_cap, fq_tiles_cap, fq_recs_cap;
+  DevBuf fq_text, fq_tiles, fq_recs;
   // host-side stats
   uint64_t num_reads, num_bases, num_gpu_calls;
   uint64_t purged, sum_counts, unique_at_finalize;
@@ -274,6 +311,17 @@ static void drain_kernel_times(kc_ctx *c) {  // stream must be idle
     (void)hipEventDestroy(p.stop);
   }
   c->kt_pend.clear();
+}
+
+// one launch of the read front end (kc_api_frontend.hpp): the timer's scope, the launch, the launch-error check
+template <class K, class... A>
+static int launch_timed(kc_ctx *c, int kind, K kernel, dim3 grid, dim3 block, size_t lds, const A &...args) {
+  {
+    KernelTimer kt(c, kind);
+    hipLaunchKernelGGL(kernel, grid, block, lds, c->stream, args...);
+  }
+  HIPCHK(hipGetLastError());
+  return KC_OK;
 }
 
 static uint64_t next_pow2(uint64_t v) {
@@ -542,21 +590,12 @@ extern "C" void kc_destroy(kc_ctx *c) {
   if (c->h_ctrs) (void)hipHostFree(c->h_ctrs);
   if (c->d_tile_first) (void)hipFree(c->d_tile_first);
   if (c->d_out_plan) (void)hipFree(c->d_out_plan);
-  if (c->d_stage_bases) (void)hipFree(c->d_stage_bases);
-  if (c->d_stage_quals) (void)hipFree(c->d_stage_quals);
-  if (c->d_stage_offsets) (void)hipFree(c->d_stage_offsets);
+  for (DevBuf *b : {&c->stage_bases, &c->stage_quals, &c->stage_offsets, &c->sm_bytes, &c->sm_packed, &c->sm_targets, &c->sm_out,
+                    &c->mg, &c->tr, &c->fq_text, &c->fq_tiles, &c->fq_recs})
+    (void)b->release();
   if (c->d_synth) (void)hipFree(c->d_synth);
-  if (c->d_sm_bytes) (void)hipFree(c->d_sm_bytes);
-  if (c->d_sm_packed) (void)hipFree(c->d_sm_packed);
-  if (c->d_sm_targets) (void)hipFree(c->d_sm_targets);
-  if (c->d_sm_out) (void)hipFree(c->d_sm_out);
   if (c->d_sm_ctr) (void)hipFree(c->d_sm_ctr);
-  if (c->d_mg) (void)hipFree(c->d_mg);
   if (c->d_ad) (void)hipFree(c->d_ad);
-  if (c->d_tr) (void)hipFree(c->d_tr);
-  if (c->d_fq_text) (void)hipFree(c->d_fq_text);
-  if (c->d_fq_tiles) (void)hipFree(c->d_fq_tiles);
-  if (c->d_fq_recs) (void)hipFree(c->d_fq_recs);
   host_pipe_free(c);
   free_ctg(c);
   bk_free(c, false);
@@ -1758,24 +1797,29 @@ static int raw_kmer_stats(kc_ctx *c, const uint64_t *d_offsets, uint64_t nreads,
   return KC_OK;
 }
 
-static int ensure_stage(kc_ctx *c, size_t bytes, size_t reads, bool need_quals) {
-  if (bytes + 64 > c->stage_bytes) {
-    if (c->d_stage_bases) HIPCHK(hipFree(c->d_stage_bases));
-    if (c->d_stage_quals) HIPCHK(hipFree(c->d_stage_quals));
-    c->d_stage_bases = c->d_stage_quals = nullptr;
-    c->stage_bytes = 0;
-    HIPCHK(hipMalloc((void **)&c->d_stage_bases, bytes + 64));
-    HIPCHK(hipMalloc((void **)&c->d_stage_quals, bytes + 64));
-    c->stage_bytes = bytes + 64;
+// A host block of reads (kc_merge_pairs, kc_trim_adapters) to the staging buffers: *bases, *quals and *offsets then point
+// at the device copies, the offsets counted from the block's first base.  The stream is idle on return.
+static int stage_host_reads(kc_ctx *c, const uint8_t **bases, const uint8_t **quals, const uint64_t **offsets, uint64_t nreads) {
+  const uint64_t *offs = *offsets;
+  const uint64_t first = offs[0], last = offs[nreads];
+  if (last < first) return KC_ERR_INVALID_ARG;
+  const size_t bytes = (size_t)(last - first);
+  KCTRY(c->stage_bases.reserve(bytes + 64));
+  KCTRY(c->stage_quals.reserve(bytes + 64));
+  KCTRY(c->stage_offsets.reserve((nreads + 1) * 8));
+  std::vector<uint64_t> rel(nreads + 1);
+  for (uint64_t r = 0; r <= nreads; r++) {
+    if (offs[r] < first || offs[r] > last) return KC_ERR_INVALID_ARG;
+    rel[r] = offs[r] - first;
   }
-  (void)need_quals;
-  if (reads + 1 > c->stage_reads) {
-    if (c->d_stage_offsets) HIPCHK(hipFree(c->d_stage_offsets));
-    c->d_stage_offsets = nullptr;
-    c->stage_reads = 0;
-    HIPCHK(hipMalloc((void **)&c->d_stage_offsets, (reads + 1) * 8));
-    c->stage_reads = reads + 1;
-  }
+  HIPCHK(hipStreamSynchronize(c->stream));  // an earlier call's kernels may still read the staging buffers
+  HIPCHK(hipMemcpyAsync(c->stage_bases.p, *bases + first, bytes, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(c->stage_quals.p, *quals + first, bytes, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(c->stage_offsets.p, rel.data(), (nreads + 1) * 8, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));  // rel goes out of scope
+  *bases = c->stage_bases.p;
+  *quals = c->stage_quals.p;
+  *offsets = c->stage_offsets.as<uint64_t>();
   return KC_OK;
 }
 
@@ -2053,890 +2097,7 @@ extern "C" int kc_submit_packed_reads(kc_ctx *c, const uint8_t *packed, const ui
   return submit_reads_impl(c, packed, nullptr, offsets, nreads, on_device, MODE_INSERT, nullptr, 0, FMT_PACKED);
 }
 
-// ---- FASTQ front end (host only) -----------------------------------------------------------------------------------
-// base codes of PackedRead (packed_reads.cpp:99-124): 255 = the reference DIEs
-static void fq_code_table(uint8_t code[256]) {
-  memset(code, 255, 256);
-  const char *acgt = "ACGT";
-  for (int i = 0; i < 4; i++) code[(uint8_t)acgt[i]] = code[(uint8_t)(acgt[i] | 0x20)] = (uint8_t)i;
-  code[(uint8_t)'N'] = code[(uint8_t)'n'] = 4;
-  for (const char *p = "URYKMSWBDHV"; *p; p++) code[(uint8_t)*p] = 4;
-}
-
-// one FASTQ record of text[pos, len): 1 with [sb, sb + *sl) the sequence and [qb, qb + *sl) the qualities, 0 at the end,
-// KC_ERR_INVALID_ARG for a malformed record (kc_last_error names the line)
-struct FqCursor {
-  const char *text;
-  uint64_t len, pos, line_no;
-};
-
-static int fq_next(FqCursor &f, uint64_t *sb, uint64_t *qb, uint64_t *sl) {
-  auto next_line = [&](uint64_t &b, uint64_t &e) -> bool {  // [b, e): the line without its end and trailing white space
-    if (f.pos >= f.len) return false;
-    b = f.pos;
-    while (f.pos < f.len && f.text[f.pos] != '\n') f.pos++;
-    e = f.pos;
-    if (f.pos < f.len) f.pos++;
-    while (e > b && (f.text[e - 1] == '\r' || f.text[e - 1] == ' ' || f.text[e - 1] == '\t')) e--;
-    f.line_no++;
-    return true;
-  };
-  const char *text = f.text;
-  const uint64_t len = f.len;
-  uint64_t b0, e0, b1, e1, b2, e2, b3, e3;
-  if (!next_line(b0, e0)) return 0;
-  if (e0 == b0 && f.pos >= len) return 0;  // a final empty line
-  if (!next_line(b1, e1) || !next_line(b2, e2) || !next_line(b3, e3)) {
-    snprintf(g_last_error, sizeof(g_last_error), "FASTQ ends inside the record that starts at line %llu", (unsigned long long)(f.line_no - (f.line_no - 1) % 4));
-    return KC_ERR_INVALID_ARG;
-  }
-  if (e0 == b0 || text[b0] != '@') {
-    snprintf(g_last_error, sizeof(g_last_error), "Invalid FASTQ: expected read name (@) at line %llu", (unsigned long long)(f.line_no - 3));
-    return KC_ERR_INVALID_ARG;
-  }
-  if (e2 == b2 || text[b2] != '+') {
-    snprintf(g_last_error, sizeof(g_last_error), "Invalid FASTQ: expected '+' at line %llu", (unsigned long long)(f.line_no - 1));
-    return KC_ERR_INVALID_ARG;
-  }
-  if (e1 - b1 != e3 - b3) {
-    snprintf(g_last_error, sizeof(g_last_error), "Invalid FASTQ: sequence length %llu != %llu quals length at line %llu",
-             (unsigned long long)(e1 - b1), (unsigned long long)(e3 - b3), (unsigned long long)(f.line_no - 2));
-    return KC_ERR_INVALID_ARG;
-  }
-  *sb = b1;
-  *qb = b3;
-  *sl = e1 - b1;
-  return 1;
-}
-
-extern "C" int kc_fastq_to_packed(const char *text, uint64_t len, int qual_offset, uint8_t *packed, uint64_t packed_capacity,
-                                  uint64_t *offsets, uint64_t reads_capacity, uint64_t *nreads, uint64_t *nbytes) {
-  if ((len && !text) || !nreads || !nbytes) return KC_ERR_INVALID_ARG;
-  uint8_t code[256];
-  fq_code_table(code);
-  uint64_t nr = 0, nb = 0;
-  bool fits = true;
-  FqCursor f{text, len, 0, 0};
-  if (offsets && reads_capacity + 1 > 0) offsets[0] = 0;
-  for (;;) {
-    uint64_t b1, b3, sl;
-    const int r = fq_next(f, &b1, &b3, &sl);
-    if (r < 0) return r;
-    if (r == 0) break;
-    const bool room = fits && packed && offsets && nr < reads_capacity && nb + sl <= packed_capacity;
-    for (uint64_t i = 0; i < sl; i++) {
-      const uint8_t cb = code[(uint8_t)text[b1 + i]];
-      if (cb == 255) {
-        snprintf(g_last_error, sizeof(g_last_error), "Illegal char in comp nucleotide (int=%d) at line %llu", (int)(uint8_t)text[b1 + i],
-                 (unsigned long long)(f.line_no - 2));
-        return KC_ERR_BAD_BASE;
-      }
-      if (room) {
-        int q = (int)(uint8_t)text[b3 + i] - qual_offset;
-        if (q > 31) q = 31;
-        packed[nb + i] = (uint8_t)(cb | ((uint8_t)q << 3));  // like the reference's (unsigned char)std::min(q, 31) << 3
-      }
-    }
-    if (!room) fits = false;
-    nb += sl;
-    nr++;
-    if (room) offsets[nr] = nb;
-  }
-  *nreads = nr;
-  *nbytes = nb;
-  if (!fits && (nr || nb)) {
-    snprintf(g_last_error, sizeof(g_last_error), "%llu reads with %llu bases do not fit the arrays", (unsigned long long)nr, (unsigned long long)nb);
-    return KC_ERR_CAPACITY;
-  }
-  return KC_OK;
-}
-
-extern "C" int kc_fastq_pairs(const char *text1, uint64_t len1, const char *text2, uint64_t len2, uint8_t *bases, uint8_t *quals,
-                              uint64_t capacity, uint64_t *offsets, uint64_t reads_capacity, uint64_t *nreads, uint64_t *nbytes) {
-  if ((len1 && !text1) || (len2 && !text2) || !nreads || !nbytes) return KC_ERR_INVALID_ARG;
-  uint8_t code[256];
-  fq_code_table(code);
-  FqCursor f[2] = {{text1, len1, 0, 0}, {text2, len2, 0, 0}};
-  const bool two = text2 != nullptr;
-  uint64_t nr = 0, nb = 0;
-  bool fits = true;
-  if (offsets && reads_capacity + 1 > 0) offsets[0] = 0;
-  for (;;) {
-    FqCursor &fc = f[two ? (nr & 1) : 0];
-    uint64_t b1, b3, sl;
-    const int r = fq_next(fc, &b1, &b3, &sl);
-    if (r < 0) return r;
-    if (r == 0) {
-      if (two && (nr & 1)) {
-        snprintf(g_last_error, sizeof(g_last_error), "the second file ends after %llu records, the first has more", (unsigned long long)(nr / 2));
-        return KC_ERR_INVALID_ARG;
-      }
-      if (two) {  // the first file ended: the second must end too
-        uint64_t x, y, z;
-        const int r2 = fq_next(f[1], &x, &y, &z);
-        if (r2 < 0) return r2;
-        if (r2 > 0) {
-          snprintf(g_last_error, sizeof(g_last_error), "the first file ends after %llu records, the second has more", (unsigned long long)(nr / 2));
-          return KC_ERR_INVALID_ARG;
-        }
-      }
-      break;
-    }
-    const bool room = fits && bases && quals && offsets && nr < reads_capacity && nb + sl <= capacity;
-    for (uint64_t i = 0; i < sl; i++) {
-      if (code[(uint8_t)fc.text[b1 + i]] == 255) {
-        snprintf(g_last_error, sizeof(g_last_error), "Illegal char in comp nucleotide (int=%d) at line %llu of file %d",
-                 (int)(uint8_t)fc.text[b1 + i], (unsigned long long)(fc.line_no - 2), two ? (int)(nr & 1) + 1 : 1);
-        return KC_ERR_BAD_BASE;
-      }
-    }
-    if (room) {
-      memcpy(bases + nb, fc.text + b1, sl);
-      memcpy(quals + nb, fc.text + b3, sl);
-    } else {
-      fits = false;
-    }
-    nb += sl;
-    nr++;
-    if (room) offsets[nr] = nb;
-  }
-  if (nr & 1) {
-    snprintf(g_last_error, sizeof(g_last_error), "an interleaved file of %llu records: pairs need an even count", (unsigned long long)nr);
-    return KC_ERR_INVALID_ARG;
-  }
-  *nreads = nr;
-  *nbytes = nb;
-  if (!fits && (nr || nb)) {
-    snprintf(g_last_error, sizeof(g_last_error), "%llu reads with %llu bases do not fit the arrays", (unsigned long long)nr, (unsigned long long)nb);
-    return KC_ERR_CAPACITY;
-  }
-  return KC_OK;
-}
-
-// ---- FASTQ front end on the device (kc_fastq.hpp) ------------------------------------------------------------------
-static int fq_grow(uint8_t **buf, size_t *cap, size_t need) {
-  if (need <= *cap) return KC_OK;
-  if (*buf) HIPCHK(hipFree(*buf));
-  *buf = nullptr;
-  *cap = 0;
-  HIPCHK(hipMalloc((void **)buf, need));
-  *cap = need;
-  return KC_OK;
-}
-
-// kc_fastq_to_packed_device (two = -1: one file, packed output) and kc_fastq_pairs_device (two = 0: one interleaved
-// file, 1: two files).  The kernels find each file's first structural and first base error; this rebuilds the host
-// parser's walk from them (fq_next's order, and the pairs' alternation), its status and its kc_last_error text.
-static int fq_device(kc_ctx *c, const char *const text_in[2], const uint64_t len_in[2], int two, int on_device, uint32_t flags,
-                     uint8_t *d_packed, uint8_t *d_bases, uint8_t *d_quals, uint64_t capacity, uint64_t *d_offsets,
-                     uint64_t reads_capacity, uint64_t *nreads, uint64_t *nbytes, uint64_t *consumed[2]) {
-  const bool packed = two < 0;
-  const int nf = two > 0 ? 2 : 1;
-  if (!c || !nreads || !nbytes || (flags & ~KC_FASTQ_PARTIAL)) return KC_ERR_INVALID_ARG;
-  for (int i = 0; i < nf; i++)
-    if (len_in[i] && !text_in[i]) return KC_ERR_INVALID_ARG;
-  const bool partial = (flags & KC_FASTQ_PARTIAL) != 0;
-  HIPCHK(hipSetDevice(c->cfg.device));
-  auto up = [](uint64_t x) { return (x + 255) & ~uint64_t(255); };
-  const uint8_t *text[2] = {(const uint8_t *)text_in[0], nf > 1 ? (const uint8_t *)text_in[1] : nullptr};
-  const uint64_t len[2] = {len_in[0], nf > 1 ? len_in[1] : 0};
-  if (!on_device) {  // one copy into context scratch
-    int rc = fq_grow(&c->d_fq_text, &c->fq_text_cap, up(len[0]) + up(len[1]) + 256);
-    if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    for (int i = 0; i < nf; i++) {
-      uint8_t *dst = c->d_fq_text + (i ? up(len[0]) : 0);
-      if (len[i]) HIPCHK(hipMemcpyAsync(dst, text[i], len[i], hipMemcpyHostToDevice, c->stream));
-      text[i] = dst;
-    }
-  }
-  FqFile f[2];
-  memset(f, 0, sizeof(f));
-  uint64_t ntiles_all = 0;
-  for (int i = 0; i < nf; i++) {
-    f[i].text = text[i];
-    f[i].len = len[i];
-    f[i].head = len[i] ? (uint64_t)((uintptr_t)text[i] & 15u) : 0;
-    f[i].ntiles = (f[i].head + len[i] + FQ_TILE - 1) / FQ_TILE;
-    ntiles_all += f[i].ntiles;
-  }
-  int rc = fq_grow(&c->d_fq_tiles, &c->fq_tiles_cap, 2 * FQC_N * 8 + up(ntiles_all * 8));
-  if (rc) return rc;
-  for (int i = 0; i < nf; i++) {
-    f[i].ctl = (uint64_t *)c->d_fq_tiles + i * FQC_N;
-    f[i].tile = (uint64_t *)c->d_fq_tiles + 2 * FQC_N + (i ? f[0].ntiles : 0);
-  }
-  f[1].ctl = (uint64_t *)c->d_fq_tiles + FQC_N;  // (unused with one file, read back all the same)
-  HIPCHK(hipMemsetAsync(c->d_fq_tiles, 0xFF, 2 * FQC_N * 8, c->stream));
-  auto grid = [](uint64_t n) { return dim3((unsigned)std::max<uint64_t>(1, std::min<uint64_t>(n, FQ_MAX_GRID))); };
-  uint8_t last[2] = {'\n', '\n'};
-  for (int i = 0; i < nf; i++) {
-    if (f[i].ntiles) {
-      KernelTimer kt(c, KT_FQ_COUNT);
-      hipLaunchKernelGGL(kc_fq_count_kernel, grid(f[i].ntiles), dim3(FQ_TPB), 0, c->stream, f[i]);
-    }
-    HIPCHK(hipGetLastError());
-    {
-      KernelTimer kt(c, KT_FQ_SCAN);
-      hipLaunchKernelGGL(kc_fq_scan_kernel, dim3(1), dim3(FQ_SCAN_TPB), 0, c->stream, f[i].tile, f[i].ntiles, f[i].ctl + FQC_NNL);
-    }
-    HIPCHK(hipGetLastError());
-    if (len[i]) HIPCHK(hipMemcpyAsync(&last[i], text[i] + len[i] - 1, 1, hipMemcpyDeviceToHost, c->stream));
-  }
-  uint64_t h_ctl[2][FQC_N];
-  HIPCHK(hipMemcpyAsync(h_ctl, c->d_fq_tiles, sizeof(h_ctl), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  for (int i = 0; i < nf; i++) {
-    f[i].nnl = h_ctl[i][FQC_NNL];
-    f[i].nl = f[i].nnl + (len[i] && last[i] != '\n' ? 1 : 0);
-  }
-  if (partial) {  // whole records only: all four lines end in '\n' inside the text
-    uint64_t w = f[0].nnl / 4;
-    if (two == 0) w &= ~uint64_t(1);  // an interleaved file: whole pairs
-    if (two > 0) w = std::min(w, f[1].nnl / 4);
-    for (int i = 0; i < nf; i++) f[i].nl = 4 * w;
-  }
-  uint64_t recs_bytes = 0;
-  for (int i = 0; i < nf; i++) {
-    f[i].nrec = (f[i].nl + 3) / 4;
-    recs_bytes += up(f[i].nnl * 8) + up(f[i].nrec * 8);
-  }
-  const uint64_t nout = two > 0 ? 2 * std::max(f[0].nrec, f[1].nrec) : f[0].nrec;
-  const uint64_t nblk = (nout + FQ_TPB - 1) / FQ_TPB;
-  rc = fq_grow(&c->d_fq_recs, &c->fq_recs_cap, recs_bytes + up(nblk * 8) + 256);
-  if (rc) return rc;
-  {
-    uint8_t *m = c->d_fq_recs;
-    for (int i = 0; i < nf; i++) {
-      f[i].ends = (uint64_t *)m;
-      m += up(f[i].nnl * 8);
-      f[i].slen = (uint64_t *)m;
-      m += up(f[i].nrec * 8);
-    }
-    if (nf == 1) f[1] = f[0];  // the kernels' second file is never read
-    f[1].ctl = (uint64_t *)c->d_fq_tiles + FQC_N;
-  }
-  uint64_t *bsum = (uint64_t *)(c->d_fq_recs + recs_bytes);
-  for (int i = 0; i < nf; i++) {
-    if (f[i].ntiles && f[i].nnl) {
-      KernelTimer kt(c, KT_FQ_INDEX);
-      hipLaunchKernelGGL(kc_fq_index_kernel, grid(f[i].ntiles), dim3(FQ_TPB), 0, c->stream, f[i]);
-    }
-    HIPCHK(hipGetLastError());
-    if (f[i].nrec) {
-      KernelTimer kt(c, KT_FQ_CHECK);
-      hipLaunchKernelGGL(kc_fq_check_kernel, grid((f[i].nrec + FQ_TPB - 1) / FQ_TPB), dim3(FQ_TPB), 0, c->stream, f[i]);
-    }
-    HIPCHK(hipGetLastError());
-    {
-      KernelTimer kt(c, KT_FQ_DETAIL);
-      hipLaunchKernelGGL(kc_fq_detail_kernel, dim3(1), dim3(64), 0, c->stream, f[i]);
-    }
-    HIPCHK(hipGetLastError());
-  }
-  if (nout) {
-    KernelTimer kt(c, KT_FQ_SUMS);
-    hipLaunchKernelGGL(kc_fq_sums_kernel, grid(nblk), dim3(FQ_TPB), 0, c->stream, f[0], f[1], two > 0 ? 1 : 0, nout, bsum);
-  }
-  HIPCHK(hipGetLastError());
-  {
-    KernelTimer kt(c, KT_FQ_SCAN);
-    hipLaunchKernelGGL(kc_fq_scan_kernel, dim3(1), dim3(FQ_SCAN_TPB), 0, c->stream, bsum, nblk, f[0].ctl + FQC_TOTAL);
-  }
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(h_ctl, c->d_fq_tiles, sizeof(h_ctl), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-
-  // the host parser's walk.  Per file: t = the record where fq_next stops (its structural error, or the end after the
-  // sound records), bb = its first record with a bad base if that comes before t.
-  uint64_t t[2] = {0, 0}, bb[2] = {FQ_NONE, FQ_NONE};
-  bool serr[2] = {false, false};
-  for (int i = 0; i < nf; i++) {
-    const uint64_t *k = h_ctl[i];
-    const uint64_t valid = f[i].nrec - (f[i].nrec && k[FQC_END] == 1 ? 1 : 0);
-    serr[i] = k[FQC_STRUCT] != FQ_NONE;
-    t[i] = serr[i] ? k[FQC_STRUCT] : valid;
-    if (k[FQC_BASE] < t[i]) bb[i] = k[FQC_BASE];
-    if (consumed[i]) *consumed[i] = partial ? k[FQC_CONSUMED] : len[i];
-  }
-  enum { EV_BASE, EV_STRUCT, EV_END } ev = EV_END;
-  int evf = 0;     // the file the walk stops in
-  uint64_t g = 0;  // output records written before it stops
-  if (two > 0) {
-    // record j of file 1 is step 2j of the walk, of file 2 step 2j + 1
-    uint64_t best = FQ_NONE;
-    auto take = [&](uint64_t step, int e, int fi) {
-      if (step < best) {
-        best = step;
-        ev = (decltype(ev))e;
-        evf = fi;
-      }
-    };
-    for (int i = 0; i < 2; i++) {
-      if (bb[i] != FQ_NONE) take(2 * bb[i] + i, EV_BASE, i);
-      take(2 * t[i] + i, serr[i] ? EV_STRUCT : EV_END, i);
-    }
-    g = best;
-  } else {
-    ev = bb[0] != FQ_NONE ? EV_BASE : serr[0] ? EV_STRUCT : EV_END;
-    g = ev == EV_BASE ? bb[0] : t[0];
-  }
-  int status = KC_OK;
-  uint64_t part_rec = FQ_NONE, part_len = 0;
-  const uint64_t *k = h_ctl[evf];
-  const uint64_t r = two > 0 ? g >> 1 : g;  // the record of file evf
-  if (ev == EV_BASE) {
-    status = KC_ERR_BAD_BASE;
-    if (packed) {
-      snprintf(g_last_error, sizeof(g_last_error), "Illegal char in comp nucleotide (int=%d) at line %llu", (int)k[FQC_BYTE],
-               (unsigned long long)(4 * r + 2));
-      part_rec = g;
-      part_len = k[FQC_POS];
-    } else {
-      snprintf(g_last_error, sizeof(g_last_error), "Illegal char in comp nucleotide (int=%d) at line %llu of file %d", (int)k[FQC_BYTE],
-               (unsigned long long)(4 * r + 2), evf + 1);
-    }
-  } else if (ev == EV_END && two > 0 && evf == 1) {
-    status = KC_ERR_INVALID_ARG;
-    snprintf(g_last_error, sizeof(g_last_error), "the second file ends after %llu records, the first has more", (unsigned long long)t[1]);
-  } else if (ev == EV_END && two > 0 && t[1] > t[0]) {  // file 1 ended; file 2's next record is sound
-    status = KC_ERR_INVALID_ARG;
-    snprintf(g_last_error, sizeof(g_last_error), "the first file ends after %llu records, the second has more", (unsigned long long)t[0]);
-  } else if (ev == EV_STRUCT || (ev == EV_END && two > 0 && serr[1] && t[1] == t[0])) {
-    int fi = ev == EV_STRUCT ? evf : 1;  // (or file 2's record after file 1's end is malformed)
-    const uint64_t *kk = h_ctl[fi];
-    const unsigned long long rr = (unsigned long long)t[fi];
-    status = KC_ERR_INVALID_ARG;
-    switch ((int)kk[FQC_KIND]) {
-      case FQK_TRUNCATED: snprintf(g_last_error, sizeof(g_last_error), "FASTQ ends inside the record that starts at line %llu", 4 * rr + 1); break;
-      case FQK_NAME: snprintf(g_last_error, sizeof(g_last_error), "Invalid FASTQ: expected read name (@) at line %llu", 4 * rr + 1); break;
-      case FQK_PLUS: snprintf(g_last_error, sizeof(g_last_error), "Invalid FASTQ: expected '+' at line %llu", 4 * rr + 3); break;
-      default:
-        snprintf(g_last_error, sizeof(g_last_error), "Invalid FASTQ: sequence length %llu != %llu quals length at line %llu",
-                 (unsigned long long)kk[FQC_A], (unsigned long long)kk[FQC_B], 4 * rr + 2);
-    }
-  } else if (two == 0 && (g & 1)) {
-    status = KC_ERR_INVALID_ARG;
-    snprintf(g_last_error, sizeof(g_last_error), "an interleaved file of %llu records: pairs need an even count", (unsigned long long)g);
-  }
-  const uint64_t nr = g, nb = h_ctl[0][FQC_TOTAL];
-  const bool arrays = d_offsets && (packed ? d_packed != nullptr : (d_bases && d_quals));
-  if (d_offsets && reads_capacity + 1 > 0) HIPCHK(hipMemsetAsync(d_offsets, 0, 8, c->stream));
-  if (arrays && (g || part_rec != FQ_NONE) && g <= nout && (part_rec == FQ_NONE || part_rec < nout)) {  // (always, by construction)
-    FqOut o;
-    memset(&o, 0, sizeof(o));
-    o.packed = d_packed;
-    o.bases = d_bases;
-    o.quals = d_quals;
-    o.offsets = d_offsets;
-    o.cap = capacity;
-    o.reads_cap = reads_capacity;
-    o.nout = nout;
-    o.lim = g;
-    o.part_rec = part_rec;
-    o.part_len = part_len;
-    o.bsum = bsum;
-    o.qoff = c->cfg.qual_offset;
-    const uint64_t nw = part_rec != FQ_NONE ? part_rec + 1 : g;
-    if (packed) {
-      KernelTimer kt(c, KT_FQ_WRITE_PACKED);
-      hipLaunchKernelGGL(kc_fq_write_kernel<true>, grid((nw + FQ_TPB - 1) / FQ_TPB), dim3(FQ_TPB), 0, c->stream, f[0], f[1], 0, o);
-    } else {
-      KernelTimer kt(c, KT_FQ_WRITE_PAIRS);
-      hipLaunchKernelGGL(kc_fq_write_kernel<false>, grid((nw + FQ_TPB - 1) / FQ_TPB), dim3(FQ_TPB), 0, c->stream, f[0], f[1],
-                         two > 0 ? 1 : 0, o);
-    }
-    HIPCHK(hipGetLastError());
-  }
-  HIPCHK(hipStreamSynchronize(c->stream));
-  if (status) return status;
-  *nreads = nr;
-  *nbytes = nb;
-  const bool fits = arrays && nr <= reads_capacity && nb <= capacity;
-  if (!fits && (nr || nb)) {
-    snprintf(g_last_error, sizeof(g_last_error), "%llu reads with %llu bases do not fit the arrays", (unsigned long long)nr, (unsigned long long)nb);
-    return KC_ERR_CAPACITY;
-  }
-  return KC_OK;
-}
-
-extern "C" int kc_fastq_to_packed_device(kc_ctx *c, const char *text, uint64_t len, int on_device, uint32_t flags, uint8_t *d_packed,
-                                         uint64_t packed_capacity, uint64_t *d_offsets, uint64_t reads_capacity, uint64_t *nreads,
-                                         uint64_t *nbytes, uint64_t *consumed) {
-  const char *t[2] = {text, nullptr};
-  const uint64_t l[2] = {len, 0};
-  uint64_t *cons[2] = {consumed, nullptr};
-  return fq_device(c, t, l, -1, on_device, flags, d_packed, nullptr, nullptr, packed_capacity, d_offsets, reads_capacity, nreads, nbytes,
-                   cons);
-}
-
-extern "C" int kc_fastq_pairs_device(kc_ctx *c, const char *text1, uint64_t len1, const char *text2, uint64_t len2, int on_device,
-                                     uint32_t flags, uint8_t *d_bases, uint8_t *d_quals, uint64_t capacity, uint64_t *d_offsets,
-                                     uint64_t reads_capacity, uint64_t *nreads, uint64_t *nbytes, uint64_t *consumed1,
-                                     uint64_t *consumed2) {
-  const char *t[2] = {text1, text2};
-  const uint64_t l[2] = {len1, len2};
-  uint64_t *cons[2] = {consumed1, consumed2};
-  return fq_device(c, t, l, text2 ? 1 : 0, on_device, flags, nullptr, d_bases, d_quals, capacity, d_offsets, reads_capacity, nreads,
-                   nbytes, cons);
-}
-
-// ---- overlap merge of read pairs (kc_merge.hpp) --------------------------------------------------------------------
-extern "C" int kc_merge_pairs(kc_ctx *c, const uint8_t *bases, const uint8_t *quals, const uint64_t *offsets, uint64_t npairs,
-                              int on_device, int min_kmer_len, uint8_t *d_packed, uint64_t packed_capacity, uint64_t *d_out_offsets,
-                              uint64_t reads_capacity, uint64_t *nreads, uint64_t *nbytes, kc_merge_stats *stats) {
-  if (!c || !nreads || !nbytes || min_kmer_len < 0 || (npairs && (!bases || !quals || !offsets))) return KC_ERR_INVALID_ARG;
-  HIPCHK(hipSetDevice(c->cfg.device));
-  kc_merge_stats ms;
-  memset(&ms, 0, sizeof(ms));
-  ms.pairs = npairs;
-  *nreads = *nbytes = 0;
-  if (stats) *stats = ms;
-  if (d_out_offsets && reads_capacity + 1 > 0) HIPCHK(hipMemsetAsync(d_out_offsets, 0, 8, c->stream));
-  if (!npairs) {
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return KC_OK;
-  }
-  if (npairs > 0xFFFFFFFFull) return KC_ERR_INVALID_ARG;  // pair indices of the long-pair list are 32-bit
-  const uint64_t nr_in = 2 * npairs;
-  if (!on_device) {  // staged the way kc_submit_seq_block stages a host block
-    const uint64_t first = offsets[0], last = offsets[nr_in];
-    if (last < first) return KC_ERR_INVALID_ARG;
-    int rc = ensure_stage(c, (size_t)(last - first), (size_t)nr_in, true);
-    if (rc) return rc;
-    std::vector<uint64_t> rel(nr_in + 1);
-    for (uint64_t r = 0; r <= nr_in; r++) {
-      if (offsets[r] < first || offsets[r] > last) return KC_ERR_INVALID_ARG;
-      rel[r] = offsets[r] - first;
-    }
-    HIPCHK(hipStreamSynchronize(c->stream));
-    HIPCHK(hipMemcpyAsync(c->d_stage_bases, bases + first, last - first, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->d_stage_quals, quals + first, last - first, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->d_stage_offsets, rel.data(), (nr_in + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));  // rel goes out of scope
-    bases = c->d_stage_bases;
-    quals = c->d_stage_quals;
-    offsets = c->d_stage_offsets;
-  }
-  const uint64_t ntiles = (npairs + MG_TILE - 1) / MG_TILE;
-  auto up = [](size_t x) { return (x + 255) & ~size_t(255); };
-  const size_t sz_pair = up(npairs * 4), sz_tile = up(ntiles * 8), sz_stats = up(MG_SLOTS * MGS_N * 8), sz_ctl = 256;
-  const size_t need = 3 * sz_pair + 2 * sz_tile + sz_stats + sz_ctl;
-  if (need > c->mg_cap) {
-    if (c->d_mg) HIPCHK(hipFree(c->d_mg));
-    c->d_mg = nullptr;
-    c->mg_cap = 0;
-    HIPCHK(hipMalloc((void **)&c->d_mg, need));
-    c->mg_cap = need;
-  }
-  MergeArgs a;
-  memset(&a, 0, sizeof(a));
-  a.bases = bases;
-  a.quals = quals;
-  a.offsets = offsets;
-  a.npairs = npairs;
-  a.qoff = c->cfg.qual_offset;
-  a.min_len = min_kmer_len ? min_kmer_len : c->k;
-  uint8_t *m = c->d_mg;
-  a.pair_dec = (uint32_t *)m;
-  a.pair_out = (uint32_t *)(m + sz_pair);
-  a.long_list = (uint32_t *)(m + 2 * sz_pair);
-  a.tile_bytes = (uint64_t *)(m + 3 * sz_pair);
-  a.tile_reads = (uint64_t *)(m + 3 * sz_pair + sz_tile);
-  a.stats = (uint64_t *)(m + 3 * sz_pair + 2 * sz_tile);
-  a.ctl = (uint32_t *)(m + 3 * sz_pair + 2 * sz_tile + sz_stats);
-  a.totals = (uint64_t *)(a.ctl + 16);
-  a.out = d_packed;
-  a.out_offsets = d_out_offsets;
-  HIPCHK(hipMemsetAsync(a.stats, 0, sz_stats + sz_ctl, c->stream));
-  {
-    KernelTimer kt(c, KT_MERGE_DECIDE);
-    hipLaunchKernelGGL(kc_merge_decide_kernel, dim3((unsigned)ntiles), dim3(64 * MG_WAVES), 0, c->stream, a);
-  }
-  HIPCHK(hipGetLastError());
-  uint32_t ctl[MG_CTL_N];
-  HIPCHK(hipMemcpyAsync(ctl, a.ctl, sizeof(ctl), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  const uint32_t nlong = ctl[MG_CTL_NLONG];
-  const int lcap = (int)((ctl[MG_CTL_LONGMAX] + 3) & ~3u);
-  const size_t lbytes = 4 * ((size_t)lcap + MG_PAD);
-  if (nlong && !ctl[MG_CTL_ERR]) {
-    int rc = set_dyn_lds(kc_merge_decide_long_kernel, lbytes);
-    if (!rc) rc = set_dyn_lds(kc_merge_write_long_kernel, lbytes);
-    if (rc) return rc;
-    {
-      KernelTimer kt(c, KT_MERGE_DECIDE_LONG);
-      hipLaunchKernelGGL(kc_merge_decide_long_kernel, dim3(nlong), dim3(64), lbytes, c->stream, a, lcap);
-    }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(ctl, a.ctl, sizeof(ctl), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-  }
-  if (ctl[MG_CTL_ERR] & MG_ERR_BASE) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_merge_pairs: a read holds a byte outside ACGTN/acgtn/IUPAC");
-    return KC_ERR_BAD_BASE;
-  }
-  if (ctl[MG_CTL_ERR]) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_merge_pairs: a quality outside [qual_offset, qual_offset + 80] or a mate longer than %d",
-             MG_MAX_LEN);
-    return KC_ERR_INVALID_ARG;
-  }
-  {
-    KernelTimer kt(c, KT_MERGE_SCAN);
-    hipLaunchKernelGGL(kc_merge_scan_kernel, dim3(1), dim3(MG_SCAN_TPB), 0, c->stream, a, ntiles);
-  }
-  HIPCHK(hipGetLastError());
-  uint64_t tot[2], hs[MG_SLOTS * MGS_N];
-  HIPCHK(hipMemcpyAsync(tot, a.totals, sizeof(tot), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipMemcpyAsync(hs, a.stats, sizeof(hs), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  for (int s = 0; s < MG_SLOTS; s++) {
-    ms.merged += hs[s * MGS_N + MGS_MERGED];
-    ms.ambiguous += hs[s * MGS_N + MGS_AMBIG];
-    ms.dropped += hs[s * MGS_N + MGS_DROPPED];
-    ms.overlap_len += hs[s * MGS_N + MGS_OVERLAP];
-    ms.merged_len += hs[s * MGS_N + MGS_MERGED_LEN];
-  }
-  ms.out_bases = tot[0];
-  ms.out_reads = tot[1];
-  *nbytes = tot[0];
-  *nreads = tot[1];
-  if (stats) *stats = ms;
-  if (!d_packed || !d_out_offsets || tot[0] > packed_capacity || tot[1] > reads_capacity) {
-    if (!tot[0] && !tot[1]) return KC_OK;
-    snprintf(g_last_error, sizeof(g_last_error), "%llu merged reads with %llu bases do not fit the arrays", (unsigned long long)tot[1],
-             (unsigned long long)tot[0]);
-    return KC_ERR_CAPACITY;
-  }
-  {
-    KernelTimer kt(c, KT_MERGE_WRITE);
-    hipLaunchKernelGGL(kc_merge_write_kernel, dim3((unsigned)ntiles), dim3(64 * MG_WAVES), 0, c->stream, a);
-  }
-  HIPCHK(hipGetLastError());
-  if (nlong) {
-    KernelTimer kt(c, KT_MERGE_WRITE_LONG);
-    hipLaunchKernelGGL(kc_merge_write_long_kernel, dim3(nlong), dim3(64), lbytes, c->stream, a, lcap);
-  }
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return KC_OK;
-}
-
-// ---- adapter trimming (kc_trim.hpp) ---------------------------------------------------------------------------------
-namespace {
-struct HostAdapters {
-  std::vector<std::string> entries;  // s at 2n, revcomp(s) at 2n+1
-  uint64_t n_short = 0;
-  std::vector<uint64_t> keys;                 // distinct k-mers in order of first insertion
-  std::vector<std::vector<uint32_t>> records; // per k-mer: entry << TR_REC_OFF_BITS | offset, in insertion order
-};
-}  // namespace
-
-// revcomp, src/utils.cpp:98-129; false for a byte the reference DIEs on
-static bool adapters_revcomp(const std::string &s, std::string &rc) {
-  rc.clear();
-  rc.reserve(s.size());
-  for (size_t i = s.size(); i-- > 0;) {
-    switch (s[i]) {
-      case 'A': case 'a': rc += 'T'; break;
-      case 'C': case 'c': rc += 'G'; break;
-      case 'G': case 'g': rc += 'C'; break;
-      case 'T': case 't': rc += 'A'; break;
-      case 'N': case 'n':
-      case 'U': case 'R': case 'Y': case 'K': case 'M': case 'S': case 'W': case 'B': case 'D': case 'H': case 'V': rc += 'N'; break;
-      default: return false;
-    }
-  }
-  return true;
-}
-
-// Adapters::load_adapter_seqs (src/adapters.cpp:48-146) on a text in memory
-static int adapters_build(const char *text, uint64_t len, int k, HostAdapters &h) {
-  if (k < 1 || (len && !text)) return KC_ERR_INVALID_ARG;
-  if (k > TR_MAX_K) {
-    snprintf(g_last_error, sizeof(g_last_error), "adapter_k %d is above MAX_ADAPTER_K = %d", k, TR_MAX_K);
-    return KC_ERR_UNSUPPORTED_K;
-  }
-  uint64_t lineno = 0;
-  for (uint64_t p = 0; p < len;) {  // getline: a last line without '\n' counts, nothing after the last '\n' does not
-    const char *nl = (const char *)memchr(text + p, '\n', len - p);
-    const uint64_t e = nl ? (uint64_t)(nl - text) : len;
-    const uint64_t n = e - p;
-    lineno++;
-    if (!(n && text[p] == '>')) {
-      if (n < (uint64_t)k) {
-        h.n_short++;
-      } else {
-        if (n > (uint64_t)TR_MAX_ENTRY_LEN) {
-          snprintf(g_last_error, sizeof(g_last_error), "adapter of %llu bases in line %llu: at most %d", (unsigned long long)n,
-                   (unsigned long long)lineno, TR_MAX_ENTRY_LEN);
-          return KC_ERR_INVALID_ARG;
-        }
-        if (h.entries.size() + 2 > (size_t)TR_MAX_ENTRIES) {
-          snprintf(g_last_error, sizeof(g_last_error), "more than %d adapter sequences", TR_MAX_ENTRIES / 2);
-          return KC_ERR_INVALID_ARG;
-        }
-        std::string s(text + p, (size_t)n), rc;
-        if (!adapters_revcomp(s, rc)) {
-          snprintf(g_last_error, sizeof(g_last_error), "adapter in line %llu holds a byte revcomp does not take", (unsigned long long)lineno);
-          return KC_ERR_BAD_BASE;
-        }
-        h.entries.push_back(std::move(s));
-        h.entries.push_back(std::move(rc));
-      }
-    }
-    p = e + 1;
-  }
-  std::unordered_map<uint64_t, uint32_t> ids;
-  const uint64_t mask = k >= 32 ? ~0ull : (1ull << (2 * k)) - 1ull;
-  for (size_t e = 0; e < h.entries.size(); e++) {
-    const std::string &s = h.entries[e];
-    uint64_t key = 0;
-    for (size_t j = 0; j < s.size(); j++) {  // base p of a k-mer in bits 2p, 2p+1 (tr_seed_keys)
-      key = (key >> 2) | ((uint64_t)tr_kcode((uint8_t)s[j]) << (2 * (k - 1)));
-      if (j + 1 < (size_t)k) continue;
-      const uint64_t kk = key & mask;
-      auto it = ids.find(kk);
-      uint32_t id;
-      if (it == ids.end()) {
-        id = (uint32_t)h.keys.size();
-        ids.emplace(kk, id);
-        h.keys.push_back(kk);
-        h.records.emplace_back();
-      } else {
-        id = it->second;
-      }
-      h.records[id].push_back((uint32_t)(e << TR_REC_OFF_BITS) | (uint32_t)(j + 1 - k));
-    }
-  }
-  return KC_OK;
-}
-
-static void adapters_counts(const HostAdapters &h, uint64_t *n_adapters, uint64_t *n_short, uint64_t *n_entries, uint64_t *n_kmers) {
-  if (n_adapters) *n_adapters = h.entries.size() / 2;
-  if (n_short) *n_short = h.n_short;
-  if (n_entries) *n_entries = h.entries.size();
-  if (n_kmers) *n_kmers = h.keys.size();
-}
-
-extern "C" int kc_adapters_index(const char *text, uint64_t len, int adapter_k, uint64_t *n_adapters, uint64_t *n_short,
-                                 uint64_t *n_entries, uint64_t *n_kmers) {
-  HostAdapters h;
-  const int rc = adapters_build(text, len, adapter_k, h);
-  if (rc) return rc;
-  adapters_counts(h, n_adapters, n_short, n_entries, n_kmers);
-  return KC_OK;
-}
-
-extern "C" int kc_adapters_clear(kc_ctx *c) {
-  if (!c) return KC_ERR_INVALID_ARG;
-  HIPCHK(hipSetDevice(c->cfg.device));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  if (c->d_ad) HIPCHK(hipFree(c->d_ad));
-  c->d_ad = nullptr;
-  c->ad_loaded = false;
-  c->ad_entries = 0;
-  return KC_OK;
-}
-
-extern "C" int kc_adapters_load(kc_ctx *c, const char *text, uint64_t len, int adapter_k, uint32_t flags, uint64_t *n_adapters,
-                                uint64_t *n_short, uint64_t *n_entries, uint64_t *n_kmers) {
-  if (!c || adapter_k < 0 || (flags & ~KC_ADAPTERS_BLASTN_SCORES)) return KC_ERR_INVALID_ARG;
-  const int k = adapter_k ? adapter_k : c->k;
-  HostAdapters h;
-  int rc = adapters_build(text, len, k, h);
-  if (rc) return rc;
-  // the device image: the k-mer table at most half full, the records, the entries' offsets and bytes
-  uint32_t lg = 4;
-  while ((1ull << lg) < 2 * h.keys.size()) lg++;
-  std::vector<TrSlot> slots((size_t)1 << lg);
-  memset(slots.data(), 0, slots.size() * sizeof(TrSlot));
-  std::vector<uint32_t> recs;
-  for (size_t i = 0; i < h.keys.size(); i++) {
-    uint32_t s = tr_hash(h.keys[i], lg);
-    while (slots[s].rec_count) s = (s + 1) & ((1u << lg) - 1u);
-    slots[s].key = h.keys[i];
-    slots[s].rec_start = (uint32_t)recs.size();
-    slots[s].rec_count = (uint32_t)h.records[i].size();
-    recs.insert(recs.end(), h.records[i].begin(), h.records[i].end());
-  }
-  std::vector<uint32_t> ent_off(h.entries.size() + 1, 0);
-  std::string bytes;
-  for (size_t e = 0; e < h.entries.size(); e++) {
-    ent_off[e] = (uint32_t)bytes.size();
-    bytes += h.entries[e];
-  }
-  ent_off[h.entries.size()] = (uint32_t)bytes.size();
-  auto up = [](size_t x) { return (x + 255) & ~size_t(255); };
-  const size_t sz_slots = up(slots.size() * sizeof(TrSlot)), sz_recs = up(recs.size() * 4 + 4), sz_ent = up(ent_off.size() * 4);
-  const size_t total = sz_slots + sz_recs + sz_ent + up(bytes.size() + 1);
-  rc = kc_adapters_clear(c);  // loading again replaces the set
-  if (rc) return rc;
-  HIPCHK(hipMalloc((void **)&c->d_ad, total));
-  HIPCHK(hipMemcpy(c->d_ad, slots.data(), slots.size() * sizeof(TrSlot), hipMemcpyHostToDevice));
-  if (!recs.empty()) HIPCHK(hipMemcpy(c->d_ad + sz_slots, recs.data(), recs.size() * 4, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(c->d_ad + sz_slots + sz_recs, ent_off.data(), ent_off.size() * 4, hipMemcpyHostToDevice));
-  if (!bytes.empty()) HIPCHK(hipMemcpy(c->d_ad + sz_slots + sz_recs + sz_ent, bytes.data(), bytes.size(), hipMemcpyHostToDevice));
-  c->ad_off_recs = sz_slots;
-  c->ad_off_ent = sz_slots + sz_recs;
-  c->ad_off_bytes = sz_slots + sz_recs + sz_ent;
-  c->ad_lg_slots = lg;
-  c->ad_entries = (uint32_t)h.entries.size();
-  c->ad_k = k;
-  c->ad_blastn = (flags & KC_ADAPTERS_BLASTN_SCORES) ? 1 : 0;
-  c->ad_loaded = true;
-  adapters_counts(h, n_adapters, n_short, n_entries, n_kmers);
-  return KC_OK;
-}
-
-extern "C" int kc_trim_adapters(kc_ctx *c, const uint8_t *bases, const uint8_t *quals, const uint64_t *offsets, uint64_t nreads,
-                                int on_device, uint32_t flags, uint8_t *d_out_bases, uint8_t *d_out_quals, uint64_t capacity,
-                                uint64_t *d_out_offsets, uint64_t *nbytes, kc_trim_stats *stats) {
-  if (!c || !nbytes || (flags & ~KC_TRIM_PAIRED) || (nreads && (!bases || !quals || !offsets))) return KC_ERR_INVALID_ARG;
-  const int paired = (flags & KC_TRIM_PAIRED) ? 1 : 0;
-  if (paired && (nreads & 1)) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_trim_adapters: KC_TRIM_PAIRED with an odd number of reads");
-    return KC_ERR_INVALID_ARG;
-  }
-  if (!c->ad_loaded) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_trim_adapters: no adapter set is loaded (kc_adapters_load)");
-    return KC_ERR_STATE;
-  }
-  HIPCHK(hipSetDevice(c->cfg.device));
-  kc_trim_stats ts;
-  memset(&ts, 0, sizeof(ts));
-  ts.reads = nreads;
-  *nbytes = 0;
-  if (stats) *stats = ts;
-  if (d_out_offsets) HIPCHK(hipMemsetAsync(d_out_offsets, 0, 8, c->stream));
-  if (!nreads) {
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return KC_OK;
-  }
-  if (nreads > 0xFFFFFFFFull) return KC_ERR_INVALID_ARG;  // read indices of the hit list are 32-bit
-  if (!on_device) {  // staged as kc_merge_pairs stages a host block
-    const uint64_t first = offsets[0], last = offsets[nreads];
-    if (last < first) return KC_ERR_INVALID_ARG;
-    int rc = ensure_stage(c, (size_t)(last - first), (size_t)nreads, true);
-    if (rc) return rc;
-    std::vector<uint64_t> rel(nreads + 1);
-    for (uint64_t r = 0; r <= nreads; r++) {
-      if (offsets[r] < first || offsets[r] > last) return KC_ERR_INVALID_ARG;
-      rel[r] = offsets[r] - first;
-    }
-    HIPCHK(hipStreamSynchronize(c->stream));
-    HIPCHK(hipMemcpyAsync(c->d_stage_bases, bases + first, last - first, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->d_stage_quals, quals + first, last - first, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->d_stage_offsets, rel.data(), (nreads + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));  // rel goes out of scope
-    bases = c->d_stage_bases;
-    quals = c->d_stage_quals;
-    offsets = c->d_stage_offsets;
-  }
-  const uint64_t ntiles = (nreads + TR_TILE - 1) / TR_TILE;
-  auto up = [](size_t x) { return (x + 255) & ~size_t(255); };
-  const size_t sz_read = up(nreads * 4), sz_tile = up(ntiles * 8), sz_ctl = 256;
-  const size_t need = 3 * sz_read + 2 * sz_tile + sz_ctl;
-  if (need > c->tr_cap) {
-    if (c->d_tr) HIPCHK(hipFree(c->d_tr));
-    c->d_tr = nullptr;
-    c->tr_cap = 0;
-    HIPCHK(hipMalloc((void **)&c->d_tr, need));
-    c->tr_cap = need;
-  }
-  TrimArgs a;
-  memset(&a, 0, sizeof(a));
-  a.bases = bases;
-  a.quals = quals;
-  a.offsets = offsets;
-  a.nreads = nreads;
-  a.k = c->ad_k;
-  a.paired = paired;
-  a.match = c->ad_blastn ? 2 : 1;  // BLASTN_ALN_SCORES 23521 / ALTERNATE_ALN_SCORES 11111
-  a.mismatch = c->ad_blastn ? 3 : 1;
-  a.gap_open = c->ad_blastn ? 5 : 1;
-  a.gap_ext = c->ad_blastn ? 2 : 1;
-  a.amb = 1;
-  a.slots = (const TrSlot *)c->d_ad;
-  a.lg_slots = c->ad_lg_slots;
-  a.slot_mask = (1u << c->ad_lg_slots) - 1u;
-  a.recs = (const uint32_t *)(c->d_ad + c->ad_off_recs);
-  a.ent_off = (const uint32_t *)(c->d_ad + c->ad_off_ent);
-  a.ent_bytes = c->d_ad + c->ad_off_bytes;
-  a.n_entries = c->ad_entries;
-  uint8_t *m = c->d_tr;
-  a.res = (uint32_t *)m;
-  a.flen = (uint32_t *)(m + sz_read);
-  a.list = (uint32_t *)(m + 2 * sz_read);
-  a.tile_bytes = (uint64_t *)(m + 3 * sz_read);
-  uint64_t *tile_reads = (uint64_t *)(m + 3 * sz_read + sz_tile);  // kc_merge_scan_kernel scans two arrays
-  a.ctl = (uint32_t *)(m + 3 * sz_read + 2 * sz_tile);
-  a.stats = (unsigned long long *)(a.ctl + 8);
-  uint64_t *totals = (uint64_t *)(a.ctl + 24);
-  a.out_bases = d_out_bases;
-  a.out_quals = d_out_quals;
-  a.out_offsets = d_out_offsets;
-  HIPCHK(hipMemsetAsync(tile_reads, 0, sz_tile + sz_ctl, c->stream));
-  {
-    KernelTimer kt(c, KT_TRIM_SEED);
-    const uint64_t per = (uint64_t)TR_SEED_WAVES * TR_RPW;
-    hipLaunchKernelGGL(kc_trim_seed_kernel, dim3((unsigned)((nreads + per - 1) / per)), dim3(64 * TR_SEED_WAVES), 0, c->stream, a);
-  }
-  HIPCHK(hipGetLastError());
-  uint32_t ctl[TR_CTL_N];
-  HIPCHK(hipMemcpyAsync(ctl, a.ctl, sizeof(ctl), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  if (ctl[TR_CTL_ERR]) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_trim_adapters: a read longer than %d, or offsets that decrease", MG_MAX_LEN);
-    return KC_ERR_INVALID_ARG;
-  }
-  if (ctl[TR_CTL_NLIST]) {
-    KernelTimer kt(c, KT_TRIM_ALIGN);
-    const uint32_t nlist = ctl[TR_CTL_NLIST];
-    const unsigned grid = (unsigned)std::min<uint64_t>(nlist, (uint64_t)c->num_cus * 32);
-    hipLaunchKernelGGL(kc_trim_align_kernel, dim3(grid), dim3(64), 0, c->stream, a, nlist);
-  }
-  HIPCHK(hipGetLastError());
-  {
-    KernelTimer kt(c, KT_TRIM_SIZES);
-    hipLaunchKernelGGL(kc_trim_sizes_kernel, dim3((unsigned)ntiles), dim3(TR_TILE), 0, c->stream, a);
-  }
-  HIPCHK(hipGetLastError());
-  {
-    MergeArgs sa;
-    memset(&sa, 0, sizeof(sa));
-    sa.tile_bytes = a.tile_bytes;
-    sa.tile_reads = tile_reads;
-    sa.totals = totals;
-    KernelTimer kt(c, KT_TRIM_SCAN);
-    hipLaunchKernelGGL(kc_merge_scan_kernel, dim3(1), dim3(MG_SCAN_TPB), 0, c->stream, sa, ntiles);
-  }
-  HIPCHK(hipGetLastError());
-  uint64_t tot[2];
-  unsigned long long hs[TRS_N];
-  HIPCHK(hipMemcpyAsync(tot, totals, sizeof(tot), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipMemcpyAsync(hs, a.stats, sizeof(hs), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  ts.trimmed = hs[TRS_TRIMMED];
-  ts.bases_trimmed = hs[TRS_BASES];
-  ts.reads_removed = hs[TRS_REMOVED];
-  ts.alignments = hs[TRS_ALIGN];
-  ts.out_bases = tot[0];
-  *nbytes = tot[0];
-  if (stats) *stats = ts;
-  if (!d_out_bases || !d_out_quals || !d_out_offsets || tot[0] > capacity) {
-    snprintf(g_last_error, sizeof(g_last_error), "%llu trimmed reads with %llu bases do not fit the arrays", (unsigned long long)nreads,
-             (unsigned long long)tot[0]);
-    return KC_ERR_CAPACITY;
-  }
-  {
-    KernelTimer kt(c, KT_TRIM_WRITE);
-    hipLaunchKernelGGL(kc_trim_write_kernel, dim3((unsigned)ntiles), dim3(TR_TILE), 0, c->stream, a);
-  }
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return KC_OK;
-}
+#include "kc_api_frontend.hpp"  // kc_fastq_*, kc_merge_pairs, kc_adapters_*, kc_trim_adapters
 
 extern "C" int kc_submit_seq_block(kc_ctx *c, const char *seqs, uint64_t len, int on_device) {
   if (!c || (len && !seqs)) return KC_ERR_INVALID_ARG;
@@ -2945,11 +2106,10 @@ extern "C" int kc_submit_seq_block(kc_ctx *c, const char *seqs, uint64_t len, in
   if (!len) return KC_OK;
   const uint8_t *d = (const uint8_t *)seqs;
   if (!on_device) {
-    int rc = ensure_stage(c, (size_t)len, 0, false);
-    if (rc) return rc;
+    KCTRY(c->stage_bases.reserve((size_t)len + 64));
     HIPCHK(hipStreamSynchronize(c->stream));
-    HIPCHK(hipMemcpyAsync(c->d_stage_bases, seqs, len, hipMemcpyHostToDevice, c->stream));
-    d = c->d_stage_bases;
+    HIPCHK(hipMemcpyAsync(c->stage_bases.p, seqs, len, hipMemcpyHostToDevice, c->stream));
+    d = c->stage_bases.p;
   }
   unsigned nblk = (unsigned)std::min<uint64_t>(((len + SEQSTAT_SPAN - 1) / SEQSTAT_SPAN + 3) / 4, 4096);  // four waves each
   hipLaunchKernelGGL(kc_seqblock_stats_kernel, dim3(nblk), dim3(256), 0, c->stream, d, len, c->k, c->d_ctrs, 1u);
@@ -2962,17 +2122,6 @@ extern "C" int kc_submit_seq_block(kc_ctx *c, const char *seqs, uint64_t len, in
 }
 
 // ---- the reference's wire format ----------------------------------------------------------------------------------
-template <typename T>
-static int grow_dev(T **p, size_t *cap, size_t need) {
-  if (need <= *cap) return KC_OK;
-  if (*p) HIPCHK(hipFree(*p));
-  *p = nullptr;
-  *cap = 0;
-  HIPCHK(hipMalloc((void **)p, need * sizeof(T)));
-  *cap = need;
-  return KC_OK;
-}
-
 extern "C" int kc_build_supermers(kc_ctx *c, const char *seqs, uint64_t len, int on_device, kc_supermer *out, uint32_t capacity,
                                   uint32_t *n_out, uint32_t *num_valid_kmers, uint8_t *packed_out) {
   static_assert(sizeof(kc_supermer) == sizeof(SupermerInfo) && sizeof(kc_supermer) == 12, "layout of kcount_gpu::SupermerInfo");
@@ -2981,25 +2130,24 @@ extern "C" int kc_build_supermers(kc_ctx *c, const char *seqs, uint64_t len, int
   if (num_valid_kmers) *num_valid_kmers = 0;
   HIPCHK(hipSetDevice(c->cfg.device));
   if (!len) return KC_OK;
-  int rc = grow_dev(&c->d_sm_targets, &c->sm_targets_cap, (size_t)len);
-  if (!rc) rc = grow_dev(&c->d_sm_out, &c->sm_out_cap, (size_t)std::max<uint32_t>(capacity, 1));
-  if (!rc) rc = grow_dev(&c->d_sm_packed, &c->sm_packed_cap, (size_t)(len + 1) / 2);
-  if (!rc && !on_device) rc = grow_dev(&c->d_sm_bytes, &c->sm_bytes_cap, (size_t)len);
-  if (rc) return rc;
+  KCTRY(c->sm_targets.reserve((size_t)len * sizeof(int32_t)));
+  KCTRY(c->sm_out.reserve((size_t)std::max<uint32_t>(capacity, 1) * sizeof(SupermerInfo)));
+  KCTRY(c->sm_packed.reserve((size_t)(len + 1) / 2));
+  if (!on_device) KCTRY(c->sm_bytes.reserve((size_t)len));
   if (!c->d_sm_ctr) HIPCHK(hipMalloc((void **)&c->d_sm_ctr, 32));
   HIPCHK(hipMemsetAsync(c->d_sm_ctr, 0, 32, c->stream));
   const uint8_t *d = (const uint8_t *)seqs;
   if (!on_device) {
-    HIPCHK(hipMemcpyAsync(c->d_sm_bytes, seqs, len, hipMemcpyHostToDevice, c->stream));
-    d = c->d_sm_bytes;
+    HIPCHK(hipMemcpyAsync(c->sm_bytes.p, seqs, len, hipMemcpyHostToDevice, c->stream));
+    d = c->sm_bytes.p;
   }
   uint64_t *d_bad = (uint64_t *)(c->d_sm_ctr + 4);
   if (c->k > SM_HALO - 1) return KC_ERR_UNSUPPORTED_K;
   hipLaunchKernelGGL(kc_supermer_targets_kernel, dim3((unsigned)((len + SM_TILE - 1) / SM_TILE)), dim3(SM_WG), 0, c->stream, d, len, c->k,
-                     (uint32_t)c->cfg.rank_n, c->d_sm_targets, d_bad);
-  hipLaunchKernelGGL(kc_supermer_build_kernel, dim3((unsigned)((len + SB_WG * SB_PER - 1) / (SB_WG * SB_PER))), dim3(SB_WG), 0, c->stream, c->d_sm_targets, len, c->k, c->d_sm_out, capacity,
+                     (uint32_t)c->cfg.rank_n, c->sm_targets.as<int32_t>(), d_bad);
+  hipLaunchKernelGGL(kc_supermer_build_kernel, dim3((unsigned)((len + SB_WG * SB_PER - 1) / (SB_WG * SB_PER))), dim3(SB_WG), 0, c->stream, c->sm_targets.as<int32_t>(), len, c->k, c->sm_out.as<SupermerInfo>(), capacity,
                      c->d_sm_ctr, c->d_sm_ctr + 1, c->d_sm_ctr + 2);
-  hipLaunchKernelGGL(kc_pack_seqs_kernel, dim3((unsigned)(((len + 15) / 16 + 255) / 256)), dim3(256), 0, c->stream, d, len, c->d_sm_packed);
+  hipLaunchKernelGGL(kc_pack_seqs_kernel, dim3((unsigned)(((len + 15) / 16 + 255) / 256)), dim3(256), 0, c->stream, d, len, c->sm_packed.p);
   c->num_gpu_calls += 3;
   HIPCHK(hipGetLastError());
   uint32_t h[6];
@@ -3016,8 +2164,8 @@ extern "C" int kc_build_supermers(kc_ctx *c, const char *seqs, uint64_t len, int
     snprintf(g_last_error, sizeof(g_last_error), "%u supermers, room for %u", h[0], capacity);
     return KC_ERR_CAPACITY;
   }
-  if (h[0]) HIPCHK(hipMemcpy(out, c->d_sm_out, (size_t)h[0] * sizeof(kc_supermer), hipMemcpyDeviceToHost));
-  if (packed_out) HIPCHK(hipMemcpy(packed_out, c->d_sm_packed, (size_t)(len + 1) / 2, hipMemcpyDeviceToHost));
+  if (h[0]) HIPCHK(hipMemcpy(out, c->sm_out.as<SupermerInfo>(), (size_t)h[0] * sizeof(kc_supermer), hipMemcpyDeviceToHost));
+  if (packed_out) HIPCHK(hipMemcpy(packed_out, c->sm_packed.p, (size_t)(len + 1) / 2, hipMemcpyDeviceToHost));
   return KC_OK;
 }
 
@@ -3028,25 +2176,24 @@ extern "C" int kc_submit_packed_supermers(kc_ctx *c, const uint8_t *packed, uint
   if (!len) return KC_OK;
   // the unpacked block of the previous call may still be read by its kernels
   HIPCHK(hipStreamSynchronize(c->stream));
-  int rc = grow_dev(&c->d_sm_bytes, &c->sm_bytes_cap, (size_t)len * 2);
-  if (!rc && !on_device) rc = grow_dev(&c->d_sm_packed, &c->sm_packed_cap, (size_t)len);
-  if (rc) return rc;
+  KCTRY(c->sm_bytes.reserve((size_t)len * 2));
+  if (!on_device) KCTRY(c->sm_packed.reserve((size_t)len));
   if (!c->d_sm_ctr) HIPCHK(hipMalloc((void **)&c->d_sm_ctr, 32));
   HIPCHK(hipMemsetAsync(c->d_sm_ctr, 0, 32, c->stream));
   const uint8_t *d = packed;
   if (!on_device) {
-    HIPCHK(hipMemcpyAsync(c->d_sm_packed, packed, len, hipMemcpyHostToDevice, c->stream));
-    d = c->d_sm_packed;
+    HIPCHK(hipMemcpyAsync(c->sm_packed.p, packed, len, hipMemcpyHostToDevice, c->stream));
+    d = c->sm_packed.p;
   }
   uint64_t *d_bad = (uint64_t *)(c->d_sm_ctr + 4);
-  hipLaunchKernelGGL(kc_unpack_supermers_kernel, dim3((unsigned)(((len + 7) / 8 + 255) / 256)), dim3(256), 0, c->stream, d, len, c->d_sm_bytes, d_bad);
+  hipLaunchKernelGGL(kc_unpack_supermers_kernel, dim3((unsigned)(((len + 7) / 8 + 255) / 256)), dim3(256), 0, c->stream, d, len, c->sm_bytes.p, d_bad);
   c->num_gpu_calls++;
   HIPCHK(hipGetLastError());
   uint32_t h[2];
   HIPCHK(hipMemcpyAsync(h, d_bad, 8, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));  // also: the caller's buffer is free to change
   if (h[0] | h[1]) return KC_ERR_BAD_BASE;  // a nibble above 9 (reference: WARN "index out of range for to_base")
-  return kc_submit_seq_block(c, (const char *)c->d_sm_bytes, len * 2, 1);
+  return kc_submit_seq_block(c, (const char *)c->sm_bytes.p, len * 2, 1);
 }
 
 // the two ends of a kc_extract_partition call.  With KC_FLAG_WIRE_UNITS the geometry decides what a unit is, so it is
@@ -3103,11 +2250,10 @@ extern "C" int kc_extract_partition_seq_block(kc_ctx *c, const char *seqs, uint6
   if (rc) return rc;
   const uint8_t *d = (const uint8_t *)seqs;
   if (len && !on_device) {
-    rc = ensure_stage(c, (size_t)len, 0, false);
-    if (rc) return rc;
+    KCTRY(c->stage_bases.reserve((size_t)len + 64));
     HIPCHK(hipStreamSynchronize(c->stream));
-    HIPCHK(hipMemcpyAsync(c->d_stage_bases, seqs, len, hipMemcpyHostToDevice, c->stream));
-    d = c->d_stage_bases;
+    HIPCHK(hipMemcpyAsync(c->stage_bases.p, seqs, len, hipMemcpyHostToDevice, c->stream));
+    d = c->stage_bases.p;
   }
   rc = run_extract_device(c, d, nullptr, nullptr, 0, len, MODE_BIN, FMT_SEQBLOCK, d_records, seg_capacity);
   if (rc) return rc;

@@ -15,8 +15,9 @@
 //                       are laid out from the 16-byte boundary at or below the text's start (FqFile::head), so every
 //                       lane's 16 bytes are one aligned load wherever the text starts; only the chunks holding the
 //                       text's first or last byte are read a byte at a time.
-//  kc_fq_scan_kernel    one workgroup: exclusive scan of a u64 array in place, and its total.  It turns the tile counts
-//                       into each tile's first line number, and the per-workgroup sequence sums into output offsets.
+//  kc_scan_kernel<1>    (kc_scan.hpp) one workgroup: exclusive scan of a u64 array in place, and its total.  It turns
+//                       the tile counts into each tile's first line number, and the per-workgroup sequence sums into
+//                       output offsets.
 //  kc_fq_index_kernel   a workgroup per tile again: every '\n' gets its line number and stores its position, so line L
 //                       ends at ends[L] (8 bytes per line, 32 per record).
 //  kc_fq_check_kernel   a lane per record: the structural checks, the sequence length; then its wave walks the bases of
@@ -42,8 +43,6 @@ constexpr int FQ_TPB = 256;
 constexpr int FQ_VEC = 16;    // text bytes per lane and step
 constexpr int FQ_STEPS = 16;  // steps per tile
 constexpr uint64_t FQ_TILE = (uint64_t)FQ_TPB * FQ_VEC * FQ_STEPS;  // 64 KiB
-constexpr int FQ_SCAN_TPB = 1024;
-constexpr int FQ_SCAN_ITEMS = 8;
 constexpr unsigned FQ_MAX_GRID = 1u << 20;  // grid-stride loops beyond this many workgroups
 constexpr uint64_t FQ_NONE = ~0ull;
 
@@ -56,7 +55,7 @@ struct FqFile {
   const uint8_t *text;
   uint64_t len;
   uint64_t head;   // text's offset above the 16-byte boundary below it: the tiles cover [text - head, text + len)
-  uint64_t *tile;  // [ntiles] '\n' counts, then (kc_fq_scan_kernel) each tile's first line number
+  uint64_t *tile;  // [ntiles] '\n' counts, then (kc_scan_kernel) each tile's first line number
   uint64_t ntiles;
   uint64_t *ends;  // [nnl] position of each '\n'
   uint64_t nnl;    // '\n' bytes in the text
@@ -141,41 +140,6 @@ __global__ void __launch_bounds__(FQ_TPB) kc_fq_count_kernel(FqFile f) {
     }
     __syncthreads();
   }
-}
-
-// exclusive scan of v[0, n) in place; *total = the sum
-__global__ void __launch_bounds__(FQ_SCAN_TPB) kc_fq_scan_kernel(uint64_t *v, uint64_t n, uint64_t *total) {
-  __shared__ uint64_t ws[FQ_SCAN_TPB / 64];
-  __shared__ uint64_t carry;
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  if (tid == 0) carry = 0;
-  __syncthreads();
-  for (uint64_t base = 0; base < n; base += (uint64_t)FQ_SCAN_TPB * FQ_SCAN_ITEMS) {
-    const uint64_t first = base + (uint64_t)tid * FQ_SCAN_ITEMS;
-    uint64_t x[FQ_SCAN_ITEMS], s = 0;
-    for (int k = 0; k < FQ_SCAN_ITEMS; k++) {
-      x[k] = first + k < n ? v[first + k] : 0;
-      s += x[k];
-    }
-    uint64_t inc = s;
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint64_t t = __shfl_up(inc, o);
-      if (lane >= o) inc += t;
-    }
-    if (lane == 63) ws[wv] = inc;
-    __syncthreads();
-    uint64_t p = carry;
-    for (int w = 0; w < wv; w++) p += ws[w];
-    p += inc - s;
-    for (int k = 0; k < FQ_SCAN_ITEMS; k++) {
-      if (first + k < n) v[first + k] = p;
-      p += x[k];
-    }
-    __syncthreads();
-    if (tid == FQ_SCAN_TPB - 1) carry = p;
-    __syncthreads();
-  }
-  if (tid == 0) *total = carry;
 }
 
 __global__ void __launch_bounds__(FQ_TPB) kc_fq_index_kernel(FqFile f) {

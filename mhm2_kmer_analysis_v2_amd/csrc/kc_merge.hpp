@@ -49,7 +49,7 @@
 //                          Stores a per-pair decision and size, per-tile sums and the statistics.  A pair with a mate
 //                          longer than MG_MAXL goes to a list instead ...
 //  <long>                  ... served by the same code, one wave per workgroup and the pair's bytes in dynamic LDS.
-//  kc_merge_scan_kernel    one workgroup: exclusive scan of the per-tile bytes and reads, and the totals.
+//  kc_scan_kernel<2>       (kc_scan.hpp) one workgroup: exclusive scan of the per-tile bytes and reads, the totals.
 //  kc_merge_write_kernel   a workgroup per tile: in-tile offsets, the pair to LDS again, the replay for pairs with an
 //                          N, then the packed bytes and the read offsets (and <long> for the listed pairs).
 #pragma once
@@ -57,6 +57,7 @@
 #include <stdint.h>
 
 #include "kc_common.hpp"
+#include "kc_scan.hpp"
 
 namespace kc {
 
@@ -72,8 +73,6 @@ constexpr int MG_PAD = 8;               // LDS bytes behind a mate: the prefilte
 constexpr int MG_WAVES = 4;
 constexpr int MG_TILE = 64;             // pairs per workgroup of the tiled kernels
 constexpr int MG_SLOTS = 64;            // spread of the statistics counters
-constexpr int MG_SCAN_TPB = 1024;
-constexpr int MG_SCAN_ITEMS = 8;
 
 enum { MGS_MERGED = 0, MGS_AMBIG, MGS_DROPPED, MGS_OVERLAP, MGS_MERGED_LEN, MGS_N };
 enum { MG_CTL_ERR = 0, MG_CTL_NLONG, MG_CTL_LONGMAX, MG_CTL_N };
@@ -101,7 +100,7 @@ struct MergeArgs {
   uint32_t *pair_dec;    // [npairs] decision word
   uint32_t *pair_out;    // [npairs] output bytes << 2 | output reads
   uint32_t *long_list;   // [npairs] pairs with a mate longer than MG_MAXL
-  uint64_t *tile_bytes;  // [ntiles] sums, then (kc_merge_scan_kernel) exclusive bases
+  uint64_t *tile_bytes;  // [ntiles] sums, then (kc_scan_kernel) exclusive bases
   uint64_t *tile_reads;
   uint64_t *totals;      // [2] bytes, reads
   uint64_t *stats;       // [MG_SLOTS][MGS_N]
@@ -522,64 +521,6 @@ __global__ void __launch_bounds__(64) kc_merge_decide_long_kernel(MergeArgs a, i
     atomicAdd((unsigned long long *)&a.tile_bytes[p / MG_TILE], (unsigned long long)(out >> 2));
     atomicAdd((unsigned long long *)&a.tile_reads[p / MG_TILE], (unsigned long long)(out & 3u));
     mg_flush_stats(a, st);
-  }
-}
-
-// exclusive scan of the per-tile sums in place; totals[0] bytes, totals[1] reads
-__global__ void __launch_bounds__(MG_SCAN_TPB) kc_merge_scan_kernel(MergeArgs a, uint64_t ntiles) {
-  __shared__ uint64_t wb[MG_SCAN_TPB / 64], wr[MG_SCAN_TPB / 64];
-  __shared__ uint64_t carry[2];
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  if (tid == 0) carry[0] = carry[1] = 0;
-  __syncthreads();
-  for (uint64_t base = 0; base < ntiles; base += (uint64_t)MG_SCAN_TPB * MG_SCAN_ITEMS) {
-    const uint64_t first = base + (uint64_t)tid * MG_SCAN_ITEMS;
-    uint64_t vb[MG_SCAN_ITEMS], vr[MG_SCAN_ITEMS], sb = 0, sr = 0;
-    for (int k = 0; k < MG_SCAN_ITEMS; k++) {
-      const bool in = first + k < ntiles;
-      vb[k] = in ? a.tile_bytes[first + k] : 0;
-      vr[k] = in ? a.tile_reads[first + k] : 0;
-      sb += vb[k];
-      sr += vr[k];
-    }
-    uint64_t ib = sb, ir = sr;  // inclusive within the wave
-    for (int s = 1; s < 64; s <<= 1) {
-      const uint64_t tb = __shfl_up(ib, s), tr = __shfl_up(ir, s);
-      if (lane >= s) {
-        ib += tb;
-        ir += tr;
-      }
-    }
-    if (lane == 63) {
-      wb[wv] = ib;
-      wr[wv] = ir;
-    }
-    __syncthreads();
-    uint64_t pb = carry[0], pr = carry[1];
-    for (int w = 0; w < wv; w++) {
-      pb += wb[w];
-      pr += wr[w];
-    }
-    pb += ib - sb;
-    pr += ir - sr;
-    for (int k = 0; k < MG_SCAN_ITEMS; k++) {
-      if (first + k < ntiles) {
-        a.tile_bytes[first + k] = pb;
-        a.tile_reads[first + k] = pr;
-      }
-      pb += vb[k];
-      pr += vr[k];
-    }
-    __syncthreads();
-    if (tid == MG_SCAN_TPB - 1) {
-      carry[0] = pb;
-      carry[1] = pr;
-    }
-    __syncthreads();
-  }
-  if (tid == 0) {
-    a.totals[0] = carry[0];
-    a.totals[1] = carry[1];
   }
 }
 

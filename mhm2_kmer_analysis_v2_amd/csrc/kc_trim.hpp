@@ -59,7 +59,7 @@
 //                        (F(j) = max over j' < j of H'(j') + j' * extend, less open + (j - 1) * extend), not a lazy
 //                        loop.  Both passes run in the same wave; the read's bytes come 64 columns at a time and are
 //                        broadcast from registers, so any read length takes the same path.
-//  kc_trim_sizes_kernel  final lengths (the pair rule) and per-tile byte sums; kc_merge_scan_kernel scans them.
+//  kc_trim_sizes_kernel  final lengths (the pair rule) and per-tile byte sums; kc_scan_kernel<1> (kc_scan.hpp) scans them.
 //  kc_trim_write_kernel  a workgroup per tile: in-tile offsets, then bases, qualities and offsets.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -412,6 +412,29 @@ def test_text_over_4_gib():
             assert np.array_equal(packed[o:o + ln].cpu().numpy(), pk0[int(of0[j]):int(of0[j]) + ln])
 
 
+def test_record_sums_scan_one_item_into_second_round():
+    """2 097 153 records are 8 193 workgroups of 256 output records: the single-workgroup scan of their sequence sums
+    takes 8 192 items a round, so it carries into a second round of exactly one item.  About 60 MB of text, made and
+    compared on the device."""
+    import torch
+    block = b"@frontend_scan_rec_1\nA\n+\nI\n@frontend_scan_rec_2\nCG\n+\n5I\n@frontend_scan_rec_3\nTNa\n+\nI!I\n"
+    st, nr0, nb0, pk0, of0, _ = host_packed(block, 33)
+    assert st == 0 and nr0 == 3 and list(of0[:4]) == [0, 1, 3, 6]
+    reps = 699051
+    n = 3 * reps
+    assert n == 2097153 and (n + 255) // 256 == 8193
+    with pkg.KmerCounter(21) as kc:
+        text = torch.frombuffer(bytearray(block), dtype=torch.uint8).cuda().repeat(reps)
+        packed, offs = kc.fastq_to_packed(text)
+        del text
+        assert offs.numel() - 1 == n  # nreads
+        want = torch.zeros(n + 1, dtype=torch.int64, device="cuda")
+        want[1:] = torch.cumsum(torch.tensor([1, 2, 3], dtype=torch.int64, device="cuda").repeat(reps), 0)
+        assert int(want[-1].item()) == 4194306 and int(offs[-1].item()) == 4194306
+        assert torch.equal(offs, want)
+        assert torch.equal(packed, torch.from_numpy(pk0[:nb0].copy()).cuda().repeat(reps))
+
+
 def _reads_text(rng, nreads, k_genome=4000):
     genome = rng.choice(np.frombuffer(b"ACGT", np.uint8), k_genome)
     recs = []

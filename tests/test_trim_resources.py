@@ -26,3 +26,16 @@ def test_trim_kernels_do_not_spill():
         assert md[n].get("vgpr_spill_count", 0) == 0, n
         assert md[n].get("private_segment_fixed_size", 0) == 0, n
         assert md[n]["vgpr_count"] <= (256 if "align" in n else 64), (n, md[n])
+
+
+@needs_llvm
+def test_shared_scan_kernel_has_two_instances_without_scratch():
+    """csrc/kc_scan.hpp: one array (FASTQ, trim) and two arrays (merge); the arrays' pointers are indexed at compile time,
+    so neither instance keeps anything in private memory."""
+    md = kernel_metadata()
+    names = sorted(n for n in md if "kc_scan_kernel" in n)
+    assert len(names) == 2, names
+    for n in names:
+        print(n, md[n])
+        assert md[n]["vgpr_spill_count"] == 0, n
+        assert md[n]["private_segment_fixed_size"] == 0, n
