@@ -106,7 +106,7 @@ typedef struct kc_stats {
  * the KmerCounts it becomes, kmer_dht.hpp:62-68).  Unordered, like a hash-map
  * iteration; entry i is keys[i*num_longs .. +num_longs), counts[i], left[i],
  * right[i] with left/right in "ACGT".  Pointers stay valid until kc_reset /
- * kc_destroy. */
+ * kc_destroy, or a successful kc_sort_results (which orders them by key). */
 typedef struct kc_result {
   uint64_t n;
   int32_t num_longs;
@@ -484,6 +484,36 @@ typedef struct kc_count_exts {
   int8_t pad[2];
 } kc_count_exts;
 int kc_copy_results_entries(kc_ctx *ctx, uint64_t *keys, kc_count_exts *vals);
+/*
+ * Put the results in key order, on the device: ascending, words 0 .. num_longs-1 compared as unsigned integers, which is
+ * the alphabetical order of the k-mer strings.  The reference has no such step -- KmerDHT::dump_kmers walks its hash map
+ * as it lies (src/kcount/kmer_dht.cpp:273-297) -- and every consumer that compares, searches or merges dumps sorts
+ * them on the host first; this is that sort, where the data already is (csrc/kc_sort.hpp: a stable LSD radix sort of a
+ * permutation over the 2k significant key bits, then one gather of keys, counts, left and right).
+ * Call after kc_finalize (KC_ERR_STATE before it).  out (may be NULL) receives the arrays as kc_finalize would.
+ * kc_result pointers obtained EARLIER are invalid after a successful call: the results move to fresh arrays and the
+ * old ones are freed.  kc_finalize called afterwards returns the sorted arrays; kc_copy_results,
+ * kc_copy_results_entries and kc_dump_text_device follow the new order; kc_lookup answers as before (its index is
+ * rebuilt on the next call).  A second call does no device work; kc_reset clears the sorted state.
+ * Failure-atomic: on KC_ERR_OUT_OF_MEMORY or KC_ERR_HIP the unsorted results are intact and still valid.  Scratch
+ * (2 x 12 bytes a result, and the digit counters) is allocated for the call and freed.
+ * The permutation is 32-bit: 2^32 results or more are KC_ERR_CAPACITY (kc_last_error says so).  No test reaches that
+ * size.
+ */
+int kc_sort_results(kc_ctx *ctx, kc_result *out);
+/*
+ * KmerDHT::dump_kmers' text (src/kcount/kmer_dht.cpp:284: kmer.to_string() << " " << count << " " << left << " " <<
+ * right << "\n"), formatted on the device: entries [first, first + count) of the results, in their current order
+ * (kc_sort_results first for a sorted dump; not required), as "<k characters ACGT> <count in decimal> <L> <R>\n" into
+ * the device memory d_text.  A line is kmer_len + 5 + digits(count) bytes and its newline.  The chunks of any partition of [0, n),
+ * laid end to end, are the text of the whole, so a dump of any size streams through a buffer of the caller's choosing
+ * (compression and the file stay with the caller).
+ * *nbytes always receives the chunk's exact size.  d_text == NULL: a size query.  capacity smaller than that:
+ * KC_ERR_CAPACITY, nothing is written.  first + count > n: KC_ERR_INVALID_ARG.  count == 0: KC_OK, *nbytes = 0.
+ * KC_ERR_STATE before kc_finalize.  The table is not touched.  The call runs on the context's stream and returns when
+ * its work there is done.
+ */
+int kc_dump_text_device(kc_ctx *ctx, uint64_t first, uint64_t count, uint8_t *d_text, uint64_t capacity, uint64_t *nbytes);
 /* KmerDHT::kmer_exists / get_kmer_count / get_local_kmer_counts (src/kcount/kmer_dht.cpp:198-245) in bulk, against the
  * results kept in HBM: nq k-mers of num_longs words each, in either orientation; counts[i] = 0 (and left/right = 0)
  * when the k-mer did not survive.  The index over the results is built on the first call after kc_finalize.

@@ -130,6 +130,8 @@ SYMBOLS = {
     "kc_ctg_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "kc_arena_probe_rate": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "kc_copy_results_entries": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "kc_sort_results": (C.c_int, [C.c_void_p, C.POINTER(kc_result)]),
+    "kc_dump_text_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "kc_lookup": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "kc_dump_table": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
     "kc_get_stats": (C.c_int, [C.c_void_p, C.POINTER(kc_stats)]),

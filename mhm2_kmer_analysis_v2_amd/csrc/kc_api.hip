@@ -29,6 +29,7 @@
 #include "kc_merge.hpp"
 #include "kc_trim.hpp"
 #include "kc_fastq.hpp"
+#include "kc_sort.hpp"
 
 using namespace kc;
 
@@ -89,9 +90,10 @@ enum { KT_EXTRACT_INSERT = 0, KT_EXTRACT_BIN, KT_INSERT_RECORDS, KT_FINALIZE, KT
        KT_L2_SPLIT, KT_COUNT_REGIONS, KT_FALLBACK, KT_SHARD_PACK, KT_L1_READS_UQ, KT_L1_READS16, KT_L2_REC6, KT_BIN16, KT_L1_WIRE6,
        KT_MERGE_DECIDE, KT_MERGE_DECIDE_LONG, KT_MERGE_SCAN, KT_MERGE_WRITE, KT_MERGE_WRITE_LONG, KT_FQ_COUNT, KT_FQ_SCAN,
        KT_FQ_INDEX, KT_FQ_CHECK, KT_FQ_DETAIL, KT_FQ_SUMS, KT_FQ_WRITE_PACKED, KT_FQ_WRITE_PAIRS, KT_TRIM_SEED, KT_TRIM_ALIGN,
-       KT_TRIM_SIZES, KT_TRIM_SCAN, KT_TRIM_WRITE, KT_COUNT };
-// KT_FQ_SCAN, KT_MERGE_SCAN and KT_TRIM_SCAN label the three uses of the one shared kc_scan_kernel (kc_scan.hpp); their
-// strings keep the names the uses were first reported under
+       KT_TRIM_SIZES, KT_TRIM_SCAN, KT_TRIM_WRITE, KT_SORT_HIST, KT_SORT_HIST_LOAD, KT_SORT_SCAN, KT_SORT_SCATTER, KT_SORT_GATHER,
+       KT_DUMP_SIZES, KT_DUMP_SCAN, KT_DUMP_WRITE, KT_COUNT };
+// KT_FQ_SCAN, KT_MERGE_SCAN and KT_TRIM_SCAN label the front end's three uses of the one shared kc_scan_kernel (kc_scan.hpp); their
+// strings keep the names the uses were first reported under.  KT_SORT_SCAN and KT_DUMP_SCAN are the back end's two.
 static const char *const kt_names[KT_COUNT] = {"kc_extract_kernel<insert>", "kc_bin_reads_kernel", "kc_insert_records_kernel",
                                                "kc_finalize_kernel", "kc_tile_first_kernel", "kc_rehash_kernel",
                                                "kc_l1_reads_kernel", "kc_l1_records_kernel", "kc_l2_split_kernel",
@@ -102,7 +104,10 @@ static const char *const kt_names[KT_COUNT] = {"kc_extract_kernel<insert>", "kc_
                                                "kc_fq_scan_kernel", "kc_fq_index_kernel", "kc_fq_check_kernel",
                                                "kc_fq_detail_kernel", "kc_fq_sums_kernel", "kc_fq_write_kernel<packed>",
                                                "kc_fq_write_kernel<pairs>", "kc_trim_seed_kernel", "kc_trim_align_kernel",
-                                               "kc_trim_sizes_kernel", "kc_merge_scan_kernel<trim>", "kc_trim_write_kernel"};
+                                               "kc_trim_sizes_kernel", "kc_merge_scan_kernel<trim>", "kc_trim_write_kernel",
+                                               "kc_sort_hist_kernel", "kc_sort_hist_kernel<load>", "kc_sort_scan_kernel",
+                                               "kc_sort_scatter_kernel", "kc_sort_gather_kernel", "kc_dump_sizes_kernel",
+                                               "kc_dump_scan_kernel", "kc_dump_write_kernel"};
 struct kt_pending {
   hipEvent_t start, stop;
   int kind;
@@ -146,6 +151,8 @@ struct kc_ctx {
   uint8_t *d_out_left, *d_out_right;
   uint64_t out_cap, out_n;
   bool finalized;
+  bool sorted;  // kc_sort_results has put the results in key order (cleared with `finalized`)
+  DevBuf dump_tiles;  // kc_dump_text_device: per-tile bytes, then offsets, and the total
   uint32_t *d_index;  // lookup index over the results (built on first kc_lookup)
   uint64_t index_cap;
   // the contig pass (kc_ctg.hpp): a table of the contigs' k-mers, merged into the results by kc_finalize
@@ -591,7 +598,7 @@ extern "C" void kc_destroy(kc_ctx *c) {
   if (c->d_tile_first) (void)hipFree(c->d_tile_first);
   if (c->d_out_plan) (void)hipFree(c->d_out_plan);
   for (DevBuf *b : {&c->stage_bases, &c->stage_quals, &c->stage_offsets, &c->sm_bytes, &c->sm_packed, &c->sm_targets, &c->sm_out,
-                    &c->mg, &c->tr, &c->fq_text, &c->fq_tiles, &c->fq_recs})
+                    &c->mg, &c->tr, &c->fq_text, &c->fq_tiles, &c->fq_recs, &c->dump_tiles})
     (void)b->release();
   if (c->d_synth) (void)hipFree(c->d_synth);
   if (c->d_sm_ctr) (void)hipFree(c->d_sm_ctr);
@@ -691,7 +698,7 @@ extern "C" int kc_reset(kc_ctx *c, int new_k) {
   HIPCHK(hipMemsetAsync(c->d_ctrs, 0, CTR_COUNT * 8, c->stream));
   st = clear_table(c);
   if (st) return st;
-  c->finalized = false;
+  c->finalized = c->sorted = false;
   c->num_reads = c->num_bases = 0;
   c->purged = c->sum_counts = c->unique_at_finalize = 0;
   // bucketed path: keep the arrays when the record width is unchanged, else choose the geometry again (so does a
@@ -3165,6 +3172,8 @@ extern "C" int kc_lookup(kc_ctx *c, const uint64_t *queries, uint64_t nq, int on
   if (sq) (void)hipFree(sq);
   return rc;
 }
+
+#include "kc_api_sort.hpp"  // kc_sort_results, kc_dump_text_device
 
 // ---- the contig pass (kc_ctg.hpp) ----------------------------------------------------------------------------------
 extern "C" int kc_begin_ctg_kmers(kc_ctx *c, uint64_t max_ctg_kmers) {

@@ -11,7 +11,9 @@
   kmer_dht->flush_updates()                           .flush()                 kc_flush
   kmer_dht->finish_updates()                          .finalize()              kc_finalize
   local_kmers (KmerMap)                               .results()               kc_copy_results
-  dump_kmers ("KMER count L R", kmer_dht.cpp:284)     .dump_lines()
+  dump_kmers ("KMER count L R", kmer_dht.cpp:284)     .dump_lines()            (host)
+                                                      .sort_results()          kc_sort_results
+                                                      .dump_text(...)          kc_dump_text_device
 """
 import ctypes as C
 
@@ -514,15 +516,48 @@ class KmerCounter:
                 for i in range(len(counts))]
 
 
-    def dump_kmers(self, directory=".", rank=None):
+    def sort_results(self):
+        """Order the results by key on the device (kc_sort_results): the order sorted_results() computes on the host.
+        Returns the refreshed kc_result; one obtained earlier is invalid."""
+        self.finalize()
+        r = kc_result()
+        check(lib().kc_sort_results(self._h, C.byref(r)), "kc_sort_results")
+        self._res = r
+        return r
+
+    def dump_text(self, first=0, count=None, sort=True):
+        """The dump text of results [first, first + count) as bytes, formatted on the device (kc_dump_text_device): what
+        "".join(line + "\n" for line in dump_lines()) gives for the whole.  sort=False: the results' current order."""
+        import torch
+        r = self.sort_results() if sort else self.finalize()
+        if count is None:
+            count = int(r.n) - first
+        nb = C.c_uint64(0)
+        check(lib().kc_dump_text_device(self._h, first, count, None, 0, C.byref(nb)), "kc_dump_text_device")
+        if not nb.value:
+            return b""
+        text = torch.empty(nb.value, dtype=torch.uint8, device="cuda:%d" % self.device)
+        torch.cuda.current_stream(self.device).synchronize()  # the fresh array is torch's until now
+        check(lib().kc_dump_text_device(self._h, first, count, text.data_ptr(), nb.value, C.byref(nb)), "kc_dump_text_device")
+        return text.cpu().numpy().tobytes()
+
+    def dump_kmers(self, directory=".", rank=None, on_device=False, chunk_lines=1 << 24):
         """KmerDHT::dump_kmers (src/kcount/kmer_dht.cpp:273-297): per-rank gzip text file "kmers-<k>.txt.gz", one
-        "KMER count L R" line per k-mer.  Returns the path."""
+        "KMER count L R" line per k-mer.  Returns the path.  on_device=True: the results are sorted and formatted on
+        the GPU and written chunk by chunk (chunk_lines lines at a time through dump_text); the default is the host
+        path, sorted_results() and dump_lines()."""
         import gzip
         import os
         r = self.rank_me if rank is None else rank
         d = os.path.join(directory, "rank_%d" % r) if self.rank_n > 1 else directory
         os.makedirs(d, exist_ok=True)
         path = os.path.join(d, "kmers-%d.txt.gz" % self.k)
+        if on_device:
+            n = int(self.sort_results().n)
+            with gzip.open(path, "wb") as f:
+                for first in range(0, n, chunk_lines):
+                    f.write(self.dump_text(first, min(chunk_lines, n - first), sort=False))
+            return path
         with gzip.open(path, "wt") as f:
             for line in self.dump_lines():
                 f.write(line + "\n")
