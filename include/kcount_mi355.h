@@ -514,6 +514,43 @@ int kc_sort_results(kc_ctx *ctx, kc_result *out);
  * its work there is done.
  */
 int kc_dump_text_device(kc_ctx *ctx, uint64_t first, uint64_t count, uint8_t *d_text, uint64_t capacity, uint64_t *nbytes);
+/*
+ * Unitigs from the results, on the device: the maximal paths of the de Bruijn graph over (kmer, count, left, right) in
+ * which every step is the unique extension on both sides -- what the reference's traverse_debruijn_graph stage would
+ * hand to the next, longer k through the contig pass.  The reference's proxy has that stage commented out
+ * (src/contigging.cpp), so the rules are THIS project's own definition (pinned by the
+ * host model tests/unitig_model.py); no parity with MetaHipMer's traversal is claimed.  In short: an oriented k-mer links
+ * to the k-mer its right extension leads to when that k-mer is among the results, its left extension (seen in the same
+ * orientation) names the base shifted out, the two are different k-mers and neither is its own reverse complement; a
+ * cycle is cut in front of its smallest k-mer; of a path and its reverse complement the one whose first k-mer is the
+ * smaller is written; unitigs are ordered by their first k-mer's key, so the output is one exact byte string.
+ * Output, in device memory, in the seq-block format: every unitig followed by '_' (d_seqs, *nbytes bytes);
+ * d_offsets[u] = start of unitig u, *n_unitigs + 1 entries, so unitig u has d_offsets[u+1] - d_offsets[u] - 1 bases;
+ * d_kmer_sums[u] (may be NULL) = the sum of its k-mers' counts; d_depths (may be NULL) = one value per byte of d_seqs,
+ * min(65535, mean count rounded half up) on a unitig's bases and 0 on its separator -- d_seqs and d_depths are what
+ * kc_submit_ctg_block(..., on_device = 1) takes.  capacity: bytes d_seqs (and values d_depths) has room for;
+ * unitigs_capacity: unitigs the arrays have room for (d_offsets holds unitigs_capacity + 1 entries, d_kmer_sums
+ * unitigs_capacity).
+ * *n_unitigs, *nbytes and *stats (may be NULL) always receive the totals.  d_seqs or d_offsets NULL: a size query.  Arrays
+ * that are too small: KC_ERR_CAPACITY, nothing is written.  KC_ERR_STATE before kc_finalize, and for a context that is
+ * one of several ranks (rank_n > 1): links across shards are not followed (kc_last_error says so).  2^31 results or
+ * more: KC_ERR_CAPACITY (oriented node ids are 32-bit).  NULL ctx, n_unitigs or nbytes: KC_ERR_INVALID_ARG before any
+ * device call.  No results: KC_OK, 0 unitigs.
+ * The call first puts the results in key order exactly as kc_sort_results does (unless they already are): kc_result
+ * pointers obtained EARLIER are invalid afterwards, as that call documents.  It uses the lookup index and builds it if
+ * absent.  The table and the results' contents are not touched.  The call runs on the context's stream and returns when
+ * its work there is done.  Scratch (73 bytes a result) lives for the call only.
+ */
+typedef struct kc_unitig_stats {
+  uint64_t kmers;      /* results walked */
+  uint64_t unitigs;
+  uint64_t singletons; /* unitigs of one k-mer */
+  uint64_t circular;   /* cycles cut open */
+  uint64_t bases;      /* without separators */
+  uint64_t longest;    /* in bases */
+} kc_unitig_stats;
+int kc_build_unitigs(kc_ctx *ctx, uint8_t *d_seqs, uint64_t capacity, uint16_t *d_depths, uint64_t *d_offsets, uint64_t unitigs_capacity,
+                     uint64_t *d_kmer_sums, uint64_t *n_unitigs, uint64_t *nbytes, kc_unitig_stats *stats);
 /* KmerDHT::kmer_exists / get_kmer_count / get_local_kmer_counts (src/kcount/kmer_dht.cpp:198-245) in bulk, against the
  * results kept in HBM: nq k-mers of num_longs words each, in either orientation; counts[i] = 0 (and left/right = 0)
  * when the k-mer did not survive.  The index over the results is built on the first call after kc_finalize.

@@ -71,6 +71,10 @@ class kc_trim_stats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("reads", "trimmed", "bases_trimmed", "reads_removed", "alignments", "out_bases")]
 
 
+class kc_unitig_stats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("kmers", "unitigs", "singletons", "circular", "bases", "longest")]
+
+
 # every symbol include/kcount_mi355.h declares: (restype, argtypes)
 SYMBOLS = {
     "kc_abi_version": (C.c_int, []),
@@ -132,6 +136,8 @@ SYMBOLS = {
     "kc_copy_results_entries": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "kc_sort_results": (C.c_int, [C.c_void_p, C.POINTER(kc_result)]),
     "kc_dump_text_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "kc_build_unitigs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64),
+                                    C.POINTER(C.c_uint64), C.POINTER(kc_unitig_stats)]),
     "kc_lookup": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "kc_dump_table": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
     "kc_get_stats": (C.c_int, [C.c_void_p, C.POINTER(kc_stats)]),

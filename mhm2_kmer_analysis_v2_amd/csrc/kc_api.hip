@@ -30,6 +30,7 @@
 #include "kc_trim.hpp"
 #include "kc_fastq.hpp"
 #include "kc_sort.hpp"
+#include "kc_unitig.hpp"
 
 using namespace kc;
 
@@ -91,9 +92,11 @@ enum { KT_EXTRACT_INSERT = 0, KT_EXTRACT_BIN, KT_INSERT_RECORDS, KT_FINALIZE, KT
        KT_MERGE_DECIDE, KT_MERGE_DECIDE_LONG, KT_MERGE_SCAN, KT_MERGE_WRITE, KT_MERGE_WRITE_LONG, KT_FQ_COUNT, KT_FQ_SCAN,
        KT_FQ_INDEX, KT_FQ_CHECK, KT_FQ_DETAIL, KT_FQ_SUMS, KT_FQ_WRITE_PACKED, KT_FQ_WRITE_PAIRS, KT_TRIM_SEED, KT_TRIM_ALIGN,
        KT_TRIM_SIZES, KT_TRIM_SCAN, KT_TRIM_WRITE, KT_SORT_HIST, KT_SORT_HIST_LOAD, KT_SORT_SCAN, KT_SORT_SCATTER, KT_SORT_GATHER,
-       KT_DUMP_SIZES, KT_DUMP_SCAN, KT_DUMP_WRITE, KT_COUNT };
+       KT_DUMP_SIZES, KT_DUMP_SCAN, KT_DUMP_WRITE, KT_UNITIG_LINKS, KT_UNITIG_MIN_JUMP, KT_UNITIG_CUT, KT_UNITIG_RANK_JUMP,
+       KT_UNITIG_SELECT, KT_UNITIG_SCAN, KT_UNITIG_WRITE, KT_UNITIG_DEPTH, KT_COUNT };
 // KT_FQ_SCAN, KT_MERGE_SCAN and KT_TRIM_SCAN label the front end's three uses of the one shared kc_scan_kernel (kc_scan.hpp); their
-// strings keep the names the uses were first reported under.  KT_SORT_SCAN and KT_DUMP_SCAN are the back end's two.
+// strings keep the names the uses were first reported under.  KT_SORT_SCAN and KT_DUMP_SCAN are the back end's two,
+// KT_UNITIG_SCAN the unitigs' (kc_scan_kernel<2>: bytes and unitig numbers in one pass).
 static const char *const kt_names[KT_COUNT] = {"kc_extract_kernel<insert>", "kc_bin_reads_kernel", "kc_insert_records_kernel",
                                                "kc_finalize_kernel", "kc_tile_first_kernel", "kc_rehash_kernel",
                                                "kc_l1_reads_kernel", "kc_l1_records_kernel", "kc_l2_split_kernel",
@@ -107,7 +110,10 @@ static const char *const kt_names[KT_COUNT] = {"kc_extract_kernel<insert>", "kc_
                                                "kc_trim_sizes_kernel", "kc_merge_scan_kernel<trim>", "kc_trim_write_kernel",
                                                "kc_sort_hist_kernel", "kc_sort_hist_kernel<load>", "kc_sort_scan_kernel",
                                                "kc_sort_scatter_kernel", "kc_sort_gather_kernel", "kc_dump_sizes_kernel",
-                                               "kc_dump_scan_kernel", "kc_dump_write_kernel"};
+                                               "kc_dump_scan_kernel", "kc_dump_write_kernel", "kc_unitig_links_kernel",
+                                               "kc_unitig_min_jump_kernel", "kc_unitig_cut_kernel", "kc_unitig_rank_jump_kernel",
+                                               "kc_unitig_select_kernel", "kc_unitig_scan_kernel", "kc_unitig_write_kernel",
+                                               "kc_unitig_depth_kernel"};
 struct kt_pending {
   hipEvent_t start, stop;
   int kind;
@@ -3174,6 +3180,7 @@ extern "C" int kc_lookup(kc_ctx *c, const uint64_t *queries, uint64_t nq, int on
 }
 
 #include "kc_api_sort.hpp"  // kc_sort_results, kc_dump_text_device
+#include "kc_api_unitig.hpp"  // kc_build_unitigs
 
 // ---- the contig pass (kc_ctg.hpp) ----------------------------------------------------------------------------------
 extern "C" int kc_begin_ctg_kmers(kc_ctx *c, uint64_t max_ctg_kmers) {

@@ -862,6 +862,22 @@ __global__ void kc_index_build_kernel(const uint64_t *keys, uint64_t n, uint32_t
   while (atomicCAS(&index[s], 0u, (uint32_t)(i + 1)) != 0u) s = (s + 1) & mask;  // result keys are unique
 }
 
+// The probe of the index: result number + 1 of the canonical k-mer f, 0 when it is not among the results.  The walk ends
+// at an empty slot, and the index always has one (it is at most half full).  kc_lookup_kernel and the unitig links
+// (kc_unitig.hpp) both ask through it.
+template <int NL>
+__device__ __forceinline__ uint32_t kc_index_find(const uint64_t (&f)[NL], const uint32_t *index, uint64_t mask, const uint64_t *keys) {
+  uint64_t s = kc_hash<NL>(f) & mask;
+  for (;;) {
+    const uint32_t e = index[s];
+    if (!e) return 0u;
+    bool same = true;
+    for (int j = 0; j < NL; j++) same &= keys[(uint64_t)(e - 1) * NL + j] == f[j];
+    if (same) return e;
+    s = (s + 1) & mask;
+  }
+}
+
 // queries may be given in either orientation; counts[i] = 0 and left/right = 0 when the k-mer is not in the results
 template <int NL>
 __global__ void kc_lookup_kernel(const uint64_t *queries, uint64_t nq, int k, const uint32_t *index, uint64_t mask, const uint64_t *keys,
@@ -874,21 +890,13 @@ __global__ void kc_lookup_kernel(const uint64_t *queries, uint64_t nq, int k, co
   kc_revcomp<NL>(f, k, r);
   if (kc_less<NL>(r, f))
     for (int j = 0; j < NL; j++) f[j] = r[j];
-  uint64_t s = kc_hash<NL>(f) & mask;
   uint16_t c = 0;
   uint8_t l = 0, rr = 0;
-  for (;;) {
-    const uint32_t e = index[s];
-    if (!e) break;
-    bool same = true;
-    for (int j = 0; j < NL; j++) same &= keys[(uint64_t)(e - 1) * NL + j] == f[j];
-    if (same) {
-      c = counts[e - 1];
-      l = left[e - 1];
-      rr = right[e - 1];
-      break;
-    }
-    s = (s + 1) & mask;
+  const uint32_t e = kc_index_find<NL>(f, index, mask, keys);
+  if (e) {
+    c = counts[e - 1];
+    l = left[e - 1];
+    rr = right[e - 1];
   }
   out_counts[i] = c;
   if (out_left) out_left[i] = l;

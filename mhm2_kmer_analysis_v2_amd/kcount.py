@@ -14,6 +14,7 @@
   dump_kmers ("KMER count L R", kmer_dht.cpp:284)     .dump_lines()            (host)
                                                       .sort_results()          kc_sort_results
                                                       .dump_text(...)          kc_dump_text_device
+  (traverse_debruijn_graph: commented out there)      .unitigs()               kc_build_unitigs
 """
 import ctypes as C
 
@@ -21,7 +22,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (check, kc_config, kc_kernel_time, kc_merge_stats, kc_result, kc_stats, kc_synth_params, kc_trim_stats, kc_tuning,
-                   lib)
+                   kc_unitig_stats, lib)
 
 
 def _ptr(a):
@@ -496,10 +497,10 @@ class KmerCounter:
 
     def kernel_times(self, clear=False):
         """{kernel name: (launches, total_ms)} from HIP events on the launch stream (needs time_kernels=True)."""
-        arr = (kc_kernel_time * 32)()
+        arr = (kc_kernel_time * 64)()  # more than the library has kinds of kernels
         n = C.c_int(0)
-        check(lib().kc_get_kernel_times(self._h, arr, 32, C.byref(n)), "kc_get_kernel_times")
-        out = {arr[i].name.decode(): (int(arr[i].launches), float(arr[i].total_ms)) for i in range(min(n.value, 32))}
+        check(lib().kc_get_kernel_times(self._h, arr, 64, C.byref(n)), "kc_get_kernel_times")
+        out = {arr[i].name.decode(): (int(arr[i].launches), float(arr[i].total_ms)) for i in range(min(n.value, 64))}
         if clear:
             check(lib().kc_clear_kernel_times(self._h), "kc_clear_kernel_times")
         return out
@@ -540,6 +541,53 @@ class KmerCounter:
         torch.cuda.current_stream(self.device).synchronize()  # the fresh array is torch's until now
         check(lib().kc_dump_text_device(self._h, first, count, text.data_ptr(), nb.value, C.byref(nb)), "kc_dump_text_device")
         return text.cpu().numpy().tobytes()
+
+    def _unitigs(self, with_depths, with_sums):
+        import torch
+        self.finalize()
+        L = lib()
+        nu, nb, st = C.c_uint64(0), C.c_uint64(0), kc_unitig_stats()
+        check(L.kc_build_unitigs(self._h, None, 0, None, None, 0, None, C.byref(nu), C.byref(nb), C.byref(st)), "kc_build_unitigs")
+        dev = "cuda:%d" % self.device
+        seqs = torch.empty(nb.value, dtype=torch.uint8, device=dev)
+        offsets = torch.zeros(nu.value + 1, dtype=torch.int64, device=dev)
+        depths = torch.empty(nb.value, dtype=torch.int16, device=dev) if with_depths else None
+        sums = torch.empty(nu.value, dtype=torch.int64, device=dev) if with_sums else None
+        torch.cuda.current_stream(self.device).synchronize()  # the fresh arrays are torch's until now
+        check(L.kc_build_unitigs(self._h, seqs.data_ptr(), nb.value, depths.data_ptr() if with_depths else None, offsets.data_ptr(),
+                                 nu.value, sums.data_ptr() if with_sums else None, C.byref(nu), C.byref(nb), C.byref(st)),
+              "kc_build_unitigs")
+        self._res = None  # the results may have moved (kc_sort_results)
+        return seqs, depths, offsets, sums, {n: int(getattr(st, n)) for n, _ in kc_unitig_stats._fields_}
+
+    def unitigs(self):
+        """The unitigs of the results, built on the device (kc_build_unitigs): (seqs, offsets,
+        kmer_sums, stats) -- seqs a uint8 device tensor in the seq-block format (every unitig followed by '_'), offsets an
+        int64 device tensor of len(unitigs) + 1 starts, kmer_sums an int64 device tensor of the summed counts, stats a
+        dict of kc_unitig_stats.  A size query, then the call.  The results end up in key order (sort_results())."""
+        seqs, _, offsets, sums, st = self._unitigs(False, True)
+        return seqs, offsets, sums, st
+
+    def unitig_block(self):
+        """(seqs, depths): the unitigs as a device seq block and, per byte, the unitig's depth as int16 bits of the
+        uint16 value (0 on a separator) -- what kc_submit_ctg_block takes with on_device = 1 (submit_ctg_block)."""
+        seqs, depths, _, _, _ = self._unitigs(True, False)
+        return seqs, depths
+
+    def unitig_strings(self):
+        """Host list of (sequence, kmer_sum), in the output's order: for tests and small inputs."""
+        seqs, offsets, sums, _ = self.unitigs()
+        text, offs, ks = seqs.cpu().numpy().tobytes().decode(), offsets.cpu().tolist(), sums.cpu().tolist()
+        return [(text[offs[u]:offs[u + 1] - 1], ks[u]) for u in range(len(ks))]
+
+    def submit_ctg_block(self, seqs, depths):
+        """kc_submit_ctg_block with device tensors (a '_'-joined block and one 16-bit depth per byte), e.g. those of
+        unitig_block(); begin_ctg_kmers first."""
+        ps, dev = _ptr(seqs)
+        pd, _ = _ptr(depths)
+        if not dev:
+            raise ValueError("submit_ctg_block takes device tensors; submit_ctgs is the host path")
+        check(lib().kc_submit_ctg_block(self._h, ps, pd, seqs.numel(), 1), "kc_submit_ctg_block")
 
     def dump_kmers(self, directory=".", rank=None, on_device=False, chunk_lines=1 << 24):
         """KmerDHT::dump_kmers (src/kcount/kmer_dht.cpp:273-297): per-rank gzip text file "kmers-<k>.txt.gz", one
