@@ -80,8 +80,9 @@ typedef struct kc_config {
                                  * of the level-1 buckets holding all of max_elems (see kc_shard_capacity) */
 #define KC_FLAG_WIRE_UNITS 8u /* kc_extract_partition / kc_insert_records exchange UNITS of the library's own wire record where the
                                  geometry has one (kc_wire_unit: four six-byte records of a mixed k-mer per three words for k = 21;
-                                 one k-mer record otherwise) and the owner of a k-mer is kc_partition_owner, not kc_owner.  All
-                                 shards of an exchange must be created alike. */
+                                 one k-mer record otherwise) and the owner of a k-mer is kc_partition_owner, not kc_owner -- for the reads'
+                                 k-mers that kc_extract_partition sends and for the contig k-mers that kc_submit_ctg_block keeps.
+                                 All shards of an exchange must be created alike. */
 #define KC_FLAG_TIME_KERNELS 1u /* bracket every kernel launch with HIP events on its own stream (kc_get_kernel_times) */
 
 /* Scalars the reference logs (src/kcount/kcount.cpp:94-102,158-160;
@@ -453,12 +454,14 @@ int kc_begin_ctg_kmers(kc_ctx *ctx, uint64_t max_ctg_kmers);
  * and, per character, the depth of its contig (the layout of SeqBlockInserterState::depth_block, kcount_gpu.cpp:74-91).
  * kc_finalize then returns what the reference's insert_into_local_hashtable would after inserting the contigs behind
  * the reads: the reads' results, plus the contig k-mers that are not among them, whose occurrences agree on both
- * extensions (both bases) and all have a depth of 2 or more, with the smallest depth as their count (kc_ctg.hpp).
+ * extensions (both bases) and whose smallest depth is at least max(2, dmin_thres), with that depth as their count
+ * (kc_ctg.hpp).
  * KC_ERR_BAD_BASE for a character outside ACGTN anywhere in the block (the reference DIEs), KC_ERR_CAPACITY when more
  * distinct k-mers came than kc_begin_ctg_kmers made room for (the table is never filled beyond three quarters: a block is
  * taken in as many launches as its free room asks for).  A context that is one of several ranks (rank_n > 1) keeps of a
- * block only the k-mers the read path would keep there -- its share by the k-mer hash, by the reference's target rank
- * (KC_FLAG_REFERENCE_OWNER) or, in the shard flow, by the owner of the k-mer's level-1 bucket -- so every rank may be
+ * block only the k-mers the read path would keep there -- what kc_partition_owner names (its share by the k-mer hash, by
+ * the reference's target rank with KC_FLAG_REFERENCE_OWNER, by the wire units' owner bits with KC_FLAG_WIRE_UNITS where the
+ * geometry has wire units) or, in the shard flow, the owner of the k-mer's level-1 bucket (kc_shard_owner) -- so every rank may be
  * given every contig, or (like the C++ driver, whose host routes supermers by target) only its own. */
 int kc_submit_ctg_block(kc_ctx *ctx, const char *seqs, const uint16_t *depths, uint64_t len, int on_device);
 /* The contig pass so far: distinct contig k-mers in its table (what done_ctg_kmer_inserts reports as new inserts,

@@ -1129,8 +1129,9 @@ static int launch_bin_reads_t(kc_ctx *c, const ExtractArgs &a, uint64_t nsuper) 
   return KC_OK;
 }
 
-// pieces per destination of the wire units (kc_wire6.hpp)
-static uint32_t bin_lg_pieces(const kc_ctx *c) { return c->wire6 ? wire6_lg_pieces((uint32_t)c->cfg.rank_n) : 0; }
+// pieces per destination of the wire units (kc_wire6.hpp): a piece is a value of the top bits of the level-1 bucket, so there
+// are never more pieces than buckets (kc_bin16_kernel shifts the bucket by la - lgQ)
+static uint32_t bin_lg_pieces(const kc_ctx *c) { return c->wire6 ? std::min<uint32_t>(wire6_lg_pieces((uint32_t)c->cfg.rank_n), c->gm.la) : 0; }
 static uint32_t bin_pieces(const kc_ctx *c) { return 1u << bin_lg_pieces(c); }
 
 template <int FMT>
@@ -3231,7 +3232,13 @@ extern "C" int kc_submit_ctg_block(kc_ctx *c, const char *seqs, const uint16_t *
       own.own_lo = shard_first_bucket((uint32_t)c->cfg.rank_me, c->gm.P1, (uint32_t)c->cfg.rank_n);
       own.own_hi = shard_first_bucket((uint32_t)c->cfg.rank_me + 1, c->gm.P1, (uint32_t)c->cfg.rank_n);
     } else {
-      own.mode = (c->cfg.flags & KC_FLAG_REFERENCE_OWNER) ? CTG_OWN_REFERENCE : CTG_OWN_HASH;
+      if ((c->cfg.flags & KC_FLAG_WIRE_UNITS) && bk_active(c)) rc = bk_init(c);  // the geometry decides (kc_partition_owner)
+      if (c->wire6) {  // the records flow with wire units: the owner kc_extract_partition sends the k-mer to
+        own.mode = CTG_OWN_WIRE6;
+        own.gm = c->gm;
+      } else {
+        own.mode = (c->cfg.flags & KC_FLAG_REFERENCE_OWNER) ? CTG_OWN_REFERENCE : CTG_OWN_HASH;
+      }
     }
   }
   // A launch may add as many distinct k-mers as it has positions: it gets no more positions than the table has room for
@@ -3288,12 +3295,13 @@ static int ctg_merge_t(kc_ctx *c) {
   if (rc) return rc;
   const uint64_t n_res = c->out_n;
   uint64_t *cur = c->d_ctg_status + 2;  // [2] cursor, [3] sum of the appended counts
+  const uint32_t min_depth = (uint32_t)std::max(2, c->cfg.dmin_thres);  // what get_ext asks of an entry whose one counter is its count
   const unsigned nblk = (unsigned)((c->ctg_cap + 255) / 256);
   for (int pass = 0; pass < 2; pass++) {
     uint64_t init[2] = {n_res, 0};
     HIPCHK(hipMemcpyAsync(cur, init, 16, hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(kc_ctg_merge_kernel<NL>, dim3(nblk), dim3(256), 0, c->stream, c->ctg_table, c->ctg_cap, c->d_index, c->index_cap - 1, n_res,
-                       c->d_out_keys, c->d_out_counts, c->d_out_left, c->d_out_right, pass == 0 ? (uint64_t)0 : c->out_cap, NL, cur, cur + 1);
+                       c->d_out_keys, c->d_out_counts, c->d_out_left, c->d_out_right, pass == 0 ? (uint64_t)0 : c->out_cap, NL, cur, cur + 1, min_depth);
     c->num_gpu_calls++;
     HIPCHK(hipGetLastError());
     uint64_t got[2];

@@ -10,11 +10,14 @@
 //   * contig occurrences among themselves: the entry holds {count, left, right} of the last one taken; a later
 //     occurrence with other extensions sets the count to 0 for good, one with the same extensions sets it to the smaller
 //     of the two counts -- where "the same" compares against get_ext of an entry whose only counter is its count, which is
-//     the base itself only from a count of 2 upwards (dmin_thres), so one occurrence with a count below 2 also ends at
-//     0 or 1; what insert_into_local_hashtable finally keeps is count >= 2 with both extensions a base.
+//     the base itself only from a count of dmin_thres upwards (the vote's threshold max(dmin_thres, (int)(0.1 * count))
+//     is dmin_thres here: a tenth of the count never exceeds the count).  So a shallower occurrence ends at 0 when a later
+//     one meets it (its extension reads as X, which no occurrence carries), or as the smaller count with an extension X
+//     when it comes last; what insert_into_local_hashtable finally keeps is count >= 2 with both extensions a base.
 // Hence: result = the reads' results, plus every k-mer that is not among them, whose contig occurrences all carry the same
-// pair of extensions, both of them bases, and all have a count of 2 or more -- with the smallest of those counts.
-// (tests/test_gpu_ctg.py checks this against the oracle's statement-for-statement restatement, contigs in random order.)
+// pair of extensions, both of them bases, and whose smallest count is at least max(2, dmin_thres) -- with that smallest
+// count.  (tests/ctg_cases.py builds this table row by row; tests/test_ctg_cases.py holds it against the oracle's
+// statement-for-statement restatement, tests/test_gpu_ctg_edges.py and tests/test_gpu_ctg.py hold the device against both.)
 //
 // Device side: the occurrences go into a table of their own -- per k-mer the smallest count (an atomic max of its
 // complement) and the extension pair (first writer sets it, anybody who differs marks the conflict) -- and kc_finalize
@@ -22,6 +25,7 @@
 #pragma once
 #include "kc_bucketed.hpp"
 #include "kc_supermer.hpp"
+#include "kc_wire6.hpp"
 
 namespace kc {
 
@@ -29,11 +33,12 @@ constexpr uint32_t CTG_EXT_CONFLICT = 0xFFFFFFFFu;
 
 // Which contig k-mers a context of several ranks keeps: the ones the read path would keep there (a caller that routes its
 // supermers by target, like the C++ driver, submits only those anyway).
-enum { CTG_OWN_ALL = 0, CTG_OWN_HASH, CTG_OWN_REFERENCE, CTG_OWN_BUCKET };
+// CTG_OWN_WIRE6: a context that exchanges wire units (kc_wire6.hpp) -- the shard kc_partition_owner names.
+enum { CTG_OWN_ALL = 0, CTG_OWN_HASH, CTG_OWN_REFERENCE, CTG_OWN_BUCKET, CTG_OWN_WIRE6 };
 struct CtgOwn {
   uint32_t mode, rank_me, rank_n;
   uint32_t own_lo, own_hi;  // CTG_OWN_BUCKET (the shard flow): the level-1 buckets this shard owns
-  Geom gm;
+  Geom gm;                  // CTG_OWN_BUCKET, CTG_OWN_WIRE6
 };
 
 // One thread per position [p0, p1) of a '_'-joined block of contigs (any case: a lower-case neighbour counts as low
@@ -91,6 +96,8 @@ __global__ void kc_ctg_insert_kernel(const uint8_t *seqs, const uint16_t *depths
       o = kc_reference_owner<KL>(f, rr, k, own.rank_n);
     } else if (own.mode == CTG_OWN_HASH) {
       o = kc_owner_of_hash(kc_hash<KL>(f), own.rank_n);
+    } else if (own.mode == CTG_OWN_WIRE6) {  // (one-word k-mers only: Geom::rec6)
+      o = wire6_owner((uint32_t)kc_feistel_fwd(f[0] >> (64u - own.gm.k2), k), own.rank_n);
     } else {
       const uint32_t b1 = (KL == 1 && own.gm.cp) ? (uint32_t)(kc_feistel_fwd(f[0] >> (64u - own.gm.k2), k) >> (own.gm.k2 - own.gm.la))
                                                   : hash_b1(kc_hash<KL>(f), own.gm);
@@ -112,12 +119,13 @@ __global__ void kc_ctg_insert_kernel(const uint8_t *seqs, const uint16_t *depths
   }
 }
 
-// Every contig k-mer that qualifies and is not among the first n_res results is appended behind them.  out_cap = 0:
-// only counts (cursor starts at n_res either way).
+// Every contig k-mer that qualifies -- one pair of extensions, the smallest count at least min_depth = max(2, dmin_thres) --
+// and is not among the first n_res results is appended behind them.  out_cap = 0: only counts (cursor starts at n_res
+// either way).
 template <int NL>
 __global__ void kc_ctg_merge_kernel(Table t, uint64_t capacity, const uint32_t *index, uint64_t imask, uint64_t n_res, uint64_t *out_keys,
                                     uint16_t *out_counts, uint8_t *out_left, uint8_t *out_right, uint64_t out_cap, int out_nl, uint64_t *cursor,
-                                    uint64_t *sum) {
+                                    uint64_t *sum, uint32_t min_depth) {
   const uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= capacity) return;
   uint64_t key[NL];
@@ -125,7 +133,7 @@ __global__ void kc_ctg_merge_kernel(Table t, uint64_t capacity, const uint32_t *
   for (int j = 0; j < NL; j++) key[j] = t.keys[s * NL + j];
   if (key[NL - 1] == KEY_EMPTY) return;
   const uint32_t count = 0xFFFFFFFFu - t.vals[s * 2], e = t.vals[s * 2 + 1];
-  if (e == 0u || e == CTG_EXT_CONFLICT || count < 2u) return;
+  if (e == 0u || e == CTG_EXT_CONFLICT || count < min_depth) return;
   // among the reads' results?  (their keys have out_nl words: the k-mer's, then zeros)
   uint64_t h = kc_hash<NL>(key) & imask;
   for (;;) {

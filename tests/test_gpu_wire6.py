@@ -30,6 +30,7 @@ def run_flow(reads, quals, k, R, tuning, blocks=3, wire_units=True, together=Fal
     recs = torch.zeros(R * Q * seg * uw, dtype=torch.int64, device="cuda")
     per = (len(reads) + blocks - 1) // blocks
     shipped = 0
+    run_flow.pieces = [set() for _ in range(R)]  # (of the last call: per destination, the pieces that held units)
     for part in range(blocks):
         sl = slice(part * per, min(len(reads), (part + 1) * per))
         if sl.start >= sl.stop:
@@ -42,6 +43,7 @@ def run_flow(reads, quals, k, R, tuning, blocks=3, wire_units=True, together=Fal
         assert n_here <= int(counts.sum()) * ur <= n_here + 4096 * ur  # whole units: a few marker slots per run
         shipped += int(counts.sum())
         for d in range(R):
+            run_flow.pieces[d].update(q for q in range(Q) if int(counts[d * Q + q]))
             pieces = [recs[(d * Q + q) * seg * uw:(d * Q + q) * seg * uw + int(counts[d * Q + q]) * uw] for q in range(Q)]
             if together == "strided":  # where they lie, in one call (kc_insert_record_pieces)
                 shards[d].insert_record_pieces(recs[d * Q * seg * uw:], seg, [int(counts[d * Q + q]) for q in range(Q)])
@@ -79,6 +81,32 @@ def test_wire_units_flow_matches_the_oracle(R):
     if R > 1:  # the owner bits spread the k-mers over the shards
         sizes = [len(p[1]) for p in parts]
         assert min(sizes) > 0.5 * max(sizes)
+    for s in shards:
+        s.close()
+
+
+def test_wire_units_with_fewer_level_1_buckets_than_pieces():
+    """k = 17 with four level-1 buckets (la = 2, lb = 8: the mix keeps 34 - 2 - 8 = 24 >= 21 bits below the region, so the
+    geometry has wire units) and eight shards, which would like eight pieces per destination: a piece is a value of the
+    top bits of the bucket, so there are four at most (kc_bin16_kernel's shift la - lgQ must not go below zero)."""
+    k, R = 17, 8
+    tuning = dict(p1=4, p2=256)
+    with pkg.KmerCounter(k, rank_me=0, rank_n=R, tuning=tuning, wire_units=True) as kc:
+        assert kc.wire_unit()[:2] == (3, 4)  # this geometry really is one of six-byte wire records
+        assert kc.wire_unit()[2] <= 4
+    rng = np.random.default_rng(1717)
+    reads, quals = random_reads(rng, 1500, min_len=30, max_len=150, genome_len=4000)
+    b, q, offs = arrays(reads, quals)
+    want, _, wst = oracle_run(b, q, offs, k)
+    shards, (uw, ur, Q), _ = run_flow(reads, quals, k, R, tuning)
+    assert (uw, ur) == (3, 4) and 1 < Q <= 4
+    parts = [s.sorted_results() for s in shards]
+    assert_same(union(parts), want)
+    assert sum(s.stats()["kmers_inserted"] for s in shards) == wst["kmers_inserted"]
+    assert all(len(p) > 1 for p in run_flow.pieces), run_flow.pieces  # more than one piece per destination holds records
+    for r, (s, p) in enumerate(zip(shards, parts)):
+        for i in range(0, len(p[1]), 29):
+            assert s.partition_owner(p[0][i]) == r
     for s in shards:
         s.close()
 
