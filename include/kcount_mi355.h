@@ -554,6 +554,78 @@ typedef struct kc_unitig_stats {
 } kc_unitig_stats;
 int kc_build_unitigs(kc_ctx *ctx, uint8_t *d_seqs, uint64_t capacity, uint16_t *d_depths, uint64_t *d_offsets, uint64_t unitigs_capacity,
                      uint64_t *d_kmer_sums, uint64_t *n_unitigs, uint64_t *nbytes, kc_unitig_stats *stats);
+/*
+ * A seed index over a block of contigs, kept by the context: the first half of putting the reads back onto the contigs
+ * just built -- the role of find_alignments in src/contigging.cpp:150-163, which the reference's proxy has commented out
+ * like the traversal before it and for which it holds no code (no klign in src/).  So the rules are THIS project's own
+ * definition (pinned by the host model tests/align_model.py); no parity with MetaHipMer's klign is
+ * claimed.
+ * seqs: a seq block as kc_build_unitigs writes it and kc_submit_ctg_block takes it -- nbytes bytes, every contig
+ * followed by '_', upper-case A C G T N only; offsets[0] = 0, offsets[u+1] - 1 = the position of contig u's '_',
+ * offsets[n_ctgs] = nbytes; empty contigs are allowed.  on_device != 0: seqs and offsets are device pointers.
+ * The seed length is the context's kmer_len.  A window is a contig position whose k characters are all ACGT (an N is not
+ * G here); its key is the canonical k-mer; a key is a seed iff exactly one window of the whole block has it and it is
+ * not its own reverse complement; every other key is "repeated" and never used.
+ * The context keeps its own device copy of block and offsets (the caller's arrays are free afterwards) and a table of
+ * 8-byte slots, at most half full: 16 to 32 bytes per byte of the block.  The call replaces an earlier index.
+ * KC_ERR_BAD_BASE: a byte outside the alphabet; KC_ERR_INVALID_ARG: offsets that do not match the '_'s, a NULL ctx or
+ * offsets; KC_ERR_CAPACITY: 2^31 bytes or more (slots hold 32-bit positions); out of memory.  Each of them leaves an
+ * earlier index intact (failure-atomic, as kc_sort_results is).  Works before or after kc_finalize and in a context with
+ * rank_n > 1; kc_reset and kc_destroy drop the index, kc_ctg_index_clear does so on request.  *stats may be NULL.
+ */
+typedef struct kc_ctg_index_stats {
+  uint64_t contigs;
+  uint64_t bases;    /* without separators */
+  uint64_t windows;  /* positions whose k characters are all ACGT */
+  uint64_t seeds;    /* keys of exactly one window */
+  uint64_t repeated; /* keys of several windows, or their own reverse complement */
+} kc_ctg_index_stats;
+int kc_ctg_index_build(kc_ctx *ctx, const uint8_t *seqs, uint64_t nbytes, const uint64_t *offsets, uint64_t n_ctgs, int on_device,
+                       kc_ctg_index_stats *stats);
+int kc_ctg_index_clear(kc_ctx *ctx);
+/*
+ * Reads onto the indexed contigs by seed hits, every hit checked without gaps -- the second half of the role of
+ * find_alignments (src/contigging.cpp:150-163); the rules are this project's own (DESIGN.md section 15,
+ * tests/align_model.py), gapped alignment is out of scope.
+ * bases / offsets as for kc_merge_pairs (ASCII, nreads + 1 offsets), no qualities; A C G T in either case are bases,
+ * anything else is "no base"; a read has at most KC_ALIGN_MAX_READ_LEN bases.  The windows of a read of length L start
+ * at p = 0, s, 2s, ... with p + k <= L (s = seed_space >= 1) and consist of bases only.  A window w whose canonical key
+ * is a seed at contig u, window offset j, contig text y gives the candidate (u, orient, d): w = y -> orient 0,
+ * d = j - p; w = revcomp(y) -> orient 1, d = j - (L - k - p).  With R' the read (orient 0) or its reverse complement:
+ * cstart = max(0, d), cstop = min(len_u, d + L), rstart = cstart - d, rstop = cstop - d, mismatches = the i in
+ * [rstart, rstop) where R'[i] is no base, or contig[d + i] is N, or the two differ; seeds = the windows that gave the
+ * candidate.  A candidate is emitted iff mismatches <= max_mismatches (0xFFFFFFFF keeps all).
+ * alns receives one record per emitted candidate, ordered by read, then (ctg, orient, d) ascending -- one exact byte
+ * string; read_first (may be NULL) receives nreads + 1 entries: every read's first record, then the total.
+ * on_device applies to bases, offsets, alns and read_first alike (a device alns is 16-byte aligned).
+ * *n_alns and *stats (may be NULL) always receive the totals.  alns == NULL: a size query, nothing else is written.
+ * capacity (records) too small: KC_ERR_CAPACITY, nothing is written.  No index: KC_ERR_STATE.  seed_space == 0, a NULL
+ * ctx or n_alns, or a read over the limit (kc_last_error names it): KC_ERR_INVALID_ARG; the pointer checks come before
+ * any device call.  nreads == 0: KC_OK.  Neither the table nor the results are touched.  The call runs on the context's
+ * stream and returns when its work there is done.  Scratch (8 bytes a read, and the staged input and output of a host
+ * caller) lives for the call only.
+ */
+#define KC_ALIGN_MAX_READ_LEN 1024
+typedef struct kc_read_aln {
+  uint32_t read, ctg;
+  uint32_t cstart, cstop; /* the contig interval */
+  uint16_t rstart, rstop; /* the same interval in R' */
+  uint16_t mismatches, seeds;
+  uint8_t orient;
+  uint8_t pad[7]; /* zero */
+} kc_read_aln;
+typedef struct kc_align_stats {
+  uint64_t reads;
+  uint64_t reads_aligned; /* reads with at least one record */
+  uint64_t windows;       /* windows looked up: all bases */
+  uint64_t seed_hits;     /* ... whose key is a seed */
+  uint64_t repeated_hits; /* ... whose key is repeated */
+  uint64_t alignments;    /* records */
+  uint64_t perfect;       /* mismatches 0, rstart 0, rstop = the read's length */
+} kc_align_stats;
+int kc_align_reads(kc_ctx *ctx, const uint8_t *bases, const uint64_t *offsets, uint64_t nreads, int on_device, uint32_t seed_space,
+                   uint32_t max_mismatches, kc_read_aln *alns, uint64_t capacity, uint64_t *read_first, uint64_t *n_alns,
+                   kc_align_stats *stats);
 /* KmerDHT::kmer_exists / get_kmer_count / get_local_kmer_counts (src/kcount/kmer_dht.cpp:198-245) in bulk, against the
  * results kept in HBM: nq k-mers of num_longs words each, in either orientation; counts[i] = 0 (and left/right = 0)
  * when the k-mer did not survive.  The index over the results is built on the first call after kc_finalize.

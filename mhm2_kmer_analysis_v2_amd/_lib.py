@@ -75,6 +75,22 @@ class kc_unitig_stats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("kmers", "unitigs", "singletons", "circular", "bases", "longest")]
 
 
+class kc_ctg_index_stats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("contigs", "bases", "windows", "seeds", "repeated")]
+
+
+class kc_align_stats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("reads", "reads_aligned", "windows", "seed_hits", "repeated_hits", "alignments", "perfect")]
+
+
+class kc_read_aln(C.Structure):
+    _fields_ = [("read", C.c_uint32), ("ctg", C.c_uint32), ("cstart", C.c_uint32), ("cstop", C.c_uint32), ("rstart", C.c_uint16),
+                ("rstop", C.c_uint16), ("mismatches", C.c_uint16), ("seeds", C.c_uint16), ("orient", C.c_uint8), ("pad", C.c_uint8 * 7)]
+
+
+KC_ALIGN_MAX_READ_LEN = 1024
+KC_ALIGN_KEEP_ALL = 0xFFFFFFFF
+
 # every symbol include/kcount_mi355.h declares: (restype, argtypes)
 SYMBOLS = {
     "kc_abi_version": (C.c_int, []),
@@ -138,6 +154,10 @@ SYMBOLS = {
     "kc_dump_text_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "kc_build_unitigs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64),
                                     C.POINTER(C.c_uint64), C.POINTER(kc_unitig_stats)]),
+    "kc_ctg_index_build": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.POINTER(kc_ctg_index_stats)]),
+    "kc_ctg_index_clear": (C.c_int, [C.c_void_p]),
+    "kc_align_reads": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64,
+                                  C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(kc_align_stats)]),
     "kc_lookup": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "kc_dump_table": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
     "kc_get_stats": (C.c_int, [C.c_void_p, C.POINTER(kc_stats)]),

@@ -31,6 +31,7 @@
 #include "kc_fastq.hpp"
 #include "kc_sort.hpp"
 #include "kc_unitig.hpp"
+#include "kc_align.hpp"
 
 using namespace kc;
 
@@ -93,10 +94,12 @@ enum { KT_EXTRACT_INSERT = 0, KT_EXTRACT_BIN, KT_INSERT_RECORDS, KT_FINALIZE, KT
        KT_FQ_INDEX, KT_FQ_CHECK, KT_FQ_DETAIL, KT_FQ_SUMS, KT_FQ_WRITE_PACKED, KT_FQ_WRITE_PAIRS, KT_TRIM_SEED, KT_TRIM_ALIGN,
        KT_TRIM_SIZES, KT_TRIM_SCAN, KT_TRIM_WRITE, KT_SORT_HIST, KT_SORT_HIST_LOAD, KT_SORT_SCAN, KT_SORT_SCATTER, KT_SORT_GATHER,
        KT_DUMP_SIZES, KT_DUMP_SCAN, KT_DUMP_WRITE, KT_UNITIG_LINKS, KT_UNITIG_MIN_JUMP, KT_UNITIG_CUT, KT_UNITIG_RANK_JUMP,
-       KT_UNITIG_SELECT, KT_UNITIG_SCAN, KT_UNITIG_WRITE, KT_UNITIG_DEPTH, KT_COUNT };
+       KT_UNITIG_SELECT, KT_UNITIG_SCAN, KT_UNITIG_WRITE, KT_UNITIG_DEPTH, KT_ALIGN_CHECK, KT_ALIGN_INDEX, KT_ALIGN_SWEEP, KT_ALIGN_LENGTHS,
+       KT_ALIGN_COUNT, KT_ALIGN_SCAN, KT_ALIGN_WRITE, KT_COUNT };
 // KT_FQ_SCAN, KT_MERGE_SCAN and KT_TRIM_SCAN label the front end's three uses of the one shared kc_scan_kernel (kc_scan.hpp); their
 // strings keep the names the uses were first reported under.  KT_SORT_SCAN and KT_DUMP_SCAN are the back end's two,
-// KT_UNITIG_SCAN the unitigs' (kc_scan_kernel<2>: bytes and unitig numbers in one pass).
+// KT_UNITIG_SCAN the unitigs' (kc_scan_kernel<2>: bytes and unitig numbers in one pass), KT_ALIGN_SCAN the alignments' (the
+// reads' record counts).  KT_ALIGN_COUNT and KT_ALIGN_WRITE are the two passes of kc_align_reads_kernel.
 static const char *const kt_names[KT_COUNT] = {"kc_extract_kernel<insert>", "kc_bin_reads_kernel", "kc_insert_records_kernel",
                                                "kc_finalize_kernel", "kc_tile_first_kernel", "kc_rehash_kernel",
                                                "kc_l1_reads_kernel", "kc_l1_records_kernel", "kc_l2_split_kernel",
@@ -113,7 +116,9 @@ static const char *const kt_names[KT_COUNT] = {"kc_extract_kernel<insert>", "kc_
                                                "kc_dump_scan_kernel", "kc_dump_write_kernel", "kc_unitig_links_kernel",
                                                "kc_unitig_min_jump_kernel", "kc_unitig_cut_kernel", "kc_unitig_rank_jump_kernel",
                                                "kc_unitig_select_kernel", "kc_unitig_scan_kernel", "kc_unitig_write_kernel",
-                                               "kc_unitig_depth_kernel"};
+                                               "kc_unitig_depth_kernel", "kc_align_check_kernel", "kc_align_index_kernel", "kc_align_sweep_kernel",
+                                               "kc_align_lengths_kernel", "kc_align_reads_kernel<count>", "kc_align_scan_kernel",
+                                               "kc_align_reads_kernel<write>"};
 struct kt_pending {
   hipEvent_t start, stop;
   int kind;
@@ -166,6 +171,11 @@ struct kc_ctx {
   uint64_t ctg_cap;
   uint64_t *d_ctg_status;  // [0] a character outside the alphabet was seen, [1] entries
   uint64_t ctg_attempted, ctg_new;
+  // the contigs' seed index (kc_ctg_index_build, kc_align.hpp): slots, 32-bit offsets and the block in one allocation; it
+  // belongs to a pass, like the contig table (kc_reset drops it)
+  uint8_t *d_ai;
+  AlignIndex ai;
+  bool ai_ready;
   double arena_probe_tbps;  // rate of level 1's write pattern on the arena pick_fast_arena chose (0: no probe ran)
   kc_synth_table *d_synth;
   // scratch of the reference-wire entry points (kc_build_supermers, kc_submit_packed_supermers)
@@ -576,6 +586,13 @@ static void free_ctg(kc_ctx *c) {
   c->ctg_cap = c->ctg_attempted = c->ctg_new = 0;
 }
 
+static void free_align_index(kc_ctx *c) {
+  if (c->d_ai) (void)hipFree(c->d_ai);
+  c->d_ai = nullptr;
+  memset(&c->ai, 0, sizeof(c->ai));
+  c->ai_ready = false;
+}
+
 static void free_results(kc_ctx *c) {
   free_index(c);
   if (c->d_out_keys) (void)hipFree(c->d_out_keys);
@@ -611,6 +628,7 @@ extern "C" void kc_destroy(kc_ctx *c) {
   if (c->d_ad) (void)hipFree(c->d_ad);
   host_pipe_free(c);
   free_ctg(c);
+  free_align_index(c);
   bk_free(c, false);
   shard_free(c);
   if (c->d_cb) (void)hipFree(c->d_cb);
@@ -689,6 +707,7 @@ extern "C" int kc_reset(kc_ctx *c, int new_k) {
   const int old_nl = c->nl, old_k = c->k;
   if (kc_record_longs(new_k) != old_nl) free_results(c);  // else the result arrays are reused by the next finalize
   free_ctg(c);  // a contig pass belongs to one pass over the reads
+  free_align_index(c);  // ... and so do the contigs the reads are aligned to (their seeds have the old k)
   c->out_n = 0;
   c->k = new_k;
   c->cfg.kmer_len = new_k;
@@ -3182,6 +3201,7 @@ extern "C" int kc_lookup(kc_ctx *c, const uint64_t *queries, uint64_t nq, int on
 
 #include "kc_api_sort.hpp"  // kc_sort_results, kc_dump_text_device
 #include "kc_api_unitig.hpp"  // kc_build_unitigs
+#include "kc_api_align.hpp"  // kc_ctg_index_build, kc_ctg_index_clear, kc_align_reads
 
 // ---- the contig pass (kc_ctg.hpp) ----------------------------------------------------------------------------------
 extern "C" int kc_begin_ctg_kmers(kc_ctx *c, uint64_t max_ctg_kmers) {

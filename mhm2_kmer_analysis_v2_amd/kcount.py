@@ -21,7 +21,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (check, kc_config, kc_kernel_time, kc_merge_stats, kc_result, kc_stats, kc_synth_params, kc_trim_stats, kc_tuning,
+from ._lib import (check, kc_align_stats, kc_config, kc_ctg_index_stats, kc_kernel_time, kc_merge_stats, kc_result, kc_stats, kc_synth_params, kc_trim_stats, kc_tuning,
                    kc_unitig_stats, lib)
 
 
@@ -580,6 +580,64 @@ class KmerCounter:
         text, offs, ks = seqs.cpu().numpy().tobytes().decode(), offsets.cpu().tolist(), sums.cpu().tolist()
         return [(text[offs[u]:offs[u + 1] - 1], ks[u]) for u in range(len(ks))]
 
+    def index_contigs(self, seqs, offsets):
+        """Seed index over a block of contigs (kc_ctg_index_build): seqs a uint8 seq block (every
+        contig followed by '_'), offsets its len(contigs) + 1 starts as 64-bit integers -- numpy arrays, or device tensors
+        as unitigs() returns them.  The counter keeps its own copy; an earlier index is replaced.  Returns
+        kc_ctg_index_stats as a dict."""
+        ps, dev = _ptr(seqs)
+        po, dev_o = _ptr(offsets)
+        if dev != dev_o:
+            raise ValueError("seqs and offsets must both be host arrays or both be device tensors")
+        n = len(offsets) - 1
+        nbytes = seqs.numel() if dev else len(seqs)
+        st = kc_ctg_index_stats()
+        if dev:
+            import torch
+            torch.cuda.current_stream(self.device).synchronize()  # the arrays are torch's until now
+        check(lib().kc_ctg_index_build(self._h, ps if nbytes else None, nbytes, po, n, 1 if dev else 0, C.byref(st)), "kc_ctg_index_build")
+        return {f: int(getattr(st, f)) for f, _ in kc_ctg_index_stats._fields_}
+
+    def index_unitigs(self):
+        """unitigs() straight into the seed index, on the device.  Returns kc_ctg_index_stats as a dict."""
+        seqs, _, offsets, _, _ = self._unitigs(False, False)
+        return self.index_contigs(seqs, offsets)
+
+    def clear_contig_index(self):
+        check(lib().kc_ctg_index_clear(self._h), "kc_ctg_index_clear")
+
+    def align_reads(self, bases, offsets, seed_space=1, max_mismatches=None, nreads=None):
+        """Reads onto the indexed contigs (kc_align_reads): a size query, then the call.  bases
+        uint8 ASCII, offsets nreads + 1 64-bit integers.  Returns (alns, read_first, stats): for host arrays alns is a
+        numpy structured array (ALN_DTYPE) and read_first a uint64 array; for device tensors alns is a uint8 device tensor
+        of 32-byte records and read_first an int64 device tensor.  max_mismatches None keeps every candidate."""
+        pb, dev = _ptr(bases)
+        po, dev_o = _ptr(offsets)
+        n = (len(offsets) - 1) if nreads is None else nreads
+        if n and dev != dev_o:
+            raise ValueError("bases and offsets must both be host arrays or both be device tensors")
+        dev = dev_o
+        mm = _lib.KC_ALIGN_KEEP_ALL if max_mismatches is None else max_mismatches
+        L = lib()
+        na, st = C.c_uint64(0), kc_align_stats()
+        if dev:
+            import torch
+            torch.cuda.current_stream(self.device).synchronize()  # the input is torch's until now
+        check(L.kc_align_reads(self._h, pb, po, n, 1 if dev else 0, seed_space, mm, None, 0, None, C.byref(na), C.byref(st)), "kc_align_reads")
+        if dev:
+            d = "cuda:%d" % self.device
+            alns = torch.empty(max(na.value, 1) * 32, dtype=torch.uint8, device=d)
+            first = torch.empty(n + 1, dtype=torch.int64, device=d)
+            torch.cuda.current_stream(self.device).synchronize()  # the fresh arrays are torch's until now
+            pa, pf = alns.data_ptr(), first.data_ptr()
+        else:
+            alns = np.zeros(max(na.value, 1), dtype=ALN_DTYPE)
+            first = np.zeros(n + 1, dtype=np.uint64)
+            pa, pf = alns.ctypes.data, first.ctypes.data
+        check(L.kc_align_reads(self._h, pb, po, n, 1 if dev else 0, seed_space, mm, pa, na.value, pf, C.byref(na), C.byref(st)), "kc_align_reads")
+        alns = alns[:na.value * 32] if dev else alns[:na.value]
+        return alns, first, {f: int(getattr(st, f)) for f, _ in kc_align_stats._fields_}
+
     def submit_ctg_block(self, seqs, depths):
         """kc_submit_ctg_block with device tensors (a '_'-joined block and one 16-bit depth per byte), e.g. those of
         unitig_block(); begin_ctg_kmers first."""
@@ -610,6 +668,11 @@ class KmerCounter:
             for line in self.dump_lines():
                 f.write(line + "\n")
         return path
+
+
+# a record of kc_align_reads (kc_read_aln): 32 bytes
+ALN_DTYPE = np.dtype([("read", "<u4"), ("ctg", "<u4"), ("cstart", "<u4"), ("cstop", "<u4"), ("rstart", "<u2"), ("rstop", "<u2"),
+                      ("mismatches", "<u2"), ("seeds", "<u2"), ("orient", "u1"), ("pad", "u1", (7,))])
 
 
 def kmer_to_string(words, k):
