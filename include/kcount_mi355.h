@@ -586,7 +586,7 @@ int kc_ctg_index_clear(kc_ctx *ctx);
 /*
  * Reads onto the indexed contigs by seed hits, every hit checked without gaps -- the second half of the role of
  * find_alignments (src/contigging.cpp:150-163); the rules are this project's own (DESIGN.md section 15,
- * tests/align_model.py), gapped alignment is out of scope.
+ * tests/align_model.py); gapped alignment is kc_align_gapped's step behind this one.
  * bases / offsets as for kc_merge_pairs (ASCII, nreads + 1 offsets), no qualities; A C G T in either case are bases,
  * anything else is "no base"; a read has at most KC_ALIGN_MAX_READ_LEN bases.  The windows of a read of length L start
  * at p = 0, s, 2s, ... with p + k <= L (s = seed_space >= 1) and consist of bases only.  A window w whose canonical key
@@ -626,6 +626,60 @@ typedef struct kc_align_stats {
 int kc_align_reads(kc_ctx *ctx, const uint8_t *bases, const uint64_t *offsets, uint64_t nreads, int on_device, uint32_t seed_space,
                    uint32_t max_mismatches, kc_read_aln *alns, uint64_t capacity, uint64_t *read_first, uint64_t *n_alns,
                    kc_align_stats *stats);
+/*
+ * Gapped refinement of kc_align_reads' records: one kc_gap_aln for every kc_read_aln, in the same order -- the role of
+ * klign's fallback to SSW.  The step around the dynamic programme is this project's own definition (DESIGN.md section
+ * 16, tests/gap_model.py); the dynamic programme is the reference's ssw_align (src/ssw/ssw_core.cpp), all five results
+ * of Aligner::Align(report_cigar = false), pinned by tests/golden/gap_ref_alignments.json.
+ * bases / offsets / nreads: the reads kc_align_reads saw.  alns: n_alns records as it emits them, in any order, several
+ * of one read allowed.  With L the read's length, len_u the contig's and d = cstart - rstart, a record is valid iff
+ * read < nreads, ctg < the index's contigs, orient <= 1, cstart < cstop <= len_u, rstart < rstop <= L,
+ * cstop - cstart == rstop - rstart, cstart == max(0, d) and cstop == min(len_u, d + L); its mismatches field is not
+ * read.  Codes: a read's A C G T in either case are 0..3 and anything else 4, a contig's N is 4; R' is the read
+ * (orient 0) or its reverse complement (a code c < 4 becomes 3 - c).
+ * out[i].mismatches = the positions of [rstart, rstop) where R' or the contig holds a 4 or the two differ; read, ctg,
+ * orient and seeds are copied.  mismatches == 0 without KC_GAP_ALWAYS_DP: the input interval with
+ * score = match * (rstop - rstart), kind KC_GAP_EXACT.  Every other record: ssw_align of all of R' against
+ * contig[wlo, whi), wlo = max(0, d - pad), whi = min(len_u, d + L + pad), in exact integers with the reference's tie
+ * rules; a score > 0 gives cstart = wlo + ref_begin, cstop = wlo + ref_end + 1, rstart = query_begin,
+ * rstop = query_end + 1, kind KC_GAP_DP; a score of 0 gives four zeros, kind KC_GAP_NONE.
+ * scores: 1 <= match <= 9, mismatch and ambiguity <= 9, 1 <= gap_ext <= gap_open <= 9 (what Aligner::ReBuild(string),
+ * src/ssw/ssw.cpp:468-480, can express); pad <= KC_GAP_MAX_PAD; flags: KC_GAP_ALWAYS_DP only.
+ * on_device applies to bases, offsets, alns and out alike; device record arrays are 16-byte aligned.
+ * KC_ERR_INVALID_ARG: a NULL ctx, scores or out, or scores, pad or flags out of range (kc_last_error names the values):
+ * all checked before any device call, the ranges before ctx; a read over KC_ALIGN_MAX_READ_LEN or an invalid record
+ * (kc_last_error names the read, or the lowest bad record index).  No index: KC_ERR_STATE.  2^32 records or more (the
+ * list of records holds 32-bit indices): KC_ERR_CAPACITY.  For every error, of whichever kind, nothing is written
+ * through any pointer: neither out nor *stats.  n_alns == 0: KC_OK with zero statistics.  *stats (may be NULL) is
+ * written once, on success, and does not depend on the records' order.  Neither the index, the table nor the results are touched.  The call runs on the
+ * context's stream and returns when its work there is done.  Scratch (8 bytes a record, and the staged arrays of a host
+ * caller) lives for the call only.  Works before or after kc_finalize and in a context with rank_n > 1.
+ */
+#define KC_GAP_MAX_PAD 1024
+#define KC_GAP_ALWAYS_DP 1u
+enum { KC_GAP_EXACT = 0, KC_GAP_DP = 1, KC_GAP_NONE = 2 };
+typedef struct kc_aln_scores {
+  uint32_t match, mismatch, gap_open, gap_ext, ambiguity; /* penalties as positive numbers */
+} kc_aln_scores;
+typedef struct kc_gap_aln {
+  uint32_t read, ctg;
+  uint32_t cstart, cstop; /* the contig interval */
+  uint16_t rstart, rstop; /* the interval of R' */
+  uint32_t score;
+  uint16_t mismatches, seeds; /* of the input record's diagonal */
+  uint8_t orient, kind;
+  uint8_t pad[2]; /* zero */
+} kc_gap_aln;
+typedef struct kc_gap_stats {
+  uint64_t records;
+  uint64_t exact;     /* KC_GAP_EXACT */
+  uint64_t dp;        /* KC_GAP_DP */
+  uint64_t none;      /* KC_GAP_NONE */
+  uint64_t cells;     /* sum of L * (whi - wlo) over the records the dynamic programme ran for */
+  uint64_t score_sum; /* over all records */
+} kc_gap_stats;
+int kc_align_gapped(kc_ctx *ctx, const uint8_t *bases, const uint64_t *offsets, uint64_t nreads, const kc_read_aln *alns, uint64_t n_alns,
+                    int on_device, uint32_t pad, const kc_aln_scores *scores, uint32_t flags, kc_gap_aln *out, kc_gap_stats *stats);
 /* KmerDHT::kmer_exists / get_kmer_count / get_local_kmer_counts (src/kcount/kmer_dht.cpp:198-245) in bulk, against the
  * results kept in HBM: nq k-mers of num_longs words each, in either orientation; counts[i] = 0 (and left/right = 0)
  * when the k-mer did not survive.  The index over the results is built on the first call after kc_finalize.

@@ -91,6 +91,25 @@ class kc_read_aln(C.Structure):
 KC_ALIGN_MAX_READ_LEN = 1024
 KC_ALIGN_KEEP_ALL = 0xFFFFFFFF
 
+
+class kc_aln_scores(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("match", "mismatch", "gap_open", "gap_ext", "ambiguity")]
+
+
+class kc_gap_aln(C.Structure):
+    _fields_ = [("read", C.c_uint32), ("ctg", C.c_uint32), ("cstart", C.c_uint32), ("cstop", C.c_uint32), ("rstart", C.c_uint16),
+                ("rstop", C.c_uint16), ("score", C.c_uint32), ("mismatches", C.c_uint16), ("seeds", C.c_uint16), ("orient", C.c_uint8),
+                ("kind", C.c_uint8), ("pad", C.c_uint8 * 2)]
+
+
+class kc_gap_stats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("records", "exact", "dp", "none", "cells", "score_sum")]
+
+
+KC_GAP_MAX_PAD = 1024
+KC_GAP_ALWAYS_DP = 1
+KC_GAP_EXACT, KC_GAP_DP, KC_GAP_NONE = 0, 1, 2
+
 # every symbol include/kcount_mi355.h declares: (restype, argtypes)
 SYMBOLS = {
     "kc_abi_version": (C.c_int, []),
@@ -158,6 +177,8 @@ SYMBOLS = {
     "kc_ctg_index_clear": (C.c_int, [C.c_void_p]),
     "kc_align_reads": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64,
                                   C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(kc_align_stats)]),
+    "kc_align_gapped": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.c_uint32,
+                                   C.POINTER(kc_aln_scores), C.c_uint32, C.c_void_p, C.POINTER(kc_gap_stats)]),
     "kc_lookup": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "kc_dump_table": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
     "kc_get_stats": (C.c_int, [C.c_void_p, C.POINTER(kc_stats)]),

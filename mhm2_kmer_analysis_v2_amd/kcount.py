@@ -21,7 +21,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (check, kc_align_stats, kc_config, kc_ctg_index_stats, kc_kernel_time, kc_merge_stats, kc_result, kc_stats, kc_synth_params, kc_trim_stats, kc_tuning,
+from ._lib import (check, kc_align_stats, kc_aln_scores, kc_config, kc_ctg_index_stats, kc_gap_stats, kc_kernel_time, kc_merge_stats, kc_result, kc_stats, kc_synth_params, kc_trim_stats, kc_tuning,
                    kc_unitig_stats, lib)
 
 
@@ -638,6 +638,36 @@ class KmerCounter:
         alns = alns[:na.value * 32] if dev else alns[:na.value]
         return alns, first, {f: int(getattr(st, f)) for f, _ in kc_align_stats._fields_}
 
+    def align_gapped(self, bases, offsets, alns, pad=16, scores=None, always_dp=False):
+        """Gapped refinement of align_reads' records (kc_align_gapped): the same reads and the
+        records as align_reads returned them -- host arrays (alns a structured array of ALN_DTYPE) or device tensors (alns
+        a uint8 tensor of 32-byte records).  scores: (match, mismatch, gap open, gap extend, ambiguity), by default
+        BLASTN_ALN_SCORES.  Returns (gap_alns, stats): one record per input record, in the same order -- a structured
+        array of GAP_ALN_DTYPE for host arrays, a uint8 device tensor of 32-byte records for device tensors."""
+        pb, dev_b = _ptr(bases)
+        po, dev = _ptr(offsets)
+        pa, dev_a = _ptr(alns)
+        n = len(offsets) - 1
+        n_alns = alns.numel() // 32 if dev_a else len(alns)
+        if (n_alns and dev_a != dev) or (n and len(bases) and dev_b != dev):
+            raise ValueError("bases, offsets and alns must all be host arrays or all be device tensors")
+        if not dev and n_alns and (alns.dtype.itemsize != 32 or not alns.flags["C_CONTIGUOUS"]):
+            raise ValueError("alns: a contiguous array of 32-byte records (ALN_DTYPE)")
+        sc = kc_aln_scores(*(BLASTN_ALN_SCORES if scores is None else scores))
+        st = kc_gap_stats()
+        if dev:
+            import torch
+            out = torch.empty(max(n_alns, 1) * 32, dtype=torch.uint8, device="cuda:%d" % self.device)
+            torch.cuda.current_stream(self.device).synchronize()  # the input and the fresh array are torch's until now
+            pout = out.data_ptr()
+        else:
+            out = np.zeros(max(n_alns, 1), dtype=GAP_ALN_DTYPE)
+            pout = out.ctypes.data
+        check(lib().kc_align_gapped(self._h, pb, po, n, pa if n_alns else None, n_alns, 1 if dev else 0, pad, C.byref(sc),
+                                    _lib.KC_GAP_ALWAYS_DP if always_dp else 0, pout, C.byref(st)), "kc_align_gapped")
+        out = out[:n_alns * 32] if dev else out[:n_alns]
+        return out, {f: int(getattr(st, f)) for f, _ in kc_gap_stats._fields_}
+
     def submit_ctg_block(self, seqs, depths):
         """kc_submit_ctg_block with device tensors (a '_'-joined block and one 16-bit depth per byte), e.g. those of
         unitig_block(); begin_ctg_kmers first."""
@@ -673,6 +703,14 @@ class KmerCounter:
 # a record of kc_align_reads (kc_read_aln): 32 bytes
 ALN_DTYPE = np.dtype([("read", "<u4"), ("ctg", "<u4"), ("cstart", "<u4"), ("cstop", "<u4"), ("rstart", "<u2"), ("rstop", "<u2"),
                       ("mismatches", "<u2"), ("seeds", "<u2"), ("orient", "u1"), ("pad", "u1", (7,))])
+
+
+# a record of kc_align_gapped (kc_gap_aln): 32 bytes
+GAP_ALN_DTYPE = np.dtype([("read", "<u4"), ("ctg", "<u4"), ("cstart", "<u4"), ("cstop", "<u4"), ("rstart", "<u2"), ("rstop", "<u2"),
+                          ("score", "<u4"), ("mismatches", "<u2"), ("seeds", "<u2"), ("orient", "u1"), ("kind", "u1"), ("pad", "u1", (2,))])
+# match, mismatch, gap open, gap extend, ambiguity (CMakeDefinitions.txt:133-134)
+BLASTN_ALN_SCORES = (2, 3, 5, 2, 1)
+ALTERNATE_ALN_SCORES = (1, 1, 1, 1, 1)
 
 
 def kmer_to_string(words, k):

@@ -1,0 +1,432 @@
+"""kc_align_gapped (csrc/kc_gap.hpp) against the host model tests/gap_model.py, byte for byte: the records and the
+statistics on the same inputs.  The model is never replaced by a second device run.
+
+Every device call goes through device_gap: reads, input records and output records in device arrays of exactly their
+size, the two record arrays inside canaries.  The dynamic-programme kernel is instantiated for 1, 3, 8 and 16 rows a lane
+and the host picks the class by the longest read of a call, so the row-class cases run one call each."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import align_model as A
+import gap_model as G
+import mhm2_kmer_analysis_v2_amd as pkg
+from mhm2_kmer_analysis_v2_amd import _lib
+
+pytestmark = pytest.mark.gpu
+
+K = 21
+PAD = 64  # canary bytes in front of and behind a record array
+SETS = (G.SCORES_ALTERNATE, G.SCORES_BLASTN, G.SCORES_13521)
+
+
+def rand_seq(rng, n):
+    return "".join("ACGT"[i] for i in rng.integers(0, 4, size=n))
+
+
+def sub(s, x):
+    return s[:x] + "ACGT"[("ACGT".index(s[x].upper()) + 1) % 4] + s[x + 1:]
+
+
+RC = str.maketrans("ACGTacgt", "TGCAtgca")
+
+
+def revc(s):
+    """the read whose R' for orient 1 is s: reversed, bases complemented in their case, anything else as it is"""
+    return s.translate(RC)[::-1]
+
+
+def read_arrays(reads):
+    offs = np.zeros(len(reads) + 1, dtype=np.uint64)
+    offs[1:] = np.cumsum([len(r) for r in reads])
+    return np.frombuffer("".join(reads).encode(), dtype=np.uint8).copy(), offs
+
+
+def block_arrays(contigs):
+    block, offsets = A.join_block(contigs)
+    return np.frombuffer(block.encode(), dtype=np.uint8).copy(), np.array(offsets, dtype=np.uint64)
+
+
+def indexed(contigs, **kw):
+    kc = pkg.KmerCounter(K, **kw)
+    kc.index_contigs(*block_arrays(contigs))
+    return kc
+
+
+def diag(reads, contigs, r, u, orient, d, seeds=1):
+    """the record kc_align_reads emits for read r on diagonal d of contig u; its mismatches field is junk on purpose"""
+    L, n = len(reads[r]), len(contigs[u])
+    cstart, cstop = max(0, d), min(n, d + L)
+    assert cstart < cstop
+    return (r, u, cstart, cstop, cstart - d, cstop - d, 0xBEEF, seeds, orient, (0,) * 7)
+
+
+def records(rows):
+    return np.array(rows, dtype=A.ALN_DTYPE)
+
+
+def stats_dict(st):
+    return {n: int(getattr(st, n)) for n, _ in st._fields_}
+
+
+def raw_gap(kc, pb, po, n, pa, na, on_device, pad, scores, flags, pout):
+    st = _lib.kc_gap_stats(records=99)
+    sc = _lib.kc_aln_scores(*scores)
+    rc = pkg.lib().kc_align_gapped(kc._h, pb, po, n, pa, na, on_device, pad, C.byref(sc), flags, pout, C.byref(st))
+    return rc, stats_dict(st)
+
+
+def device_gap(kc, reads, alns, pad=16, scores=G.SCORES_BLASTN, flags=0, expect=0, shift=0):
+    """the call on device arrays of exactly the needed size inside canaries: (records, stats).  expect != 0: the status
+    is checked, and that nothing at all was written; shift: bytes by which both record arrays are misaligned."""
+    import torch
+    b, o = read_arrays(reads)
+    na = len(alns)
+    raw = np.frombuffer(alns.tobytes(), dtype=np.uint8)
+    h_in = np.full(na * 32 + 2 * PAD + 16, 0xCD, dtype=np.uint8)
+    h_in[PAD + shift:PAD + shift + na * 32] = raw
+    d_b = torch.from_numpy(b).cuda() if len(b) else None
+    d_o = torch.from_numpy(o.view(np.int64)).cuda()
+    d_in = torch.from_numpy(h_in).cuda()
+    d_out = torch.full((na * 32 + 2 * PAD + 16,), 0xAB, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    rc, st = raw_gap(kc, d_b.data_ptr() if d_b is not None else None, d_o.data_ptr(), len(reads), d_in.data_ptr() + PAD + shift, na, 1, pad,
+                     scores, flags, d_out.data_ptr() + PAD + shift)
+    h_out = d_out.cpu().numpy()
+    assert (d_in.cpu().numpy() == h_in).all(), "the input records were written"
+    if expect:
+        assert rc == expect
+        assert (h_out == 0xAB).all(), "a refused call wrote records"
+        assert st == dict(dict.fromkeys(G.GAP_STATS, 0), records=99), "a refused call wrote statistics"
+        return rc
+    assert rc == 0, pkg.lib().kc_last_error()
+    assert (h_out[:PAD] == 0xAB).all() and (h_out[PAD + na * 32:] == 0xAB).all(), "a canary was written"
+    return h_out[PAD:PAD + na * 32].copy().view(G.GAP_ALN_DTYPE), st
+
+
+def compare(kc, contigs, reads, alns, pad=16, scores=G.SCORES_BLASTN, always_dp=False):
+    want, want_st = G.align_gapped(contigs, reads, alns, pad, scores, always_dp)
+    got, got_st = device_gap(kc, reads, alns, pad, scores, _lib.KC_GAP_ALWAYS_DP if always_dp else 0)
+    assert got_st == want_st
+    if got.tobytes() != want.tobytes():
+        diff = [i for i in range(len(want)) if got[i].tobytes() != want[i].tobytes()]
+        assert not diff, (diff[:5], got[diff[:5]], want[diff[:5]])
+    return want, want_st
+
+
+def with_indel(rng, ctg, a, L):
+    """R' of exactly L bases (L >= 8) cut from ctg at a, a deletion or an insertion of 1 to 3 bases in its middle"""
+    ln = int(rng.integers(1, 4))
+    if rng.integers(0, 2):
+        return ctg[a:a + L // 2] + ctg[a + L // 2 + ln:a + L + ln]
+    return ctg[a:a + L // 2] + rand_seq(rng, ln) + ctg[a + L // 2:a + L - ln]
+
+
+# ---- rows a lane ------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("lengths", [(1, 63, 64), (65, 191, 192), (193, 511, 512), (513, 1023, 1024)])
+def test_row_classes(lengths):
+    rng = np.random.default_rng(lengths[0])
+    contigs = [rand_seq(rng, 1500), rand_seq(rng, 1300)]
+    reads, rows = [], []
+    for L in lengths:
+        for u, ctg in enumerate(contigs):
+            a = 100 + int(rng.integers(0, 100))
+            rp = with_indel(rng, ctg, a, L) if L >= 8 else sub(ctg[a:a + L], 0)
+            assert len(rp) == L
+            for orient in (0, 1):
+                reads.append(rp if orient == 0 else revc(rp))
+                rows.append(diag(reads, contigs, len(reads) - 1, u, orient, a, seeds=L))
+    alns = records(rows)
+    with indexed(contigs) as kc:
+        for scores in SETS:
+            want, st = compare(kc, contigs, reads, alns, 16, scores)
+            assert st["exact"] == 0 and st["dp"] >= 8
+            full = [w for w in want if int(w["rstop"]) - int(w["rstart"]) == len(reads[int(w["read"])])]
+            assert len(full) >= 6  # the indel is bridged: the whole read aligns
+        compare(kc, contigs, reads, alns, 16, G.SCORES_BLASTN, always_dp=True)
+
+
+# ---- columns, 64 at a time --------------------------------------------------------------------------------------------
+def test_column_batches():
+    rng = np.random.default_rng(21)
+    widths = (63, 64, 65, 127, 128, 129)
+    # a contig of exactly W columns under a pad that reaches both ends: the window is the contig
+    contigs = [rand_seq(rng, W) for W in widths]
+    reads, rows = [], []
+    for u, W in enumerate(widths):
+        rp = with_indel(rng, contigs[u], 2, W - 4)
+        for orient in (0, 1):
+            reads.append(rp if orient == 0 else revc(rp))
+            rows.append(diag(reads, contigs, len(reads) - 1, u, orient, 2))
+    # alignments of 62 .. 66 and 126 .. 130 reference columns: the second pass ends on a batch's last and first column
+    long_ctg = rand_seq(rng, 600)
+    contigs.append(long_ctg)
+    for span in (62, 63, 64, 65, 66, 126, 127, 128, 129, 130):
+        a = 200 + int(rng.integers(0, 50))
+        rp = sub(long_ctg[a:a + span], span // 2)
+        for orient in (0, 1):
+            reads.append(rp if orient == 0 else revc(rp))
+            rows.append(diag(reads, contigs, len(reads) - 1, len(contigs) - 1, orient, a))
+    alns = records(rows)
+    with indexed(contigs) as kc:
+        want, st = compare(kc, contigs, reads, alns, 1024)
+        assert st["dp"] == len(alns)
+        want, _ = compare(kc, contigs, reads, alns, 16)
+        spans = {int(w["cstop"]) - int(w["cstart"]) for w in want[12:]}
+        assert {63, 64, 65, 127, 128, 129} <= spans
+        compare(kc, contigs, reads, alns, 0, G.SCORES_ALTERNATE)
+
+
+# ---- pads and the contig's ends ---------------------------------------------------------------------------------------
+@pytest.mark.parametrize("pad", [0, 1, 16, 1024])
+def test_pads_and_contig_ends(pad):
+    rng = np.random.default_rng(30 + pad)
+    contigs = [rand_seq(rng, 700), rand_seq(rng, 80), rand_seq(rng, 1200)]
+    c0, c1, c2 = contigs
+    rps = [(rand_seq(rng, 30) + with_indel(rng, c0, 0, 120), 0, -30),            # over the contig's start
+           (with_indel(rng, c0, 580, 120) + rand_seq(rng, 30), 0, 580),          # over its end
+           (with_indel(rng, c0, 3, 150), 0, 3), (with_indel(rng, c0, 548, 150), 0, 548),  # windows clipped at either end
+           (rand_seq(rng, 35) + sub(c1, 40) + rand_seq(rng, 35), 1, -35),        # a contig shorter than the read
+           (c1[:40] + c1[42:], 1, 0),
+           (with_indel(rng, c2, 20, 1000), 2, 20), (with_indel(rng, c2, 150, 1024), 2, 150)]
+    reads, rows = [], []
+    for rp, u, d in rps:
+        for orient in (0, 1):
+            reads.append(rp if orient == 0 else revc(rp))
+            rows.append(diag(reads, contigs, len(reads) - 1, u, orient, d))
+    with indexed(contigs) as kc:
+        for scores in SETS:
+            compare(kc, contigs, reads, records(rows), pad, scores)
+
+
+# ---- content and scoring ----------------------------------------------------------------------------------------------
+def test_content_and_scoring():
+    rng = np.random.default_rng(40)
+    base = rand_seq(rng, 400)
+    with_n = base[:150] + "N" + base[151:260] + "NN" + base[262:]
+    contigs = [base, with_n, "A" * 300, "AC" * 150, "ACG" * 100, "T" * 40 + rand_seq(rng, 100) + "T" * 40]
+    rp0 = with_indel(rng, base, 100, 150)
+    cases = [(rp0[:30] + "N" + rp0[31:90] + "nn" + rp0[92:], 0, 100), (rp0.lower(), 0, 100), (rp0[:70] + "U-*" + rp0[73:], 0, 100),
+             (rp0, 1, 100), (with_indel(rng, with_n, 120, 180), 1, 120), ("N" * 150, 0, 10),
+             ("A" * 60 + "C" + "A" * 60, 2, 50), ("A" * 100, 2, 0), ("A" * 50 + "AA" + "A" * 50, 2, 198),
+             (("AC" * 40) + "A" + ("AC" * 40), 3, 20), (("AC" * 30) + ("AC" * 30)[1:], 3, 100), ("CA" * 60, 3, 7),
+             (("ACG" * 20) + "AC" + ("ACG" * 20), 4, 30), ("ACG" * 33 + "T", 4, 0),
+             ("T" * 30 + contigs[5][40:90] + "G" + contigs[5][90:140] + "T" * 30, 5, 10)]
+    reads, rows = [], []
+    for rp, u, d in cases:
+        for orient in (0, 1):
+            reads.append(rp if orient == 0 else revc(rp))
+            rows.append(diag(reads, contigs, len(reads) - 1, u, orient, d))
+    alns = records(rows)
+    with indexed(contigs) as kc:
+        for scores in SETS + ((1, 0, 1, 1, 0), (3, 9, 1, 1, 0), (9, 9, 9, 9, 9)):  # and the corners of the range
+            for pad in (0, 16) if scores in SETS else (16,):
+                want, st = compare(kc, contigs, reads, alns, pad, scores)
+        compare(kc, contigs, reads, alns, 16, G.SCORES_ALTERNATE, always_dp=True)  # the exact homopolymer reads: ties
+        assert st["none"] >= 2  # the all-N read, both ways
+
+
+# ---- record sets ------------------------------------------------------------------------------------------------------
+def test_record_sets():
+    rng = np.random.default_rng(50)
+    contigs = [rand_seq(rng, 500), "C" * 30, rand_seq(rng, 300)]
+    c0 = contigs[0]
+    reads = [c0[100:250],                                 # exact
+             revc(c0[300:450]),                      # exact, other strand
+             c0[100:175] + c0[177:252],                   # a deletion: two diagonals
+             "A" * 100,                                   # scores nothing against the C contig
+             sub(c0[20:120], 50),
+             rand_seq(rng, 40) + c0[:60]]                 # exact over its overlap
+    rows = [diag(reads, contigs, 0, 0, 0, 100, 130), diag(reads, contigs, 1, 0, 1, 300, 130), diag(reads, contigs, 2, 0, 0, 100, 55),
+            diag(reads, contigs, 2, 0, 0, 102, 55), diag(reads, contigs, 3, 1, 0, -99), diag(reads, contigs, 3, 1, 1, 29),
+            diag(reads, contigs, 4, 0, 0, 20, 60), diag(reads, contigs, 5, 0, 0, -40, 40),
+            diag(reads, contigs, 0, 2, 0, 17), diag(reads, contigs, 0, 2, 1, 200), diag(reads, contigs, 0, 0, 0, 101)]  # forged diagonals
+    alns = records(rows)
+    with indexed(contigs) as kc:
+        want, st = compare(kc, contigs, reads, alns)
+        assert [int(x) for x in want["kind"][:8]] == [0, 0, 1, 1, 2, 2, 1, 0] and st["exact"] == 3 and st["none"] == 2
+        assert want[4].tobytes()[8:24] == bytes(16)
+        want_dp, st_dp = compare(kc, contigs, reads, alns, always_dp=True)
+        assert st_dp["exact"] == 0 and [int(x) for x in want_dp["score"][[0, 1, 7]]] == [300, 300, 120]
+        # shuffled, and every record many times over: more records than the launch has waves
+        order = rng.permutation(len(alns))
+        compare(kc, contigs, reads, alns[order])
+        many = alns[rng.integers(0, len(alns), size=40000)]
+        want_many, st_many = compare(kc, contigs, reads, many)
+        assert st_many["records"] == 40000 and st_many["dp"] > 10000
+        # no records
+        rc, st0 = raw_gap(kc, None, None, 0, None, 0, 0, 16, G.SCORES_BLASTN, 0, C.addressof(C.create_string_buffer(32)))
+        assert rc == 0 and st0 == dict.fromkeys(G.GAP_STATS, 0)
+
+
+def test_a_thousand_reads_with_errors():
+    rng = np.random.default_rng(51)
+    contigs = [rand_seq(rng, 3000) for _ in range(4)]
+    reads, rows = [], []
+    for i in range(1000):
+        u = int(rng.integers(0, 4))
+        a = int(rng.integers(0, 2850))
+        rp = G._plant(rng, contigs[u][a:a + 150], int(rng.integers(0, 4)), int(rng.integers(0, 3)))[:150]
+        orient = i & 1
+        reads.append(rp if orient == 0 else revc(rp))
+        rows.append(diag(reads, contigs, i, u, orient, a, seeds=i % 130))
+    with indexed(contigs) as kc:
+        want, st = compare(kc, contigs, reads, records(rows))
+        assert st["dp"] > 700 and st["exact"] > 30
+
+
+# ---- the protocol -----------------------------------------------------------------------------------------------------
+def small_case(rng):
+    contigs = [rand_seq(rng, 300), "", rand_seq(rng, 250)]
+    c0, c2 = contigs[0], contigs[2]
+    reads = [c0[10:160], revc(c2[50:120] + c2[121:200]), sub(c0[200:], 30) + rand_seq(rng, 30), ""]
+    rows = [diag(reads, contigs, 0, 0, 0, 10, 130), diag(reads, contigs, 1, 2, 1, 50, 50), diag(reads, contigs, 1, 2, 1, 51, 59),
+            diag(reads, contigs, 2, 0, 0, 200, 40)]
+    return contigs, reads, records(rows)
+
+
+def test_host_and_device_inputs_and_alignment():
+    import torch
+    rng = np.random.default_rng(60)
+    contigs, reads, alns = small_case(rng)
+    with indexed(contigs) as kc:
+        want, st = compare(kc, contigs, reads, alns)
+        b, o = read_arrays(reads)
+        out = np.full(len(alns) + 2, 0xAB, dtype=np.uint8).repeat(32).view(G.GAP_ALN_DTYPE)
+        rc, h_st = raw_gap(kc, b.ctypes.data, o.ctypes.data, len(reads), alns.ctypes.data, len(alns), 0, 16, G.SCORES_BLASTN, 0,
+                           out.ctypes.data + 32)
+        assert rc == 0 and h_st == st and out[1:-1].tobytes() == want.tobytes()
+        assert (out[[0, -1]].view(np.uint8) == 0xAB).all()
+        # the names under which the call's launches are timed
+        with indexed(contigs, time_kernels=True) as kt:
+            kt.kernel_times(clear=True)
+            assert compare(kt, contigs, reads, alns)[1] == st
+            times = {n: v[0] for n, v in kt.kernel_times().items() if n.startswith("kc_gap") or n.endswith("<gap>")}
+            assert times == {"kc_align_lengths_kernel<gap>": 1, "kc_gap_check_kernel": 1, "kc_gap_sort_kernel": 1, "kc_gap_dp_kernel": 1}
+        # the wrapper, both modes
+        g, g_st = kc.align_gapped(b, o, alns)
+        assert g.dtype == G.GAP_ALN_DTYPE and g.tobytes() == want.tobytes() and g_st == st
+        d_alns = torch.from_numpy(np.frombuffer(alns.tobytes(), dtype=np.uint8).copy()).cuda()
+        g, g_st = kc.align_gapped(torch.from_numpy(b).cuda(), torch.from_numpy(o.view(np.int64)).cuda(), d_alns, pad=3, scores=G.SCORES_ALTERNATE,
+                                  always_dp=True)
+        w3, st3 = G.align_gapped(contigs, reads, alns, 3, G.SCORES_ALTERNATE, True)
+        assert g.is_cuda and g.cpu().numpy().tobytes() == w3.tobytes() and g_st == st3
+        # device record arrays are 16-byte aligned
+        assert device_gap(kc, reads, alns, shift=8, expect=_lib.KC_ERR_INVALID_ARG) == _lib.KC_ERR_INVALID_ARG
+        assert b"16-byte aligned" in pkg.lib().kc_last_error()
+        # ranges, with a context this time
+        for bad in ((0, 3, 5, 2, 1), (10, 3, 5, 2, 1), (2, 10, 5, 2, 1), (2, 3, 5, 6, 1), (2, 3, 5, 0, 1), (2, 3, 10, 2, 1), (2, 3, 5, 2, 10)):
+            device_gap(kc, reads, alns, scores=bad, expect=_lib.KC_ERR_INVALID_ARG)
+        device_gap(kc, reads, alns, pad=1025, expect=_lib.KC_ERR_INVALID_ARG)
+        device_gap(kc, reads, alns, flags=2, expect=_lib.KC_ERR_INVALID_ARG)
+        compare(kc, contigs, reads, alns)
+
+
+def test_invalid_records_are_named_and_nothing_is_written():
+    rng = np.random.default_rng(61)
+    contigs, reads, alns = small_case(rng)
+    good = alns[3]  # read 2 of 130 bases on contig 0 (300 bases): d = 200, cstart 200, cstop 300, rstart 0, rstop 100
+
+    def forged(**kw):
+        r = good.copy()
+        for k, v in kw.items():
+            r[k] = v
+        return r
+
+    bad = [forged(read=4), forged(read=0xFFFFFFFF), forged(ctg=3), forged(ctg=0xFFFFFFFF), forged(orient=2), forged(orient=255),
+           forged(cstop=301), forged(cstart=300, cstop=300, rstart=100, rstop=100), forged(cstop=200, rstop=0), forged(rstop=131, cstop=231),
+           forged(rstop=99), forged(cstart=201), forged(cstart=201, rstart=1), forged(cstop=299, rstop=99), forged(rstart=1, rstop=101),
+           forged(read=3), forged(ctg=1)]  # an empty read, an empty contig
+    with indexed(contigs) as kc:
+        L = pkg.lib()
+        for b in bad:
+            with pytest.raises(G.BadRecord):
+                G.align_gapped(contigs, reads, records([b]))
+            assert device_gap(kc, reads, records([b]), expect=_lib.KC_ERR_INVALID_ARG)
+            assert b"record 0 " in L.kc_last_error()
+            many = np.concatenate([alns, alns, records([b]), alns, records([b]), alns])
+            with pytest.raises(G.BadRecord) as e:
+                G.align_gapped(contigs, reads, many)
+            assert e.value.index == 8
+            device_gap(kc, reads, many, expect=_lib.KC_ERR_INVALID_ARG)
+            assert b"record 8 " in L.kc_last_error()
+        compare(kc, contigs, reads, alns)
+        # a read over the limit, named
+        long_reads = reads[:3] + ["C" * 1025]
+        device_gap(kc, long_reads, alns, expect=_lib.KC_ERR_INVALID_ARG)
+        assert b"read 3" in L.kc_last_error()
+        compare(kc, contigs, reads[:3] + ["C" * 1024], alns)
+
+
+def test_state_rebuilt_index_and_ranks():
+    rng = np.random.default_rng(62)
+    contigs, reads, alns = small_case(rng)
+    with pkg.KmerCounter(K) as kc:
+        assert device_gap(kc, reads, alns, expect=_lib.KC_ERR_STATE) == _lib.KC_ERR_STATE  # no index
+        kc.index_contigs(*block_arrays(contigs))
+        want, _ = compare(kc, contigs, reads, alns)
+        kc.clear_contig_index()
+        device_gap(kc, reads, alns, expect=_lib.KC_ERR_STATE)
+        kc.index_contigs(*block_arrays(contigs))
+        kc.reset()
+        device_gap(kc, reads, alns, expect=_lib.KC_ERR_STATE)
+        # a rebuilt index: other contigs, other answers (contig 0 is the old contig 2 now)
+        contigs2 = [contigs[2], rand_seq(rng, 200), contigs[0]]
+        kc.index_contigs(*block_arrays(contigs2))
+        alns2 = alns.copy()
+        alns2["ctg"] = [2, 0, 0, 2]
+        want2, _ = compare(kc, contigs2, reads, alns2)
+        assert (want2["score"] == want["score"]).all()
+        device_gap(kc, reads, alns, expect=_lib.KC_ERR_INVALID_ARG)  # the old records do not fit the new contigs
+    with indexed(contigs, rank_me=1, rank_n=2) as kc:
+        compare(kc, contigs, reads, alns)
+
+
+def test_the_whole_chain_and_nothing_else_changes():
+    """Count reads over a few chains, index the unitigs on the device, align reads with planted indels, refine them:
+    both steps against their models on unitig_strings(); results, lookups and kc_align_reads' answers are the same
+    before and after."""
+    READ = 150
+    rng = np.random.default_rng(63)
+    chains = [rand_seq(rng, m) for m in (700, 400, 1000)]
+    cover = []
+    for seq in chains:
+        for a in range(0, len(seq) - K, 100):
+            cover += [seq[a:a + 200]] * 2
+    b, o = read_arrays(cover)
+    queries = []
+    for i in range(60):
+        seq = chains[i % 3]
+        a = int(rng.integers(1, len(seq) - READ - 4))
+        rp = [seq[a:a + READ], with_indel(rng, seq, a, READ), sub(seq[a:a + READ], 70), G._plant(rng, seq[a:a + READ], 2, 2)[:READ]][i % 4]
+        queries.append(rp if i % 2 else revc(rp))
+    qb, qo = read_arrays(queries)
+    with pkg.KmerCounter(K) as kc:
+        kc.submit_reads(b, np.full(len(b), ord("I"), dtype=np.uint8), o)
+        kc.finalize()
+        strings = kc.unitig_strings()
+        contigs = [s for s, _ in strings]
+        keys, counts, left, right = [np.array(x) for x in kc.sorted_results()]
+        looked = [np.array(x) for x in kc.lookup(keys)]
+        ix = A.Index(*A.join_block(contigs), K)
+        assert kc.index_unitigs() == ix.stats
+        alns, first, a_st = kc.align_reads(qb, qo)
+        m_alns, m_first, m_st = A.align_reads(ix, queries)
+        assert alns.tobytes() == m_alns.tobytes() and a_st == m_st
+        want, st = compare(kc, contigs, queries, alns)
+        g, g_st = kc.align_gapped(qb, qo, alns)
+        assert g.tobytes() == want.tobytes() and g_st == st
+        assert st["exact"] >= 15 and st["dp"] >= 40
+        per_read = np.diff(m_first.astype(np.int64))
+        for r in range(1, 60, 4):  # a read with one indel: two diagonals, both refined to the whole read
+            recs = want[int(m_first[r]):int(m_first[r + 1])]
+            assert per_read[r] == 2 and all(int(x["rstart"]) == 0 and int(x["rstop"]) == READ for x in recs)
+            assert recs[0].tobytes()[8:24] == recs[1].tobytes()[8:24]
+        again, _, again_st = kc.align_reads(qb, qo)
+        assert again.tobytes() == alns.tobytes() and again_st == a_st
+        for x, y in zip((keys, counts, left, right), [np.array(x) for x in kc.sorted_results()]):
+            assert (x == y).all()
+        for x, y in zip(looked, [np.array(x) for x in kc.lookup(keys)]):
+            assert (x == y).all()
+        assert kc.unitig_strings() == strings
