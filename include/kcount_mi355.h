@@ -680,6 +680,98 @@ typedef struct kc_gap_stats {
 } kc_gap_stats;
 int kc_align_gapped(kc_ctx *ctx, const uint8_t *bases, const uint64_t *offsets, uint64_t nreads, const kc_read_aln *alns, uint64_t n_alns,
                     int on_device, uint32_t pad, const kc_aln_scores *scores, uint32_t flags, kc_gap_aln *out, kc_gap_stats *stats);
+/*
+ * What the kept contig index holds: *nbytes the block's bytes (separators included), *n_ctgs its contigs -- the sizes of
+ * kc_aln_depths' arrays.  Either pointer may be NULL.  KC_ERR_STATE without an index.
+ */
+int kc_ctg_index_info(kc_ctx *ctx, uint64_t *nbytes, uint64_t *n_ctgs);
+/*
+ * Contig depths and insert sizes from kc_align_gapped's records, where the records are: the role of the depths the
+ * contig pass is fed and of histogrammer.calculate_insert_size(alns) behind find_alignments (src/contigging.cpp:164).
+ * The reference holds no code for either (no Alns, no CtgsDepths, no histogrammer in src/), so the rules below are THIS
+ * project's own definition (pinned by the host model tests/depth_model.py); no parity with
+ * MetaHipMer is claimed.  All quantities are integers; every output is one exact byte string for a given input.
+ *
+ * Shared by both calls.  alns: n_alns records as kc_align_gapped writes them, in any order.  With len_u the length of
+ * contig u of the kept index, a record is VALID iff ctg < n_ctgs, orient <= 1, kind <= 2 and -- unless kind is
+ * KC_GAP_NONE, which needs nothing more -- cstart < cstop <= len_u and rstart < rstop <= KC_ALIGN_MAX_READ_LEN; where a
+ * call uses reads, also read < nreads, and where it has their lengths, rstop <= L(read) unless kind is KC_GAP_NONE.  An
+ * invalid record is KC_ERR_INVALID_ARG and kc_last_error names the lowest bad index; validation is a pass of its own in
+ * front of the first store.  A record PASSES THE FILTER iff kind != KC_GAP_NONE, score >= min_score and
+ * cstop - cstart >= min_len.  A read's BEST record: among its records that pass, the greatest score, and among equal
+ * scores the lowest record index.
+ * on_device applies to all arrays alike; device record arrays (alns, ctgs, pairs) are 16-byte aligned.  No index:
+ * KC_ERR_STATE.  2^32 records or more: KC_ERR_CAPACITY.  On every error nothing is written through any pointer.  *stats
+ * (may be NULL) is written once, on success.  Both calls work before or after kc_finalize and with rank_n > 1, touch
+ * neither the index, the table nor the results, run on the context's stream and return when done; scratch lives for
+ * the call only.
+ *
+ * kc_aln_depths.  A record that passes contributes, with e = edge_clip <= KC_DEPTH_MAX_EDGE,
+ * lo = cstart + (cstart > 0 ? e : 0) and hi = cstop - (cstop < len_u ? e : 0): 1 to every contig position in [lo, hi)
+ * iff lo < hi (an alignment's ends are its least trusted bases, unless the end is the contig's own).  With
+ * KC_DEPTH_BEST_ONLY only every read's best record contributes; then read < nreads is part of validity; without the
+ * flag neither nreads nor the read field is read.  depth[j], for every byte j of the block, is the number of
+ * contributions covering it (exact in 32 bits; 0 on a separator).
+ * depths (may be NULL): uint16_t[nbytes], min(depth[j], 65535) -- the layout of kc_submit_ctg_block's depths; with
+ * KC_DEPTH_PER_CONTIG every byte of contig u holds u's mean instead, separators 0.
+ * ctgs (may be NULL): kc_ctg_depth[n_ctgs]; covered = bases with depth > 0, min_depth / max_depth over the contig's
+ * bases, unsaturated (0 for an empty contig), alns = records that contributed,
+ * mean = min(65535, floor((depth_sum + len / 2) / len)), 0 for an empty contig.
+ * stats: records = none + filtered + not_best + clipped_away + used.
+ * n_alns == 0: KC_OK, all-zero outputs (the arrays are written).  Unknown flags or edge_clip over the limit:
+ * KC_ERR_INVALID_ARG, checked in front of ctx (kc_last_error names the values).
+ */
+#define KC_DEPTH_MAX_EDGE 1024
+#define KC_DEPTH_BEST_ONLY 1u
+#define KC_DEPTH_PER_CONTIG 2u
+typedef struct kc_ctg_depth {
+  uint64_t depth_sum;
+  uint32_t len, covered, min_depth, max_depth, alns, mean;
+} kc_ctg_depth;
+typedef struct kc_depth_stats {
+  uint64_t records;
+  uint64_t none;          /* kind KC_GAP_NONE */
+  uint64_t filtered;      /* below min_score or min_len */
+  uint64_t not_best;      /* only with KC_DEPTH_BEST_ONLY */
+  uint64_t clipped_away;  /* passed, but lo >= hi */
+  uint64_t used;
+  uint64_t bases_covered; /* depth > 0 */
+  uint64_t depth_sum;
+  uint64_t saturated;     /* bytes whose depth exceeds 65535 */
+} kc_depth_stats;
+int kc_aln_depths(kc_ctx *ctx, const kc_gap_aln *alns, uint64_t n_alns, uint64_t nreads, int on_device, uint32_t min_score, uint32_t min_len,
+                  uint32_t edge_clip, uint32_t flags, uint16_t *depths, kc_ctg_depth *ctgs, kc_depth_stats *stats);
+/*
+ * kc_pair_inserts.  Reads 2p and 2p + 1 are mates (KC_TRIM_PAIRED's convention); an odd nreads is KC_ERR_INVALID_ARG, as
+ * is max_insert outside 1 .. KC_INSERT_MAX (both checked in front of ctx).  offsets: the reads' nreads + 1 offsets (no
+ * bases are needed); a read over KC_ALIGN_MAX_READ_LEN is refused as in kc_align_gapped.  Validity includes
+ * read < nreads and rstop <= L(read).  With b0, b1 the mates' best records the class of pair p is the first that applies:
+ * KC_PAIR_NONE: neither mate has one; KC_PAIR_ONE: exactly one has; KC_PAIR_DIFF_CTG: b0.ctg != b1.ctg;
+ * KC_PAIR_SAME_ORIENT: b0.orient == b1.orient; otherwise, with F the orient-0 record, R the orient-1 record and L_R the
+ * length of R's read, in signed 64-bit: fs = F.cstart - F.rstart, rs = R.cstart - R.rstart,
+ * re = R.cstop + (L_R - R.rstop); KC_PAIR_EVERTED iff rs < fs; else insert = re - fs (at least 1) and KC_PAIR_PROPER iff
+ * insert <= max_insert, else KC_PAIR_TOO_LONG.
+ * hist (may be NULL): uint64_t[max_insert + 1], hist[i] = the proper pairs with insert i.  pairs (may be NULL):
+ * kc_pair_rec[nreads / 2]; aln0 / aln1 the indices of the best records (0xFFFFFFFF: none), insert for PROPER and
+ * TOO_LONG, else 0.  stats: insert_sum and insert_sq_sum over the proper pairs; mean and deviation are the caller's.
+ */
+#define KC_INSERT_MAX 65535
+enum { KC_PAIR_NONE = 0, KC_PAIR_ONE = 1, KC_PAIR_DIFF_CTG = 2, KC_PAIR_SAME_ORIENT = 3, KC_PAIR_EVERTED = 4, KC_PAIR_TOO_LONG = 5,
+       KC_PAIR_PROPER = 6 };
+typedef struct kc_pair_rec {
+  uint32_t aln0, aln1;
+  uint32_t insert;
+  uint8_t cls;
+  uint8_t pad[3]; /* zero */
+} kc_pair_rec;
+typedef struct kc_insert_stats {
+  uint64_t pairs;
+  uint64_t cls[7]; /* by KC_PAIR_* */
+  uint64_t insert_sum, insert_sq_sum;
+  uint64_t reads_with_best;
+} kc_insert_stats;
+int kc_pair_inserts(kc_ctx *ctx, const uint64_t *offsets, uint64_t nreads, const kc_gap_aln *alns, uint64_t n_alns, int on_device,
+                    uint32_t min_score, uint32_t min_len, uint32_t max_insert, uint64_t *hist, kc_pair_rec *pairs, kc_insert_stats *stats);
 /* KmerDHT::kmer_exists / get_kmer_count / get_local_kmer_counts (src/kcount/kmer_dht.cpp:198-245) in bulk, against the
  * results kept in HBM: nq k-mers of num_longs words each, in either orientation; counts[i] = 0 (and left/right = 0)
  * when the k-mer did not survive.  The index over the results is built on the first call after kc_finalize.

@@ -110,6 +110,30 @@ KC_GAP_MAX_PAD = 1024
 KC_GAP_ALWAYS_DP = 1
 KC_GAP_EXACT, KC_GAP_DP, KC_GAP_NONE = 0, 1, 2
 
+
+class kc_ctg_depth(C.Structure):
+    _fields_ = [("depth_sum", C.c_uint64)] + [(n, C.c_uint32) for n in ("len", "covered", "min_depth", "max_depth", "alns", "mean")]
+
+
+class kc_depth_stats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("records", "none", "filtered", "not_best", "clipped_away", "used", "bases_covered", "depth_sum",
+                                          "saturated")]
+
+
+class kc_pair_rec(C.Structure):
+    _fields_ = [("aln0", C.c_uint32), ("aln1", C.c_uint32), ("insert", C.c_uint32), ("cls", C.c_uint8), ("pad", C.c_uint8 * 3)]
+
+
+class kc_insert_stats(C.Structure):
+    _fields_ = [("pairs", C.c_uint64), ("cls", C.c_uint64 * 7), ("insert_sum", C.c_uint64), ("insert_sq_sum", C.c_uint64),
+                ("reads_with_best", C.c_uint64)]
+
+
+KC_DEPTH_MAX_EDGE = 1024
+KC_DEPTH_BEST_ONLY, KC_DEPTH_PER_CONTIG = 1, 2
+KC_INSERT_MAX = 65535
+KC_PAIR_NONE, KC_PAIR_ONE, KC_PAIR_DIFF_CTG, KC_PAIR_SAME_ORIENT, KC_PAIR_EVERTED, KC_PAIR_TOO_LONG, KC_PAIR_PROPER = range(7)
+
 # every symbol include/kcount_mi355.h declares: (restype, argtypes)
 SYMBOLS = {
     "kc_abi_version": (C.c_int, []),
@@ -179,6 +203,11 @@ SYMBOLS = {
                                   C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(kc_align_stats)]),
     "kc_align_gapped": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.c_uint32,
                                    C.POINTER(kc_aln_scores), C.c_uint32, C.c_void_p, C.POINTER(kc_gap_stats)]),
+    "kc_ctg_index_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "kc_aln_depths": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                 C.c_void_p, C.c_void_p, C.POINTER(kc_depth_stats)]),
+    "kc_pair_inserts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32,
+                                   C.c_void_p, C.c_void_p, C.POINTER(kc_insert_stats)]),
     "kc_lookup": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "kc_dump_table": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
     "kc_get_stats": (C.c_int, [C.c_void_p, C.POINTER(kc_stats)]),

@@ -33,6 +33,7 @@
 #include "kc_unitig.hpp"
 #include "kc_align.hpp"
 #include "kc_gap.hpp"
+#include "kc_depth.hpp"
 
 using namespace kc;
 
@@ -96,12 +97,15 @@ enum { KT_EXTRACT_INSERT = 0, KT_EXTRACT_BIN, KT_INSERT_RECORDS, KT_FINALIZE, KT
        KT_TRIM_SIZES, KT_TRIM_SCAN, KT_TRIM_WRITE, KT_SORT_HIST, KT_SORT_HIST_LOAD, KT_SORT_SCAN, KT_SORT_SCATTER, KT_SORT_GATHER,
        KT_DUMP_SIZES, KT_DUMP_SCAN, KT_DUMP_WRITE, KT_UNITIG_LINKS, KT_UNITIG_MIN_JUMP, KT_UNITIG_CUT, KT_UNITIG_RANK_JUMP,
        KT_UNITIG_SELECT, KT_UNITIG_SCAN, KT_UNITIG_WRITE, KT_UNITIG_DEPTH, KT_ALIGN_CHECK, KT_ALIGN_INDEX, KT_ALIGN_SWEEP, KT_ALIGN_LENGTHS,
-       KT_ALIGN_COUNT, KT_ALIGN_SCAN, KT_ALIGN_WRITE, KT_GAP_LENGTHS, KT_GAP_CHECK, KT_GAP_SORT, KT_GAP_DP, KT_COUNT };
+       KT_ALIGN_COUNT, KT_ALIGN_SCAN, KT_ALIGN_WRITE, KT_GAP_LENGTHS, KT_GAP_CHECK, KT_GAP_SORT, KT_GAP_DP, KT_DEPTH_CHECK,
+       KT_DEPTH_BEST, KT_DEPTH_MARK, KT_DEPTH_TILE_SUMS, KT_DEPTH_SCAN, KT_DEPTH_RESCAN, KT_DEPTH_CTG, KT_DEPTH_FILL, KT_PAIR_LENGTHS, KT_PAIR_CHECK,
+       KT_PAIR_BEST, KT_PAIR_CLASSIFY, KT_PAIR_CLASSIFY_LDS, KT_COUNT };
 // KT_FQ_SCAN, KT_MERGE_SCAN and KT_TRIM_SCAN label the front end's three uses of the one shared kc_scan_kernel (kc_scan.hpp); their
 // strings keep the names the uses were first reported under.  KT_SORT_SCAN and KT_DUMP_SCAN are the back end's two,
 // KT_UNITIG_SCAN the unitigs' (kc_scan_kernel<2>: bytes and unitig numbers in one pass), KT_ALIGN_SCAN the alignments' (the
 // reads' record counts).  KT_ALIGN_COUNT and KT_ALIGN_WRITE are the two passes of kc_align_reads_kernel.  KT_GAP_LENGTHS is
-// kc_align_gapped's use of kc_align_lengths_kernel.
+// kc_align_gapped's use of kc_align_lengths_kernel, KT_PAIR_LENGTHS kc_pair_inserts'.  KT_DEPTH_SCAN is kc_aln_depths' use of kc_scan_kernel<1>
+// (the tile sums); KT_PAIR_CHECK and KT_PAIR_BEST are kc_pair_inserts' launches of the two kernels it shares with kc_aln_depths.
 static const char *const kt_names[KT_COUNT] = {"kc_extract_kernel<insert>", "kc_bin_reads_kernel", "kc_insert_records_kernel",
                                                "kc_finalize_kernel", "kc_tile_first_kernel", "kc_rehash_kernel",
                                                "kc_l1_reads_kernel", "kc_l1_records_kernel", "kc_l2_split_kernel",
@@ -121,7 +125,11 @@ static const char *const kt_names[KT_COUNT] = {"kc_extract_kernel<insert>", "kc_
                                                "kc_unitig_depth_kernel", "kc_align_check_kernel", "kc_align_index_kernel", "kc_align_sweep_kernel",
                                                "kc_align_lengths_kernel", "kc_align_reads_kernel<count>", "kc_align_scan_kernel",
                                                "kc_align_reads_kernel<write>", "kc_align_lengths_kernel<gap>", "kc_gap_check_kernel",
-                                               "kc_gap_sort_kernel", "kc_gap_dp_kernel"};
+                                               "kc_gap_sort_kernel", "kc_gap_dp_kernel", "kc_depth_check_kernel", "kc_depth_best_kernel",
+                                               "kc_depth_mark_kernel", "kc_depth_tile_sums_kernel", "kc_depth_scan_kernel",
+                                               "kc_depth_rescan_kernel", "kc_depth_ctg_kernel", "kc_depth_fill_kernel",
+                                               "kc_align_lengths_kernel<pair>", "kc_depth_check_kernel<pair>", "kc_depth_best_kernel<pair>",
+                                               "kc_pair_classify_kernel", "kc_pair_classify_kernel<lds>"};
 struct kt_pending {
   hipEvent_t start, stop;
   int kind;
@@ -178,6 +186,7 @@ struct kc_ctx {
   // belongs to a pass, like the contig table (kc_reset drops it)
   uint8_t *d_ai;
   AlignIndex ai;
+  uint64_t ai_nbytes;  // the block's bytes (kc_ctg_index_info)
   bool ai_ready;
   double arena_probe_tbps;  // rate of level 1's write pattern on the arena pick_fast_arena chose (0: no probe ran)
   kc_synth_table *d_synth;
@@ -3206,6 +3215,7 @@ extern "C" int kc_lookup(kc_ctx *c, const uint64_t *queries, uint64_t nq, int on
 #include "kc_api_unitig.hpp"  // kc_build_unitigs
 #include "kc_api_align.hpp"  // kc_ctg_index_build, kc_ctg_index_clear, kc_align_reads
 #include "kc_api_gap.hpp"    // kc_align_gapped
+#include "kc_api_depth.hpp"  // kc_ctg_index_info, kc_aln_depths, kc_pair_inserts
 
 // ---- the contig pass (kc_ctg.hpp) ----------------------------------------------------------------------------------
 extern "C" int kc_begin_ctg_kmers(kc_ctx *c, uint64_t max_ctg_kmers) {

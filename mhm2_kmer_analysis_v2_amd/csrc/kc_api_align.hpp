@@ -118,6 +118,7 @@ extern "C" int kc_ctg_index_build(kc_ctx *c, const uint8_t *seqs, uint64_t nbyte
   free_align_index(c);
   c->d_ai = b.a;
   c->ai = ix;
+  c->ai_nbytes = nbytes;
   c->ai_ready = true;
   b.a = nullptr;
   b.release();

@@ -21,7 +21,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (check, kc_align_stats, kc_aln_scores, kc_config, kc_ctg_index_stats, kc_gap_stats, kc_kernel_time, kc_merge_stats, kc_result, kc_stats, kc_synth_params, kc_trim_stats, kc_tuning,
+from ._lib import (check, kc_align_stats, kc_aln_scores, kc_config, kc_ctg_index_stats, kc_depth_stats, kc_gap_stats, kc_insert_stats, kc_kernel_time, kc_merge_stats, kc_result, kc_stats, kc_synth_params, kc_trim_stats, kc_tuning,
                    kc_unitig_stats, lib)
 
 
@@ -497,10 +497,10 @@ class KmerCounter:
 
     def kernel_times(self, clear=False):
         """{kernel name: (launches, total_ms)} from HIP events on the launch stream (needs time_kernels=True)."""
-        arr = (kc_kernel_time * 64)()  # more than the library has kinds of kernels
+        arr = (kc_kernel_time * 128)()  # more than the library has kinds of kernels
         n = C.c_int(0)
-        check(lib().kc_get_kernel_times(self._h, arr, 64, C.byref(n)), "kc_get_kernel_times")
-        out = {arr[i].name.decode(): (int(arr[i].launches), float(arr[i].total_ms)) for i in range(min(n.value, 64))}
+        check(lib().kc_get_kernel_times(self._h, arr, 128, C.byref(n)), "kc_get_kernel_times")
+        out = {arr[i].name.decode(): (int(arr[i].launches), float(arr[i].total_ms)) for i in range(min(n.value, 128))}
         if clear:
             check(lib().kc_clear_kernel_times(self._h), "kc_clear_kernel_times")
         return out
@@ -668,6 +668,83 @@ class KmerCounter:
         out = out[:n_alns * 32] if dev else out[:n_alns]
         return out, {f: int(getattr(st, f)) for f, _ in kc_gap_stats._fields_}
 
+    def contig_index_info(self):
+        """(nbytes, n_ctgs) of the kept contig index (kc_ctg_index_info): the sizes of aln_depths' arrays."""
+        nb, nc = C.c_uint64(0), C.c_uint64(0)
+        check(lib().kc_ctg_index_info(self._h, C.byref(nb), C.byref(nc)), "kc_ctg_index_info")
+        return int(nb.value), int(nc.value)
+
+    def _gap_records(self, gap_alns):
+        pa, dev = _ptr(gap_alns)
+        n = gap_alns.numel() // 32 if dev else len(gap_alns)
+        if not dev and n and (gap_alns.dtype.itemsize != 32 or not gap_alns.flags["C_CONTIGUOUS"]):
+            raise ValueError("gap_alns: a contiguous array of 32-byte records (GAP_ALN_DTYPE)")
+        return (pa if n else None), n, dev
+
+    def aln_depths(self, gap_alns, min_score=0, min_len=0, edge_clip=0, best_only=False, per_contig=False, nreads=None):
+        """Per-base and per-contig depths from align_gapped's records (kc_aln_depths).  Returns
+        (depths, ctgs, stats): depths one 16-bit value per byte of the indexed block -- what submit_ctg_block takes;
+        with per_contig every byte holds its contig's mean -- and ctgs one CTG_DEPTH_DTYPE record per contig.  Host
+        records give numpy arrays; a uint8 device tensor of records gives device tensors (depths int16 holding the
+        16 bits, ctgs uint8 of 32-byte records).  best_only: only every read's best record counts (nreads: the reads
+        the records index)."""
+        pa, n, dev = self._gap_records(gap_alns)
+        if best_only and nreads is None:
+            raise ValueError("best_only needs nreads")
+        nbytes, n_ctgs = self.contig_index_info()
+        flags = (_lib.KC_DEPTH_BEST_ONLY if best_only else 0) | (_lib.KC_DEPTH_PER_CONTIG if per_contig else 0)
+        st = kc_depth_stats()
+        if dev:
+            import torch
+            d = "cuda:%d" % self.device
+            depths = torch.empty(max(nbytes, 1), dtype=torch.int16, device=d)
+            ctgs = torch.empty(max(n_ctgs, 1) * 32, dtype=torch.uint8, device=d)
+            torch.cuda.current_stream(self.device).synchronize()  # the input and the fresh arrays are torch's until now
+            pd, pc = depths.data_ptr(), ctgs.data_ptr()
+        else:
+            depths = np.zeros(max(nbytes, 1), dtype=np.uint16)
+            ctgs = np.zeros(max(n_ctgs, 1), dtype=CTG_DEPTH_DTYPE)
+            pd, pc = depths.ctypes.data, ctgs.ctypes.data
+        check(lib().kc_aln_depths(self._h, pa, n, nreads or 0, 1 if dev else 0, min_score, min_len, edge_clip, flags, pd, pc, C.byref(st)),
+              "kc_aln_depths")
+        ctgs = ctgs[:n_ctgs * 32] if dev else ctgs[:n_ctgs]
+        return depths[:nbytes], ctgs, {f: int(getattr(st, f)) for f, _ in kc_depth_stats._fields_}
+
+    def pair_inserts(self, offsets, gap_alns, max_insert=_lib.KC_INSERT_MAX, min_score=0, min_len=0):
+        """Every read's best record, every pair's class and the insert-size histogram (kc_pair_inserts; DESIGN.md
+        section 17); reads 2p and 2p + 1 are mates.  Returns (hist, pairs, stats): hist max_insert + 1 counts, pairs one
+        PAIR_DTYPE record per pair (host) or a uint8 device tensor of 16-byte records, hist an int64 device tensor then.
+        stats: kc_insert_stats as a dict, cls a list by KC_PAIR_*, with mean and stddev of the proper pairs' inserts
+        (0.0 without any) beside the integers."""
+        pa, n, dev_a = self._gap_records(gap_alns)
+        po, dev = _ptr(offsets)
+        nreads = len(offsets) - 1
+        if n and dev_a != dev:
+            raise ValueError("offsets and gap_alns must both be host arrays or both be device tensors")
+        st = kc_insert_stats()
+        npairs = nreads // 2
+        if dev:
+            import torch
+            d = "cuda:%d" % self.device
+            hist = torch.empty(max_insert + 1, dtype=torch.int64, device=d)
+            pairs = torch.empty(max(npairs, 1) * 16, dtype=torch.uint8, device=d)
+            torch.cuda.current_stream(self.device).synchronize()  # the input and the fresh arrays are torch's until now
+            ph, pp = hist.data_ptr(), pairs.data_ptr()
+        else:
+            hist = np.zeros(max_insert + 1, dtype=np.uint64)
+            pairs = np.zeros(max(npairs, 1), dtype=PAIR_DTYPE)
+            ph, pp = hist.ctypes.data, pairs.ctypes.data
+        check(lib().kc_pair_inserts(self._h, po, nreads, pa, n, 1 if dev else 0, min_score, min_len, max_insert, ph, pp, C.byref(st)),
+              "kc_pair_inserts")
+        pairs = pairs[:npairs * 16] if dev else pairs[:npairs]
+        out = {"pairs": int(st.pairs), "cls": [int(x) for x in st.cls], "insert_sum": int(st.insert_sum),
+               "insert_sq_sum": int(st.insert_sq_sum), "reads_with_best": int(st.reads_with_best)}
+        proper = out["cls"][_lib.KC_PAIR_PROPER]
+        out["mean"] = out["insert_sum"] / proper if proper else 0.0
+        # the variance from exact integers: n * sum(x^2) - sum(x)^2 >= 0
+        out["stddev"] = (proper * out["insert_sq_sum"] - out["insert_sum"] ** 2) ** 0.5 / proper if proper else 0.0
+        return hist, pairs, out
+
     def submit_ctg_block(self, seqs, depths):
         """kc_submit_ctg_block with device tensors (a '_'-joined block and one 16-bit depth per byte), e.g. those of
         unitig_block(); begin_ctg_kmers first."""
@@ -709,6 +786,10 @@ ALN_DTYPE = np.dtype([("read", "<u4"), ("ctg", "<u4"), ("cstart", "<u4"), ("csto
 GAP_ALN_DTYPE = np.dtype([("read", "<u4"), ("ctg", "<u4"), ("cstart", "<u4"), ("cstop", "<u4"), ("rstart", "<u2"), ("rstop", "<u2"),
                           ("score", "<u4"), ("mismatches", "<u2"), ("seeds", "<u2"), ("orient", "u1"), ("kind", "u1"), ("pad", "u1", (2,))])
 # match, mismatch, gap open, gap extend, ambiguity (CMakeDefinitions.txt:133-134)
+# kc_aln_depths' record of a contig (kc_ctg_depth, 32 bytes) and kc_pair_inserts' record of a pair (kc_pair_rec, 16 bytes)
+CTG_DEPTH_DTYPE = np.dtype([("depth_sum", "<u8"), ("len", "<u4"), ("covered", "<u4"), ("min_depth", "<u4"), ("max_depth", "<u4"),
+                            ("alns", "<u4"), ("mean", "<u4")])
+PAIR_DTYPE = np.dtype([("aln0", "<u4"), ("aln1", "<u4"), ("insert", "<u4"), ("cls", "u1"), ("pad", "u1", (3,))])
 BLASTN_ALN_SCORES = (2, 3, 5, 2, 1)
 ALTERNATE_ALN_SCORES = (1, 1, 1, 1, 1)
 
