@@ -767,7 +767,12 @@ constexpr size_t l1x16_lds_bytes() { return ((sizeof(L1LDS) + 15) & ~size_t(15))
 // scan (of the run lengths rounded up to even), reserve, scatter.  br[j] = bucket | extension codes << 10 | rank << 16,
 // or ~0.  dst[b] = {x, y as in split_stage, start | run length << 16, records that found room | of which in the old
 // last chunk << 16}.  Returns the staged total (pads included).
+// Nearly every run is SIMPLE: all its records found room, and they lie in the old last chunk alone or in the new chunks
+// alone, so that one base addresses the whole run.  Such a run says so in bit 31 of .z (a run has at most 16384 records)
+// and carries that base in x (y too where the run lies in new chunks): the copy-out then needs neither fit nor the old
+// chunk's share.
 // mid(): what the kernel has to do between the scatter and the barrier behind it (the next super-tile's staging)
+constexpr uint32_t DST_SIMPLE = 0x80000000u;
 template <class MidFn>
 __device__ __forceinline__ uint32_t split_stage_pairs(SplitLDS &L, uint32_t *slo, uint16_t *sbk, int buf, uint32_t P, const uint32_t (&lo)[R16],
                                                       const uint32_t (&br)[R16], const ChainDest &D, ChainState &st, MidFn mid) {
@@ -807,11 +812,18 @@ __device__ __forceinline__ uint32_t split_stage_pairs(SplitLDS &L, uint32_t *slo
       uint32_t *ch = D.chain + (size_t)tid * D.LMAX + have;
       for (uint32_t i = 0; i < k; i++) ch[i] = D.arena_base + a + i;
     }
+    const uint32_t wold = (base & CHm) ? min(fit, (CHm + 1u) - (base & CHm)) : 0u;
+    const bool simple = fit == v && (wold == 0u || wold >= v);
+    // (the flag as a shifted 0 / 1 the compiler cannot see through: the 32-bit constant it would make of it instead is kept
+    // in a vector register through the whole main loop, where the kernels have none to spare)
+    uint32_t flag = simple ? 1u : 0u;
+    asm("" : "+v"(flag));
     uint4 d;
     d.x = ((st.last - D.arena_base - (base >> D.log2CH)) << D.log2CH) + base - excl;
     d.y = ((a - have) << D.log2CH) + base - excl;
-    d.z = excl | (v << 16);
-    d.w = fit | (((base & CHm) ? min(fit, (CHm + 1u) - (base & CHm)) : 0u) << 16);
+    if (simple && !wold) d.x = d.y;
+    d.z = excl | (v << 16) | (flag << 31);
+    d.w = fit | (wold << 16);
     L.dst[tid] = d;
     if (k) st.last = D.arena_base + a + k - 1;
     st.cur = base + fit;
@@ -852,6 +864,21 @@ struct __attribute__((packed, aligned(2))) Rec6 {
   uint16_t bk;
 };
 static_assert(sizeof(Rec6Pair) == 12 && sizeof(Rec6) == 6, "six bytes a record");
+// lo2, bk2: the two staged records of a pair as they lie in the staging; at: the first one's place in the arena
+__device__ __forceinline__ void store_rec6_pair(uint8_t *arena0, uint32_t at, uint64_t lo2, uint32_t bk2) {
+  const uint32_t l1 = (uint32_t)(lo2 >> 32);
+  Rec6Pair r;
+  r.w0 = (uint32_t)lo2;
+  r.w1 = (bk2 & 0xFFFFu) | (l1 << 16);
+  r.w2 = (l1 >> 16) | (bk2 & 0xFFFF0000u);
+  *reinterpret_cast<Rec6Pair *>(arena0 + (size_t)at * 6) = r;
+}
+__device__ __forceinline__ void store_rec6(uint8_t *arena0, uint32_t at, uint32_t lo, uint32_t bk) {
+  Rec6 r;
+  r.lo = lo;
+  r.bk = (uint16_t)bk;
+  *reinterpret_cast<Rec6 *>(arena0 + (size_t)at * 6) = r;
+}
 
 template <class OvfFn>
 __device__ __forceinline__ void split_copy_out_pairs(SplitLDS &L, const uint32_t *slo, const uint16_t *sbk, uint32_t total, const ChainDest &D,
@@ -874,29 +901,34 @@ __device__ __forceinline__ void split_copy_out_pairs(SplitLDS &L, const uint32_t
     }
 #pragma unroll
     for (int u = 0; u < U; u++) d[u] = L.dst[bk2[u] & (PMAX - 1)];
+    // every live pair of this trip in a simple run (split_stage_pairs): the place is base + position, and the second half
+    // exists unless the pair is an odd run's last
+    bool simple = true;
+#pragma unroll
+    for (int u = 0; u < U; u++) simple = simple && (i0 + 2u * (uint32_t)u * WGB >= total || (d[u].z & DST_SIMPLE));
+    if (__all(simple)) {
+#pragma unroll
+      for (int u = 0; u < U; u++) {
+        const uint32_t i = i0 + 2u * (uint32_t)u * WGB;
+        if (i >= total) continue;
+        const uint32_t j = i - (d[u].z & 0xFFFFu), v = (d[u].z >> 16) & 0x7FFFu, at0 = d[u].x + i;
+        if (j + 1u < v) store_rec6_pair(arena0, at0, lo2[u], bk2[u]);
+        else store_rec6(arena0, at0, (uint32_t)lo2[u], bk2[u]);
+      }
+      continue;
+    }
     bool odd = false;
 #pragma unroll
     for (int u = 0; u < U; u++) {
       const uint32_t i = i0 + 2u * (uint32_t)u * WGB;
-      const uint32_t j = i - (d[u].z & 0xFFFFu), v = d[u].z >> 16, fit = d[u].w & 0xFFFFu, wold = d[u].w >> 16;
+      const uint32_t j = i - (d[u].z & 0xFFFFu), v = (d[u].z >> 16) & 0x7FFFu, fit = d[u].w & 0xFFFFu, wold = d[u].w >> 16;
       const bool live = i < total;  // (a pair's first position always holds a record: runs start on even positions)
       const bool f0 = live && j < fit, real1 = live && j + 1u < v, f1 = real1 && j + 1u < fit;
       // x and y are "index minus staging position" modulo 2^32: the sums must wrap in 32 bits before they are widened
       const uint32_t at0 = (j < wold ? d[u].x : d[u].y) + i, at1 = (j + 1u < wold ? d[u].x : d[u].y) + i + 1u;
       const bool pair = f0 && f1 && at1 == at0 + 1u;
-      if (pair) {
-        const uint32_t l1 = (uint32_t)(lo2[u] >> 32);
-        Rec6Pair r;
-        r.w0 = (uint32_t)lo2[u];
-        r.w1 = (bk2[u] & 0xFFFFu) | (l1 << 16);
-        r.w2 = (l1 >> 16) | (bk2[u] & 0xFFFF0000u);
-        *reinterpret_cast<Rec6Pair *>(arena0 + (size_t)at0 * 6) = r;
-      } else if (f0) {
-        Rec6 r;
-        r.lo = (uint32_t)lo2[u];
-        r.bk = (uint16_t)bk2[u];
-        *reinterpret_cast<Rec6 *>(arena0 + (size_t)at0 * 6) = r;
-      }
+      if (pair) store_rec6_pair(arena0, at0, lo2[u], bk2[u]);
+      else if (f0) store_rec6(arena0, at0, (uint32_t)lo2[u], bk2[u]);
       odd |= (real1 && !pair) || (live && !f0);
     }
     if (__any(odd)) {  // seldom: a pair across two chunks of its chain; a full chain or arena
@@ -904,7 +936,7 @@ __device__ __forceinline__ void split_copy_out_pairs(SplitLDS &L, const uint32_t
       for (int u = 0; u < U; u++) {
         const uint32_t i = i0 + 2u * (uint32_t)u * WGB;
         if (i >= total) continue;
-        const uint32_t j = i - (d[u].z & 0xFFFFu), v = d[u].z >> 16, fit = d[u].w & 0xFFFFu, wold = d[u].w >> 16;
+        const uint32_t j = i - (d[u].z & 0xFFFFu), v = (d[u].z >> 16) & 0x7FFFu, fit = d[u].w & 0xFFFFu, wold = d[u].w >> 16;
         const uint32_t at0 = (j < wold ? d[u].x : d[u].y) + i, at1 = (j + 1u < wold ? d[u].x : d[u].y) + i + 1u;
         const uint32_t l0 = (uint32_t)lo2[u], l1 = (uint32_t)(lo2[u] >> 32);
         // (where the 32 bits hold some of the bucket's as well -- k < 16 + la / 2 -- the two ORs put the same bits in the same place)
@@ -914,14 +946,8 @@ __device__ __forceinline__ void split_copy_out_pairs(SplitLDS &L, const uint32_t
         const bool f0 = j < fit, real1 = j + 1u < v, f1 = real1 && j + 1u < fit;
         if (!f0) overflow(ra);
         if (real1 && !(f0 && f1 && at1 == at0 + 1u)) {
-          if (f1) {
-            Rec6 r;
-            r.lo = l1;
-            r.bk = (uint16_t)(bk2[u] >> 16);
-            *reinterpret_cast<Rec6 *>(arena0 + (size_t)at1 * 6) = r;
-          } else {
-            overflow(rb);
-          }
+          if (f1) store_rec6(arena0, at1, l1, bk2[u] >> 16);
+          else overflow(rb);
         }
       }
     }

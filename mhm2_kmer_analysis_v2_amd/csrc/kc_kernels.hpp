@@ -18,6 +18,7 @@
 // shift per word instead of being re-packed from k ASCII bytes per thread.
 #pragma once
 #include "kc_common.hpp"
+#include "kc_encode.hpp"
 
 namespace kc {
 
@@ -44,12 +45,7 @@ constexpr uint64_t KEY_BUSY = ~0ULL - 1;
 constexpr uint64_t KEY_NEVER = ~0ULL - 2;  // no claim word ever holds it (a key's last word ends in six zero bits)
 
 enum { MODE_INSERT = 0, MODE_BIN = 1 };
-// input formats: ASCII bases + qualities; the reference's '_'-joined case-masked block; the reference's read
-// cache bytes (3-bit base | 5-bit quality << 3, src/packed_reads.cpp:99-126)
-// FMT_READS_UQ: FMT_READS whose quality array is not 16-byte co-aligned with the base array (its own
-// instantiation: the byte loads it needs would otherwise cost the common case registers)
-enum { FMT_READS = 0, FMT_SEQBLOCK = 1, FMT_PACKED = 2, FMT_READS_UQ = 3 };
-constexpr bool fmt_is_reads(int fmt) { return fmt == FMT_READS || fmt == FMT_READS_UQ; }
+// (the input formats FMT_*: kc_encode.hpp)
 
 // device-side counters, one u64 each (host mirror in kc_api)
 enum {
@@ -202,71 +198,7 @@ struct alignas(16) TileLDS {
   uint64_t far_off;            // offsets[first read of the tile + THREADS - 1] (~0 past the end): see tile_encode
 };
 
-__device__ __forceinline__ uint32_t pack4(uint32_t v) {  // 4 ASCII bytes -> 4 codes, first byte highest
-  uint32_t b = (v >> 1) & 0x03030303u;
-  uint32_t c = b ^ ((b >> 1) & 0x01010101u);
-  return (c * 0x40100401u) >> 24;
-}
-
-__device__ __forceinline__ uint32_t pack4_cache(uint32_t v) {  // 4 read-cache bytes (base 0-4 = ACGTN) -> 4 codes, N -> G
-  uint32_t c = (v & 0x03030303u) | ((v >> 1) & 0x02020202u);
-  return (c * 0x40100401u) >> 24;
-}
-
-constexpr uint32_t BM_ACGT = (1u << 1) | (1u << 3) | (1u << 7) | (1u << 20);
-constexpr uint32_t BM_ACGTN = BM_ACGT | (1u << 14);
-__device__ __forceinline__ bool in_bitmap(uint32_t c, uint32_t bm) { return ((c & 0xC0u) == 0x40u) && ((bm >> (c & 31u)) & 1u); }
-
-// ---- sixteen bytes at a time -----------------------------------------------------------------------------------
-// Byte-parallel predicates: a result word carries its answer in bit 7 of every byte, the other bits are garbage
-// until the final gather.  nz7(x): bit 7 set where the byte of x is not zero.
-__device__ __forceinline__ uint32_t nz7(uint32_t x) { return ((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x; }
-// S2/S5 for a group whose sixteen bytes are all real data: okm bit i = byte i may serve as an extension,
-// sepm bit i = byte i is a separator (FMT_SEQBLOCK), bad |= a byte outside the alphabet
-template <int FMT>
-__device__ __forceinline__ void encode_group_swar(const uint32_t (&bw)[4], const uint32_t (&qw)[4], uint32_t qual_cut, uint32_t &okm,
-                                                  uint32_t &sepm, bool &bad) {
-  // one word after the other, each folded into the running gathers at once (few values live at a time)
-  uint32_t badacc = 0, ok_lo = 0, ok_hi = 0, sp_lo = 0, sp_hi = 0;
-#pragma unroll
-  for (int j = 0; j < 4; j++) {
-    const uint32_t w = bw[j];
-    const uint32_t weight = (j & 1) ? 0x80402010u : 0x08040201u;  // byte i of the half-group -> bit i (times 0x80)
-    uint32_t ok, sp = 0;
-    if (FMT == FMT_PACKED) {
-      // base = low 3 bits (0-4), quality = high 5: quality >= 20 <=> byte >= 0xA0; base > 4 <=> bit2 & (bit1 | bit0)
-      const uint32_t x = w & ((w << 1) | (w << 2));  // bit 7: high quality, bit 2: bad base code
-      badacc |= x << 5;
-      ok = x & ~(w << 5);                            // high quality and base < 4
-    } else {
-      const uint32_t u = w & 0xDFDFDFDFu;  // upper case
-      const uint32_t not_acgt = nz7(u ^ 0x41414141u) & nz7(u ^ 0x43434343u) & nz7(u ^ 0x47474747u) & nz7(u ^ 0x54545454u);
-      const uint32_t not_n = nz7(u ^ 0x4E4E4E4Eu);
-      uint32_t hq;
-      if (fmt_is_reads(FMT)) {
-        const uint32_t q = qw[j];
-        hq = (((q & 0x7F7F7F7Fu) | 0x80808080u) - qual_cut * 0x01010101u) | q;  // S2: byte >= qual_cut (<= 128)
-        badacc |= not_acgt & not_n;
-      } else {
-        hq = ~(w << 2);                    // case carries the quality: bit 5 clear
-        const uint32_t not_sep = nz7(w ^ 0x5F5F5F5Fu);
-        sp = ~not_sep;
-        badacc |= not_acgt & not_n & not_sep;
-      }
-      ok = hq & ~not_acgt;
-    }
-    if (j < 2) {
-      ok_lo = __builtin_amdgcn_udot4(ok & 0x80808080u, weight, ok_lo, false);
-      if (FMT == FMT_SEQBLOCK) sp_lo = __builtin_amdgcn_udot4(sp & 0x80808080u, weight, sp_lo, false);
-    } else {
-      ok_hi = __builtin_amdgcn_udot4(ok & 0x80808080u, weight, ok_hi, false);
-      if (FMT == FMT_SEQBLOCK) sp_hi = __builtin_amdgcn_udot4(sp & 0x80808080u, weight, sp_hi, false);
-    }
-  }
-  okm = (ok_lo >> 7) | ((ok_hi >> 7) << 8);
-  if (FMT == FMT_SEQBLOCK) sepm = (sp_lo >> 7) | ((sp_hi >> 7) << 8);
-  if (badacc & 0x80808080u) bad = true;
-}
+// (a group's codes, ok bits, separator bits and bad-byte flag: kc_encode.hpp)
 
 // Staging a tile has two halves so that a kernel can keep the next tile's bytes in flight while it works on the
 // current one: tile_prefetch issues the global loads into registers (nothing waits on them), tile_encode turns
@@ -368,40 +300,13 @@ __device__ __forceinline__ void tile_encode_fill(TileLDS<G> &L, const TileRaw<G>
     const uint32_t(&qw)[4] = R.qw[gi];
     const bool any = (X0 + 16 > lo) && (X0 < hi);
     const bool full = (X0 >= lo) && (X0 + 16 <= hi);
-    uint32_t code = FMT == FMT_PACKED ? (pack4_cache(bw[0]) << 24) | (pack4_cache(bw[1]) << 16) | (pack4_cache(bw[2]) << 8) | pack4_cache(bw[3])
-                                      : (pack4(bw[0]) << 24) | (pack4(bw[1]) << 16) | (pack4(bw[2]) << 8) | pack4(bw[3]);
+    const uint32_t code = encode_group_codes<FMT>(bw);
     uint32_t okm = 0, sepm = 0;
     if (full && (!fmt_is_reads(FMT) || a.qual_cut <= 128)) {
       encode_group_swar<FMT>(bw, qw, (uint32_t)a.qual_cut, okm, sepm, bad);
     } else {
       // groups at the edges of the data: byte by byte, bytes outside [lo, hi) masked
-#pragma unroll
-      for (int j = 0; j < 4; j++) {
-        uint32_t wb = bw[j], wq = qw[j];
-#pragma unroll 1
-        for (int i = 4 * j; i < 4 * j + 4; i++, wb >>= 8, wq >>= 8) {
-          const uint32_t c = wb & 0xFFu;
-          const bool real = full || (any && (X0 + i >= lo) && (X0 + i < hi));
-          bool hq;
-          if (FMT == FMT_PACKED) {
-            hq = (c >> 3) >= KC_QUAL_CUTOFF;                      // S2 on the stored quality (already relative to qual_offset)
-            if (real && (c & 7u) > 4u) bad = true;
-            if (real && hq && (c & 7u) < 4u) okm |= 1u << i;
-            continue;
-          }
-          if (fmt_is_reads(FMT)) {
-            const int q = (int)(wq & 0xFFu);
-            hq = q >= a.qual_cut;                                 // S2
-            if (real && !in_bitmap(c, BM_ACGTN)) bad = true;
-          } else {
-            hq = (c & 0x20u) == 0;                                // case carries the quality
-            const bool sep = (c == '_');
-            if (real && sep) sepm |= 1u << i;
-            if (real && !sep && !in_bitmap(c, BM_ACGTN)) bad = true;
-          }
-          if (real && hq && in_bitmap(c, BM_ACGT)) okm |= 1u << i;
-        }
-      }
+      encode_group_edge<FMT>(bw, qw, a.qual_cut, X0, lo, hi, okm, sepm, bad);
     }
     L.codes[g ^ 1] = code;
     L.ok[g] = (uint16_t)okm;
