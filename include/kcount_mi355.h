@@ -772,6 +772,101 @@ typedef struct kc_insert_stats {
 } kc_insert_stats;
 int kc_pair_inserts(kc_ctx *ctx, const uint64_t *offsets, uint64_t nreads, const kc_gap_aln *alns, uint64_t n_alns, int on_device,
                     uint32_t min_score, uint32_t min_len, uint32_t max_insert, uint64_t *hist, kc_pair_rec *pairs, kc_insert_stats *stats);
+/*
+ * Contig ends extended by local assembly: the role of localassm(LASSM_MAX_KMER_LEN, kmer_len, packed_reads_list, ins_avg,
+ * ins_stddev, qual_offset, ctgs, alns), src/contigging.cpp:167-172, commented out in the proxy.  The reference holds no
+ * code for it (no localassm in src/), so the rules below are THIS project's own definition (pinned
+ * by the host model tests/lassm_model.py); no parity with MetaHipMer is claimed.  All quantities are integers; every
+ * output is one exact byte string for a given input, whatever order the waves or the atomics arrive in.
+ *
+ * Input.  The reads (bases, quals, offsets as kc_align_gapped takes them; reads 2p and 2p + 1 are mates, an odd nreads is
+ * KC_ERR_INVALID_ARG; a read over KC_ALIGN_MAX_READ_LEN is refused as in kc_align_gapped), kc_align_gapped's records
+ * alns, kc_pair_inserts' records pairs (nreads / 2 of them) and, optionally, kc_aln_depths' records ctgs (NULL: depth 0
+ * for every contig); the contigs are the kept index's.  quals == NULL: every base is high quality; the quality offset is
+ * the context's.  alns are valid by the rule above, with read < nreads and rstop <= L(read).  A pairs record is valid iff
+ * each of aln0 / aln1 is 0xFFFFFFFF, or is below n_alns with that record's read equal to 2p / 2p + 1 and its kind not
+ * KC_GAP_NONE; cls and insert are not read.  An invalid record is KC_ERR_INVALID_ARG and kc_last_error names the lowest
+ * bad index; validation is a pass of its own in front of the first store.
+ *
+ * Codes.  A read's A C G T in either case are 0..3, anything else is 4; a contig's N is 4.  The reverse complement maps
+ * c < 4 to 3 - c, keeps 4, and reverses the qualities with the text.  With q = a base's quality byte minus the offset
+ * its CLASS is hi iff q >= hi_qual, lo iff min_qual <= q < hi_qual, otherwise none.
+ *
+ * Ends and candidates.  End 2u is the left end of contig u, end 2u + 1 its right end.  Every walk runs rightwards: a left
+ * end is the right end of the contig's reverse complement.  Read r has length L > 0 and a best record b (from pairs);
+ * u = b.ctg, R' is the read in contig orientation (its reverse complement iff b.orient is 1), and in signed 64-bit
+ * ps = b.cstart - b.rstart, pe = b.cstop + (L - b.rstop).  pe > len_u makes R' a candidate of u's right end; ps < 0
+ * makes revcomp(R') a candidate of u's left end.  The mate m = r ^ 1 is UNPLACED FOR u iff its length is > 0 and it has no
+ * best record or its best record's contig is not u.  An unplaced m with b.orient == 0 and ps + max_insert > len_u makes
+ * revcomp(m) a candidate of u's right end; an unplaced m with b.orient == 1 and pe - max_insert < 0 makes revcomp(m) a
+ * candidate of u's left end.  cands counts an end's candidates; an end with none is KC_LASSM_NO_CANDS, one with more
+ * than max_cands KC_LASSM_TOO_MANY; either has ext_len, iters and mer_len 0.
+ *
+ * The table of an end at mer length m.  For every candidate text T of length n and every p with p + m < n: if the window
+ * T[p, p + m) is all bases and e = T[p + m] is a base whose class is not none, hi[window][e] or lo[window][e] goes up by
+ * one.  Counts are exact.
+ *
+ * One walk step.  thr = max(min_viable, viable_permille * ctgs[u].mean / 1000) by integer division.  S is the end's tail
+ * -- the last min(len_u, max_mer_len) codes of the contig in walk orientation -- followed by the extension so far.  The
+ * step yields DEAD_END if |S| < m, or the current mer M (the last m of S) holds a 4, or has no counts; LOOP if M was
+ * already visited in this iteration; otherwise M is marked visited and base b is VIABLE iff hi_b + lo_b >= thr and
+ * hi_b >= 1: no viable base yields DEAD_END, two or more FORK, exactly one is appended -- and then MAX_LEN is reached iff
+ * the extension has max_walk_len bases, else the next step is taken.
+ *
+ * Iterations.  m starts at min(max(k, min_mer_len), max_mer_len), k the context's kmer_len.  The extension persists across
+ * iterations; the table and the visited marks do not.  After FORK, if the last shift was not downward and
+ * m + shift <= max_mer_len: m += shift and the next iteration starts.  After DEAD_END, if the last shift was not upward
+ * and m - shift >= min_mer_len: m -= shift and the next iteration starts.  Everything else ends the end with that status,
+ * the final m in mer_len and the number of iterations in iters.
+ *
+ * Output.  Contig u becomes revcomp(left extension) + the contig's bytes as they are + the right extension + '_';
+ * extensions are upper-case A C G T.  seqs_out / offsets_out (n_ctgs + 1 entries) are in the layout kc_ctg_index_build and
+ * kc_submit_ctg_block take; ends (2 n_ctgs records) has out_pos = the block position of the extension's first byte, set
+ * for ends without an extension too.  offsets_out, ends and stats may be NULL.  stats: ends = 2 n_ctgs, status by
+ * KC_LASSM_*, cands_overhang / cands_mate / cand_bases over every end's candidates (TOO_MANY ends included), iterations
+ * and ext_bases summed over the ends, ctgs_extended the contigs with at least one extension base.
+ *
+ * Protocol.  The parameter ranges (see kc_lassm_params), unknown flags and an odd nreads are checked in front of ctx and
+ * kc_last_error names the values.  on_device applies to all arrays alike; device record arrays (alns, pairs, ctgs, ends)
+ * are 16-byte aligned, device offsets 8-byte.  No index: KC_ERR_STATE.  2^30 reads or more, 2^32 records or more, or a
+ * result of 2^31 bytes or more: KC_ERR_CAPACITY.  On every error nothing is written through any pointer, with one
+ * exception: when capacity is too small for the block, or seqs_out is NULL (a size query, KC_OK), *nbytes_out and *stats
+ * receive the totals and nothing else is written; a non-NULL seqs_out with too small a capacity is KC_ERR_CAPACITY.
+ * nbytes_out is required.  The call works before or after kc_finalize and with rank_n > 1, touches neither the index, the
+ * table nor the results, runs on the context's stream and returns when done; scratch lives for the call only: 10 bytes a
+ * candidate base and 26 a candidate (the oriented text and the entries of every end that walks), 80 to 160 bytes a
+ * candidate base for the tables, but only of the ends of one batch (table_budget_mb bounds the tables of a batch; an
+ * end over the budget runs alone), 88 + max_walk_len bytes an end and, for host arrays, the inputs' copies and the
+ * outputs' staging (8 bytes a read and the reads' bytes among them).  A read gives at most three candidates.  The
+ * result does not depend on table_budget_mb.
+ */
+#define KC_LASSM_MAX_MER_LEN 128
+#define KC_LASSM_MAX_WALK 4096
+#define KC_LASSM_MAX_CANDS (1u << 20)
+enum { KC_LASSM_NO_CANDS = 0, KC_LASSM_TOO_MANY = 1, KC_LASSM_DEAD_END = 2, KC_LASSM_FORK = 3, KC_LASSM_LOOP = 4, KC_LASSM_MAX_LEN = 5 };
+typedef struct kc_lassm_params {
+  uint32_t min_mer_len, max_mer_len, shift; /* 4 <= min <= max <= 128, 1 <= shift <= 64 */
+  uint32_t max_walk_len;                    /* 1 .. KC_LASSM_MAX_WALK */
+  uint32_t max_insert;                      /* 1 .. KC_INSERT_MAX: how far a mate may reach */
+  uint32_t min_qual, hi_qual;               /* min_qual <= hi_qual <= 93 */
+  uint32_t min_viable, viable_permille;     /* min_viable >= 1, permille <= 1000 */
+  uint32_t max_cands;                       /* 1 .. KC_LASSM_MAX_CANDS */
+  uint32_t table_budget_mb;                 /* 0 = 1024 */
+  uint32_t flags;                           /* 0 */
+} kc_lassm_params;                          /* 48 bytes */
+typedef struct kc_lassm_end {               /* 16 bytes; index 2u = left end of contig u, 2u + 1 = right */
+  uint32_t cands, ext_len, out_pos;         /* out_pos: block position of the extension's first byte */
+  uint16_t iters;
+  uint8_t mer_len, status;
+} kc_lassm_end;
+typedef struct kc_lassm_stats {
+  uint64_t ends, status[6], cands_overhang, cands_mate, cand_bases, iterations, ext_bases, ctgs_extended;
+  uint64_t reserved[5]; /* zero: 144 bytes in all */
+} kc_lassm_stats;
+int kc_local_assm(kc_ctx *ctx, const uint8_t *bases, const uint8_t *quals, const uint64_t *offsets, uint64_t nreads,
+                  const kc_gap_aln *alns, uint64_t n_alns, const kc_pair_rec *pairs, const kc_ctg_depth *ctgs, int on_device,
+                  const kc_lassm_params *params, uint8_t *seqs_out, uint64_t capacity, uint64_t *offsets_out,
+                  kc_lassm_end *ends, uint64_t *nbytes_out, kc_lassm_stats *stats);
 /* KmerDHT::kmer_exists / get_kmer_count / get_local_kmer_counts (src/kcount/kmer_dht.cpp:198-245) in bulk, against the
  * results kept in HBM: nq k-mers of num_longs words each, in either orientation; counts[i] = 0 (and left/right = 0)
  * when the k-mer did not survive.  The index over the results is built on the first call after kc_finalize.

@@ -134,6 +134,27 @@ KC_DEPTH_BEST_ONLY, KC_DEPTH_PER_CONTIG = 1, 2
 KC_INSERT_MAX = 65535
 KC_PAIR_NONE, KC_PAIR_ONE, KC_PAIR_DIFF_CTG, KC_PAIR_SAME_ORIENT, KC_PAIR_EVERTED, KC_PAIR_TOO_LONG, KC_PAIR_PROPER = range(7)
 
+
+class kc_lassm_params(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("min_mer_len", "max_mer_len", "shift", "max_walk_len", "max_insert", "min_qual", "hi_qual",
+                                          "min_viable", "viable_permille", "max_cands", "table_budget_mb", "flags")]
+
+
+class kc_lassm_end(C.Structure):
+    _fields_ = [("cands", C.c_uint32), ("ext_len", C.c_uint32), ("out_pos", C.c_uint32), ("iters", C.c_uint16), ("mer_len", C.c_uint8),
+                ("status", C.c_uint8)]
+
+
+class kc_lassm_stats(C.Structure):
+    _fields_ = [("ends", C.c_uint64), ("status", C.c_uint64 * 6)] + [(n, C.c_uint64) for n in (
+        "cands_overhang", "cands_mate", "cand_bases", "iterations", "ext_bases", "ctgs_extended")] + [("reserved", C.c_uint64 * 5)]
+
+
+KC_LASSM_MAX_MER_LEN = 128
+KC_LASSM_MAX_WALK = 4096
+KC_LASSM_MAX_CANDS = 1 << 20
+KC_LASSM_NO_CANDS, KC_LASSM_TOO_MANY, KC_LASSM_DEAD_END, KC_LASSM_FORK, KC_LASSM_LOOP, KC_LASSM_MAX_LEN = range(6)
+
 # every symbol include/kcount_mi355.h declares: (restype, argtypes)
 SYMBOLS = {
     "kc_abi_version": (C.c_int, []),
@@ -208,6 +229,9 @@ SYMBOLS = {
                                  C.c_void_p, C.c_void_p, C.POINTER(kc_depth_stats)]),
     "kc_pair_inserts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32,
                                    C.c_void_p, C.c_void_p, C.POINTER(kc_insert_stats)]),
+    "kc_local_assm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                 C.c_int, C.POINTER(kc_lassm_params), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64),
+                                 C.POINTER(kc_lassm_stats)]),
     "kc_lookup": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "kc_dump_table": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
     "kc_get_stats": (C.c_int, [C.c_void_p, C.POINTER(kc_stats)]),

@@ -34,6 +34,7 @@
 #include "kc_align.hpp"
 #include "kc_gap.hpp"
 #include "kc_depth.hpp"
+#include "kc_lassm.hpp"
 
 using namespace kc;
 
@@ -99,13 +100,17 @@ enum { KT_EXTRACT_INSERT = 0, KT_EXTRACT_BIN, KT_INSERT_RECORDS, KT_FINALIZE, KT
        KT_UNITIG_SELECT, KT_UNITIG_SCAN, KT_UNITIG_WRITE, KT_UNITIG_DEPTH, KT_ALIGN_CHECK, KT_ALIGN_INDEX, KT_ALIGN_SWEEP, KT_ALIGN_LENGTHS,
        KT_ALIGN_COUNT, KT_ALIGN_SCAN, KT_ALIGN_WRITE, KT_GAP_LENGTHS, KT_GAP_CHECK, KT_GAP_SORT, KT_GAP_DP, KT_DEPTH_CHECK,
        KT_DEPTH_BEST, KT_DEPTH_MARK, KT_DEPTH_TILE_SUMS, KT_DEPTH_SCAN, KT_DEPTH_RESCAN, KT_DEPTH_CTG, KT_DEPTH_FILL, KT_PAIR_LENGTHS, KT_PAIR_CHECK,
-       KT_PAIR_BEST, KT_PAIR_CLASSIFY, KT_PAIR_CLASSIFY_LDS, KT_COUNT };
+       KT_PAIR_BEST, KT_PAIR_CLASSIFY, KT_PAIR_CLASSIFY_LDS, KT_LASSM_LENGTHS, KT_LASSM_CHECK, KT_LASSM_PAIR_CHECK, KT_LASSM_COUNT,
+       KT_LASSM_PLAN, KT_LASSM_SCAN, KT_LASSM_SCATTER, KT_LASSM_TEXT, KT_LASSM_WALK, KT_LASSM_LENS, KT_LASSM_ENDS, KT_LASSM_WRITE, KT_COUNT };
 // KT_FQ_SCAN, KT_MERGE_SCAN and KT_TRIM_SCAN label the front end's three uses of the one shared kc_scan_kernel (kc_scan.hpp); their
 // strings keep the names the uses were first reported under.  KT_SORT_SCAN and KT_DUMP_SCAN are the back end's two,
 // KT_UNITIG_SCAN the unitigs' (kc_scan_kernel<2>: bytes and unitig numbers in one pass), KT_ALIGN_SCAN the alignments' (the
 // reads' record counts).  KT_ALIGN_COUNT and KT_ALIGN_WRITE are the two passes of kc_align_reads_kernel.  KT_GAP_LENGTHS is
 // kc_align_gapped's use of kc_align_lengths_kernel, KT_PAIR_LENGTHS kc_pair_inserts'.  KT_DEPTH_SCAN is kc_aln_depths' use of kc_scan_kernel<1>
 // (the tile sums); KT_PAIR_CHECK and KT_PAIR_BEST are kc_pair_inserts' launches of the two kernels it shares with kc_aln_depths.
+// KT_LASSM_LENGTHS and KT_LASSM_CHECK are kc_local_assm's launches of kc_align_lengths_kernel and kc_depth_check_kernel, KT_LASSM_SCAN its
+// uses of kc_scan_kernel<2> (entries and text) and <1> (slots; the new lengths); KT_LASSM_COUNT and KT_LASSM_SCATTER are the two passes of
+// kc_lassm_cands_kernel.
 static const char *const kt_names[KT_COUNT] = {"kc_extract_kernel<insert>", "kc_bin_reads_kernel", "kc_insert_records_kernel",
                                                "kc_finalize_kernel", "kc_tile_first_kernel", "kc_rehash_kernel",
                                                "kc_l1_reads_kernel", "kc_l1_records_kernel", "kc_l2_split_kernel",
@@ -129,7 +134,11 @@ static const char *const kt_names[KT_COUNT] = {"kc_extract_kernel<insert>", "kc_
                                                "kc_depth_mark_kernel", "kc_depth_tile_sums_kernel", "kc_depth_scan_kernel",
                                                "kc_depth_rescan_kernel", "kc_depth_ctg_kernel", "kc_depth_fill_kernel",
                                                "kc_align_lengths_kernel<pair>", "kc_depth_check_kernel<pair>", "kc_depth_best_kernel<pair>",
-                                               "kc_pair_classify_kernel", "kc_pair_classify_kernel<lds>"};
+                                               "kc_pair_classify_kernel", "kc_pair_classify_kernel<lds>",
+                                               "kc_align_lengths_kernel<lassm>", "kc_depth_check_kernel<lassm>", "kc_lassm_pair_check_kernel",
+                                               "kc_lassm_cands_kernel<count>", "kc_lassm_plan_kernel", "kc_lassm_scan_kernel",
+                                               "kc_lassm_cands_kernel<write>", "kc_lassm_text_kernel", "kc_lassm_walk_kernel",
+                                               "kc_lassm_lens_kernel", "kc_lassm_ends_kernel", "kc_lassm_write_kernel"};
 struct kt_pending {
   hipEvent_t start, stop;
   int kind;
@@ -3216,6 +3225,7 @@ extern "C" int kc_lookup(kc_ctx *c, const uint64_t *queries, uint64_t nq, int on
 #include "kc_api_align.hpp"  // kc_ctg_index_build, kc_ctg_index_clear, kc_align_reads
 #include "kc_api_gap.hpp"    // kc_align_gapped
 #include "kc_api_depth.hpp"  // kc_ctg_index_info, kc_aln_depths, kc_pair_inserts
+#include "kc_api_lassm.hpp"  // kc_local_assm
 
 // ---- the contig pass (kc_ctg.hpp) ----------------------------------------------------------------------------------
 extern "C" int kc_begin_ctg_kmers(kc_ctx *c, uint64_t max_ctg_kmers) {

@@ -21,7 +21,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (check, kc_align_stats, kc_aln_scores, kc_config, kc_ctg_index_stats, kc_depth_stats, kc_gap_stats, kc_insert_stats, kc_kernel_time, kc_merge_stats, kc_result, kc_stats, kc_synth_params, kc_trim_stats, kc_tuning,
+from ._lib import (check, kc_align_stats, kc_aln_scores, kc_config, kc_ctg_index_stats, kc_depth_stats, kc_gap_stats, kc_insert_stats, kc_kernel_time, kc_lassm_params, kc_lassm_stats, kc_merge_stats, kc_result, kc_stats, kc_synth_params, kc_trim_stats, kc_tuning,
                    kc_unitig_stats, lib)
 
 
@@ -745,6 +745,65 @@ class KmerCounter:
         out["stddev"] = (proper * out["insert_sq_sum"] - out["insert_sum"] ** 2) ** 0.5 / proper if proper else 0.0
         return hist, pairs, out
 
+    def local_assm(self, bases, quals, offsets, gap_alns, pairs, ctg_depths=None, min_mer_len=13, max_mer_len=121, shift=8, max_walk_len=400,
+                   max_insert=1000, min_qual=10, hi_qual=20, min_viable=2, viable_permille=200, max_cands=2000, table_budget_mb=0):
+        """The indexed contigs, every end extended by a walk through the mers of the reads that hang over it and of the
+        mates that fall beyond it (kc_local_assm).  bases / quals / offsets: the reads align_gapped
+        took (quals None: every base is high quality); gap_alns its records, pairs pair_inserts' records, ctg_depths
+        aln_depths' per-contig records (None: depth 0).  Returns (seqs, offsets, ends, stats): the new seq block and its
+        len(contigs) + 1 starts -- what index_contigs and submit_ctg_block take -- one LASSM_END_DTYPE record per end
+        (2u: left end of contig u, 2u + 1: right) and kc_lassm_stats as a dict, status a list by KC_LASSM_*.  Host arrays in
+        give numpy arrays out; device tensors in give device tensors out (ends a uint8 tensor of 16-byte records, offsets
+        int64).  The block is allocated at the indexed block's size plus a quarter; if that is too small the call is
+        made once more with the size it reported."""
+        pa, n_alns, dev_a = self._gap_records(gap_alns)
+        po, dev = _ptr(offsets)
+        nreads = len(offsets) - 1
+        pb, dev_b = _ptr(bases)
+        pq, dev_q = (None, dev) if quals is None else _ptr(quals)
+        pp, dev_p = _ptr(pairs)
+        npairs = pairs.numel() // 16 if dev_p else len(pairs)
+        pc, dev_c = (None, dev) if ctg_depths is None else _ptr(ctg_depths)
+        nbytes, n_ctgs = self.contig_index_info()
+        if ((n_alns and dev_a != dev) or (nreads and len(bases) and (dev_b != dev or dev_q != dev)) or (npairs and dev_p != dev) or
+                (n_ctgs and dev_c != dev)):
+            raise ValueError("bases, quals, offsets, gap_alns, pairs and ctg_depths must all be host arrays or all be device tensors")
+        if npairs != nreads // 2 or (not dev and npairs and (pairs.dtype.itemsize != 16 or not pairs.flags["C_CONTIGUOUS"])):
+            raise ValueError("pairs: a contiguous array of nreads / 2 16-byte records (PAIR_DTYPE)")
+        if ctg_depths is not None:
+            if (ctg_depths.numel() // 32 if dev else len(ctg_depths)) != n_ctgs or (not dev and n_ctgs and ctg_depths.dtype.itemsize != 32):
+                raise ValueError("ctg_depths: one 32-byte record (CTG_DEPTH_DTYPE) per indexed contig")
+        prm = kc_lassm_params(min_mer_len, max_mer_len, shift, max_walk_len, max_insert, min_qual, hi_qual, min_viable, viable_permille,
+                              max_cands, table_budget_mb, 0)
+        st, nb = kc_lassm_stats(), C.c_uint64(0)
+        if dev:
+            import torch
+            d = "cuda:%d" % self.device
+            offs_out = torch.empty(n_ctgs + 1, dtype=torch.int64, device=d)
+            ends = torch.empty(max(2 * n_ctgs, 1) * 16, dtype=torch.uint8, device=d)
+        else:
+            offs_out = np.zeros(n_ctgs + 1, dtype=np.uint64)
+            ends = np.zeros(max(2 * n_ctgs, 1), dtype=LASSM_END_DTYPE)
+        capacity = nbytes + nbytes // 4
+        for attempt in (0, 1):
+            if dev:
+                seqs = torch.empty(max(capacity, 1), dtype=torch.uint8, device=d)
+                torch.cuda.current_stream(self.device).synchronize()  # the input and the fresh arrays are torch's until now
+                ps, pf, pe = seqs.data_ptr(), offs_out.data_ptr(), ends.data_ptr()
+            else:
+                seqs = np.zeros(max(capacity, 1), dtype=np.uint8)
+                ps, pf, pe = seqs.ctypes.data, offs_out.ctypes.data, ends.ctypes.data
+            rc = lib().kc_local_assm(self._h, pb, pq, po, nreads, pa, n_alns, pp if npairs else None, pc, 1 if dev else 0, C.byref(prm), ps,
+                                     capacity, pf, pe, C.byref(nb), C.byref(st))
+            if rc != _lib.KC_ERR_CAPACITY or attempt or not capacity < nb.value < (1 << 31):
+                break
+            capacity = int(nb.value)  # the size it was told
+        check(rc, "kc_local_assm")
+        ends = ends[:2 * n_ctgs * 16] if dev else ends[:2 * n_ctgs]
+        out = {f: int(getattr(st, f)) for f, _ in kc_lassm_stats._fields_ if f not in ("status", "reserved")}
+        out["status"] = [int(x) for x in st.status]
+        return seqs[:int(nb.value)], offs_out, ends, out
+
     def submit_ctg_block(self, seqs, depths):
         """kc_submit_ctg_block with device tensors (a '_'-joined block and one 16-bit depth per byte), e.g. those of
         unitig_block(); begin_ctg_kmers first."""
@@ -790,6 +849,8 @@ GAP_ALN_DTYPE = np.dtype([("read", "<u4"), ("ctg", "<u4"), ("cstart", "<u4"), ("
 CTG_DEPTH_DTYPE = np.dtype([("depth_sum", "<u8"), ("len", "<u4"), ("covered", "<u4"), ("min_depth", "<u4"), ("max_depth", "<u4"),
                             ("alns", "<u4"), ("mean", "<u4")])
 PAIR_DTYPE = np.dtype([("aln0", "<u4"), ("aln1", "<u4"), ("insert", "<u4"), ("cls", "u1"), ("pad", "u1", (3,))])
+# kc_local_assm's record of a contig end (kc_lassm_end, 16 bytes)
+LASSM_END_DTYPE = np.dtype([("cands", "<u4"), ("ext_len", "<u4"), ("out_pos", "<u4"), ("iters", "<u2"), ("mer_len", "u1"), ("status", "u1")])
 BLASTN_ALN_SCORES = (2, 3, 5, 2, 1)
 ALTERNATE_ALN_SCORES = (1, 1, 1, 1, 1)
 

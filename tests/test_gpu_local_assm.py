@@ -1,0 +1,500 @@
+"""kc_local_assm (csrc/kc_lassm.hpp) against the host model tests/lassm_model.py, byte for byte: the new block, its
+offsets, the ends' records and the statistics on the same inputs.  The model is never replaced by a second device run.
+
+Most cases forge their records (tests/lassm_cases.py): the call reads coordinates and never compares a read with its
+contig.  One case runs the device's own steps in front of it.  Every raw device call goes through device_lassm: all arrays
+of exactly their size inside canaries."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import depth_model as D
+import lassm_cases as LC
+import lassm_model as M
+import mhm2_kmer_analysis_v2_amd as pkg
+from align_model import revcomp
+from mhm2_kmer_analysis_v2_amd import _lib, kcount
+from test_gpu_gap_align import block_arrays, read_arrays
+
+pytestmark = pytest.mark.gpu
+
+PAD = 64
+UNTOUCHED = (99, 98)
+
+
+def indexed(contigs, k=21, **kw):
+    kc = pkg.KmerCounter(k, **kw)
+    kc.index_contigs(*block_arrays(contigs))
+    return kc
+
+
+def host_arrays(c):
+    alns, pairs, quals = c.arrays()
+    b, o = read_arrays(c.reads)
+    q = None if quals is None else np.frombuffer("".join(quals).encode(), dtype=np.uint8).copy()
+    ctgs = None
+    if c.means is not None:
+        ctgs = np.zeros(len(c.contigs), dtype=kcount.CTG_DEPTH_DTYPE)
+        ctgs["mean"] = c.means
+        ctgs["len"] = [len(s) for s in c.contigs]
+    return b, q, o, alns, pairs, ctgs
+
+
+def stats_dict(st):
+    out = {f: int(getattr(st, f)) for f, _ in _lib.kc_lassm_stats._fields_ if f not in ("status", "reserved")}
+    out["status"] = [int(x) for x in st.status]
+    assert [int(x) for x in st.reserved] == [0] * 5
+    return out
+
+
+def canaried(arr, shift=0, fill=0xCD):
+    """device bytes PAD + shift in front of and PAD behind a copy of arr (None: nothing): (tensor, pointer or None)"""
+    import torch
+    if arr is None:
+        return None, None
+    raw = np.frombuffer(arr.tobytes(), dtype=np.uint8)
+    h = np.full(len(raw) + 2 * PAD + 16, fill, dtype=np.uint8)
+    h[PAD + shift:PAD + shift + len(raw)] = raw
+    t = torch.from_numpy(h).cuda()
+    return t, t.data_ptr() + PAD + shift
+
+
+def device_lassm(kc, c, expect=0, capacity=None, seqs_null=False, want_offsets=True, want_ends=True, want_stats=True, misalign=0, total=None,
+                 nreads=None, arrays=None, **params):
+    """the call on device arrays of exactly the needed size inside canaries: (block, offsets, ends, stats, nbytes).
+    expect != 0: the status is checked, and that nothing was written (for KC_ERR_CAPACITY of the block: nothing but the
+    totals); misalign: bytes by which the record arrays are misaligned; total: the block's size where no model run gives it"""
+    import torch
+    b, q, o, alns, pairs, ctgs = arrays or host_arrays(c)
+    n_ctgs = len(c.contigs)
+    if total is None:
+        total = len(M.local_assm(c.contigs, c.reads, c.arrays()[2], alns, pairs, c.means, k=kc.k, **params)[0]) if not expect else 64
+    cap = total if capacity is None else capacity
+    inputs = [canaried(x, s) for x, s in ((b, 0), (q, 0), (o, 0), (alns, misalign), (pairs, misalign), (ctgs, misalign))]
+    before = [None if t is None else t.cpu().numpy().copy() for t, _ in inputs]
+    d_seqs = torch.full((cap + 2 * PAD,), 0xAB, dtype=torch.uint8, device="cuda")
+    d_offs = torch.full(((n_ctgs + 1) * 8 + 2 * PAD,), 0xAB, dtype=torch.uint8, device="cuda")
+    d_ends = torch.full((2 * n_ctgs * 16 + 2 * PAD + 16,), 0xAB, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    st, nb = _lib.kc_lassm_stats(ends=UNTOUCHED[0]), C.c_uint64(UNTOUCHED[1])
+    p = _lib.kc_lassm_params(**dict(M.DEFAULTS, **params))
+    rc = pkg.lib().kc_local_assm(kc._h, inputs[0][1], inputs[1][1], inputs[2][1], len(c.reads) if nreads is None else nreads, inputs[3][1],
+                                 len(alns), inputs[4][1], inputs[5][1], 1, C.byref(p), None if seqs_null else d_seqs.data_ptr() + PAD, cap,
+                                 d_offs.data_ptr() + PAD if want_offsets else None, d_ends.data_ptr() + PAD + misalign if want_ends else None,
+                                 C.byref(nb), C.byref(st) if want_stats else None)
+    for (t, _), h in zip(inputs, before):
+        assert t is None or (t.cpu().numpy() == h).all(), "an input was written"
+    h_seqs, h_offs, h_ends = d_seqs.cpu().numpy(), d_offs.cpu().numpy(), d_ends.cpu().numpy()
+    size_only = seqs_null or expect == _lib.KC_ERR_CAPACITY
+    if expect or seqs_null:
+        assert rc == expect, pkg.lib().kc_last_error()
+        assert (h_seqs == 0xAB).all() and (h_offs == 0xAB).all() and (h_ends == 0xAB).all(), "a refused call or a size query wrote"
+        if not size_only:
+            assert (int(st.ends), nb.value) == UNTOUCHED, "a refused call wrote totals"
+            return rc
+        return None, None, None, stats_dict(st) if want_stats else None, int(nb.value)
+    assert rc == 0, pkg.lib().kc_last_error()
+    n = int(nb.value)
+    assert n <= cap
+    assert (h_seqs[:PAD] == 0xAB).all() and (h_seqs[PAD + n:] == 0xAB).all(), "a canary was written"
+    assert (h_offs[:PAD] == 0xAB).all() and (h_offs[PAD + (n_ctgs + 1) * 8:] == 0xAB).all(), "a canary was written"
+    assert (h_ends[:PAD + misalign] == 0xAB).all() and (h_ends[PAD + misalign + 2 * n_ctgs * 16:] == 0xAB).all(), "a canary was written"
+    if not want_offsets:
+        assert (h_offs == 0xAB).all()
+    if not want_ends:
+        assert (h_ends == 0xAB).all()
+    if not want_stats:
+        assert int(st.ends) == UNTOUCHED[0]
+    return (h_seqs[PAD:PAD + n].tobytes(), h_offs[PAD:PAD + (n_ctgs + 1) * 8].copy().view(np.uint64),
+            h_ends[PAD + misalign:PAD + misalign + 2 * n_ctgs * 16].copy().view(M.LASSM_END_DTYPE), stats_dict(st) if want_stats else None, n)
+
+
+def same(got, want):
+    block, offsets, ends, st = want
+    assert got[3] == st
+    if got[2].tobytes() != ends.tobytes():
+        diff = [e for e in range(len(ends)) if got[2][e].tobytes() != ends[e].tobytes()]
+        assert not diff, (diff[:5], got[2][diff[:5]], ends[diff[:5]])
+    assert (got[1] == offsets).all()
+    assert got[0] == block, [(i, a, b) for i, (a, b) in enumerate(zip(LC.new_contigs(got[0], offsets), LC.new_contigs(block, offsets))) if a != b][:3]
+    assert got[4] == len(block)
+
+
+def compare(c, k=21, kc=None, **params):
+    alns, pairs, quals = c.arrays()
+    want = M.local_assm(c.contigs, c.reads, quals, alns, pairs, c.means, k=k, **params)
+    if kc is None:
+        with indexed(c.contigs, k) as own:
+            same(device_lassm(own, c, total=len(want[0]), **params), want)
+    else:
+        same(device_lassm(kc, c, total=len(want[0]), **params), want)
+    return want
+
+
+def right(want, u=0):
+    e = want[2][2 * u + 1]
+    return int(e["ext_len"]), int(e["status"]), int(e["iters"]), int(e["mer_len"])
+
+
+# ---- the walk's rules -------------------------------------------------------------------------------------------------
+def test_prototype_cases():
+    c, G = LC.overhang_case(2)
+    assert right(compare(c)) == (100, M.DEAD_END, 2, 13)
+    assert right(compare(LC.overhang_case(1)[0])) == (0, M.DEAD_END, 2, 13)
+    assert right(compare(LC.haplotype_case()[0], max_mer_len=61)) == (50, M.FORK, 6, 61)
+    assert right(compare(LC.repeat_case(25)[0], max_mer_len=61)) == (60, M.DEAD_END, 2, 29)  # resolved upward; the direction lock
+    assert right(compare(LC.repeat_case(70)[0], max_mer_len=61)) == (0, M.FORK, 6, 61)
+    assert right(compare(LC.overhang_case(2, start=185, stop=285)[0])) == (85, M.DEAD_END, 2, 13)  # rescued downward
+    assert right(compare(LC.tandem_case()[0])) == (30, M.LOOP, 1, 21)
+    for w, want in ((1, (1, M.MAX_LEN, 1, 21)), (99, (99, M.MAX_LEN, 1, 21)), (100, (100, M.MAX_LEN, 1, 21)), (101, (100, M.DEAD_END, 2, 13))):
+        assert right(compare(c, max_walk_len=w)) == want
+
+
+@pytest.mark.parametrize("n", [0, 1, 63, 64, 65])
+def test_candidate_counts_around_a_wave(n):
+    G = LC.genome(1, 400)
+    c = LC.Case([G[:200]])
+    for i in range(n):
+        c.pair(G[150 + i % 7:260 + i % 5], 0, 150 + i % 7)
+    if not n:
+        c.pair(G[10:110], 0, 10)
+    want = compare(c)
+    assert int(want[2][1]["cands"]) == n and int(want[2][1]["status"]) == (M.DEAD_END if n else M.NO_CANDS)
+    assert (int(want[2][1]["ext_len"]) > 50) == (n >= 63)
+
+
+def test_a_deep_end_with_errors():
+    """1500 candidates of 100 bases with substitutions, N and low qualities over one end: a table of 2^19 slots, most mers
+    counted many times, the errors' mers once"""
+    rng = np.random.default_rng(11)
+    G = LC.genome(11, 700)
+    c = LC.Case([G[:300]])
+    for i in range(1500):
+        s = int(rng.integers(201, 400))
+        t = list(G[s:s + 100])
+        for x in np.nonzero(rng.random(100) < 0.02)[0]:
+            t[x] = "ACGTN"[int(rng.integers(0, 5))]
+        q = "".join(chr(33 + int(v)) for v in rng.choice([5, 12, 30], size=100, p=[0.05, 0.15, 0.8]))
+        if s < 300:
+            c.pair("".join(t), 0, s, orient=i & 1, qual=q)
+        else:  # beyond the contig: the unplaced mate of a read inside it
+            c.pair(G[150:250], 0, 150, mate=revcomp("".join(t)), mate_qual=q[::-1])
+    c.means = [300]  # thr = 60
+    want = compare(c, max_walk_len=150)
+    assert right(want)[:2] == (150, M.MAX_LEN) and int(want[2][1]["cands"]) == 1500
+    assert LC.new_contigs(want[0], want[1]) == [G[:450]]
+
+
+def test_max_cands_at_the_count_and_one_under():
+    c, G = LC.overhang_case(5)
+    assert int(compare(c, max_cands=5)[2][1]["status"]) == M.DEAD_END
+    assert tuple(compare(c, max_cands=4)[2][1]) == (5, 0, 200, 0, 0, M.TOO_MANY)
+
+
+@pytest.mark.parametrize("m", [4, 63, 64, 65, 127, 128])
+def test_mer_lengths(m):
+    G = LC.genome(m, 1500)
+    c = LC.Case([G[:300]])
+    for n in (m, m + 1):  # reads too short for a window, and with exactly one
+        c.pair(G[300 - n + 1:301], 0, 300 - n + 1)
+        c.pair(G[300 - n + 1:301], 0, 300 - n + 1)
+    c.pair(G[100:200], 0, 100, mate="A")  # a candidate of one base: the unplaced mate
+    for _ in range(2):
+        c.pair(G[140:1164], 0, 140)  # 1024 bases
+    want = compare(c, k=63 if m == 63 else 21, min_mer_len=m, max_mer_len=m, shift=64, max_walk_len=900)
+    assert right(want)[1:] == (M.DEAD_END if m > 4 else right(want)[1], 1, m) and (m == 4 or right(want)[0] == 864)
+
+
+def test_shift_one_and_shift_sixty_four():
+    c, _ = LC.repeat_case(25)
+    assert right(compare(c, shift=1, max_mer_len=40)) == (60, M.DEAD_END, 6, 26)
+    assert right(compare(c, shift=64, min_mer_len=4, max_mer_len=128)) == (0, M.DEAD_END, 2, 85)  # the reads hold 30 bases in front of the repeat
+    c, _ = LC.overhang_case(2, start=185, stop=285)
+    assert right(compare(c, k=77, shift=64, min_mer_len=13)) == (85, M.DEAD_END, 2, 13)
+
+
+def test_n_and_lower_case_in_reads_and_contig():
+    c, G = LC.overhang_case(3)
+    c.reads[0] = c.reads[0][:60] + "N" + c.reads[0][61:]
+    c.reads[2] = c.reads[2][:75].lower() + "n" + c.reads[2][76:90] + c.reads[2][90:].lower()
+    assert right(compare(c))[0] == 100
+    c, G = LC.overhang_case(2)
+    c.reads[0] = c.reads[0][:60] + "N" + c.reads[0][61:]  # the N as the extension base
+    assert right(compare(c))[0] == 20
+    for at, want in ((190, 0), (185, 100), (199, 0), (100, 100)):
+        c, G = LC.overhang_case(2)
+        c.contigs[0] = G[:at] + "N" + G[at + 1:200]
+        assert right(compare(c))[0] == want, at
+
+
+@pytest.mark.parametrize("n", [0, 1, 12, 120, 121, 122])
+def test_contig_lengths_around_the_tail(n):
+    G = LC.genome(1, 600)
+    c = LC.Case([G[200:200 + n], G[400:600]])
+    for _ in range(2):
+        if n:
+            c.pair(G[100:300 + n], 0, -100)
+        c.pair(G[350:450], 1, -50, orient=1)
+    want = compare(c, max_walk_len=50)
+    if n >= 21:
+        assert [int(e["ext_len"]) for e in want[2]] == [50, 50, 50, 0]
+
+
+@pytest.mark.parametrize("quals", [True, False])
+def test_qualities_at_their_boundaries(quals):
+    for q0, q1, ext in ((20, 10, 100), (19, 19, 0), (20, 9, 0), (19, 20, 100), (10, 10, 0), (9, 9, 0)):
+        G = LC.genome(1, 350)
+        c = LC.Case([G[:200]])
+        for q in (q0, q1):
+            c.pair(G[160:300], 0, 160, orient=q & 1, qual=("I" * 40 + chr(33 + q) + "I" * 99) if quals else None)
+        assert right(compare(c))[0] == (ext if quals else 100)
+
+
+def test_the_quality_offset_is_the_contexts():
+    c, G = LC.overhang_case(2, qual="5" * 140)  # '5' is 10 over an offset of 43 (lo + lo) and 20 over 33 (hi + hi)
+    alns, pairs, quals = c.arrays()
+    for offset, ext in ((43, 0), (33, 100)):
+        want = M.local_assm(c.contigs, c.reads, quals, alns, pairs, None, k=21, qual_offset=offset)
+        with indexed(c.contigs, qual_offset=offset) as kc:
+            same(device_lassm(kc, c, total=len(want[0])), want)
+        assert right(want)[0] == ext
+
+
+def test_support_at_the_threshold_with_and_without_depths():
+    for copies, mean, ext in ((4, 25, 0), (5, 25, 100), (4, 24, 100), (2, None, 100), (2, 14, 100), (2, 15, 0)):
+        c, G = LC.overhang_case(copies)
+        c.means = None if mean is None else [mean]
+        assert right(compare(c))[0] == ext
+    c, G = LC.overhang_case(2)
+    assert right(compare(c, min_viable=3))[0] == 0
+    c.means = [0xFFFFFFFF]
+    assert right(compare(c, viable_permille=1000))[0] == 0
+
+
+@pytest.mark.parametrize("seed", [1, 2, 3, 4])
+def test_random_ends_and_the_mirror_property(seed):
+    c = LC.random_case(seed, pairs=100)
+    kw = dict(k=15, min_mer_len=7, max_walk_len=60, max_insert=300)
+    want = compare(c, **kw)
+    assert want[3]["ext_bases"] > 0 and want[3]["cands_mate"] > 0
+    m = c.mirrored()
+    mwant = compare(m, **kw)
+    assert LC.new_contigs(mwant[0], mwant[1]) == [revcomp(s) for s in LC.new_contigs(want[0], want[1])]
+
+
+def test_shuffled_records_and_renumbered_pairs_give_the_same_block():
+    c = LC.random_case(5, pairs=80)
+    kw = dict(k=15, min_mer_len=7, max_walk_len=60, max_insert=300)
+    want = compare(c, **kw)
+    rng = np.random.default_rng(5)
+    order = rng.permutation(len(c.reads) // 2)
+    s = LC.Case(c.contigs)
+    s.means = c.means
+    new_id = {}
+    for p in order:
+        for side in (0, 1):
+            new_id[2 * int(p) + side] = s.read(c.reads[2 * p + side], c.quals[2 * p + side])
+    rows = [(new_id[r[0]],) + tuple(r[1:]) for r in c.rows]
+    s.rows = [rows[i] for i in rng.permutation(len(rows))]
+    got = compare(s, **kw)
+    assert got[0] == want[0] and got[2].tobytes() == want[2].tobytes() and got[3] == want[3]
+
+
+def many_contigs():
+    rng = np.random.default_rng(9)
+    G = LC.genome(9, 900000)
+    cuts, at = [], 100
+    for u in range(5001):
+        n = 300020 if u == 2500 else int(rng.integers(25, 61))
+        cuts.append((at, at + n))
+        at += n + 70
+    c = LC.Case([G[a:b] for a, b in cuts])
+    both = set(rng.choice(5001, size=900, replace=False).tolist()) | {2500}
+    for u, (a, b) in enumerate(cuts):  # every contig has two candidates at its right end, 901 of them at the left end too
+        for _ in range(2):
+            c.pair(G[b - 22:b + 18], u, b - a - 22)
+            if u in both:
+                c.pair(G[a - 15:a + 23], u, -15, orient=1)
+    return c, 5001 + len(both)
+
+
+def test_many_short_contigs_around_a_long_one_and_the_table_budget():
+    c, n_walked = many_contigs()
+    arrays = host_arrays(c)
+    want = M.local_assm(c.contigs, c.reads, None, arrays[3], arrays[4], None, k=21, max_walk_len=12)
+    assert want[3]["ext_bases"] == 12 * n_walked and want[3]["status"][M.MAX_LEN] == n_walked and want[3]["ctgs_extended"] == 5001
+    # a table of an end here has 256 slots of 40 bytes: 1 MB holds 102 of the ends that walk, so the budget forces batches
+    with indexed(c.contigs, time_kernels=True) as kc:
+        for budget, walks in ((0, 1), (1, None)):
+            kc.kernel_times(clear=True)
+            same(device_lassm(kc, c, total=len(want[0]), arrays=arrays, max_walk_len=12, table_budget_mb=budget), want)
+            times = {n: v[0] for n, v in kc.kernel_times(clear=True).items() if "lassm" in n}
+            if walks is None:
+                assert times["kc_lassm_walk_kernel"] >= 3
+                walks = times["kc_lassm_walk_kernel"]
+            assert times == {"kc_align_lengths_kernel<lassm>": 1, "kc_depth_check_kernel<lassm>": 1, "kc_lassm_pair_check_kernel": 1,
+                             "kc_lassm_cands_kernel<count>": 1, "kc_lassm_plan_kernel": 1, "kc_lassm_scan_kernel": 3,
+                             "kc_lassm_cands_kernel<write>": 1, "kc_lassm_text_kernel": 1, "kc_lassm_walk_kernel": walks,
+                             "kc_lassm_lens_kernel": 1, "kc_lassm_ends_kernel": 1, "kc_lassm_write_kernel": 1}, (budget, times)
+
+
+# ---- the protocol -----------------------------------------------------------------------------------------------------
+def test_capacity_size_query_and_optional_outputs():
+    c = LC.random_case(6, pairs=60)
+    kw = dict(k=15, min_mer_len=7, max_walk_len=60, max_insert=300)
+    alns, pairs, quals = c.arrays()
+    want = M.local_assm(c.contigs, c.reads, quals, alns, pairs, c.means, **kw)
+    total = len(want[0])
+    par = {x: kw[x] for x in kw if x != "k"}
+    with indexed(c.contigs, 15) as kc:
+        same(device_lassm(kc, c, total=total, **par), want)
+        same(device_lassm(kc, c, total=total, capacity=total + 5, **par), want)
+        got = device_lassm(kc, c, total=total, capacity=total - 1, expect=_lib.KC_ERR_CAPACITY, **par)
+        assert got[3] == want[3] and got[4] == total
+        assert str(total).encode() in pkg.lib().kc_last_error()
+        got = device_lassm(kc, c, total=total, seqs_null=True, **par)
+        assert got[3] == want[3] and got[4] == total
+        for off in ("want_offsets", "want_ends", "want_stats"):
+            got = device_lassm(kc, c, total=total, **dict(par, **{off: False}))
+            assert got[0] == want[0] and got[4] == total
+        # host arrays, and the wrapper in both modes
+        b, q, o, a, p, ctgs = host_arrays(c)
+        seqs, offs, ends, st = kc.local_assm(b, q, o, a, p, ctgs, **par)
+        assert isinstance(seqs, np.ndarray) and seqs.tobytes() == want[0] and (offs == want[1]).all() and ends.tobytes() == want[2].tobytes()
+        assert st == want[3] and ends.dtype == kcount.LASSM_END_DTYPE
+        import torch
+        t = [None if x is None else torch.from_numpy(np.frombuffer(x.tobytes(), dtype=np.uint8).copy()).cuda() for x in (b, q, a, p, ctgs)]
+        to = torch.from_numpy(o.view(np.int64)).cuda()
+        seqs, offs, ends, st = kc.local_assm(t[0], t[1], to, t[2], t[3], t[4], **par)
+        assert seqs.is_cuda and offs.is_cuda and ends.is_cuda and offs.dtype == torch.int64
+        assert seqs.cpu().numpy().tobytes() == want[0] and (offs.cpu().numpy().view(np.uint64) == want[1]).all()
+        assert ends.cpu().numpy().tobytes() == want[2].tobytes() and st == want[3]
+        seqs, offs, ends, st = kc.local_assm(b, None, o, a, p, None, **par)
+        assert seqs.tobytes() == M.local_assm(c.contigs, c.reads, None, alns, pairs, None, **kw)[0]
+
+
+def test_the_wrapper_calls_once_more_when_a_quarter_is_not_enough():
+    G = LC.genome(1, 400)
+    c = LC.Case([G[100:130]])
+    for _ in range(2):
+        c.pair(G[105:230], 0, 5)
+        c.pair(G[0:125], 0, -100)
+    want = c.model()
+    assert len(want[0]) > 31 + 31 // 4
+    with indexed(c.contigs) as kc:
+        b, q, o, a, p, _ = host_arrays(c)
+        seqs, offs, ends, st = kc.local_assm(b, q, o, a, p)
+        assert seqs.tobytes() == want[0] == G[:230].encode() + b"_" and st == want[3]
+
+
+def test_invalid_pairs_reads_and_alignment():
+    c = LC.random_case(7, pairs=40)
+    alns, pairs, quals = c.arrays()
+    placed = [i for i in range(len(pairs)) if pairs[i]["aln0"] != D.NO_ALN and pairs[i]["aln1"] != D.NO_ALN]
+    i, j = placed[1], placed[-1]
+    par = dict(min_mer_len=7, max_walk_len=60)
+
+    def refused(kc, pr=pairs, al=alns, text=None, **kw):
+        arrays = host_arrays(c)
+        arrays = arrays[:3] + (al, pr) + arrays[5:]
+        assert device_lassm(kc, c, expect=_lib.KC_ERR_INVALID_ARG, arrays=arrays, **dict(par, **kw)) == _lib.KC_ERR_INVALID_ARG
+        if text:
+            assert text in pkg.lib().kc_last_error(), pkg.lib().kc_last_error()
+
+    with indexed(c.contigs, 15) as kc:
+        # an index at and far over the records' number, the mate's record, the other read's record
+        for field, value_of in (("aln0", lambda x: len(alns)), ("aln1", lambda x: 0xFFFFFFFE), ("aln0", lambda x: int(pairs[x]["aln1"])),
+                                ("aln1", lambda x: int(pairs[x]["aln0"]))):
+            for at in ((j,), (i,), (j, i)):
+                p = pairs.copy()
+                for x in at:
+                    p[x][field] = value_of(x)
+                refused(kc, pr=p, text=b"kc_local_assm: pair %d " % min(at))
+        a = alns.copy()
+        a[int(pairs[j]["aln1"])]["kind"] = M.KIND_NONE
+        refused(kc, al=a, text=b"kc_local_assm: pair %d " % j)
+        a[int(pairs[i]["aln0"])]["kind"] = M.KIND_NONE
+        refused(kc, al=a, text=b"kc_local_assm: pair %d " % i)
+        a = alns.copy()
+        a[3]["ctg"] = len(c.contigs)
+        refused(kc, al=a, text=b"kc_local_assm: record 3 ")
+        assert device_lassm(kc, c, expect=_lib.KC_ERR_INVALID_ARG, misalign=8, **par) == _lib.KC_ERR_INVALID_ARG
+        assert b"16-byte aligned" in pkg.lib().kc_last_error()
+        assert device_lassm(kc, c, expect=_lib.KC_ERR_INVALID_ARG, nreads=len(c.reads) - 1, **par) == _lib.KC_ERR_INVALID_ARG
+        assert b"reads are no pairs" in pkg.lib().kc_last_error()
+    long_c = LC.Case([LC.genome(1, 100)])
+    long_c.pair("A" * 100, 0, 50)
+    long_c.pair("C" * 1024, 0, 50, mate="G" * 1024)
+    with indexed(long_c.contigs) as kc:
+        arrays = host_arrays(long_c)
+        long_c.reads[3] = LC.genome(2, 1025)  # one base more than the records and the model's pairs were made for
+        arrays = read_arrays(long_c.reads)[:1] + (None,) + read_arrays(long_c.reads)[1:] + arrays[3:]
+        assert device_lassm(kc, long_c, expect=_lib.KC_ERR_INVALID_ARG, arrays=arrays) == _lib.KC_ERR_INVALID_ARG
+        assert b"kc_local_assm: read 3 is longer than 1024" in pkg.lib().kc_last_error()
+
+
+def test_index_states_and_ranks():
+    c = LC.random_case(8, pairs=40)
+    kw = dict(k=15, min_mer_len=7, max_walk_len=60, max_insert=300)
+    par = {x: kw[x] for x in kw if x != "k"}
+    with pkg.KmerCounter(15) as kc:
+        assert device_lassm(kc, c, expect=_lib.KC_ERR_STATE, **par) == _lib.KC_ERR_STATE
+        assert b"kc_local_assm: no contig index" in pkg.lib().kc_last_error()
+        kc.index_contigs(*block_arrays(c.contigs))
+        want = compare(c, kc=kc, **kw)
+        kc.clear_contig_index()
+        assert device_lassm(kc, c, expect=_lib.KC_ERR_STATE, **par) == _lib.KC_ERR_STATE
+        kc.index_contigs(*block_arrays(c.contigs))
+        compare(c, kc=kc, **kw)
+    with indexed(c.contigs, 15, rank_me=1, rank_n=2) as kc:
+        same(device_lassm(kc, c, total=len(want[0]), **par), want)
+    none = LC.Case(c.contigs)  # no reads at all: the block comes back as it is
+    with indexed(c.contigs, 15) as kc:
+        got = device_lassm(kc, none, total=sum(len(s) + 1 for s in c.contigs))
+        assert got[0] == block_arrays(c.contigs)[0].tobytes() and got[3]["status"] == [2 * len(c.contigs), 0, 0, 0, 0, 0]
+
+
+# ---- through the device's own steps -----------------------------------------------------------------------------------
+def test_after_the_devices_own_alignment_steps():
+    rng = np.random.default_rng(42)
+    G = LC.genome(42, 3000)
+    contigs = [G[1000:2000], G[2300:2700]]
+    reads = []
+    for rep in range(4):  # 300-base fragments tiling G at depth 4: a pair covers 200 of them, so steps of 100 / 2
+        for a in range(rep * 12, len(G) - 300, 50):
+            f = G[a:a + 300]
+            pair = [f[:100], revcomp(f[-100:])]
+            reads += pair[::-1] if (a // 50 + rep) & 1 else pair
+    b, o = read_arrays(reads)
+    with indexed(contigs) as kc:
+        kc.submit_reads(b, np.full(len(b), ord("I"), dtype=np.uint8), o)
+        res_before = [np.array(x) for x in kc.sorted_results()]
+        looked = [np.array(x) for x in kc.lookup(res_before[0][:50])]
+        kc.index_contigs(*block_arrays(contigs))
+        alns, first, _ = kc.align_reads(b, o)
+        gaps, _ = kc.align_gapped(b, o, alns)
+        hist, pairs, ist = kc.pair_inserts(o, gaps)
+        depths, ctgs, _ = kc.aln_depths(gaps)
+        seqs, offs, ends, st = kc.local_assm(b, None, o, gaps, pairs, ctgs)
+        want = M.local_assm(contigs, reads, None, gaps, pairs, [int(x) for x in ctgs["mean"]], k=21)
+        assert seqs.tobytes() == want[0] and (offs == want[1]).all() and ends.tobytes() == want[2].tobytes() and st == want[3]
+        new = LC.new_contigs(seqs, offs)
+        for old, ext, e in zip(contigs, new, (0, 2)):
+            assert ext in G and int(ends[e]["ext_len"]) > 0 and int(ends[e + 1]["ext_len"]) > 0
+            at = ext.index(old)
+            assert at == int(ends[e]["ext_len"]) and len(ext) == at + len(old) + int(ends[e + 1]["ext_len"])
+        # the earlier calls answer as before, and the new block is taken as it is
+        alns2, first2, _ = kc.align_reads(b, o)
+        assert alns2.tobytes() == alns.tobytes() and (first2 == first).all()
+        assert kc.pair_inserts(o, gaps)[1].tobytes() == pairs.tobytes()
+        assert all((x == np.array(y)).all() for x, y in zip(res_before, kc.sorted_results()))
+        assert all((x == np.array(y)).all() for x, y in zip(looked, kc.lookup(res_before[0][:50])))
+        ix = kc.index_contigs(seqs, offs)
+        assert ix["contigs"] == 2 and ix["bases"] == len(seqs) - 2
+        import torch
+        with pkg.KmerCounter(21) as kc2:
+            kc2.begin_ctg_kmers(len(seqs))
+            depths = torch.ones(len(seqs), dtype=torch.int16, device="cuda")
+            torch.cuda.synchronize()
+            kc2.submit_ctg_block(torch.from_numpy(seqs.copy()).cuda(), depths)
