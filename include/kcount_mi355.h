@@ -867,6 +867,89 @@ int kc_local_assm(kc_ctx *ctx, const uint8_t *bases, const uint8_t *quals, const
                   const kc_gap_aln *alns, uint64_t n_alns, const kc_pair_rec *pairs, const kc_ctg_depth *ctgs, int on_device,
                   const kc_lassm_params *params, uint8_t *seqs_out, uint64_t capacity, uint64_t *offsets_out,
                   kc_lassm_end *ends, uint64_t *nbytes_out, kc_lassm_stats *stats);
+/*
+ * Links between contig ends from the alignments: the first half of scaffolding, the adjacency list of the contig graph.
+ * The reference holds no code for it (no cgraph, no Alns, no scaffolding in src/), so the rules below are THIS project's
+ * own definition (pinned by the host model tests/links_model.py); no parity with MetaHipMer is
+ * claimed.  All quantities are integers (signed 64-bit where they are compared); the output is one exact byte string for a
+ * given input, whatever order the records come in and whatever order the waves or the atomics arrive in.
+ *
+ * Input.  The reads' nreads + 1 offsets (no bases are needed; reads 2p and 2p + 1 are mates, an odd nreads is
+ * KC_ERR_INVALID_ARG; a read over KC_ALIGN_MAX_READ_LEN is refused as in kc_align_gapped), kc_align_gapped's records alns
+ * in ANY order, and kc_pair_inserts' nreads / 2 records pairs (NULL: there are no spans); the contigs are the kept
+ * index's.  alns are valid by the rule above, with read < nreads and rstop <= L(read); a pairs record is valid by
+ * kc_local_assm's rule (cls and insert are not read).  An invalid read, record or pair -- checked in this order -- is
+ * KC_ERR_INVALID_ARG and kc_last_error names the lowest bad index; validation is a pass of its own in front of the first
+ * store.  A record PASSES iff it passes the filter above with params->min_score and params->min_len.
+ *
+ * Ends.  End 2u is the left end of contig u, end 2u + 1 its right end, as in kc_local_assm.
+ *
+ * Splints.  A passing record a of read r (length L) covers [qs, qe) of the read in the read's own direction:
+ * [rstart, rstop) for orient 0, [L - rstop, L - rstart) for orient 1.  With u = a.ctg, a LEAVES u through end 2u + 1 with
+ * e = len_u - cstop iff orient is 0 and e <= end_slack, and through end 2u with e = cstart iff orient is 1 and
+ * e <= end_slack; it ENTERS u through end 2u with e = cstart iff orient is 0 and e <= end_slack, and through end 2u + 1
+ * with e = len_u - cstop iff orient is 1 and e <= end_slack.  Every ordered pair (a, b) of passing records of one read
+ * with a.ctg != b.ctg, qs_a < qs_b, qe_a < qe_b, a leaving and b entering has gap = (qs_b - qe_a) - e_a - e_b and is a
+ * splint candidate between a's leaving end and b's entering end iff -max_overlap <= gap <= max_splint_gap (otherwise it
+ * counts in splints_gap_out).  A read with more than max_read_alns passing records gives no splints and counts in
+ * reads_over_cap.  The rule is over all ordered pairs, so it does not depend on the records' order, and the reverse
+ * complement of a read gives the same candidates.
+ *
+ * Spans.  Pair p gives a candidate iff pairs is given, both aln0 and aln1 are present and their contigs differ.  A mate
+ * with record b and length L points out of its contig u through end 2u + 1 with d = len_u - (b.cstart - b.rstart) for
+ * orient 0, and through end 2u with d = b.cstop + (L - b.rstop) for orient 1.  The pair is a span candidate between the two
+ * ends with gap = insert_avg - d0 - d1 iff d0 + d1 <= max_insert; otherwise it counts in spans_too_far.  The filter does
+ * not apply to the pairs' records: they were chosen by kc_pair_inserts.
+ *
+ * Links.  Candidates with the same unordered pair of ends are one link.  A link appears TWICE in links, once in each
+ * direction (from, to) and (to, from), with the same figures; links is ordered by (from, to) ascending: the adjacency
+ * list of the ends.  The fields of a kind (splint / span) with count 0 are 0; the sums are exact.  end_first (may be
+ * NULL): 2 n_ctgs + 1 entries, the index of every end's first record and then the total.  *n_links (required): the
+ * number of directed records.  stats (may be NULL): reads = nreads; records = none + filtered + passed;
+ * links (undirected) = links_splint_only + links_span_only + links_both; ends_linked = the ends with a record.
+ *
+ * Protocol.  The parameter ranges (see kc_link_params) and an odd nreads are checked in front of ctx and kc_last_error
+ * names the values.  on_device applies to all arrays alike; device record arrays (alns, pairs, links) are 16-byte
+ * aligned, device offsets and end_first 8-byte.  No index: KC_ERR_STATE.  2^32 records or more, or 2^31 candidates or
+ * more: KC_ERR_CAPACITY.  links == NULL is a size query: KC_OK, *n_links and *stats are written and nothing else; a
+ * non-NULL links with capacity (in records) below *n_links is KC_ERR_CAPACITY, with *n_links and *stats written and
+ * nothing else.  On every other error nothing is written through any pointer.  n_alns == 0: KC_OK, no records and an
+ * all-zero end_first.  The call works before or after kc_finalize and with rank_n > 1, touches neither the index, the
+ * table nor the results, runs on the context's stream and returns when done; scratch lives for the call only: 20 bytes
+ * a read, 8 a pair, 16 a passing record, 52 a candidate (each is sorted once in either direction) and 48 a directed
+ * record, beside the inputs' copies and the outputs' staging for host arrays.
+ */
+typedef struct kc_link_params {
+  uint32_t min_score, min_len; /* the filter */
+  uint32_t end_slack;          /* <= KC_LINK_MAX_SLACK: how far from a contig's end an alignment may stop and still reach it */
+  uint32_t max_overlap;        /* <= KC_LINK_MAX_OVERLAP: a splint gap of -max_overlap .. max_splint_gap is kept */
+  uint32_t max_splint_gap;     /* <= KC_LINK_MAX_SLACK */
+  uint32_t insert_avg;         /* 1 <= insert_avg <= max_insert <= KC_INSERT_MAX: a span's gap is insert_avg - d0 - d1 */
+  uint32_t max_insert;
+  uint16_t max_read_alns;      /* 2 .. KC_LINK_MAX_READ_ALNS passing records a read */
+  uint16_t flags;              /* 0 */
+} kc_link_params;              /* 32 bytes */
+#define KC_LINK_MAX_SLACK 1024
+#define KC_LINK_MAX_OVERLAP 65535
+#define KC_LINK_MAX_READ_ALNS 64
+typedef struct kc_ctg_link { /* 48 bytes */
+  uint32_t from, to;         /* ends */
+  uint32_t splints, spans;   /* supporting candidates of either kind */
+  int32_t splint_gap_min, splint_gap_max, span_gap_min, span_gap_max;
+  int64_t splint_gap_sum, span_gap_sum;
+} kc_ctg_link;
+typedef struct kc_link_stats {
+  uint64_t reads, reads_over_cap;
+  uint64_t records, none, filtered, passed;
+  uint64_t splint_cands, splints_gap_out;
+  uint64_t span_cands, spans_too_far;
+  uint64_t links, links_splint_only, links_span_only, links_both;
+  uint64_t ends_linked;
+  uint64_t reserved; /* zero: 128 bytes in all */
+} kc_link_stats;
+int kc_ctg_links(kc_ctx *ctx, const uint64_t *offsets, uint64_t nreads, const kc_gap_aln *alns, uint64_t n_alns, const kc_pair_rec *pairs,
+                 int on_device, const kc_link_params *params, kc_ctg_link *links, uint64_t capacity, uint64_t *end_first,
+                 uint64_t *n_links, kc_link_stats *stats);
 /* KmerDHT::kmer_exists / get_kmer_count / get_local_kmer_counts (src/kcount/kmer_dht.cpp:198-245) in bulk, against the
  * results kept in HBM: nq k-mers of num_longs words each, in either orientation; counts[i] = 0 (and left/right = 0)
  * when the k-mer did not survive.  The index over the results is built on the first call after kc_finalize.

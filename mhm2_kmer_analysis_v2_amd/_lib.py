@@ -155,6 +155,27 @@ KC_LASSM_MAX_WALK = 4096
 KC_LASSM_MAX_CANDS = 1 << 20
 KC_LASSM_NO_CANDS, KC_LASSM_TOO_MANY, KC_LASSM_DEAD_END, KC_LASSM_FORK, KC_LASSM_LOOP, KC_LASSM_MAX_LEN = range(6)
 
+
+class kc_link_params(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("min_score", "min_len", "end_slack", "max_overlap", "max_splint_gap", "insert_avg", "max_insert")] + [
+        ("max_read_alns", C.c_uint16), ("flags", C.c_uint16)]
+
+
+class kc_ctg_link(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("from_", "to", "splints", "spans")] + [(n, C.c_int32) for n in (
+        "splint_gap_min", "splint_gap_max", "span_gap_min", "span_gap_max")] + [("splint_gap_sum", C.c_int64), ("span_gap_sum", C.c_int64)]
+
+
+class kc_link_stats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("reads", "reads_over_cap", "records", "none", "filtered", "passed", "splint_cands", "splints_gap_out",
+                                          "span_cands", "spans_too_far", "links", "links_splint_only", "links_span_only", "links_both",
+                                          "ends_linked", "reserved")]
+
+
+KC_LINK_MAX_SLACK = 1024
+KC_LINK_MAX_OVERLAP = 65535
+KC_LINK_MAX_READ_ALNS = 64
+
 # every symbol include/kcount_mi355.h declares: (restype, argtypes)
 SYMBOLS = {
     "kc_abi_version": (C.c_int, []),
@@ -232,6 +253,8 @@ SYMBOLS = {
     "kc_local_assm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                  C.c_int, C.POINTER(kc_lassm_params), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64),
                                  C.POINTER(kc_lassm_stats)]),
+    "kc_ctg_links": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int, C.POINTER(kc_link_params), C.c_void_p,
+                                C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(kc_link_stats)]),
     "kc_lookup": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "kc_dump_table": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
     "kc_get_stats": (C.c_int, [C.c_void_p, C.POINTER(kc_stats)]),

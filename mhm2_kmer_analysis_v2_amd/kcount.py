@@ -21,7 +21,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (check, kc_align_stats, kc_aln_scores, kc_config, kc_ctg_index_stats, kc_depth_stats, kc_gap_stats, kc_insert_stats, kc_kernel_time, kc_lassm_params, kc_lassm_stats, kc_merge_stats, kc_result, kc_stats, kc_synth_params, kc_trim_stats, kc_tuning,
+from ._lib import (check, kc_align_stats, kc_aln_scores, kc_config, kc_ctg_index_stats, kc_depth_stats, kc_gap_stats, kc_insert_stats, kc_kernel_time, kc_lassm_params, kc_lassm_stats, kc_link_params, kc_link_stats, kc_merge_stats, kc_result, kc_stats, kc_synth_params, kc_trim_stats, kc_tuning,
                    kc_unitig_stats, lib)
 
 
@@ -804,6 +804,59 @@ class KmerCounter:
         out["status"] = [int(x) for x in st.status]
         return seqs[:int(nb.value)], offs_out, ends, out
 
+    def ctg_links(self, offsets, gap_alns, pairs=None, insert_avg=300, max_insert=1000, min_score=0, min_len=0, end_slack=5, max_overlap=200,
+                  max_splint_gap=100, max_read_alns=8):
+        """The links between the ends of the indexed contigs (kc_ctg_links): splints from reads
+        aligned across two contigs, spans from pairs whose mates' best records lie on different contigs.  offsets: the
+        reads' (2p and 2p + 1 are mates); gap_alns align_gapped's records in any order; pairs pair_inserts' records
+        (None: no spans); insert_avg the insert size a span's gap is measured against.  Returns (links, end_first, stats,
+        gap): every link once in each direction, ordered by (from, to) -- LINK_DTYPE records for host arrays, a uint8
+        device tensor of 48-byte records for device tensors -- end_first the index of every end's first record and the
+        total (uint64 array / int64 tensor; end 2u is the left end of contig u, 2u + 1 its right end), kc_link_stats as a
+        dict, and gap a float64 numpy column: a link's mean splint gap where it has splints, else its mean span gap.  The
+        records are allocated at four a contig; if that is too few the call is made once more with the number it reported."""
+        pa, n_alns, dev_a = self._gap_records(gap_alns)
+        po, dev = _ptr(offsets)
+        nreads = len(offsets) - 1
+        pp, dev_p = _ptr(pairs)
+        npairs = 0 if pairs is None else (pairs.numel() // 16 if dev_p else len(pairs))
+        if (n_alns and dev_a != dev) or (npairs and dev_p != dev):
+            raise ValueError("offsets, gap_alns and pairs must all be host arrays or all be device tensors")
+        if pairs is not None and (npairs != nreads // 2 or (not dev and npairs and (pairs.dtype.itemsize != 16 or not pairs.flags["C_CONTIGUOUS"]))):
+            raise ValueError("pairs: a contiguous array of nreads / 2 16-byte records (PAIR_DTYPE)")
+        _, n_ctgs = self.contig_index_info()
+        prm = kc_link_params(min_score, min_len, end_slack, max_overlap, max_splint_gap, insert_avg, max_insert, max_read_alns, 0)
+        st, n = kc_link_stats(), C.c_uint64(0)
+        pp = pp if npairs else None
+        if dev:
+            import torch
+            d = "cuda:%d" % self.device
+            end_first = torch.empty(2 * n_ctgs + 1, dtype=torch.int64, device=d)
+        else:
+            end_first = np.zeros(2 * n_ctgs + 1, dtype=np.uint64)
+        capacity = 4 * n_ctgs + 16  # two records an end: a chain of contigs and as much again
+        for attempt in (0, 1):
+            if dev:
+                links = torch.empty(max(capacity, 1) * 48, dtype=torch.uint8, device=d)
+                torch.cuda.current_stream(self.device).synchronize()  # the input and the fresh arrays are torch's until now
+                pl, pe = links.data_ptr(), end_first.data_ptr()
+            else:
+                links = np.zeros(max(capacity, 1), dtype=LINK_DTYPE)
+                pl, pe = links.ctypes.data, end_first.ctypes.data
+            rc = lib().kc_ctg_links(self._h, po, nreads, pa, n_alns, pp, 1 if dev else 0, C.byref(prm), pl, capacity, pe, C.byref(n), C.byref(st))
+            if rc != _lib.KC_ERR_CAPACITY or attempt or not capacity < n.value:
+                break
+            capacity = int(n.value)  # the size it was told
+        check(rc, "kc_ctg_links")
+        cap = int(n.value)
+        links = links[:cap * 48] if dev else links[:cap]
+        host = links.cpu().numpy().view(LINK_DTYPE) if dev else links
+        gap = np.zeros(cap, dtype=np.float64)
+        if cap:
+            s, m = host["splints"].astype(np.float64), host["spans"].astype(np.float64)
+            gap = np.where(s > 0, host["splint_gap_sum"] / np.maximum(s, 1), host["span_gap_sum"] / np.maximum(m, 1))
+        return links, end_first, {f: int(getattr(st, f)) for f, _ in kc_link_stats._fields_ if f != "reserved"}, gap
+
     def submit_ctg_block(self, seqs, depths):
         """kc_submit_ctg_block with device tensors (a '_'-joined block and one 16-bit depth per byte), e.g. those of
         unitig_block(); begin_ctg_kmers first."""
@@ -851,6 +904,8 @@ CTG_DEPTH_DTYPE = np.dtype([("depth_sum", "<u8"), ("len", "<u4"), ("covered", "<
 PAIR_DTYPE = np.dtype([("aln0", "<u4"), ("aln1", "<u4"), ("insert", "<u4"), ("cls", "u1"), ("pad", "u1", (3,))])
 # kc_local_assm's record of a contig end (kc_lassm_end, 16 bytes)
 LASSM_END_DTYPE = np.dtype([("cands", "<u4"), ("ext_len", "<u4"), ("out_pos", "<u4"), ("iters", "<u2"), ("mer_len", "u1"), ("status", "u1")])
+LINK_DTYPE = np.dtype([("from", "<u4"), ("to", "<u4"), ("splints", "<u4"), ("spans", "<u4"), ("splint_gap_min", "<i4"), ("splint_gap_max", "<i4"),
+                       ("span_gap_min", "<i4"), ("span_gap_max", "<i4"), ("splint_gap_sum", "<i8"), ("span_gap_sum", "<i8")])
 BLASTN_ALN_SCORES = (2, 3, 5, 2, 1)
 ALTERNATE_ALN_SCORES = (1, 1, 1, 1, 1)
 
