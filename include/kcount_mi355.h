@@ -950,6 +950,100 @@ typedef struct kc_link_stats {
 int kc_ctg_links(kc_ctx *ctx, const uint64_t *offsets, uint64_t nreads, const kc_gap_aln *alns, uint64_t n_alns, const kc_pair_rec *pairs,
                  int on_device, const kc_link_params *params, kc_ctg_link *links, uint64_t capacity, uint64_t *end_first,
                  uint64_t *n_links, kc_link_stats *stats);
+/*
+ * Scaffolds from the links: the walk over kc_ctg_links' adjacency list, the second half of scaffolding.  The reference
+ * holds no code for it (no cgraph, no scaffolding in src/; src/contigging.cpp stops before it), so the rules below are
+ * THIS project's own definition (pinned by the host model tests/scaffold_model.py); no parity with
+ * MetaHipMer is claimed.  All quantities are integers (signed 64-bit where they are compared); the output is one exact
+ * byte string for a given input.
+ *
+ * Input.  links: n_links kc_ctg_link records exactly as kc_ctg_links writes them; the contigs are the kept index's block
+ * (upper-case A C G T N, every contig followed by '_').  A record is VALID iff from and to are below 2 n_ctgs;
+ * from >> 1 != to >> 1; splints + spans >= 1; a kind with count 0 has all its fields 0; a kind with count c > 0 has
+ * -KC_LINK_MAX_OVERLAP <= min <= max <= KC_INSERT_MAX and c * min <= sum <= c * max; its key (from, to) is strictly above
+ * its predecessor's; and the binary search for the first record whose key is not below (to, from) finds that key with the
+ * same eight figures.  An invalid record is KC_ERR_INVALID_ARG and kc_last_error names the lowest bad index; validation is
+ * a pass of its own whose verdict is read before anything is stored.
+ *
+ * Ends and nodes.  End 2u is the left end of contig u, 2u + 1 its right end.  An oriented node is v = 2u + s: s = 0 reads
+ * the contig as it stands and is left through end 2u + 1, s = 1 reads its reverse complement (A<->T, C<->G, N stays) and
+ * is left through end 2u; twin(v) = v ^ 1.  A node is entered through the end that has its own number.
+ *
+ * Choosing.  A record QUALIFIES iff splints >= min_splints or spans >= min_spans; its support is splints + spans; its
+ * gap is the mean of the splint gaps if splints > 0, else of the span gaps, rounded half up: floor((2 sum + c) / (2 c)).
+ * best(e) is the qualifying record of end e's row with the greatest (support, splints), on a tie the smallest `to`;
+ * second(e) the greatest of the rest.  e is AMBIGUOUS iff second(e) exists and
+ * second.support * 1000 > best.support * max_second_permille.  The edge {e, f} is CHOSEN iff best(e).to = f,
+ * best(f).to = e and neither end is ambiguous.
+ *
+ * Verifying.  With A the text of the node left through e and B the text of the node entered through f: gap >= 0 gives
+ * join = gap.  gap < 0, o = -gap: o' is tried in the order o, o + 1, o - 1, o + 2, o - 2, ... up to overlap_slack away, only
+ * values with 1 <= o' < min(|A|, |B|); the first o' for which the last o' bytes of A equal the first o' bytes of B (a byte
+ * that is not A C G T never matches) gives join = -o'.  If none verifies the edge is dropped (overlaps_rejected).
+ *
+ * Walking.  next(v) is the node entered through the partner of the end v is left through, or none.  The components are
+ * simple paths and cycles, none its own twin.  A cycle is cut open in front of (u*, +), u* its smallest contig, the twin
+ * cycle behind (u*, -); such a scaffold has KC_SCAF_CIRCULAR set and its closing join is not written.  Of a path and its
+ * twin the one whose head has the smaller contig number is emitted, a single contig as (u, +).  Every contig is a member
+ * of exactly one scaffold.
+ *
+ * Text and order.  A scaffold's text is its head's text, then for every further member with join j: j >= 0 gives j 'N'
+ * and the member's text, j < 0 the member's text from byte -j on; then '_'.  Scaffolds are ordered by their head's contig
+ * number.  2^31 bytes or more: KC_ERR_CAPACITY.
+ *
+ * Output.  seqs_out (capacity bytes) / offsets_out (n_scaffolds + 1 entries; n_ctgs + 1 always suffice) in the layout
+ * kc_ctg_index_build and kc_submit_ctg_block take; scaffolds: n_scaffolds (at most n_ctgs) records; members: exactly
+ * n_ctgs records in scaffold order, out_pos = the block position of the first byte of the member's own text that is
+ * written (behind its N run, behind the bytes an overlap merges away); ctg_member: n_ctgs entries, a contig's index in
+ * members.  *n_scaffolds and *nbytes_out are required; every other output may be NULL.  stats: edges_chosen =
+ * edges_joined + overlaps_rejected; ends_not_mutual counts the ends with a best link whose partner's best is another;
+ * edges_joined counts a cycle's closing edge; bases = *nbytes_out - *n_scaffolds.
+ *
+ * Protocol.  The parameter ranges are checked in front of ctx and kc_last_error names the values.  on_device applies to
+ * all arrays alike; device record arrays (links, scaffolds, members) are 16-byte aligned, offsets_out 8-byte, ctg_member
+ * 4-byte; seqs_out may have any alignment.  No index: KC_ERR_STATE.  seqs_out == NULL is a size query: KC_OK,
+ * *n_scaffolds, *nbytes_out and *stats are written and nothing else; a non-NULL seqs_out with capacity below *nbytes_out
+ * is KC_ERR_CAPACITY with the same three written.  On every other error nothing is written through any pointer.
+ * n_links == 0: every contig is its own scaffold.  The call works before or after kc_finalize and with rank_n > 1, touches
+ * neither the index, the table nor the results, runs on the context's stream and returns when done; scratch lives for the
+ * call only: 216 bytes a contig and 8 a record, 24 a contig more while the block is written, none per output byte,
+ * beside the records' copy and the outputs' staging for host arrays.
+ */
+typedef struct kc_scaf_params {
+  uint32_t min_splints;         /* >= 1 */
+  uint32_t min_spans;           /* >= 1 */
+  uint32_t max_second_permille; /* <= 1000 */
+  uint32_t overlap_slack;       /* <= KC_SCAF_MAX_SLACK */
+  uint32_t flags;               /* 0 */
+  uint32_t reserved[3];         /* zero */
+} kc_scaf_params;               /* 32 bytes */
+#define KC_SCAF_MAX_SLACK 64
+#define KC_SCAF_CIRCULAR 1u
+typedef struct kc_scaffold_rec { /* 32 bytes; the function has the name kc_scaffold */
+  uint32_t first_member, n_members;
+  uint32_t len;           /* without the separator */
+  uint32_t n_bases;       /* from gaps */
+  uint32_t overlap_bases; /* merged away */
+  uint32_t flags;         /* KC_SCAF_CIRCULAR: a cycle cut open */
+  uint32_t reserved[2];   /* zero */
+} kc_scaffold_rec;
+typedef struct kc_scaf_member { /* 16 bytes */
+  uint32_t ctg;
+  int32_t join; /* 0 for a head */
+  uint32_t out_pos;
+  uint8_t orient, reserved[3];
+} kc_scaf_member;
+typedef struct kc_scaf_stats {
+  uint64_t contigs, records, qualifying;
+  uint64_t ends_best, ends_ambiguous, ends_not_mutual, edges_chosen;
+  uint64_t overlaps_checked, overlaps_rejected, edges_joined;
+  uint64_t scaffolds, singletons, circular;
+  uint64_t bases, n_bases, overlap_bases, longest;
+  uint64_t reserved[3]; /* zero: 160 bytes in all */
+} kc_scaf_stats;
+int kc_scaffold(kc_ctx *ctx, const kc_ctg_link *links, uint64_t n_links, int on_device, const kc_scaf_params *params, uint8_t *seqs_out,
+                uint64_t capacity, uint64_t *offsets_out, kc_scaffold_rec *scaffolds, kc_scaf_member *members, uint32_t *ctg_member,
+                uint64_t *n_scaffolds, uint64_t *nbytes_out, kc_scaf_stats *stats);
 /* KmerDHT::kmer_exists / get_kmer_count / get_local_kmer_counts (src/kcount/kmer_dht.cpp:198-245) in bulk, against the
  * results kept in HBM: nq k-mers of num_longs words each, in either orientation; counts[i] = 0 (and left/right = 0)
  * when the k-mer did not survive.  The index over the results is built on the first call after kc_finalize.

@@ -176,6 +176,28 @@ KC_LINK_MAX_SLACK = 1024
 KC_LINK_MAX_OVERLAP = 65535
 KC_LINK_MAX_READ_ALNS = 64
 
+
+class kc_scaf_params(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("min_splints", "min_spans", "max_second_permille", "overlap_slack", "flags")] + [("reserved", C.c_uint32 * 3)]
+
+
+class kc_scaffold_rec(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("first_member", "n_members", "len", "n_bases", "overlap_bases", "flags")] + [("reserved", C.c_uint32 * 2)]
+
+
+class kc_scaf_member(C.Structure):
+    _fields_ = [("ctg", C.c_uint32), ("join", C.c_int32), ("out_pos", C.c_uint32), ("orient", C.c_uint8), ("reserved", C.c_uint8 * 3)]
+
+
+class kc_scaf_stats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("contigs", "records", "qualifying", "ends_best", "ends_ambiguous", "ends_not_mutual", "edges_chosen",
+                                          "overlaps_checked", "overlaps_rejected", "edges_joined", "scaffolds", "singletons", "circular",
+                                          "bases", "n_bases", "overlap_bases", "longest")] + [("reserved", C.c_uint64 * 3)]
+
+
+KC_SCAF_MAX_SLACK = 64
+KC_SCAF_CIRCULAR = 1
+
 # every symbol include/kcount_mi355.h declares: (restype, argtypes)
 SYMBOLS = {
     "kc_abi_version": (C.c_int, []),
@@ -255,6 +277,8 @@ SYMBOLS = {
                                  C.POINTER(kc_lassm_stats)]),
     "kc_ctg_links": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int, C.POINTER(kc_link_params), C.c_void_p,
                                 C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(kc_link_stats)]),
+    "kc_scaffold": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.POINTER(kc_scaf_params), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                              C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(kc_scaf_stats)]),
     "kc_lookup": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "kc_dump_table": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
     "kc_get_stats": (C.c_int, [C.c_void_p, C.POINTER(kc_stats)]),

@@ -36,6 +36,7 @@
 #include "kc_depth.hpp"
 #include "kc_lassm.hpp"
 #include "kc_links.hpp"
+#include "kc_scaffold.hpp"
 
 using namespace kc;
 
@@ -104,7 +105,9 @@ enum { KT_EXTRACT_INSERT = 0, KT_EXTRACT_BIN, KT_INSERT_RECORDS, KT_FINALIZE, KT
        KT_PAIR_BEST, KT_PAIR_CLASSIFY, KT_PAIR_CLASSIFY_LDS, KT_LASSM_LENGTHS, KT_LASSM_CHECK, KT_LASSM_PAIR_CHECK, KT_LASSM_COUNT,
        KT_LASSM_PLAN, KT_LASSM_SCAN, KT_LASSM_SCATTER, KT_LASSM_TEXT, KT_LASSM_WALK, KT_LASSM_LENS, KT_LASSM_ENDS, KT_LASSM_WRITE, KT_LINK_LENGTHS,
        KT_LINK_CHECK, KT_LINK_PAIR_CHECK, KT_LINK_GROUP_COUNT, KT_LINK_GROUP_FILL, KT_LINK_TILE_SCAN, KT_LINK_SCAN, KT_LINK_CANDS_COUNT, KT_LINK_CANDS_WRITE,
-       KT_LINK_SORT_HIST, KT_LINK_SORT_SCAN, KT_LINK_SORT_SCATTER, KT_LINK_HEADS, KT_LINK_REDUCE, KT_LINK_EMIT, KT_LINK_END_FIRST, KT_COUNT };
+       KT_LINK_SORT_HIST, KT_LINK_SORT_SCAN, KT_LINK_SORT_SCATTER, KT_LINK_HEADS, KT_LINK_REDUCE, KT_LINK_EMIT, KT_LINK_END_FIRST,
+       KT_SCAF_CHECK, KT_SCAF_END_FIRST, KT_SCAF_CHOOSE, KT_SCAF_EDGE, KT_SCAF_NEXT, KT_SCAF_MIN_JUMP, KT_SCAF_CUT, KT_SCAF_WEIGHT, KT_SCAF_RANK_JUMP,
+       KT_SCAF_POS_JUMP, KT_SCAF_SELECT, KT_SCAF_SCAN, KT_SCAF_MEMBERS, KT_SCAF_RECORDS, KT_SCAF_WRITE, KT_COUNT };
 // KT_FQ_SCAN, KT_MERGE_SCAN and KT_TRIM_SCAN label the front end's three uses of the one shared kc_scan_kernel (kc_scan.hpp); their
 // strings keep the names the uses were first reported under.  KT_SORT_SCAN and KT_DUMP_SCAN are the back end's two,
 // KT_UNITIG_SCAN the unitigs' (kc_scan_kernel<2>: bytes and unitig numbers in one pass), KT_ALIGN_SCAN the alignments' (the
@@ -116,6 +119,9 @@ enum { KT_EXTRACT_INSERT = 0, KT_EXTRACT_BIN, KT_INSERT_RECORDS, KT_FINALIZE, KT
 // kc_lassm_cands_kernel.  KT_LINK_LENGTHS, KT_LINK_CHECK and KT_LINK_PAIR_CHECK are kc_ctg_links' launches of the three check kernels,
 // KT_LINK_SCAN its uses of kc_scan_kernel<1> (the tiles of the reads' slots, of the candidates and of the runs), KT_LINK_SORT_* its radix passes through
 // kc_sort.hpp's kernels; KT_LINK_GROUP_* and KT_LINK_CANDS_* are the two passes of kc_link_group_kernel and kc_link_cands_kernel.
+// KT_SCAF_END_FIRST is kc_scaffold's launch of kc_link_end_first_kernel, KT_SCAF_MIN_JUMP, KT_SCAF_CUT and KT_SCAF_RANK_JUMP its launches of the
+// three kc_unitig.hpp kernels (KT_SCAF_POS_JUMP: kc_unitig_rank_jump_kernel again, over the byte positions), KT_SCAF_SCAN its uses of
+// kc_scan_kernel<2> (bytes and scaffold numbers) and <1> (first members).
 static const char *const kt_names[KT_COUNT] = {"kc_extract_kernel<insert>", "kc_bin_reads_kernel", "kc_insert_records_kernel",
                                                "kc_finalize_kernel", "kc_tile_first_kernel", "kc_rehash_kernel",
                                                "kc_l1_reads_kernel", "kc_l1_records_kernel", "kc_l2_split_kernel",
@@ -148,7 +154,12 @@ static const char *const kt_names[KT_COUNT] = {"kc_extract_kernel<insert>", "kc_
                                                "kc_link_group_kernel<count>", "kc_link_group_kernel<fill>", "kc_link_tile_scan_kernel", "kc_link_scan_kernel",
                                                "kc_link_cands_kernel<count>", "kc_link_cands_kernel<write>", "kc_sort_hist_kernel<links>",
                                                "kc_sort_scan_kernel<links>", "kc_sort_scatter_kernel<links>", "kc_link_heads_kernel",
-                                               "kc_link_reduce_kernel", "kc_link_emit_kernel", "kc_link_end_first_kernel"};
+                                               "kc_link_reduce_kernel", "kc_link_emit_kernel", "kc_link_end_first_kernel",
+                                               "kc_scaf_check_kernel", "kc_link_end_first_kernel<scaffold>", "kc_scaf_choose_kernel",
+                                               "kc_scaf_edge_kernel", "kc_scaf_next_kernel", "kc_unitig_min_jump_kernel<scaffold>",
+                                               "kc_unitig_cut_kernel<scaffold>", "kc_scaf_weight_kernel", "kc_unitig_rank_jump_kernel<scaffold>",
+                                               "kc_unitig_rank_jump_kernel<scaffold pos>", "kc_scaf_select_kernel", "kc_scaf_scan_kernel",
+                                               "kc_scaf_members_kernel", "kc_scaf_records_kernel", "kc_scaf_write_kernel"};
 struct kt_pending {
   hipEvent_t start, stop;
   int kind;
@@ -3237,6 +3248,7 @@ extern "C" int kc_lookup(kc_ctx *c, const uint64_t *queries, uint64_t nq, int on
 #include "kc_api_depth.hpp"  // kc_ctg_index_info, kc_aln_depths, kc_pair_inserts
 #include "kc_api_lassm.hpp"  // kc_local_assm
 #include "kc_api_links.hpp"  // kc_ctg_links
+#include "kc_api_scaffold.hpp"  // kc_scaffold
 
 // ---- the contig pass (kc_ctg.hpp) ----------------------------------------------------------------------------------
 extern "C" int kc_begin_ctg_kmers(kc_ctx *c, uint64_t max_ctg_kmers) {

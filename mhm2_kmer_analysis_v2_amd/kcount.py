@@ -857,6 +857,61 @@ class KmerCounter:
             gap = np.where(s > 0, host["splint_gap_sum"] / np.maximum(s, 1), host["span_gap_sum"] / np.maximum(m, 1))
         return links, end_first, {f: int(getattr(st, f)) for f, _ in kc_link_stats._fields_ if f != "reserved"}, gap
 
+    def scaffolds(self, links, min_splints=1, min_spans=2, max_second_permille=0, overlap_slack=0):
+        """The scaffolds the links give over the indexed contigs (kc_scaffold): one partner per contig
+        end (a link qualifies with min_splints splints or min_spans spans; an end whose second-best link has more than
+        max_second_permille thousandths of the best's support is left alone), claimed overlaps checked against the text
+        up to overlap_slack bases either way, the chosen edges walked into paths.  links: ctg_links' records (LINK_DTYPE
+        array, or the uint8 device tensor).  Returns (seqs, offsets, scaffolds, members, stats): the seq block index_contigs
+        takes as it is, SCAFFOLD_DTYPE and MEMBER_DTYPE records -- numpy for host input; uint8 / int64 device tensors and
+        uint8 tensors of 32- and 16-byte records for a device tensor -- and kc_scaf_stats as a dict.  A size query first,
+        then the call."""
+        pl, dev = _ptr(links)
+        if dev:
+            n_links = links.numel() // 48
+        else:
+            if len(links) and (links.dtype.itemsize != 48 or not links.flags["C_CONTIGUOUS"]):
+                raise ValueError("links: a contiguous array of 48-byte records (LINK_DTYPE)")
+            n_links = len(links)
+        pl = pl if n_links else None
+        _, n_ctgs = self.contig_index_info()
+        prm = _lib.kc_scaf_params(min_splints, min_spans, max_second_permille, overlap_slack, 0)
+        st, ns, nb = _lib.kc_scaf_stats(), C.c_uint64(0), C.c_uint64(0)
+        if dev:
+            import torch
+            torch.cuda.current_stream(self.device).synchronize()  # the input is torch's until now
+        d = 1 if dev else 0
+        check(lib().kc_scaffold(self._h, pl, n_links, d, C.byref(prm), None, 0, None, None, None, None, C.byref(ns), C.byref(nb), C.byref(st)),
+              "kc_scaffold")
+        n_scaf, nbytes = int(ns.value), int(nb.value)
+        if dev:
+            dv = "cuda:%d" % self.device
+            seqs = torch.empty(nbytes, dtype=torch.uint8, device=dv)
+            offsets = torch.empty(n_scaf + 1, dtype=torch.int64, device=dv)
+            scafs = torch.empty(max(n_scaf, 1) * 32, dtype=torch.uint8, device=dv)
+            members = torch.empty(max(n_ctgs, 1) * 16, dtype=torch.uint8, device=dv)
+            torch.cuda.current_stream(self.device).synchronize()
+            ptrs = (seqs.data_ptr(), offsets.data_ptr(), scafs.data_ptr(), members.data_ptr())
+        else:
+            seqs = np.zeros(nbytes, dtype=np.uint8)
+            offsets = np.zeros(n_scaf + 1, dtype=np.uint64)
+            scafs = np.zeros(max(n_scaf, 1), dtype=SCAFFOLD_DTYPE)
+            members = np.zeros(max(n_ctgs, 1), dtype=MEMBER_DTYPE)
+            ptrs = (seqs.ctypes.data, offsets.ctypes.data, scafs.ctypes.data, members.ctypes.data)
+        check(lib().kc_scaffold(self._h, pl, n_links, d, C.byref(prm), ptrs[0], nbytes, ptrs[1], ptrs[2], ptrs[3], None, C.byref(ns), C.byref(nb),
+                                C.byref(st)), "kc_scaffold")
+        scafs = scafs[:n_scaf * 32] if dev else scafs[:n_scaf]
+        members = members[:n_ctgs * 16] if dev else members[:n_ctgs]
+        return seqs, offsets, scafs, members, {f: int(getattr(st, f)) for f, _ in _lib.kc_scaf_stats._fields_ if f != "reserved"}
+
+    def scaffold_strings(self, links, **kw):
+        """The scaffolds' texts as Python strings (for tests and small inputs): scaffolds() without its records."""
+        seqs, offsets = self.scaffolds(links, **kw)[:2]
+        if not isinstance(seqs, np.ndarray):
+            seqs, offsets = seqs.cpu().numpy(), offsets.cpu().numpy()
+        text = seqs.tobytes().decode()
+        return [text[int(offsets[i]):int(offsets[i + 1]) - 1] for i in range(len(offsets) - 1)]
+
     def submit_ctg_block(self, seqs, depths):
         """kc_submit_ctg_block with device tensors (a '_'-joined block and one 16-bit depth per byte), e.g. those of
         unitig_block(); begin_ctg_kmers first."""
@@ -906,6 +961,10 @@ PAIR_DTYPE = np.dtype([("aln0", "<u4"), ("aln1", "<u4"), ("insert", "<u4"), ("cl
 LASSM_END_DTYPE = np.dtype([("cands", "<u4"), ("ext_len", "<u4"), ("out_pos", "<u4"), ("iters", "<u2"), ("mer_len", "u1"), ("status", "u1")])
 LINK_DTYPE = np.dtype([("from", "<u4"), ("to", "<u4"), ("splints", "<u4"), ("spans", "<u4"), ("splint_gap_min", "<i4"), ("splint_gap_max", "<i4"),
                        ("span_gap_min", "<i4"), ("span_gap_max", "<i4"), ("splint_gap_sum", "<i8"), ("span_gap_sum", "<i8")])
+# kc_scaffold's records of a scaffold (kc_scaffold_rec, 32 bytes) and of a member (kc_scaf_member, 16 bytes)
+SCAFFOLD_DTYPE = np.dtype([("first_member", "<u4"), ("n_members", "<u4"), ("len", "<u4"), ("n_bases", "<u4"), ("overlap_bases", "<u4"),
+                           ("flags", "<u4"), ("pad", "<u4", (2,))])
+MEMBER_DTYPE = np.dtype([("ctg", "<u4"), ("join", "<i4"), ("out_pos", "<u4"), ("orient", "u1"), ("pad", "u1", (3,))])
 BLASTN_ALN_SCORES = (2, 3, 5, 2, 1)
 ALTERNATE_ALN_SCORES = (1, 1, 1, 1, 1)
 
