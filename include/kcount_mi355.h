@@ -1044,6 +1044,104 @@ typedef struct kc_scaf_stats {
 int kc_scaffold(kc_ctx *ctx, const kc_ctg_link *links, uint64_t n_links, int on_device, const kc_scaf_params *params, uint8_t *seqs_out,
                 uint64_t capacity, uint64_t *offsets_out, kc_scaffold_rec *scaffolds, kc_scaf_member *members, uint32_t *ctg_member,
                 uint64_t *n_scaffolds, uint64_t *nbytes_out, kc_scaf_stats *stats);
+/* Closing the scaffolds' gaps from splint reads.  A splint -- one read aligned across two contigs -- holds the bases
+ * between the two contig ends; where enough splints agree on the distance, the N run of a join becomes their consensus
+ * (or the run goes: the contigs abut, or overlap as their text confirms).  The reference holds no gap closing
+ * (src/contigging.cpp stops before scaffolding), so the rules below are this project's own definition (DESIGN.md section
+ * 21, tests/close_model.py); no parity with MetaHipMer is claimed.  All quantities are integers, signed 64-bit where
+ * they are compared; the output is one exact byte string for a given input, whatever order the records come in.
+ *
+ * Input.  bases / offsets / alns: the reads and their records exactly as kc_ctg_links takes them (nreads may be odd: no
+ * pairs are read), with the same validity, the same filter (min_score, min_len) and the same max_read_alns; the contigs
+ * are the kept index's.  scaffolds / members: as kc_scaffold writes them; read are first_member, n_members, ctg, orient and
+ * join only (flags is copied; out_pos, len, n_bases, overlap_bases are not read).  Valid iff n_scaffolds >= 1, scaffold 0
+ * starts at member 0, every scaffold has n_members >= 1 and starts where its predecessor ends, the last ends at n_ctgs;
+ * ctg < n_ctgs, orient <= 1, a member's reserved bytes zero, every contig a member exactly once (of two members with one
+ * contig the higher index is the bad one), a head's join 0, any other join in [-KC_LINK_MAX_OVERLAP, KC_INSERT_MAX] and a
+ * negative join j with -j < min(len of the member before, len of this member).  Otherwise KC_ERR_INVALID_ARG, and
+ * kc_last_error names the lowest bad scaffold, or the lowest bad member, index.  The checks run in the order reads,
+ * records, scaffolds, members, each a pass whose verdict is read before anything is stored.
+ *
+ * Joins.  Member m (not a head) follows member m - 1: the node left is 2 ctg(m-1) + orient(m-1), left through end
+ * ea = that ^ 1; the node entered is fb = 2 ctg(m) + orient(m) (kc_scaffold's conventions).  m is a GAP JOIN iff
+ * join(m) > 0; only gap joins collect candidates.  A circular scaffold's closing join has no member and is not closed.
+ *
+ * Candidates.  Exactly kc_ctg_links' splint candidates: an ordered pair (a, b) of passing records of one read with
+ * leaving end X, entering end Y, slacks e_a, e_b and gap = (qs_b - qe_a) - e_a - e_b in [-max_overlap, max_splint_gap]; a
+ * read over max_read_alns gives none (reads_over_cap).  It supports gap join m FORWARD iff (X, Y) = (ea, fb), BACKWARD
+ * iff (X, Y) = (fb, ea); every other candidate counts in cands_off_join.  Its segment is the read's bytes
+ * [qe_a + e_a, qs_b - e_b) in the read's own direction (gap bytes for gap >= 0); a backward candidate contributes the
+ * segment's reverse complement.
+ *
+ * Choosing.  g* is the gap value with the most of the join's candidates, on a tie the smallest.  The join is closed iff
+ * votes(g*) >= min_reads and votes(g*) * 1000 >= cands * min_agree_permille.  No candidates: KC_CLOSE_NO_READS; not closed:
+ * KC_CLOSE_WEAK; in both the run stays and new_join = old_join.
+ *
+ * Closing.  g* > 0, KC_CLOSE_FILLED: column c of the fill is the base with the most votes among the g*-candidates'
+ * segments at c; A C G T in either case vote (a backward candidate's byte is complemented first), every other byte does
+ * not; a tie goes to the first of A, C, G, T; a column without votes is 'N'; new_join = g* and the fill stands where the
+ * run stood.  g* == 0, KC_CLOSE_ABUT: the run goes, new_join = 0.  g* < 0, o = -g*: KC_CLOSE_OVERLAP with new_join = -o
+ * iff 1 <= o < min(|A|, |B|) and the last o bytes of the text left equal the first o bytes of the text entered (a byte
+ * that is not A C G T never matches); otherwise KC_CLOSE_OVERLAP_REJECTED and the run is kept.
+ *
+ * Text and order.  kc_scaffold's rule with the new joins, a filled join's fill in place of its 'N'.  Scaffolds and
+ * members keep their order and number.  scaffolds_out: first_member, n_members and flags copied, len, n_bases (the N
+ * left) and overlap_bases new; members_out: new_join and the new out_pos; closures: one record a member, in member
+ * order; offsets_out: n_scaffolds + 1 entries.  fill_pos is the block position of the first fill byte (filled), of the
+ * first 'N' (run kept), otherwise of the member's first written byte.  2^31 bytes or more: KC_ERR_CAPACITY.
+ * gaps = gaps_no_reads + gaps_weak + filled + abutted + overlapped + overlaps_rejected; cands counts every splint
+ * candidate, cands_off_join those that support no gap join.
+ *
+ * Protocol.  The parameter ranges are checked in front of ctx and kc_last_error names the values.  on_device applies to
+ * all arrays alike; device record arrays (alns, scaffolds, members, scaffolds_out, members_out, closures) are 16-byte
+ * aligned, offsets and offsets_out 8-byte; bases and seqs_out may have any alignment.  No index: KC_ERR_STATE.
+ * seqs_out == NULL is a size query: KC_OK, *nbytes_out and *stats are written and nothing else; a non-NULL seqs_out with
+ * capacity below *nbytes_out is KC_ERR_CAPACITY with the same two written.  On every other error nothing is written
+ * through any pointer.  Every output except nbytes_out may be NULL.  n_alns == 0 copies the scaffolds: records and
+ * members are rewritten, every gap is KC_CLOSE_NO_READS.  The call works before or after kc_finalize and with rank_n > 1,
+ * touches neither the index, the table nor the results, runs on the context's stream and returns when done; scratch lives
+ * for the call only: 12 bytes a read, 16 a passing record, 16 a candidate on a gap join, 84 a contig, 8 a scaffold and 1
+ * a fill byte, beside the copies of host arrays and the outputs' staging for them.
+ */
+typedef struct kc_close_params {
+  uint32_t min_score, min_len; /* kc_ctg_links' filter */
+  uint32_t end_slack;          /* <= KC_LINK_MAX_SLACK */
+  uint32_t max_overlap;        /* <= KC_LINK_MAX_OVERLAP */
+  uint32_t max_splint_gap;     /* <= KC_LINK_MAX_SLACK */
+  uint32_t min_reads;          /* >= 1: supporters a closure needs */
+  uint32_t min_agree_permille; /* <= 1000: share of a join's candidates that must agree on the gap */
+  uint16_t max_read_alns;      /* 2 .. KC_LINK_MAX_READ_ALNS */
+  uint16_t flags;              /* 0 */
+} kc_close_params;             /* 32 bytes */
+enum {
+  KC_CLOSE_HEAD = 0,
+  KC_CLOSE_NOT_A_GAP = 1, /* old join <= 0, copied */
+  KC_CLOSE_NO_READS = 2,
+  KC_CLOSE_WEAK = 3,
+  KC_CLOSE_FILLED = 4,
+  KC_CLOSE_ABUT = 5,
+  KC_CLOSE_OVERLAP = 6,
+  KC_CLOSE_OVERLAP_REJECTED = 7
+};
+typedef struct kc_closure { /* 32 bytes, one a member */
+  uint32_t cands;           /* the join's candidates */
+  uint32_t reads;           /* candidates of the chosen gap; 0 where none was chosen */
+  int32_t old_join, new_join;
+  uint32_t fill_pos;
+  uint32_t disputed; /* fill columns whose voters do not all agree */
+  uint8_t status, pad[3];
+  uint32_t reserved; /* zero */
+} kc_closure;
+typedef struct kc_close_stats { /* 128 bytes */
+  uint64_t members, joins, gaps;
+  uint64_t reads_over_cap, passed, cands, cands_off_join;
+  uint64_t gaps_no_reads, gaps_weak, filled, abutted, overlapped, overlaps_rejected;
+  uint64_t fill_bases, n_bases_left, disputed_cols;
+} kc_close_stats;
+int kc_close_gaps(kc_ctx *ctx, const uint8_t *bases, const uint64_t *offsets, uint64_t nreads, const kc_gap_aln *alns, uint64_t n_alns,
+                  const kc_scaffold_rec *scaffolds, uint64_t n_scaffolds, const kc_scaf_member *members, int on_device,
+                  const kc_close_params *params, uint8_t *seqs_out, uint64_t capacity, uint64_t *offsets_out, kc_scaffold_rec *scaffolds_out,
+                  kc_scaf_member *members_out, kc_closure *closures, uint64_t *nbytes_out, kc_close_stats *stats);
 /* KmerDHT::kmer_exists / get_kmer_count / get_local_kmer_counts (src/kcount/kmer_dht.cpp:198-245) in bulk, against the
  * results kept in HBM: nq k-mers of num_longs words each, in either orientation; counts[i] = 0 (and left/right = 0)
  * when the k-mer did not survive.  The index over the results is built on the first call after kc_finalize.

@@ -198,6 +198,26 @@ class kc_scaf_stats(C.Structure):
 KC_SCAF_MAX_SLACK = 64
 KC_SCAF_CIRCULAR = 1
 
+
+class kc_close_params(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("min_score", "min_len", "end_slack", "max_overlap", "max_splint_gap", "min_reads",
+                                          "min_agree_permille")] + [("max_read_alns", C.c_uint16), ("flags", C.c_uint16)]
+
+
+class kc_closure(C.Structure):
+    _fields_ = [("cands", C.c_uint32), ("reads", C.c_uint32), ("old_join", C.c_int32), ("new_join", C.c_int32), ("fill_pos", C.c_uint32),
+                ("disputed", C.c_uint32), ("status", C.c_uint8), ("pad", C.c_uint8 * 3), ("reserved", C.c_uint32)]
+
+
+class kc_close_stats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("members", "joins", "gaps", "reads_over_cap", "passed", "cands", "cands_off_join", "gaps_no_reads",
+                                          "gaps_weak", "filled", "abutted", "overlapped", "overlaps_rejected", "fill_bases", "n_bases_left",
+                                          "disputed_cols")]
+
+
+(KC_CLOSE_HEAD, KC_CLOSE_NOT_A_GAP, KC_CLOSE_NO_READS, KC_CLOSE_WEAK, KC_CLOSE_FILLED, KC_CLOSE_ABUT, KC_CLOSE_OVERLAP,
+ KC_CLOSE_OVERLAP_REJECTED) = range(8)
+
 # every symbol include/kcount_mi355.h declares: (restype, argtypes)
 SYMBOLS = {
     "kc_abi_version": (C.c_int, []),
@@ -279,6 +299,9 @@ SYMBOLS = {
                                 C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(kc_link_stats)]),
     "kc_scaffold": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.POINTER(kc_scaf_params), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                               C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(kc_scaf_stats)]),
+    "kc_close_gaps": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int,
+                                C.POINTER(kc_close_params), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                C.POINTER(C.c_uint64), C.POINTER(kc_close_stats)]),
     "kc_lookup": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "kc_dump_table": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
     "kc_get_stats": (C.c_int, [C.c_void_p, C.POINTER(kc_stats)]),

@@ -37,6 +37,7 @@
 #include "kc_lassm.hpp"
 #include "kc_links.hpp"
 #include "kc_scaffold.hpp"
+#include "kc_close.hpp"
 
 using namespace kc;
 
@@ -107,7 +108,10 @@ enum { KT_EXTRACT_INSERT = 0, KT_EXTRACT_BIN, KT_INSERT_RECORDS, KT_FINALIZE, KT
        KT_LINK_CHECK, KT_LINK_PAIR_CHECK, KT_LINK_GROUP_COUNT, KT_LINK_GROUP_FILL, KT_LINK_TILE_SCAN, KT_LINK_SCAN, KT_LINK_CANDS_COUNT, KT_LINK_CANDS_WRITE,
        KT_LINK_SORT_HIST, KT_LINK_SORT_SCAN, KT_LINK_SORT_SCATTER, KT_LINK_HEADS, KT_LINK_REDUCE, KT_LINK_EMIT, KT_LINK_END_FIRST,
        KT_SCAF_CHECK, KT_SCAF_END_FIRST, KT_SCAF_CHOOSE, KT_SCAF_EDGE, KT_SCAF_NEXT, KT_SCAF_MIN_JUMP, KT_SCAF_CUT, KT_SCAF_WEIGHT, KT_SCAF_RANK_JUMP,
-       KT_SCAF_POS_JUMP, KT_SCAF_SELECT, KT_SCAF_SCAN, KT_SCAF_MEMBERS, KT_SCAF_RECORDS, KT_SCAF_WRITE, KT_COUNT };
+       KT_SCAF_POS_JUMP, KT_SCAF_SELECT, KT_SCAF_SCAN, KT_SCAF_MEMBERS, KT_SCAF_RECORDS, KT_SCAF_WRITE, KT_CLOSE_LENGTHS, KT_CLOSE_CHECK,
+       KT_CLOSE_CHECK_SCAF, KT_CLOSE_CLAIM, KT_CLOSE_CHECK_MEMBER, KT_CLOSE_GROUP_COUNT, KT_CLOSE_GROUP_FILL, KT_CLOSE_TILE_SCAN, KT_CLOSE_SCAN,
+       KT_CLOSE_ENDS, KT_CLOSE_CANDS_COUNT, KT_CLOSE_CANDS_WRITE, KT_CLOSE_DECIDE, KT_CLOSE_PLACE, KT_CLOSE_VOTE, KT_CLOSE_RECORDS, KT_CLOSE_WRITE,
+       KT_COUNT };
 // KT_FQ_SCAN, KT_MERGE_SCAN and KT_TRIM_SCAN label the front end's three uses of the one shared kc_scan_kernel (kc_scan.hpp); their
 // strings keep the names the uses were first reported under.  KT_SORT_SCAN and KT_DUMP_SCAN are the back end's two,
 // KT_UNITIG_SCAN the unitigs' (kc_scan_kernel<2>: bytes and unitig numbers in one pass), KT_ALIGN_SCAN the alignments' (the
@@ -122,6 +126,9 @@ enum { KT_EXTRACT_INSERT = 0, KT_EXTRACT_BIN, KT_INSERT_RECORDS, KT_FINALIZE, KT
 // KT_SCAF_END_FIRST is kc_scaffold's launch of kc_link_end_first_kernel, KT_SCAF_MIN_JUMP, KT_SCAF_CUT and KT_SCAF_RANK_JUMP its launches of the
 // three kc_unitig.hpp kernels (KT_SCAF_POS_JUMP: kc_unitig_rank_jump_kernel again, over the byte positions), KT_SCAF_SCAN its uses of
 // kc_scan_kernel<2> (bytes and scaffold numbers) and <1> (first members).
+// KT_CLOSE_LENGTHS, KT_CLOSE_CHECK, KT_CLOSE_GROUP_*, KT_CLOSE_TILE_SCAN and KT_CLOSE_SCAN are kc_close_gaps' launches of kc_align_lengths_kernel,
+// kc_depth_check_kernel, kc_link_group_kernel, kc_link_tile_scan_kernel and kc_scan_kernel<1> (the reads' slots, the joins' candidates, the
+// segments' and the fills' bytes); KT_CLOSE_CANDS_* are the two passes of kc_close_cands_kernel.
 static const char *const kt_names[KT_COUNT] = {"kc_extract_kernel<insert>", "kc_bin_reads_kernel", "kc_insert_records_kernel",
                                                "kc_finalize_kernel", "kc_tile_first_kernel", "kc_rehash_kernel",
                                                "kc_l1_reads_kernel", "kc_l1_records_kernel", "kc_l2_split_kernel",
@@ -159,7 +166,13 @@ static const char *const kt_names[KT_COUNT] = {"kc_extract_kernel<insert>", "kc_
                                                "kc_scaf_edge_kernel", "kc_scaf_next_kernel", "kc_unitig_min_jump_kernel<scaffold>",
                                                "kc_unitig_cut_kernel<scaffold>", "kc_scaf_weight_kernel", "kc_unitig_rank_jump_kernel<scaffold>",
                                                "kc_unitig_rank_jump_kernel<scaffold pos>", "kc_scaf_select_kernel", "kc_scaf_scan_kernel",
-                                               "kc_scaf_members_kernel", "kc_scaf_records_kernel", "kc_scaf_write_kernel"};
+                                               "kc_scaf_members_kernel", "kc_scaf_records_kernel", "kc_scaf_write_kernel",
+                                               "kc_align_lengths_kernel<close>", "kc_depth_check_kernel<close>", "kc_close_check_scaf_kernel",
+                                               "kc_close_claim_kernel", "kc_close_check_member_kernel", "kc_link_group_kernel<close count>",
+                                               "kc_link_group_kernel<close fill>", "kc_link_tile_scan_kernel<close>", "kc_close_scan_kernel",
+                                               "kc_close_ends_kernel", "kc_close_cands_kernel<count>", "kc_close_cands_kernel<write>",
+                                               "kc_close_decide_kernel", "kc_close_place_kernel", "kc_close_vote_kernel",
+                                               "kc_close_records_kernel", "kc_close_write_kernel"};
 struct kt_pending {
   hipEvent_t start, stop;
   int kind;
@@ -3249,6 +3262,7 @@ extern "C" int kc_lookup(kc_ctx *c, const uint64_t *queries, uint64_t nq, int on
 #include "kc_api_lassm.hpp"  // kc_local_assm
 #include "kc_api_links.hpp"  // kc_ctg_links
 #include "kc_api_scaffold.hpp"  // kc_scaffold
+#include "kc_api_close.hpp"  // kc_close_gaps
 
 // ---- the contig pass (kc_ctg.hpp) ----------------------------------------------------------------------------------
 extern "C" int kc_begin_ctg_kmers(kc_ctx *c, uint64_t max_ctg_kmers) {

@@ -912,6 +912,72 @@ class KmerCounter:
         text = seqs.tobytes().decode()
         return [text[int(offsets[i]):int(offsets[i + 1]) - 1] for i in range(len(offsets) - 1)]
 
+    def close_gaps(self, bases, offsets, gap_alns, scaffolds, members, min_reads=2, min_agree_permille=500, min_score=0, min_len=0, end_slack=5,
+                   max_overlap=200, max_splint_gap=100, max_read_alns=8):
+        """The scaffolds with their gaps closed from splint reads (kc_close_gaps): where at least
+        min_reads reads aligned across a join's two contigs -- and min_agree_permille thousandths of the join's candidates --
+        agree on the distance, the N run becomes the consensus of their bases, goes (the contigs abut) or becomes an overlap
+        the text confirms.  bases / offsets: the reads; gap_alns: align_gapped's records; scaffolds / members: scaffolds()'
+        records over the indexed contigs; the filter parameters are ctg_links'.  Returns (seqs, offsets, scaffolds, members,
+        closures, stats): the seq block index_contigs takes as it is, SCAFFOLD_DTYPE, MEMBER_DTYPE and CLOSURE_DTYPE records
+        -- numpy for host input; uint8 / int64 device tensors and uint8 tensors of 32-, 16- and 32-byte records for device
+        tensors -- and kc_close_stats as a dict.  A size query first, then the call."""
+        pa, n_alns, dev_a = self._gap_records(gap_alns)
+        pb, dev = _ptr(bases)
+        po, dev_o = _ptr(offsets)
+        ps, dev_s = _ptr(scaffolds)
+        pm, dev_m = _ptr(members)
+        nreads = len(offsets) - 1
+        if dev_o != dev or dev_s != dev or dev_m != dev or (n_alns and dev_a != dev):
+            raise ValueError("bases, offsets, gap_alns, scaffolds and members must all be host arrays or all be device tensors")
+        if dev:
+            n_scaf = scaffolds.numel() // 32
+        else:
+            if scaffolds.dtype.itemsize != 32 or members.dtype.itemsize != 16 or not scaffolds.flags["C_CONTIGUOUS"] or not members.flags["C_CONTIGUOUS"]:
+                raise ValueError("scaffolds, members: contiguous arrays of 32- and 16-byte records (SCAFFOLD_DTYPE, MEMBER_DTYPE)")
+            n_scaf = len(scaffolds)
+        _, n_ctgs = self.contig_index_info()
+        if (members.numel() // 16 if dev else len(members)) != n_ctgs:
+            raise ValueError("members: one record for each of the %d indexed contigs" % n_ctgs)
+        prm = _lib.kc_close_params(min_score, min_len, end_slack, max_overlap, max_splint_gap, min_reads, min_agree_permille, max_read_alns, 0)
+        st, nb = _lib.kc_close_stats(), C.c_uint64(0)
+        if dev:
+            import torch
+            torch.cuda.current_stream(self.device).synchronize()  # the input is torch's until now
+        d = 1 if dev else 0
+        head = (self._h, pb, po, nreads, pa, n_alns, ps, n_scaf, pm, d, C.byref(prm))
+        check(lib().kc_close_gaps(*head, None, 0, None, None, None, None, C.byref(nb), C.byref(st)), "kc_close_gaps")
+        nbytes = int(nb.value)
+        if dev:
+            dv = "cuda:%d" % self.device
+            seqs = torch.empty(nbytes, dtype=torch.uint8, device=dv)
+            offs_out = torch.empty(n_scaf + 1, dtype=torch.int64, device=dv)
+            scafs = torch.empty(max(n_scaf, 1) * 32, dtype=torch.uint8, device=dv)
+            mem = torch.empty(max(n_ctgs, 1) * 16, dtype=torch.uint8, device=dv)
+            clo = torch.empty(max(n_ctgs, 1) * 32, dtype=torch.uint8, device=dv)
+            torch.cuda.current_stream(self.device).synchronize()
+            ptrs = (seqs.data_ptr(), offs_out.data_ptr(), scafs.data_ptr(), mem.data_ptr(), clo.data_ptr())
+        else:
+            seqs = np.zeros(nbytes, dtype=np.uint8)
+            offs_out = np.zeros(n_scaf + 1, dtype=np.uint64)
+            scafs = np.zeros(max(n_scaf, 1), dtype=SCAFFOLD_DTYPE)
+            mem = np.zeros(max(n_ctgs, 1), dtype=MEMBER_DTYPE)
+            clo = np.zeros(max(n_ctgs, 1), dtype=CLOSURE_DTYPE)
+            ptrs = (seqs.ctypes.data, offs_out.ctypes.data, scafs.ctypes.data, mem.ctypes.data, clo.ctypes.data)
+        check(lib().kc_close_gaps(*head, ptrs[0], nbytes, ptrs[1], ptrs[2], ptrs[3], ptrs[4], C.byref(nb), C.byref(st)), "kc_close_gaps")
+        scafs = scafs[:n_scaf * 32] if dev else scafs[:n_scaf]
+        mem = mem[:n_ctgs * 16] if dev else mem[:n_ctgs]
+        clo = clo[:n_ctgs * 32] if dev else clo[:n_ctgs]
+        return seqs, offs_out, scafs, mem, clo, {f: int(getattr(st, f)) for f, _ in _lib.kc_close_stats._fields_}
+
+    def close_gaps_strings(self, bases, offsets, gap_alns, scaffolds, members, **kw):
+        """The closed scaffolds' texts as Python strings (for tests and small inputs): close_gaps() without its records."""
+        seqs, offs = self.close_gaps(bases, offsets, gap_alns, scaffolds, members, **kw)[:2]
+        if not isinstance(seqs, np.ndarray):
+            seqs, offs = seqs.cpu().numpy(), offs.cpu().numpy()
+        text = seqs.tobytes().decode()
+        return [text[int(offs[i]):int(offs[i + 1]) - 1] for i in range(len(offs) - 1)]
+
     def submit_ctg_block(self, seqs, depths):
         """kc_submit_ctg_block with device tensors (a '_'-joined block and one 16-bit depth per byte), e.g. those of
         unitig_block(); begin_ctg_kmers first."""
@@ -965,6 +1031,9 @@ LINK_DTYPE = np.dtype([("from", "<u4"), ("to", "<u4"), ("splints", "<u4"), ("spa
 SCAFFOLD_DTYPE = np.dtype([("first_member", "<u4"), ("n_members", "<u4"), ("len", "<u4"), ("n_bases", "<u4"), ("overlap_bases", "<u4"),
                            ("flags", "<u4"), ("pad", "<u4", (2,))])
 MEMBER_DTYPE = np.dtype([("ctg", "<u4"), ("join", "<i4"), ("out_pos", "<u4"), ("orient", "u1"), ("pad", "u1", (3,))])
+# kc_close_gaps' record of a member's join (kc_closure, 32 bytes)
+CLOSURE_DTYPE = np.dtype([("cands", "<u4"), ("reads", "<u4"), ("old_join", "<i4"), ("new_join", "<i4"), ("fill_pos", "<u4"), ("disputed", "<u4"),
+                          ("status", "u1"), ("pad", "u1", (3,)), ("reserved", "<u4")])
 BLASTN_ALN_SCORES = (2, 3, 5, 2, 1)
 ALTERNATE_ALN_SCORES = (1, 1, 1, 1, 1)
 
