@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/kcount_mi355.h"
+#include "kc_kinds.hpp"
 #include "kc_bucketed.hpp"
 #include "kc_shard.hpp"
 #include "kc_wire6.hpp"
@@ -93,86 +94,7 @@ struct Carver {
     if (rc_) return rc_;      \
   } while (0)
 
-// ---- kernel timing kinds and their reported names -------------------------------------------------
-enum { KT_EXTRACT_INSERT = 0, KT_EXTRACT_BIN, KT_INSERT_RECORDS, KT_FINALIZE, KT_TILE_FIRST, KT_REHASH, KT_L1_READS, KT_L1_RECORDS,
-       KT_L2_SPLIT, KT_COUNT_REGIONS, KT_FALLBACK, KT_SHARD_PACK, KT_L1_READS_UQ, KT_L1_READS16, KT_L2_REC6, KT_BIN16, KT_L1_WIRE6,
-       KT_MERGE_DECIDE, KT_MERGE_DECIDE_LONG, KT_MERGE_SCAN, KT_MERGE_WRITE, KT_MERGE_WRITE_LONG, KT_FQ_COUNT, KT_FQ_SCAN,
-       KT_FQ_INDEX, KT_FQ_CHECK, KT_FQ_DETAIL, KT_FQ_SUMS, KT_FQ_WRITE_PACKED, KT_FQ_WRITE_PAIRS, KT_TRIM_SEED, KT_TRIM_ALIGN,
-       KT_TRIM_SIZES, KT_TRIM_SCAN, KT_TRIM_WRITE, KT_SORT_HIST, KT_SORT_HIST_LOAD, KT_SORT_SCAN, KT_SORT_SCATTER, KT_SORT_GATHER,
-       KT_DUMP_SIZES, KT_DUMP_SCAN, KT_DUMP_WRITE, KT_UNITIG_LINKS, KT_UNITIG_MIN_JUMP, KT_UNITIG_CUT, KT_UNITIG_RANK_JUMP,
-       KT_UNITIG_SELECT, KT_UNITIG_SCAN, KT_UNITIG_WRITE, KT_UNITIG_DEPTH, KT_ALIGN_CHECK, KT_ALIGN_INDEX, KT_ALIGN_SWEEP, KT_ALIGN_LENGTHS,
-       KT_ALIGN_COUNT, KT_ALIGN_SCAN, KT_ALIGN_WRITE, KT_GAP_LENGTHS, KT_GAP_CHECK, KT_GAP_SORT, KT_GAP_DP, KT_DEPTH_CHECK,
-       KT_DEPTH_BEST, KT_DEPTH_MARK, KT_DEPTH_TILE_SUMS, KT_DEPTH_SCAN, KT_DEPTH_RESCAN, KT_DEPTH_CTG, KT_DEPTH_FILL, KT_PAIR_LENGTHS, KT_PAIR_CHECK,
-       KT_PAIR_BEST, KT_PAIR_CLASSIFY, KT_PAIR_CLASSIFY_LDS, KT_LASSM_LENGTHS, KT_LASSM_CHECK, KT_LASSM_PAIR_CHECK, KT_LASSM_COUNT,
-       KT_LASSM_PLAN, KT_LASSM_SCAN, KT_LASSM_SCATTER, KT_LASSM_TEXT, KT_LASSM_WALK, KT_LASSM_LENS, KT_LASSM_ENDS, KT_LASSM_WRITE, KT_LINK_LENGTHS,
-       KT_LINK_CHECK, KT_LINK_PAIR_CHECK, KT_LINK_GROUP_COUNT, KT_LINK_GROUP_FILL, KT_LINK_TILE_SCAN, KT_LINK_SCAN, KT_LINK_CANDS_COUNT, KT_LINK_CANDS_WRITE,
-       KT_LINK_SORT_HIST, KT_LINK_SORT_SCAN, KT_LINK_SORT_SCATTER, KT_LINK_HEADS, KT_LINK_REDUCE, KT_LINK_EMIT, KT_LINK_END_FIRST,
-       KT_SCAF_CHECK, KT_SCAF_END_FIRST, KT_SCAF_CHOOSE, KT_SCAF_EDGE, KT_SCAF_NEXT, KT_SCAF_MIN_JUMP, KT_SCAF_CUT, KT_SCAF_WEIGHT, KT_SCAF_RANK_JUMP,
-       KT_SCAF_POS_JUMP, KT_SCAF_SELECT, KT_SCAF_SCAN, KT_SCAF_MEMBERS, KT_SCAF_RECORDS, KT_SCAF_WRITE, KT_CLOSE_LENGTHS, KT_CLOSE_CHECK,
-       KT_CLOSE_CHECK_SCAF, KT_CLOSE_CLAIM, KT_CLOSE_CHECK_MEMBER, KT_CLOSE_GROUP_COUNT, KT_CLOSE_GROUP_FILL, KT_CLOSE_TILE_SCAN, KT_CLOSE_SCAN,
-       KT_CLOSE_ENDS, KT_CLOSE_CANDS_COUNT, KT_CLOSE_CANDS_WRITE, KT_CLOSE_DECIDE, KT_CLOSE_PLACE, KT_CLOSE_VOTE, KT_CLOSE_RECORDS, KT_CLOSE_WRITE,
-       KT_COUNT };
-// KT_FQ_SCAN, KT_MERGE_SCAN and KT_TRIM_SCAN label the front end's three uses of the one shared kc_scan_kernel (kc_scan.hpp); their
-// strings keep the names the uses were first reported under.  KT_SORT_SCAN and KT_DUMP_SCAN are the back end's two,
-// KT_UNITIG_SCAN the unitigs' (kc_scan_kernel<2>: bytes and unitig numbers in one pass), KT_ALIGN_SCAN the alignments' (the
-// reads' record counts).  KT_ALIGN_COUNT and KT_ALIGN_WRITE are the two passes of kc_align_reads_kernel.  KT_GAP_LENGTHS is
-// kc_align_gapped's use of kc_align_lengths_kernel, KT_PAIR_LENGTHS kc_pair_inserts'.  KT_DEPTH_SCAN is kc_aln_depths' use of kc_scan_kernel<1>
-// (the tile sums); KT_PAIR_CHECK and KT_PAIR_BEST are kc_pair_inserts' launches of the two kernels it shares with kc_aln_depths.
-// KT_LASSM_LENGTHS and KT_LASSM_CHECK are kc_local_assm's launches of kc_align_lengths_kernel and kc_depth_check_kernel, KT_LASSM_SCAN its
-// uses of kc_scan_kernel<2> (entries and text) and <1> (slots; the new lengths); KT_LASSM_COUNT and KT_LASSM_SCATTER are the two passes of
-// kc_lassm_cands_kernel.  KT_LINK_LENGTHS, KT_LINK_CHECK and KT_LINK_PAIR_CHECK are kc_ctg_links' launches of the three check kernels,
-// KT_LINK_SCAN its uses of kc_scan_kernel<1> (the tiles of the reads' slots, of the candidates and of the runs), KT_LINK_SORT_* its radix passes through
-// kc_sort.hpp's kernels; KT_LINK_GROUP_* and KT_LINK_CANDS_* are the two passes of kc_link_group_kernel and kc_link_cands_kernel.
-// KT_SCAF_END_FIRST is kc_scaffold's launch of kc_link_end_first_kernel, KT_SCAF_MIN_JUMP, KT_SCAF_CUT and KT_SCAF_RANK_JUMP its launches of the
-// three kc_unitig.hpp kernels (KT_SCAF_POS_JUMP: kc_unitig_rank_jump_kernel again, over the byte positions), KT_SCAF_SCAN its uses of
-// kc_scan_kernel<2> (bytes and scaffold numbers) and <1> (first members).
-// KT_CLOSE_LENGTHS, KT_CLOSE_CHECK, KT_CLOSE_GROUP_*, KT_CLOSE_TILE_SCAN and KT_CLOSE_SCAN are kc_close_gaps' launches of kc_align_lengths_kernel,
-// kc_depth_check_kernel, kc_link_group_kernel, kc_link_tile_scan_kernel and kc_scan_kernel<1> (the reads' slots, the joins' candidates, the
-// segments' and the fills' bytes); KT_CLOSE_CANDS_* are the two passes of kc_close_cands_kernel.
-static const char *const kt_names[KT_COUNT] = {"kc_extract_kernel<insert>", "kc_bin_reads_kernel", "kc_insert_records_kernel",
-                                               "kc_finalize_kernel", "kc_tile_first_kernel", "kc_rehash_kernel",
-                                               "kc_l1_reads_kernel", "kc_l1_records_kernel", "kc_l2_split_kernel",
-                                               "kc_count_kernel", "kc_flagged_to_table_kernel", "kc_shard_pack_kernel",
-                                               "kc_l1_reads_kernel<byte-loaded qualities>", "kc_l1_reads16_kernel", "kc_l2_rec6_kernel", "kc_bin16_kernel", "kc_l1_wire6_kernel",
-                                               "kc_merge_decide_kernel", "kc_merge_decide_kernel<long>", "kc_merge_scan_kernel",
-                                               "kc_merge_write_kernel", "kc_merge_write_kernel<long>", "kc_fq_count_kernel",
-                                               "kc_fq_scan_kernel", "kc_fq_index_kernel", "kc_fq_check_kernel",
-                                               "kc_fq_detail_kernel", "kc_fq_sums_kernel", "kc_fq_write_kernel<packed>",
-                                               "kc_fq_write_kernel<pairs>", "kc_trim_seed_kernel", "kc_trim_align_kernel",
-                                               "kc_trim_sizes_kernel", "kc_merge_scan_kernel<trim>", "kc_trim_write_kernel",
-                                               "kc_sort_hist_kernel", "kc_sort_hist_kernel<load>", "kc_sort_scan_kernel",
-                                               "kc_sort_scatter_kernel", "kc_sort_gather_kernel", "kc_dump_sizes_kernel",
-                                               "kc_dump_scan_kernel", "kc_dump_write_kernel", "kc_unitig_links_kernel",
-                                               "kc_unitig_min_jump_kernel", "kc_unitig_cut_kernel", "kc_unitig_rank_jump_kernel",
-                                               "kc_unitig_select_kernel", "kc_unitig_scan_kernel", "kc_unitig_write_kernel",
-                                               "kc_unitig_depth_kernel", "kc_align_check_kernel", "kc_align_index_kernel", "kc_align_sweep_kernel",
-                                               "kc_align_lengths_kernel", "kc_align_reads_kernel<count>", "kc_align_scan_kernel",
-                                               "kc_align_reads_kernel<write>", "kc_align_lengths_kernel<gap>", "kc_gap_check_kernel",
-                                               "kc_gap_sort_kernel", "kc_gap_dp_kernel", "kc_depth_check_kernel", "kc_depth_best_kernel",
-                                               "kc_depth_mark_kernel", "kc_depth_tile_sums_kernel", "kc_depth_scan_kernel",
-                                               "kc_depth_rescan_kernel", "kc_depth_ctg_kernel", "kc_depth_fill_kernel",
-                                               "kc_align_lengths_kernel<pair>", "kc_depth_check_kernel<pair>", "kc_depth_best_kernel<pair>",
-                                               "kc_pair_classify_kernel", "kc_pair_classify_kernel<lds>",
-                                               "kc_align_lengths_kernel<lassm>", "kc_depth_check_kernel<lassm>", "kc_lassm_pair_check_kernel",
-                                               "kc_lassm_cands_kernel<count>", "kc_lassm_plan_kernel", "kc_lassm_scan_kernel",
-                                               "kc_lassm_cands_kernel<write>", "kc_lassm_text_kernel", "kc_lassm_walk_kernel",
-                                               "kc_lassm_lens_kernel", "kc_lassm_ends_kernel", "kc_lassm_write_kernel",
-                                               "kc_align_lengths_kernel<links>", "kc_depth_check_kernel<links>", "kc_lassm_pair_check_kernel<links>",
-                                               "kc_link_group_kernel<count>", "kc_link_group_kernel<fill>", "kc_link_tile_scan_kernel", "kc_link_scan_kernel",
-                                               "kc_link_cands_kernel<count>", "kc_link_cands_kernel<write>", "kc_sort_hist_kernel<links>",
-                                               "kc_sort_scan_kernel<links>", "kc_sort_scatter_kernel<links>", "kc_link_heads_kernel",
-                                               "kc_link_reduce_kernel", "kc_link_emit_kernel", "kc_link_end_first_kernel",
-                                               "kc_scaf_check_kernel", "kc_link_end_first_kernel<scaffold>", "kc_scaf_choose_kernel",
-                                               "kc_scaf_edge_kernel", "kc_scaf_next_kernel", "kc_unitig_min_jump_kernel<scaffold>",
-                                               "kc_unitig_cut_kernel<scaffold>", "kc_scaf_weight_kernel", "kc_unitig_rank_jump_kernel<scaffold>",
-                                               "kc_unitig_rank_jump_kernel<scaffold pos>", "kc_scaf_select_kernel", "kc_scaf_scan_kernel",
-                                               "kc_scaf_members_kernel", "kc_scaf_records_kernel", "kc_scaf_write_kernel",
-                                               "kc_align_lengths_kernel<close>", "kc_depth_check_kernel<close>", "kc_close_check_scaf_kernel",
-                                               "kc_close_claim_kernel", "kc_close_check_member_kernel", "kc_link_group_kernel<close count>",
-                                               "kc_link_group_kernel<close fill>", "kc_link_tile_scan_kernel<close>", "kc_close_scan_kernel",
-                                               "kc_close_ends_kernel", "kc_close_cands_kernel<count>", "kc_close_cands_kernel<write>",
-                                               "kc_close_decide_kernel", "kc_close_place_kernel", "kc_close_vote_kernel",
-                                               "kc_close_records_kernel", "kc_close_write_kernel"};
+// ---- kernel timing kinds and their reported names: kc_kinds.hpp -------------------------------------
 struct kt_pending {
   hipEvent_t start, stop;
   int kind;
@@ -3254,6 +3176,7 @@ extern "C" int kc_lookup(kc_ctx *c, const uint64_t *queries, uint64_t nq, int on
   return rc;
 }
 
+#include "kc_api_call.hpp"  // what the entry points below share
 #include "kc_api_sort.hpp"  // kc_sort_results, kc_dump_text_device
 #include "kc_api_unitig.hpp"  // kc_build_unitigs
 #include "kc_api_align.hpp"  // kc_ctg_index_build, kc_ctg_index_clear, kc_align_reads

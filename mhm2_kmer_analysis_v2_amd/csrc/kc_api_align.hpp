@@ -4,19 +4,8 @@
 static_assert(sizeof(kc_read_aln) == 32, "a record is two 16-byte stores");
 static_assert(KC_ALIGN_MAX_READ_LEN == ALIGN_MAX_READ_LEN, "the header's limit is the kernels'");
 
-// device memory a call holds until it returns
-struct AlignBufs {
-  uint8_t *a = nullptr, *b = nullptr, *c = nullptr;
-  void release() {
-    if (a) (void)hipFree(a);
-    if (b) (void)hipFree(b);
-    if (c) (void)hipFree(c);
-    a = b = c = nullptr;
-  }
-};
-
 template <int NL>
-static int ctg_index_run(kc_ctx *c, AlignBufs &b, const uint8_t *seqs, uint64_t nbytes, const uint64_t *offsets, uint64_t n_ctgs, int on_device,
+static int ctg_index_run(kc_ctx *c, CallBufs &b, const uint8_t *seqs, uint64_t nbytes, const uint64_t *offsets, uint64_t n_ctgs, int on_device,
                          AlignIndex &ix, kc_ctg_index_stats *stats) {
   // the table: at most half full whatever the block holds (a block of n bytes has fewer than n windows)
   const uint64_t cap = next_pow2(std::max<uint64_t>(2 * nbytes, 64));
@@ -36,22 +25,18 @@ static int ctg_index_run(kc_ctx *c, AlignBufs &b, const uint8_t *seqs, uint64_t 
     d_in_offs = m.take<uint64_t>(n_ctgs + 1);
     return m.used;
   };
-  HIPCHK(hipMalloc((void **)&b.a, layout(nullptr)));
-  layout(b.a);
-  HIPCHK(hipMalloc((void **)&b.b, scratch(nullptr)));
-  scratch(b.b);
+  KCTRY(b.carve(layout));
+  KCTRY(b.carve(scratch));
   const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
   if (nbytes) HIPCHK(hipMemcpyAsync(d_seqs, seqs, nbytes, kind, c->stream));
   HIPCHK(hipMemcpyAsync(d_in_offs, offsets, (n_ctgs + 1) * 8, kind, c->stream));
   HIPCHK(hipMemsetAsync(d_status, 0, AIS_COUNT * 8, c->stream));
   HIPCHK(hipMemsetAsync(d_slots, 0, cap * 8, c->stream));
   const dim3 tpb(256);
-  auto blocks = [](uint64_t n) { return dim3((unsigned)((n + 255) / 256)); };
-  KCTRY(launch_timed(c, KT_ALIGN_CHECK, kc_align_check_kernel, blocks(std::max(nbytes, n_ctgs + 1)), tpb, 0, (const uint8_t *)d_seqs, nbytes,
+  KCTRY(launch_timed(c, KT_ALIGN_CHECK, kc_align_check_kernel, blocks_for(std::max(nbytes, n_ctgs + 1)), tpb, 0, (const uint8_t *)d_seqs, nbytes,
                      (const uint64_t *)d_in_offs, n_ctgs, d_offs, d_status));
   uint64_t h[AIS_COUNT];
-  HIPCHK(hipMemcpyAsync(h, d_status, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  KCTRY(read_back(c, h, d_status));
   if (h[AIS_BAD_BASE]) {
     snprintf(g_last_error, sizeof(g_last_error), "kc_ctg_index_build: a byte outside ACGTN and '_' in the block");
     return KC_ERR_BAD_BASE;
@@ -62,11 +47,10 @@ static int ctg_index_run(kc_ctx *c, AlignBufs &b, const uint8_t *seqs, uint64_t 
     return KC_ERR_INVALID_ARG;
   }
   if (nbytes) {
-    KCTRY(launch_timed(c, KT_ALIGN_INDEX, kc_align_index_kernel<NL>, blocks(nbytes), tpb, 0, (const uint8_t *)d_seqs, (uint32_t)nbytes, c->k,
+    KCTRY(launch_timed(c, KT_ALIGN_INDEX, kc_align_index_kernel<NL>, blocks_for(nbytes), tpb, 0, (const uint8_t *)d_seqs, (uint32_t)nbytes, c->k,
                        d_slots, cap - 1, d_status));
-    KCTRY(launch_timed(c, KT_ALIGN_SWEEP, kc_align_sweep_kernel, blocks(cap), tpb, 0, (const uint64_t *)d_slots, cap, d_status));
-    HIPCHK(hipMemcpyAsync(h, d_status, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    KCTRY(launch_timed(c, KT_ALIGN_SWEEP, kc_align_sweep_kernel, blocks_for(cap), tpb, 0, (const uint64_t *)d_slots, cap, d_status));
+    KCTRY(read_back(c, h, d_status));
   }
   ix.seqs = d_seqs;
   ix.offs = d_offs;
@@ -105,24 +89,19 @@ extern "C" int kc_ctg_index_build(kc_ctx *c, const uint8_t *seqs, uint64_t nbyte
              (unsigned long long)nbytes);
     return KC_ERR_INVALID_ARG;
   }
-  HIPCHK(hipSetDevice(c->cfg.device));
-  AlignBufs b;
-  AlignIndex ix;
-  memset(&ix, 0, sizeof(ix));
-  const int rc = with_nl(c, [&](auto nl) { return ctg_index_run<nl>(c, b, seqs, nbytes, offsets, n_ctgs, on_device, ix, stats); });
-  if (rc) {  // the earlier index, if any, answers as before
-    (void)hipStreamSynchronize(c->stream);
-    b.release();
-    return rc;
-  }
-  free_align_index(c);
-  c->d_ai = b.a;
-  c->ai = ix;
-  c->ai_nbytes = nbytes;
-  c->ai_ready = true;
-  b.a = nullptr;
-  b.release();
-  return KC_OK;
+  return call_with_bufs(c, [&](CallBufs &b) {
+    AlignIndex ix;
+    memset(&ix, 0, sizeof(ix));
+    KCTRY(with_nl(c, [&](auto nl) { return ctg_index_run<nl>(c, b, seqs, nbytes, offsets, n_ctgs, on_device, ix, stats); }));
+    // only now: had it failed, the earlier index, if any, would answer as before
+    free_align_index(c);
+    c->d_ai = (uint8_t *)ix.slots;  // the table is the front of the index's allocation, which the context keeps
+    b.disown(c->d_ai);
+    c->ai = ix;
+    c->ai_nbytes = nbytes;
+    c->ai_ready = true;
+    return (int)KC_OK;
+  });
 }
 
 template <int NL>
@@ -139,45 +118,27 @@ static int align_launch(kc_ctx *c, int kind, uint32_t wpl, dim3 grid, const uint
   return go(int_c<16>{});
 }
 
-static int align_run(kc_ctx *c, AlignBufs &b, const uint8_t *bases, const uint64_t *offsets, uint64_t nreads, int on_device, uint32_t seed_space,
+static int align_run(kc_ctx *c, CallBufs &b, const uint8_t *bases, const uint64_t *offsets, uint64_t nreads, int on_device, uint32_t seed_space,
                      uint32_t max_mismatches, kc_read_aln *alns, uint64_t capacity, uint64_t *read_first, uint64_t *n_alns,
                      kc_align_stats *stats) {
-  uint64_t *d_st, *d_first, *d_offs = nullptr;
-  auto layout = [&](uint8_t *base) {
+  uint64_t *d_st, *d_first;
+  StagedIn<uint64_t> offs = staged_offsets(offsets, nreads, on_device);
+  KCTRY(b.carve([&](uint8_t *base) {
     Carver m{base, 0};
     d_st = m.take<uint64_t>(ALS_COUNT);
     d_first = m.take<uint64_t>(nreads + 1);  // the reads' counts, scanned in place; the total behind them
-    if (!on_device) d_offs = m.take<uint64_t>(nreads + 1);
+    offs.reserve(m);
     return m.used;
-  };
-  HIPCHK(hipMalloc((void **)&b.a, layout(nullptr)));
-  layout(b.a);
-  if (!on_device) {
-    HIPCHK(hipMemcpyAsync(d_offs, offsets, (nreads + 1) * 8, hipMemcpyHostToDevice, c->stream));
-  } else {
-    d_offs = const_cast<uint64_t *>(offsets);
-  }
+  }));
+  KCTRY(offs.upload(c));
+  const uint64_t *d_offs = offs.d;
   HIPCHK(hipMemsetAsync(d_st, 0, ALS_COUNT * 8, c->stream));
-  HIPCHK(hipMemsetAsync(d_st + ALS_BAD_READ, 0xFF, 8, c->stream));
-  KCTRY(launch_timed(c, KT_ALIGN_LENGTHS, kc_align_lengths_kernel, dim3((unsigned)((nreads + 255) / 256)), dim3(256), 0, (const uint64_t *)d_offs,
-                     nreads, d_st));
-  uint64_t h[ALS_COUNT], last = 0;
-  HIPCHK(hipMemcpyAsync(h, d_st, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipMemcpyAsync(&last, d_offs + nreads, 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  if (h[ALS_BAD_READ] != ~0ull) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_align_reads: read %llu is longer than %d bases, or its offsets decrease",
-             (unsigned long long)h[ALS_BAD_READ], KC_ALIGN_MAX_READ_LEN);
-    return KC_ERR_INVALID_ARG;
-  }
+  uint64_t max_len, last;
+  KCTRY(check_read_lengths(c, KT_ALIGN_LENGTHS, "kc_align_reads", d_offs, nreads, d_st, &max_len, &last));
   if (last && !bases) return KC_ERR_INVALID_ARG;
   const uint8_t *d_bases = bases;
-  if (!on_device && last) {  // lengths are checked: the reads are the first `last` bytes
-    HIPCHK(hipMalloc((void **)&b.b, last));
-    HIPCHK(hipMemcpyAsync(b.b, bases, last, hipMemcpyHostToDevice, c->stream));
-    d_bases = b.b;
-  }
-  const uint64_t max_len = h[ALS_MAX_LEN], k = (uint64_t)c->k;
+  if (!on_device && last) KCTRY(upload_reads(c, b, bases, last, &d_bases));
+  const uint64_t k = (uint64_t)c->k;
   const uint64_t starts = max_len >= k ? (max_len - k) / seed_space + 1 : 0;
   const uint32_t wpl = (uint32_t)((starts + 63) / 64);
   const dim3 grid((unsigned)((nreads + ALIGN_WAVES - 1) / ALIGN_WAVES));
@@ -189,8 +150,8 @@ static int align_run(kc_ctx *c, AlignBufs &b, const uint8_t *bases, const uint64
   KCTRY(pass(KT_ALIGN_COUNT, nullptr));
   KCTRY(launch_timed(c, KT_ALIGN_SCAN, kc_scan_kernel<1>, dim3(1), dim3(SCAN_TPB), 0, ScanArrays<1>{{d_first}}, nreads, d_st + ALS_TOTAL));
   HIPCHK(hipMemcpyAsync(d_first + nreads, d_st + ALS_TOTAL, 8, hipMemcpyDeviceToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(h, d_st, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  uint64_t h[ALS_COUNT];
+  KCTRY(read_back(c, h, d_st));
   const uint64_t total = h[ALS_TOTAL];
   *n_alns = total;
   if (stats) {
@@ -209,10 +170,7 @@ static int align_run(kc_ctx *c, AlignBufs &b, const uint8_t *bases, const uint64
     return KC_ERR_CAPACITY;
   }
   uint4 *d_alns = (uint4 *)alns;
-  if (!on_device && total) {
-    HIPCHK(hipMalloc((void **)&b.c, total * sizeof(kc_read_aln)));
-    d_alns = (uint4 *)b.c;
-  }
+  if (!on_device) KCTRY(b.alloc(&d_alns, total * sizeof(kc_read_aln)));
   if (total) KCTRY(pass(KT_ALIGN_WRITE, d_alns));
   if (!on_device && total) HIPCHK(hipMemcpyAsync(alns, d_alns, total * sizeof(kc_read_aln), hipMemcpyDeviceToHost, c->stream));
   if (read_first)
@@ -225,18 +183,12 @@ extern "C" int kc_align_reads(kc_ctx *c, const uint8_t *bases, const uint64_t *o
                               uint32_t max_mismatches, kc_read_aln *alns, uint64_t capacity, uint64_t *read_first, uint64_t *n_alns,
                               kc_align_stats *stats) {
   if (!c || !n_alns || !seed_space || (nreads && !offsets) || nreads > 0xFFFFFFFFull) return KC_ERR_INVALID_ARG;
-  if (on_device && ((uintptr_t)alns & 15)) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_align_reads: a device record array is 16-byte aligned");
-    return KC_ERR_INVALID_ARG;
-  }
+  if (on_device && ((uintptr_t)alns & 15)) return misaligned_records("kc_align_reads");
   *n_alns = 0;
   if (stats) memset(stats, 0, sizeof(*stats));
-  if (!c->ai_ready) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_align_reads: no contig index (kc_ctg_index_build)");
-    return KC_ERR_STATE;
-  }
-  HIPCHK(hipSetDevice(c->cfg.device));
+  if (!c->ai_ready) return no_ctg_index("kc_align_reads");
   if (!nreads) {
+    HIPCHK(hipSetDevice(c->cfg.device));
     if (alns && read_first) {  // the one entry of no reads: the total
       if (on_device) {
         HIPCHK(hipMemsetAsync(read_first, 0, 8, c->stream));
@@ -247,9 +199,7 @@ extern "C" int kc_align_reads(kc_ctx *c, const uint8_t *bases, const uint64_t *o
     }
     return KC_OK;
   }
-  AlignBufs b;
-  const int rc = align_run(c, b, bases, offsets, nreads, on_device, seed_space, max_mismatches, alns, capacity, read_first, n_alns, stats);
-  if (rc) (void)hipStreamSynchronize(c->stream);
-  b.release();
-  return rc;
+  return call_with_bufs(c, [&](CallBufs &b) {
+    return align_run(c, b, bases, offsets, nreads, on_device, seed_space, max_mismatches, alns, capacity, read_first, n_alns, stats);
+  });
 }

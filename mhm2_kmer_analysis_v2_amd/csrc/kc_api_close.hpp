@@ -1,6 +1,5 @@
 // kc_api_close.hpp -- kc_close_gaps (kernels in kc_close.hpp).  Part of kc_api.hip's translation unit, behind
-// kc_api_scaffold.hpp; the buffers are kc_api_lassm.hpp's, the record check kc_api_depth.hpp's, the length check
-// kc_api_align.hpp's, the grouping of the records by read kc_links.hpp's kernels as kc_api_links.hpp launches them.
+// kc_api_scaffold.hpp; the grouping of the records by read is kc_links.hpp's kernels as kc_api_links.hpp launches them.
 
 static_assert(sizeof(kc_close_params) == 32 && sizeof(kc_closure) == 32 && sizeof(kc_close_stats) == 128, "the header's layouts");
 static_assert(KC_CLOSE_HEAD == CLOSE_HEAD && KC_CLOSE_NOT_A_GAP == CLOSE_NOT_A_GAP && KC_CLOSE_NO_READS == CLOSE_NO_READS &&
@@ -28,7 +27,7 @@ struct CloseIo {
   kc_close_stats *stats;
 };
 
-static int close_run(kc_ctx *c, LassmBufs &b, const CloseIo &io, const kc_close_params &p) {
+static int close_run(kc_ctx *c, CallBufs &b, const CloseIo &io, const kc_close_params &p) {
   const uint32_t n = c->ai.n_ctgs;
   const uint64_t nreads = io.nreads, n_alns = io.n_alns, n_scaf = io.n_scaffolds;
   const uint64_t rtiles = (nreads + LINK_SCAN_TILE - 1) / LINK_SCAN_TILE, mtiles = ((uint64_t)n + LINK_SCAN_TILE - 1) / LINK_SCAN_TILE;
@@ -41,12 +40,15 @@ static int close_run(kc_ctx *c, LassmBufs &b, const CloseIo &io, const kc_close_
   memset(&d, 0, sizeof(d));
   CloseArgs ca;
   memset(&ca, 0, sizeof(ca));
-  uint64_t *st, *d_als, *d_offs = nullptr, *jcnt, *jbase, *seglen, *segbase, *filllen, *fillbase;
+  uint64_t *st, *d_als, *jcnt, *jbase, *seglen, *segbase, *filllen, *fillbase;
   uint32_t *ishead, *jcur, *owner, *table, *seg, *fill;
-  uint4 *d_alns = nullptr, *d_scaf = nullptr, *d_members = nullptr, *dec, *members_w;
-  uint8_t *d_bases = nullptr;
+  uint4 *dec, *members_w;
+  StagedIn<uint64_t> offs = staged_offsets(io.offsets, nreads, dev);
+  StagedIn<uint4> alns{io.alns, dev, n_alns * sizeof(kc_gap_aln)}, scaf{io.scaffolds, dev, n_scaf * sizeof(kc_scaffold_rec)};
+  StagedIn<uint4> members{io.members, dev, (size_t)n * sizeof(kc_scaf_member)};
+  StagedIn<uint8_t> bases{io.bases, dev, nbases};
   size_t zeroed = 0, ff_from = 0, ff_to = 0;
-  auto layout = [&](uint8_t *base) {
+  KCTRY(b.carve([&](uint8_t *base) {
     Carver m{base, 0};
     st = m.take<uint64_t>(CLS_COUNT);
     a.st = m.take<uint64_t>(LKS_COUNT);
@@ -72,82 +74,39 @@ static int close_run(kc_ctx *c, LassmBufs &b, const CloseIo &io, const kc_close_
     seg = m.take<uint32_t>((uint64_t)n + 1);
     fill = m.take<uint32_t>(n);
     members_w = m.take<uint4>(n);
-    if (!dev) {
-      d_offs = m.take<uint64_t>(nreads + 1);
-      d_alns = m.take<uint4>(2 * n_alns);
-      d_scaf = m.take<uint4>(2 * n_scaf);
-      d_members = m.take<uint4>(n);
-    }
+    offs.reserve(m);
+    alns.reserve(m);
+    scaf.reserve(m);
+    members.reserve(m);
     return m.used;
-  };
-  HIPCHK(hipMalloc((void **)&b.p[0], layout(nullptr)));
-  layout(b.p[0]);
-  if (dev) {
-    d_offs = const_cast<uint64_t *>(io.offsets);
-    d_alns = (uint4 *)const_cast<kc_gap_aln *>(io.alns);
-    d_scaf = (uint4 *)const_cast<kc_scaffold_rec *>(io.scaffolds);
-    d_members = (uint4 *)const_cast<kc_scaf_member *>(io.members);
-    d_bases = const_cast<uint8_t *>(io.bases);
-  } else {
-    if (nreads) HIPCHK(hipMemcpyAsync(d_offs, io.offsets, (nreads + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    if (n_alns) HIPCHK(hipMemcpyAsync(d_alns, io.alns, n_alns * sizeof(kc_gap_aln), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(d_scaf, io.scaffolds, n_scaf * sizeof(kc_scaffold_rec), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(d_members, io.members, (size_t)n * sizeof(kc_scaf_member), hipMemcpyHostToDevice, c->stream));
-  }
+  }));
+  KCTRY(offs.upload(c));
+  KCTRY(alns.upload(c));
+  KCTRY(scaf.upload(c));
+  KCTRY(members.upload(c));
+  const uint64_t *d_offs = offs.d;
+  const uint4 *d_alns = alns.d, *d_scaf = scaf.d, *d_members = members.d;
   HIPCHK(hipMemsetAsync(st, 0, zeroed, c->stream));
   HIPCHK(hipMemsetAsync(owner, 0xFF, ff_to - ff_from, c->stream));
   HIPCHK(hipMemsetAsync(st + CLS_BAD, 0xFF, 8, c->stream));
   HIPCHK(hipMemsetAsync(d.st + DPS_BAD, 0xFF, 8, c->stream));
-  HIPCHK(hipMemsetAsync(d_als + ALS_BAD_READ, 0xFF, 8, c->stream));
-  auto blocks = [](uint64_t items) { return dim3((unsigned)((items + CLOSE_TPB - 1) / CLOSE_TPB)); };
-  auto stat_blocks = [](uint64_t items) { return dim3((unsigned)((items + LINK_STAT_TPB - 1) / LINK_STAT_TPB)); };
+  auto blocks = [](uint64_t items) { return blocks_for(items, CLOSE_TPB); };
+  auto stat_blocks = [](uint64_t items) { return blocks_for(items, LINK_STAT_TPB); };
   const dim3 tpb(CLOSE_TPB), stat_tpb(LINK_STAT_TPB), per_member = blocks(n), per_member_wave = blocks((uint64_t)n * 64);
-  auto lowest_bad = [&](uint64_t *bad) {
-    *bad = ~0ull;
-    HIPCHK(hipMemcpyAsync(bad, st + CLS_BAD, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return (int)KC_OK;
-  };
   // ---- the checks, in the order reads, records, scaffolds, members: nothing is stored before the last has passed
-  if (nreads) {
-    KCTRY(launch_timed(c, KT_CLOSE_LENGTHS, kc_align_lengths_kernel, blocks(nreads), tpb, 0, (const uint64_t *)d_offs, nreads, d_als));
-    uint64_t bad_read = ~0ull;
-    HIPCHK(hipMemcpyAsync(&bad_read, d_als + ALS_BAD_READ, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (bad_read != ~0ull) {
-      snprintf(g_last_error, sizeof(g_last_error), "kc_close_gaps: read %llu is longer than %d bases, or its offsets decrease",
-               (unsigned long long)bad_read, KC_ALIGN_MAX_READ_LEN);
-      return KC_ERR_INVALID_ARG;
-    }
-  }
-  d.offs = c->ai.offs;
-  d.n_ctgs = n;
-  d.nbytes = (uint32_t)c->ai_nbytes;
-  d.alns = d_alns;
-  d.n_alns = n_alns;
-  d.nreads = nreads;
-  d.offsets = d_offs;
-  KCTRY(depth_check(c, d, KT_CLOSE_CHECK, 1, "kc_close_gaps"));
-  uint64_t bad;
-  KCTRY(launch_timed(c, KT_CLOSE_CHECK_SCAF, kc_close_check_scaf_kernel, blocks(n_scaf), tpb, 0, (const uint4 *)d_scaf, n_scaf, n, ishead, st));
-  KCTRY(lowest_bad(&bad));
-  if (bad != ~0ull) {
-    snprintf(g_last_error, sizeof(g_last_error),
-             "kc_close_gaps: scaffold %llu is invalid (no member, not where its predecessor ends, or the last does not end at %u members)",
-             (unsigned long long)bad, n);
-    return KC_ERR_INVALID_ARG;
-  }
+  KCTRY(check_read_lengths(c, KT_CLOSE_LENGTHS, "kc_close_gaps", d_offs, nreads, d_als));
+  KCTRY(check_read_records(c, d, KT_CLOSE_CHECK, "kc_close_gaps", d_alns, n_alns, d_offs, nreads));
+  KCTRY(launch_timed(c, KT_CLOSE_CHECK_SCAF, kc_close_check_scaf_kernel, blocks(n_scaf), tpb, 0, d_scaf, n_scaf, n, ishead, st));
+  KCTRY(lowest_bad(c, st + CLS_BAD,
+                   "%s: scaffold %llu is invalid (no member, not where its predecessor ends, or the last does not end at %u members)",
+                   "kc_close_gaps", n));
   KCTRY(launch_timed(c, KT_CLOSE_CLAIM, kc_close_claim_kernel, per_member, tpb, 0, (const uint4 *)d_members, n, owner));
   KCTRY(launch_timed(c, KT_CLOSE_CHECK_MEMBER, kc_close_check_member_kernel, per_member, tpb, 0, (const uint4 *)d_members, n,
                      (const uint32_t *)ishead, (const uint32_t *)owner, c->ai.offs, st));
-  KCTRY(lowest_bad(&bad));
-  if (bad != ~0ull) {
-    snprintf(g_last_error, sizeof(g_last_error),
-             "kc_close_gaps: member %llu is invalid (contig or orient out of range, reserved bytes, a contig's second member, a head's join "
-             "not 0, a join out of range or an overlap not shorter than both contigs)",
-             (unsigned long long)bad);
-    return KC_ERR_INVALID_ARG;
-  }
+  KCTRY(lowest_bad(c, st + CLS_BAD,
+                   "%s: member %llu is invalid (contig or orient out of range, reserved bytes, a contig's second member, a head's join "
+                   "not 0, a join out of range or an overlap not shorter than both contigs)",
+                   "kc_close_gaps"));
   // ---- the passing records by read, as kc_ctg_links groups them
   a.offs = c->ai.offs;
   a.n_ctgs = n;
@@ -164,10 +123,8 @@ static int close_run(kc_ctx *c, LassmBufs &b, const CloseIo &io, const kc_close_
   uint64_t slots = 0, n_cands = 0;
   if (n_alns && nreads) {
     KCTRY(launch_timed(c, KT_CLOSE_GROUP_COUNT, kc_link_group_kernel<false>, stat_blocks(n_alns), stat_tpb, 0, a));
-    KCTRY(launch_timed(c, KT_CLOSE_TILE_SCAN, kc_link_tile_scan_kernel, dim3((unsigned)rtiles), dim3(LINK_TILE), 0, a.rfirst, nreads, a.rbase));
-    KCTRY(launch_timed(c, KT_CLOSE_SCAN, kc_scan_kernel<1>, dim3(1), dim3(SCAN_TPB), 0, ScanArrays<1>{{a.rbase}}, rtiles, a.st + LKS_SLOT_TOTAL));
-    HIPCHK(hipMemcpyAsync(&slots, a.st + LKS_SLOT_TOTAL, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    KCTRY(tiled_scan(c, KT_CLOSE_TILE_SCAN, KT_CLOSE_SCAN, a.rfirst, nreads, a.rbase, a.st + LKS_SLOT_TOTAL));
+    KCTRY(read_back(c, &slots, a.st + LKS_SLOT_TOTAL, 1));
   }
   // ---- the gap joins' ends, and the candidates: count, scan, write
   KCTRY(launch_timed(c, KT_CLOSE_ENDS, kc_close_ends_kernel, per_member, tpb, 0, (const uint4 *)d_members, n, (const uint32_t *)ishead, table));
@@ -186,25 +143,20 @@ static int close_run(kc_ctx *c, LassmBufs &b, const CloseIo &io, const kc_close_
   ca.st = st;
   if (slots) {
     // the slots, and a host array's read bytes: behind the checks, so that no bad offset sizes an allocation
-    auto work = [&](uint8_t *base) {
+    KCTRY(b.carve([&](uint8_t *base) {
       Carver m{base, 0};
       a.info = m.take<uint4>(slots);
-      if (!dev) d_bases = m.take<uint8_t>(nbases);
+      bases.reserve(m);
       return m.used;
-    };
-    HIPCHK(hipMalloc((void **)&b.p[1], work(nullptr)));
-    work(b.p[1]);
-    if (!dev && nbases) HIPCHK(hipMemcpyAsync(d_bases, io.bases, nbases, hipMemcpyHostToDevice, c->stream));
+    }));
+    KCTRY(bases.upload(c));
     ca.info = a.info;
     KCTRY(launch_timed(c, KT_CLOSE_GROUP_FILL, kc_link_group_kernel<true>, blocks(n_alns), tpb, 0, a));
     KCTRY(launch_timed(c, KT_CLOSE_CANDS_COUNT, kc_close_cands_kernel<false>, stat_blocks(nreads), stat_tpb, 0, ca));
-    KCTRY(launch_timed(c, KT_CLOSE_TILE_SCAN, kc_link_tile_scan_kernel, dim3((unsigned)mtiles), dim3(LINK_TILE), 0, jcnt, (uint64_t)n, jbase));
-    KCTRY(launch_timed(c, KT_CLOSE_SCAN, kc_scan_kernel<1>, dim3(1), dim3(SCAN_TPB), 0, ScanArrays<1>{{jbase}}, mtiles, st + CLS_JCAND_TOTAL));
-    HIPCHK(hipMemcpyAsync(&n_cands, st + CLS_JCAND_TOTAL, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    KCTRY(tiled_scan(c, KT_CLOSE_TILE_SCAN, KT_CLOSE_SCAN, jcnt, n, jbase, st + CLS_JCAND_TOTAL));
+    KCTRY(read_back(c, &n_cands, st + CLS_JCAND_TOTAL, 1));
     if (n_cands) {
-      HIPCHK(hipMalloc((void **)&b.p[2], n_cands * sizeof(uint4)));
-      ca.cands = (uint4 *)b.p[2];
+      KCTRY(b.alloc(&ca.cands, n_cands * sizeof(uint4)));
       KCTRY(launch_timed(c, KT_CLOSE_CANDS_WRITE, kc_close_cands_kernel<true>, blocks(nreads), tpb, 0, ca));
     }
   }
@@ -212,14 +164,11 @@ static int close_run(kc_ctx *c, LassmBufs &b, const CloseIo &io, const kc_close_
   KCTRY(launch_timed(c, KT_CLOSE_DECIDE, kc_close_decide_kernel, per_member_wave, tpb, 0, (const uint4 *)d_members, n, (const uint32_t *)ishead,
                      (const uint64_t *)jcnt, (const uint64_t *)jbase, (const uint32_t *)jcur, (const uint4 *)ca.cands, p.min_reads,
                      p.min_agree_permille, c->ai.seqs, c->ai.offs, dec, seglen, filllen));
-  KCTRY(launch_timed(c, KT_CLOSE_TILE_SCAN, kc_link_tile_scan_kernel, dim3((unsigned)mtiles), dim3(LINK_TILE), 0, seglen, (uint64_t)n, segbase));
-  KCTRY(launch_timed(c, KT_CLOSE_SCAN, kc_scan_kernel<1>, dim3(1), dim3(SCAN_TPB), 0, ScanArrays<1>{{segbase}}, mtiles, st + CLS_SEG_TOTAL));
-  KCTRY(launch_timed(c, KT_CLOSE_TILE_SCAN, kc_link_tile_scan_kernel, dim3((unsigned)mtiles), dim3(LINK_TILE), 0, filllen, (uint64_t)n, fillbase));
-  KCTRY(launch_timed(c, KT_CLOSE_SCAN, kc_scan_kernel<1>, dim3(1), dim3(SCAN_TPB), 0, ScanArrays<1>{{fillbase}}, mtiles, st + CLS_FILL_TOTAL));
+  KCTRY(tiled_scan(c, KT_CLOSE_TILE_SCAN, KT_CLOSE_SCAN, seglen, n, segbase, st + CLS_SEG_TOTAL));
+  KCTRY(tiled_scan(c, KT_CLOSE_TILE_SCAN, KT_CLOSE_SCAN, filllen, n, fillbase, st + CLS_FILL_TOTAL));
   uint64_t h[CLS_COUNT], hl[LKS_COUNT];
   HIPCHK(hipMemcpyAsync(h, st, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipMemcpyAsync(hl, a.st, sizeof(hl), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  KCTRY(read_back(c, hl, a.st));
   const uint64_t total = h[CLS_SEG_TOTAL], fill_total = h[CLS_FILL_TOTAL];
   if (total >= (1ull << 31)) {
     snprintf(g_last_error, sizeof(g_last_error), "kc_close_gaps: the scaffolds are %llu bytes, a block holds fewer than 2^31", (unsigned long long)total);
@@ -227,39 +176,33 @@ static int close_run(kc_ctx *c, LassmBufs &b, const CloseIo &io, const kc_close_
   }
   const bool fits = io.seqs_out && io.capacity >= total;
   const bool want_recs = fits && io.scaffolds_out != nullptr;
-  uint8_t *buf = nullptr, *d_seqs = nullptr;
-  uint64_t *d_offsets = nullptr;
-  uint4 *d_scaf_out = nullptr, *d_members_out = nullptr, *d_closures = nullptr;
+  uint8_t *buf = nullptr;
   uint32_t *acc = nullptr;
-  auto outs = [&](uint8_t *base) {
+  StagedOut<uint8_t> seqs{io.seqs_out, dev, total};
+  StagedOut<uint64_t> offsets{io.offsets_out, dev, (n_scaf + 1) * 8};
+  StagedOut<uint4> scaf_out{io.scaffolds_out, dev, n_scaf * sizeof(kc_scaffold_rec)}, members_out{io.members_out, dev, (size_t)n * sizeof(kc_scaf_member)};
+  StagedOut<uint4> closures{io.closures, dev, (size_t)n * sizeof(kc_closure)};
+  KCTRY(b.carve([&](uint8_t *base) {
     Carver m{base, 0};
     buf = m.take<uint8_t>(fill_total);
     acc = m.take<uint32_t>(2 * n_scaf);
-    if (!dev && fits) {
-      d_seqs = m.take<uint8_t>(total);
-      if (io.offsets_out) d_offsets = m.take<uint64_t>(n_scaf + 1);
-      if (io.scaffolds_out) d_scaf_out = m.take<uint4>(2 * n_scaf);
-      if (io.members_out) d_members_out = m.take<uint4>(n);
-      if (io.closures) d_closures = m.take<uint4>(2 * (uint64_t)n);
-    }
+    seqs.reserve(m, fits);
+    offsets.reserve(m, fits);
+    scaf_out.reserve(m, fits);
+    members_out.reserve(m, fits);
+    closures.reserve(m, fits);
     return m.used;
-  };
-  HIPCHK(hipMalloc((void **)&b.p[3], outs(nullptr)));
-  outs(b.p[3]);
-  if (dev && fits) {
-    d_seqs = io.seqs_out;
-    d_offsets = io.offsets_out;
-    d_scaf_out = (uint4 *)io.scaffolds_out;
-    d_members_out = (uint4 *)io.members_out;
-    d_closures = (uint4 *)io.closures;
-  }
+  }));
+  uint8_t *const d_seqs = seqs.d;
+  uint64_t *const d_offsets = offsets.d;
+  uint4 *const d_scaf_out = scaf_out.d, *const d_members_out = members_out.d, *const d_closures = closures.d;
   HIPCHK(hipMemsetAsync(acc, 0, 2 * n_scaf * 4, c->stream));
   KCTRY(launch_timed(c, KT_CLOSE_PLACE, kc_close_place_kernel, stat_blocks(n), stat_tpb, 0, (const uint4 *)d_members, n, (const uint4 *)dec,
                      (const uint64_t *)seglen, (const uint64_t *)segbase, (const uint64_t *)filllen, (const uint64_t *)fillbase, (uint32_t)total,
                      (const uint4 *)d_scaf, n_scaf, seg, fill, members_w, d_members_out, d_closures, want_recs ? acc : (uint32_t *)nullptr, st));
   if (fill_total)
     KCTRY(launch_timed(c, KT_CLOSE_VOTE, kc_close_vote_kernel, stat_blocks((uint64_t)n * 64), stat_tpb, 0, (const uint4 *)dec, n, (const uint64_t *)jcnt,
-                       (const uint64_t *)jbase, (const uint32_t *)jcur, (const uint4 *)ca.cands, (const uint8_t *)d_bases,
+                       (const uint64_t *)jbase, (const uint32_t *)jcur, (const uint4 *)ca.cands, (const uint8_t *)bases.d,
                        (const uint32_t *)fill, buf, d_closures, st));
   if (fits) {
     if (d_offsets || d_scaf_out)
@@ -269,16 +212,13 @@ static int close_run(kc_ctx *c, LassmBufs &b, const CloseIo &io, const kc_close_
     KCTRY(launch_timed(c, KT_CLOSE_WRITE, kc_close_write_kernel, blocks((total + mis + 15) / 16), tpb, 0, (const uint4 *)members_w,
                        (const uint32_t *)seg, (const uint32_t *)fill, n, c->ai.seqs, c->ai.offs, (const uint8_t *)buf, mis, (uint32_t)total,
                        d_seqs));
-    if (!dev) {
-      HIPCHK(hipMemcpyAsync(io.seqs_out, d_seqs, total, hipMemcpyDeviceToHost, c->stream));
-      if (d_offsets) HIPCHK(hipMemcpyAsync(io.offsets_out, d_offsets, (n_scaf + 1) * 8, hipMemcpyDeviceToHost, c->stream));
-      if (d_scaf_out) HIPCHK(hipMemcpyAsync(io.scaffolds_out, d_scaf_out, n_scaf * sizeof(kc_scaffold_rec), hipMemcpyDeviceToHost, c->stream));
-      if (d_members_out) HIPCHK(hipMemcpyAsync(io.members_out, d_members_out, (size_t)n * sizeof(kc_scaf_member), hipMemcpyDeviceToHost, c->stream));
-      if (d_closures) HIPCHK(hipMemcpyAsync(io.closures, d_closures, (size_t)n * sizeof(kc_closure), hipMemcpyDeviceToHost, c->stream));
-    }
+    KCTRY(seqs.download(c));
+    KCTRY(offsets.download(c));
+    KCTRY(scaf_out.download(c));
+    KCTRY(members_out.download(c));
+    KCTRY(closures.download(c));
   }
-  HIPCHK(hipMemcpyAsync(h, st, sizeof(h), hipMemcpyDeviceToHost, c->stream));  // again: the place kernel and the vote count
-  HIPCHK(hipStreamSynchronize(c->stream));
+  KCTRY(read_back(c, h, st));  // again: the place kernel and the vote count
   *io.nbytes_out = total;
   if (io.stats) {
     kc_close_stats s;
@@ -344,18 +284,13 @@ extern "C" int kc_close_gaps(kc_ctx *c, const uint8_t *bases, const uint64_t *of
   }
   if (!c || (nreads && (!offsets || !bases)) || (n_alns && !alns) || !scaffolds || !members || nreads > 0xFFFFFFFFull) return KC_ERR_INVALID_ARG;
   if (on_device && (((uintptr_t)alns | (uintptr_t)scaffolds | (uintptr_t)members | (uintptr_t)scaffolds_out | (uintptr_t)members_out |
-                     (uintptr_t)closures) & 15)) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_close_gaps: a device record array is 16-byte aligned");
-    return KC_ERR_INVALID_ARG;
-  }
+                     (uintptr_t)closures) & 15))
+    return misaligned_records("kc_close_gaps");
   if (on_device && (((uintptr_t)offsets | (uintptr_t)offsets_out) & 7)) {
     snprintf(g_last_error, sizeof(g_last_error), "kc_close_gaps: device offsets are 8-byte aligned");
     return KC_ERR_INVALID_ARG;
   }
-  if (!c->ai_ready) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_close_gaps: no contig index (kc_ctg_index_build)");
-    return KC_ERR_STATE;
-  }
+  if (!c->ai_ready) return no_ctg_index("kc_close_gaps");
   if (c->ai.n_ctgs == 0 || c->ai.n_ctgs >= (1u << 31)) {
     snprintf(g_last_error, sizeof(g_last_error), "kc_close_gaps: %u contigs, oriented node ids are 32-bit (1 .. 2^31 - 1 contigs)", c->ai.n_ctgs);
     return c->ai.n_ctgs ? KC_ERR_CAPACITY : KC_ERR_STATE;
@@ -368,12 +303,7 @@ extern "C" int kc_close_gaps(kc_ctx *c, const uint8_t *bases, const uint64_t *of
     snprintf(g_last_error, sizeof(g_last_error), "kc_close_gaps: scaffold 0 is invalid (no scaffolds over %u contigs)", c->ai.n_ctgs);
     return KC_ERR_INVALID_ARG;
   }
-  HIPCHK(hipSetDevice(c->cfg.device));
-  LassmBufs b;
   const CloseIo io{bases,    offsets,     nreads,        alns,        n_alns,   scaffolds,  n_scaffolds, members, on_device,
                    seqs_out, capacity,    offsets_out,   scaffolds_out, members_out, closures, nbytes_out,  stats};
-  const int rc = close_run(c, b, io, *p);
-  if (rc) (void)hipStreamSynchronize(c->stream);
-  b.release();
-  return rc;
+  return call_with_bufs(c, [&](CallBufs &b) { return close_run(c, b, io, *p); });
 }

@@ -1,5 +1,5 @@
 // kc_api_depth.hpp -- kc_ctg_index_info, kc_aln_depths, kc_pair_inserts (kernels in kc_depth.hpp).  Part of kc_api.hip's
-// translation unit, behind kc_api_gap.hpp; AlignBufs and the length check are kc_api_align.hpp's.
+// translation unit, behind kc_api_gap.hpp.
 
 static_assert(sizeof(kc_ctg_depth) == 32, "a record is two 16-byte stores");
 static_assert(sizeof(kc_pair_rec) == 16, "a record is one 16-byte store");
@@ -13,43 +13,25 @@ static_assert(KC_INSERT_MAX == PAIR_INSERT_MAX && KC_PAIR_NONE == PAIR_NONE && K
 
 extern "C" int kc_ctg_index_info(kc_ctx *c, uint64_t *nbytes, uint64_t *n_ctgs) {
   if (!c) return KC_ERR_INVALID_ARG;
-  if (!c->ai_ready) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_ctg_index_info: no contig index (kc_ctg_index_build)");
-    return KC_ERR_STATE;
-  }
+  if (!c->ai_ready) return no_ctg_index("kc_ctg_index_info");
   if (nbytes) *nbytes = c->ai_nbytes;
   if (n_ctgs) *n_ctgs = c->ai.n_ctgs;
   return KC_OK;
 }
 
-static dim3 depth_blocks(uint64_t n) { return dim3((unsigned)((n + 255) / 256)); }
-
-// the validity pass and its verdict; nothing has been stored when it returns
-static int depth_check(kc_ctx *c, const DepthArgs &a, int kind, int use_reads, const char *who) {
-  if (!a.n_alns) return KC_OK;
-  KCTRY(launch_timed(c, kind, kc_depth_check_kernel, depth_blocks(a.n_alns), dim3(256), 0, a, use_reads));
-  uint64_t bad = 0;
-  HIPCHK(hipMemcpyAsync(&bad, a.st + DPS_BAD, 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  if (bad != ~0ull) {
-    snprintf(g_last_error, sizeof(g_last_error), "%s: record %llu is not a valid kc_gap_aln for this index%s", who, (unsigned long long)bad,
-             use_reads ? " and these reads" : "");
-    return KC_ERR_INVALID_ARG;
-  }
-  return KC_OK;
-}
-
-static int depth_run(kc_ctx *c, AlignBufs &b, const kc_gap_aln *alns, uint64_t n_alns, uint64_t nreads, int on_device, uint32_t min_score,
+static int depth_run(kc_ctx *c, CallBufs &b, const kc_gap_aln *alns, uint64_t n_alns, uint64_t nreads, int on_device, uint32_t min_score,
                      uint32_t min_len, uint32_t edge_clip, uint32_t flags, uint16_t *depths, kc_ctg_depth *ctgs, kc_depth_stats *stats) {
   const uint64_t nbytes = c->ai_nbytes, n_ctgs = c->ai.n_ctgs;
   const uint64_t tiles = (nbytes + DEPTH_TILE - 1) / DEPTH_TILE;
   const bool best_only = (flags & DEPTH_BEST_ONLY) != 0, per_contig = (flags & DEPTH_PER_CONTIG) != 0;
+  const bool dev = on_device != 0;
   DepthArgs a;
   memset(&a, 0, sizeof(a));
-  uint4 *d_in = nullptr, *d_ctgs = nullptr;
-  uint16_t *d_depths = nullptr;
+  StagedIn<uint4> in{alns, dev, n_alns * sizeof(kc_gap_aln)};
+  StagedOut<uint16_t> out_depths{depths, dev, nbytes * 2};
+  StagedOut<uint4> out_ctgs{ctgs, dev, n_ctgs * sizeof(kc_ctg_depth)};
   size_t zeroed = 0;  // the front of the scratch is counters and sums: one memset
-  auto layout = [&](uint8_t *base) {
+  KCTRY(b.carve([&](uint8_t *base) {
     Carver m{base, 0};
     a.st = m.take<uint64_t>(DPS_COUNT);
     a.diff = m.take<uint32_t>(tiles * DEPTH_TILE);
@@ -62,56 +44,44 @@ static int depth_run(kc_ctx *c, AlignBufs &b, const kc_gap_aln *alns, uint64_t n
     zeroed = m.used;
     a.cmin = m.take<uint32_t>(n_ctgs);
     a.cmean = m.take<uint32_t>(n_ctgs);
-    if (!on_device) {
-      d_in = m.take<uint4>(2 * n_alns);
-      if (depths) d_depths = m.take<uint16_t>(nbytes);
-      if (ctgs) d_ctgs = m.take<uint4>(2 * n_ctgs);
-    }
+    in.reserve(m);
+    out_depths.reserve(m);
+    out_ctgs.reserve(m);
     return m.used;
-  };
-  HIPCHK(hipMalloc((void **)&b.a, layout(nullptr)));
-  layout(b.a);
-  if (on_device) {
-    d_in = (uint4 *)const_cast<kc_gap_aln *>(alns);
-    d_depths = depths;
-    d_ctgs = (uint4 *)ctgs;
-  } else if (n_alns)
-    HIPCHK(hipMemcpyAsync(d_in, alns, n_alns * sizeof(kc_gap_aln), hipMemcpyHostToDevice, c->stream));
+  }));
+  KCTRY(in.upload(c));
   HIPCHK(hipMemsetAsync(a.st, 0, zeroed, c->stream));
   HIPCHK(hipMemsetAsync(a.st + DPS_BAD, 0xFF, 8, c->stream));
   if (n_ctgs) HIPCHK(hipMemsetAsync(a.cmin, 0xFF, n_ctgs * 4, c->stream));
   a.offs = c->ai.offs;
   a.n_ctgs = (uint32_t)n_ctgs;
   a.nbytes = (uint32_t)nbytes;
-  a.alns = d_in;
+  a.alns = in.d;
   a.n_alns = n_alns;
   a.nreads = nreads;
   a.min_score = min_score;
   a.min_len = min_len;
   a.edge_clip = edge_clip;
   a.flags = flags;
-  a.depths = d_depths;
-  a.ctgs = d_ctgs;
+  a.depths = out_depths.d;
+  a.ctgs = out_ctgs.d;
   KCTRY(depth_check(c, a, KT_DEPTH_CHECK, best_only ? 1 : 0, "kc_aln_depths"));
   if (n_alns) {
-    if (best_only) KCTRY(launch_timed(c, KT_DEPTH_BEST, kc_depth_best_kernel, depth_blocks(n_alns), dim3(256), 0, a));
-    KCTRY(launch_timed(c, KT_DEPTH_MARK, kc_depth_mark_kernel, depth_blocks(n_alns), dim3(256), 0, a));
+    if (best_only) KCTRY(launch_timed(c, KT_DEPTH_BEST, kc_depth_best_kernel, blocks_for(n_alns), dim3(256), 0, a));
+    KCTRY(launch_timed(c, KT_DEPTH_MARK, kc_depth_mark_kernel, blocks_for(n_alns), dim3(256), 0, a));
   }
   if (tiles) {
     const dim3 grid((unsigned)tiles), tpb(DEPTH_TPB);
     KCTRY(launch_timed(c, KT_DEPTH_TILE_SUMS, kc_depth_tile_sums_kernel, grid, tpb, 0, a));
     KCTRY(launch_timed(c, KT_DEPTH_SCAN, kc_scan_kernel<1>, dim3(1), dim3(SCAN_TPB), 0, ScanArrays<1>{{a.tile_sums}}, tiles, a.st + DPS_TOTAL));
     KCTRY(launch_timed(c, KT_DEPTH_RESCAN, kc_depth_rescan_kernel, grid, tpb, 0, a, (depths && !per_contig) ? 1 : 0));
-    if (ctgs || (depths && per_contig)) KCTRY(launch_timed(c, KT_DEPTH_CTG, kc_depth_ctg_kernel, depth_blocks(n_ctgs), dim3(256), 0, a));
+    if (ctgs || (depths && per_contig)) KCTRY(launch_timed(c, KT_DEPTH_CTG, kc_depth_ctg_kernel, blocks_for(n_ctgs), dim3(256), 0, a));
     if (depths && per_contig) KCTRY(launch_timed(c, KT_DEPTH_FILL, kc_depth_fill_kernel, grid, tpb, 0, a));
   }
+  KCTRY(out_depths.download(c));
+  KCTRY(out_ctgs.download(c));
   uint64_t h[DPS_COUNT];
-  HIPCHK(hipMemcpyAsync(h, a.st, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-  if (!on_device) {
-    if (depths && nbytes) HIPCHK(hipMemcpyAsync(depths, d_depths, nbytes * 2, hipMemcpyDeviceToHost, c->stream));
-    if (ctgs && n_ctgs) HIPCHK(hipMemcpyAsync(ctgs, d_ctgs, n_ctgs * sizeof(kc_ctg_depth), hipMemcpyDeviceToHost, c->stream));
-  }
-  HIPCHK(hipStreamSynchronize(c->stream));
+  KCTRY(read_back(c, h, a.st));
   if (stats) {
     stats->records = n_alns;
     stats->none = h[DPS_NONE];
@@ -134,90 +104,58 @@ extern "C" int kc_aln_depths(kc_ctx *c, const kc_gap_aln *alns, uint64_t n_alns,
     return KC_ERR_INVALID_ARG;
   }
   if (!c || (n_alns && !alns)) return KC_ERR_INVALID_ARG;
-  if (on_device && (((uintptr_t)alns | (uintptr_t)ctgs) & 15)) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_aln_depths: a device record array is 16-byte aligned");
-    return KC_ERR_INVALID_ARG;
-  }
+  if (on_device && (((uintptr_t)alns | (uintptr_t)ctgs) & 15)) return misaligned_records("kc_aln_depths");
   if (on_device && ((uintptr_t)depths & 1)) {
     snprintf(g_last_error, sizeof(g_last_error), "kc_aln_depths: a device depth array is 2-byte aligned");
     return KC_ERR_INVALID_ARG;
   }
-  if (!c->ai_ready) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_aln_depths: no contig index (kc_ctg_index_build)");
-    return KC_ERR_STATE;
-  }
+  if (!c->ai_ready) return no_ctg_index("kc_aln_depths");
   if (n_alns > 0xFFFFFFFFull) {
     snprintf(g_last_error, sizeof(g_last_error), "kc_aln_depths: %llu records, a depth and a best record's index hold 32 bits",
              (unsigned long long)n_alns);
     return KC_ERR_CAPACITY;
   }
-  HIPCHK(hipSetDevice(c->cfg.device));
-  AlignBufs b;
-  const int rc = depth_run(c, b, alns, n_alns, nreads, on_device, min_score, min_len, edge_clip, flags, depths, ctgs, stats);
-  if (rc) (void)hipStreamSynchronize(c->stream);
-  b.release();
-  return rc;
+  return call_with_bufs(c, [&](CallBufs &b) {
+    return depth_run(c, b, alns, n_alns, nreads, on_device, min_score, min_len, edge_clip, flags, depths, ctgs, stats);
+  });
 }
 
-static int pair_run(kc_ctx *c, AlignBufs &b, const uint64_t *offsets, uint64_t nreads, const kc_gap_aln *alns, uint64_t n_alns, int on_device,
+static int pair_run(kc_ctx *c, CallBufs &b, const uint64_t *offsets, uint64_t nreads, const kc_gap_aln *alns, uint64_t n_alns, int on_device,
                     uint32_t min_score, uint32_t min_len, uint32_t max_insert, uint64_t *hist, kc_pair_rec *pairs, kc_insert_stats *stats) {
   const uint64_t npairs = nreads / 2, nbins = (uint64_t)max_insert + 1;
+  const bool dev = on_device != 0;
   DepthArgs a;
   memset(&a, 0, sizeof(a));
-  uint64_t *d_als, *d_pst, *d_offs = nullptr, *d_hist = nullptr;
-  uint4 *d_in = nullptr, *d_pairs = nullptr;
+  uint64_t *d_als, *d_pst;
+  StagedIn<uint64_t> offs = staged_offsets(offsets, nreads, dev);
+  StagedIn<uint4> in{alns, dev, n_alns * sizeof(kc_gap_aln)};
+  StagedOut<uint64_t> out_hist{hist, dev, nbins * 8};
+  StagedOut<uint4> out_pairs{pairs, dev, npairs * sizeof(kc_pair_rec)};
   size_t zeroed = 0;
-  auto layout = [&](uint8_t *base) {
+  KCTRY(b.carve([&](uint8_t *base) {
     Carver m{base, 0};
     a.st = m.take<uint64_t>(DPS_COUNT);
     d_als = m.take<uint64_t>(ALS_COUNT);
     d_pst = m.take<uint64_t>(PRS_COUNT);
     a.best = m.take<uint64_t>(nreads);
     zeroed = m.used;
-    if (!on_device) {
-      d_offs = m.take<uint64_t>(nreads + 1);
-      d_in = m.take<uint4>(2 * n_alns);
-      if (hist) d_hist = m.take<uint64_t>(nbins);
-      if (pairs) d_pairs = m.take<uint4>(npairs);
-    }
+    offs.reserve(m);
+    in.reserve(m);
+    out_hist.reserve(m);
+    out_pairs.reserve(m);
     return m.used;
-  };
-  HIPCHK(hipMalloc((void **)&b.a, layout(nullptr)));
-  layout(b.a);
-  if (on_device) {
-    d_offs = const_cast<uint64_t *>(offsets);
-    d_in = (uint4 *)const_cast<kc_gap_aln *>(alns);
-    d_hist = hist;
-    d_pairs = (uint4 *)pairs;
-  } else {
-    if (nreads) HIPCHK(hipMemcpyAsync(d_offs, offsets, (nreads + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    if (n_alns) HIPCHK(hipMemcpyAsync(d_in, alns, n_alns * sizeof(kc_gap_aln), hipMemcpyHostToDevice, c->stream));
-  }
+  }));
+  KCTRY(offs.upload(c));
+  KCTRY(in.upload(c));
+  uint64_t *const d_hist = out_hist.d;
+  uint4 *const d_pairs = out_pairs.d;
   HIPCHK(hipMemsetAsync(a.st, 0, zeroed, c->stream));
   HIPCHK(hipMemsetAsync(a.st + DPS_BAD, 0xFF, 8, c->stream));
-  HIPCHK(hipMemsetAsync(d_als + ALS_BAD_READ, 0xFF, 8, c->stream));
-  if (nreads) {
-    KCTRY(launch_timed(c, KT_PAIR_LENGTHS, kc_align_lengths_kernel, depth_blocks(nreads), dim3(256), 0, (const uint64_t *)d_offs, nreads, d_als));
-    uint64_t bad_read = ~0ull;
-    HIPCHK(hipMemcpyAsync(&bad_read, d_als + ALS_BAD_READ, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (bad_read != ~0ull) {
-      snprintf(g_last_error, sizeof(g_last_error), "kc_pair_inserts: read %llu is longer than %d bases, or its offsets decrease",
-               (unsigned long long)bad_read, KC_ALIGN_MAX_READ_LEN);
-      return KC_ERR_INVALID_ARG;
-    }
-  }
-  a.offs = c->ai.offs;
-  a.n_ctgs = c->ai.n_ctgs;
-  a.nbytes = (uint32_t)c->ai_nbytes;
-  a.alns = d_in;
-  a.n_alns = n_alns;
-  a.nreads = nreads;
-  a.offsets = d_offs;
+  KCTRY(check_read_lengths(c, KT_PAIR_LENGTHS, "kc_pair_inserts", offs.d, nreads, d_als));
   a.min_score = min_score;
   a.min_len = min_len;
-  KCTRY(depth_check(c, a, KT_PAIR_CHECK, 1, "kc_pair_inserts"));
-  if (n_alns) KCTRY(launch_timed(c, KT_PAIR_BEST, kc_depth_best_kernel, depth_blocks(n_alns), dim3(256), 0, a));
+  KCTRY(check_read_records(c, a, KT_PAIR_CHECK, "kc_pair_inserts", in.d, n_alns, offs.d, nreads));
+  if (n_alns) KCTRY(launch_timed(c, KT_PAIR_BEST, kc_depth_best_kernel, blocks_for(n_alns), dim3(256), 0, a));
   if (hist) HIPCHK(hipMemsetAsync(d_hist, 0, nbins * 8, c->stream));
   if (npairs) {
     // enough workgroups to fill the device; each brings its bins once
@@ -227,13 +165,10 @@ static int pair_run(kc_ctx *c, AlignBufs &b, const uint64_t *offsets, uint64_t n
     else
       KCTRY(launch_timed(c, KT_PAIR_CLASSIFY, kc_pair_classify_kernel<false>, grid, dim3(PAIR_TPB), 0, a, max_insert, d_hist, d_pairs, d_pst));
   }
+  KCTRY(out_hist.download(c));
+  KCTRY(out_pairs.download(c));
   uint64_t h[PRS_COUNT];
-  HIPCHK(hipMemcpyAsync(h, d_pst, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-  if (!on_device) {
-    if (hist) HIPCHK(hipMemcpyAsync(hist, d_hist, nbins * 8, hipMemcpyDeviceToHost, c->stream));
-    if (pairs && npairs) HIPCHK(hipMemcpyAsync(pairs, d_pairs, npairs * sizeof(kc_pair_rec), hipMemcpyDeviceToHost, c->stream));
-  }
-  HIPCHK(hipStreamSynchronize(c->stream));
+  KCTRY(read_back(c, h, d_pst));
   if (stats) {
     stats->pairs = npairs;
     for (int k = 0; k < PAIR_CLASSES; k++) stats->cls[k] = h[PRS_CLS + k];
@@ -258,26 +193,17 @@ extern "C" int kc_pair_inserts(kc_ctx *c, const uint64_t *offsets, uint64_t nrea
     return KC_ERR_INVALID_ARG;
   }
   if (!c || (nreads && !offsets) || (n_alns && !alns) || nreads > 0xFFFFFFFFull) return KC_ERR_INVALID_ARG;
-  if (on_device && (((uintptr_t)alns | (uintptr_t)pairs) & 15)) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_pair_inserts: a device record array is 16-byte aligned");
-    return KC_ERR_INVALID_ARG;
-  }
+  if (on_device && (((uintptr_t)alns | (uintptr_t)pairs) & 15)) return misaligned_records("kc_pair_inserts");
   if (on_device && (((uintptr_t)offsets | (uintptr_t)hist) & 7)) {
     snprintf(g_last_error, sizeof(g_last_error), "kc_pair_inserts: device offsets and bins are 8-byte aligned");
     return KC_ERR_INVALID_ARG;
   }
-  if (!c->ai_ready) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_pair_inserts: no contig index (kc_ctg_index_build)");
-    return KC_ERR_STATE;
-  }
+  if (!c->ai_ready) return no_ctg_index("kc_pair_inserts");
   if (n_alns > 0xFFFFFFFFull) {
     snprintf(g_last_error, sizeof(g_last_error), "kc_pair_inserts: %llu records, a best record's index holds 32 bits", (unsigned long long)n_alns);
     return KC_ERR_CAPACITY;
   }
-  HIPCHK(hipSetDevice(c->cfg.device));
-  AlignBufs b;
-  const int rc = pair_run(c, b, offsets, nreads, alns, n_alns, on_device, min_score, min_len, max_insert, hist, pairs, stats);
-  if (rc) (void)hipStreamSynchronize(c->stream);
-  b.release();
-  return rc;
+  return call_with_bufs(c, [&](CallBufs &b) {
+    return pair_run(c, b, offsets, nreads, alns, n_alns, on_device, min_score, min_len, max_insert, hist, pairs, stats);
+  });
 }

@@ -1,5 +1,5 @@
 // kc_api_scaffold.hpp -- kc_scaffold (kernels in kc_scaffold.hpp).  Part of kc_api.hip's translation unit, behind
-// kc_api_links.hpp; the buffers are kc_api_lassm.hpp's, the jump rounds' count kc_api_unitig.hpp's.
+// kc_api_links.hpp; the jump rounds' count is kc_api_unitig.hpp's.
 
 static_assert(sizeof(kc_scaf_params) == 32 && sizeof(kc_scaffold_rec) == 32 && sizeof(kc_scaf_member) == 16 && sizeof(kc_scaf_stats) == 160,
               "the header's layouts");
@@ -19,14 +19,15 @@ struct ScafIo {
   kc_scaf_stats *stats;
 };
 
-static int scaffold_run(kc_ctx *c, LassmBufs &b, const ScafIo &io, const kc_scaf_params &p) {
+static int scaffold_run(kc_ctx *c, CallBufs &b, const ScafIo &io, const kc_scaf_params &p) {
   const uint32_t n = c->ai.n_ctgs, nn = 2 * n;
   const uint64_t n_ends = nn, n_links = io.n_links;
   const bool dev = io.on_device != 0;
   uint64_t *st, *keys, *end_first, *size, *num, *mcnt;
-  uint4 *d_links = nullptr, *pick, *info;
+  uint4 *pick, *info;
   uint2 *link, *next2, *cyc[2], *rank[2], *pos[2];
-  auto layout = [&](uint8_t *base) {
+  StagedIn<uint4> links{io.links, dev, n_links * sizeof(kc_ctg_link)};
+  KCTRY(b.carve([&](uint8_t *base) {
     Carver m{base, 0};
     st = m.take<uint64_t>(SCS_COUNT);
     size = m.take<uint64_t>(n);
@@ -41,37 +42,27 @@ static int scaffold_run(kc_ctx *c, LassmBufs &b, const ScafIo &io, const kc_scaf
     for (auto &q : cyc) q = m.take<uint2>(nn);
     for (auto &q : rank) q = m.take<uint2>(nn);
     for (auto &q : pos) q = m.take<uint2>(nn);
-    if (!dev) d_links = m.take<uint4>(3 * n_links);
+    links.reserve(m);
     return m.used;
-  };
-  HIPCHK(hipMalloc((void **)&b.p[0], layout(nullptr)));
-  layout(b.p[0]);
+  }));
+  const uint4 *d_links = links.d;
   // st .. info are neighbours in the layout
   HIPCHK(hipMemsetAsync(st, 0, (size_t)((uint8_t *)keys - (uint8_t *)st), c->stream));
   HIPCHK(hipMemsetAsync(st + SCS_BAD, 0xFF, 8, c->stream));
-  if (dev)
-    d_links = (uint4 *)const_cast<kc_ctg_link *>(io.links);
-  else if (n_links)
-    HIPCHK(hipMemcpyAsync(d_links, io.links, n_links * sizeof(kc_ctg_link), hipMemcpyHostToDevice, c->stream));
-  auto blocks = [](uint64_t items) { return dim3((unsigned)((items + SCAF_TPB - 1) / SCAF_TPB)); };
+  KCTRY(links.upload(c));
+  auto blocks = [](uint64_t items) { return blocks_for(items, SCAF_TPB); };
   const dim3 tpb(SCAF_TPB), per_ctg = blocks(n), per_node = blocks(nn), per_end_wave = blocks(n_ends * 64);
   // ---- the check: its verdict is read before anything is stored
   if (n_links) {
-    KCTRY(launch_timed(c, KT_SCAF_CHECK, kc_scaf_check_kernel, blocks(n_links), tpb, 0, (const uint4 *)d_links, n_links, n_ends, keys, st));
-    uint64_t bad = ~0ull;
-    HIPCHK(hipMemcpyAsync(&bad, st + SCS_BAD, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (bad != ~0ull) {
-      snprintf(g_last_error, sizeof(g_last_error),
-               "kc_scaffold: record %llu is invalid (an end out of range, two ends of one contig, no supporter, figures out of range, "
-               "not above its predecessor, or no mirror with the same figures)",
-               (unsigned long long)bad);
-      return KC_ERR_INVALID_ARG;
-    }
+    KCTRY(launch_timed(c, KT_SCAF_CHECK, kc_scaf_check_kernel, blocks(n_links), tpb, 0, d_links, n_links, n_ends, keys, st));
+    KCTRY(lowest_bad(c, st + SCS_BAD,
+                     "%s: record %llu is invalid (an end out of range, two ends of one contig, no supporter, figures out of range, "
+                     "not above its predecessor, or no mirror with the same figures)",
+                     "kc_scaffold"));
   }
   // ---- one partner an end, the overlaps, next[]
   KCTRY(launch_timed(c, KT_SCAF_END_FIRST, kc_link_end_first_kernel, blocks(n_ends + 1), tpb, 0, (const uint64_t *)keys, n_links, n_ends, end_first));
-  KCTRY(launch_timed(c, KT_SCAF_CHOOSE, kc_scaf_choose_kernel, per_end_wave, tpb, 0, (const uint4 *)d_links, (const uint64_t *)end_first, n_ends,
+  KCTRY(launch_timed(c, KT_SCAF_CHOOSE, kc_scaf_choose_kernel, per_end_wave, tpb, 0, d_links, (const uint64_t *)end_first, n_ends,
                      p.min_splints, p.min_spans, p.max_second_permille, pick, st));
   KCTRY(launch_timed(c, KT_SCAF_EDGE, kc_scaf_edge_kernel, per_end_wave, tpb, 0, (const uint4 *)pick, n_ends, c->ai.seqs, c->ai.offs, p.overlap_slack,
                      link, st));
@@ -85,8 +76,7 @@ static int scaffold_run(kc_ctx *c, LassmBufs &b, const ScafIo &io, const kc_scaf
   KCTRY(launch_timed(c, KT_SCAF_WEIGHT, kc_scaf_weight_kernel, per_ctg, tpb, 0, (const uint4 *)rank[0], (const uint2 *)next2, (const uint2 *)link,
                      c->ai.offs, n, (uint4 *)pos[0], st));
   uint64_t h[SCS_COUNT];
-  HIPCHK(hipMemcpyAsync(h, st, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  KCTRY(read_back(c, h, st));
   // every path is counted with its twin: half the tails are scaffolds, half the bytes theirs
   const uint64_t total = h[SCS_BYTES2] / 2 + h[SCS_TAILS] / 2;
   if (total >= (1ull << 31)) {
@@ -102,8 +92,7 @@ static int scaffold_run(kc_ctx *c, LassmBufs &b, const ScafIo &io, const kc_scaf
                      (const uint32_t *)next2, c->ai.offs, nn, size, num, mcnt, info, st));
   KCTRY(launch_timed(c, KT_SCAF_SCAN, kc_scan_kernel<2>, dim3(1), dim3(SCAN_TPB), 0, ScanArrays<2>{{size, num}}, (uint64_t)n, st + SCS_TOTALS));
   KCTRY(launch_timed(c, KT_SCAF_SCAN, kc_scan_kernel<1>, dim3(1), dim3(SCAN_TPB), 0, ScanArrays<1>{{mcnt}}, (uint64_t)n, st + SCS_MTOTAL));
-  HIPCHK(hipMemcpyAsync(h, st, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  KCTRY(read_back(c, h, st));
   const uint64_t n_scaf = h[SCS_TOTALS + 1];
   if (h[SCS_TOTALS] != total || h[SCS_MTOTAL] != n) {
     snprintf(g_last_error, sizeof(g_last_error), "kc_scaffold: the walk gives %llu bytes and %llu members, the sums %llu and %u",
@@ -131,50 +120,39 @@ static int scaffold_run(kc_ctx *c, LassmBufs &b, const ScafIo &io, const kc_scaf
   s.longest = h[SCS_LONGEST];
   const bool fits = io.seqs_out && io.capacity >= total;
   if (fits) {
-    const bool want_recs = io.scaffolds != nullptr;
-    uint8_t *d_seqs = nullptr;
-    uint64_t *d_offsets = nullptr;
-    uint4 *d_scaf = nullptr, *d_members = nullptr;
-    uint32_t *d_cm = nullptr, *seg, *acc;
-    auto outs = [&](uint8_t *base) {
+    uint32_t *seg, *acc;
+    StagedOut<uint8_t> seqs{io.seqs_out, dev, total};
+    StagedOut<uint64_t> offsets{io.offsets_out, dev, (n_scaf + 1) * 8};
+    StagedOut<uint4> scaf{io.scaffolds, dev, n_scaf * sizeof(kc_scaffold_rec)}, members{io.members, dev, (size_t)n * sizeof(kc_scaf_member)};
+    StagedOut<uint32_t> cm{io.ctg_member, dev, (size_t)n * 4};
+    KCTRY(b.carve([&](uint8_t *base) {
       Carver m{base, 0};
       seg = m.take<uint32_t>((uint64_t)n + 1);
       acc = m.take<uint32_t>(2 * n_scaf);
-      if (!dev || !io.members) d_members = m.take<uint4>(n);
-      if (!dev) {
-        d_seqs = m.take<uint8_t>(total);
-        if (io.offsets_out) d_offsets = m.take<uint64_t>(n_scaf + 1);
-        if (want_recs) d_scaf = m.take<uint4>(2 * n_scaf);
-        if (io.ctg_member) d_cm = m.take<uint32_t>(n);
-      }
+      members.reserve(m);
+      if (!io.members) members.d = m.take<uint4>(n);  // the write kernel reads them, whoever else wants them
+      seqs.reserve(m);
+      offsets.reserve(m);
+      scaf.reserve(m);
+      cm.reserve(m);
       return m.used;
-    };
-    HIPCHK(hipMalloc((void **)&b.p[1], outs(nullptr)));
-    outs(b.p[1]);
-    if (dev) {
-      d_seqs = io.seqs_out;
-      d_offsets = io.offsets_out;
-      d_scaf = (uint4 *)io.scaffolds;
-      if (io.members) d_members = (uint4 *)io.members;
-      d_cm = io.ctg_member;
-    }
+    }));
+    uint8_t *const d_seqs = seqs.d;
     HIPCHK(hipMemsetAsync(acc, 0, 2 * n_scaf * 4, c->stream));
     KCTRY(launch_timed(c, KT_SCAF_MEMBERS, kc_scaf_members_kernel, per_node, tpb, 0, (const uint2 *)rank[rk], (const uint2 *)pos[rk], (const uint2 *)link,
                        (const uint4 *)info, (const uint64_t *)size, (const uint64_t *)num, (const uint64_t *)mcnt, nn, (uint32_t)total, n_scaf,
-                       d_members, seg, acc, d_offsets, d_cm));
-    if (want_recs)
+                       members.d, seg, acc, offsets.d, cm.d));
+    if (scaf.d)
       KCTRY(launch_timed(c, KT_SCAF_RECORDS, kc_scaf_records_kernel, per_ctg, tpb, 0, (const uint4 *)info, (const uint64_t *)num,
-                         (const uint64_t *)mcnt, (const uint32_t *)acc, n, d_scaf));
+                         (const uint64_t *)mcnt, (const uint32_t *)acc, n, scaf.d));
     const uint32_t mis = (uint32_t)((uintptr_t)d_seqs & 15);
-    KCTRY(launch_timed(c, KT_SCAF_WRITE, kc_scaf_write_kernel, blocks((total + mis + 15) / 16), tpb, 0, (const uint4 *)d_members,
+    KCTRY(launch_timed(c, KT_SCAF_WRITE, kc_scaf_write_kernel, blocks((total + mis + 15) / 16), tpb, 0, (const uint4 *)members.d,
                        (const uint32_t *)seg, n, c->ai.seqs, c->ai.offs, mis, (uint32_t)total, d_seqs));
-    if (!dev) {
-      HIPCHK(hipMemcpyAsync(io.seqs_out, d_seqs, total, hipMemcpyDeviceToHost, c->stream));
-      if (d_offsets) HIPCHK(hipMemcpyAsync(io.offsets_out, d_offsets, (n_scaf + 1) * 8, hipMemcpyDeviceToHost, c->stream));
-      if (d_scaf) HIPCHK(hipMemcpyAsync(io.scaffolds, d_scaf, n_scaf * sizeof(kc_scaffold_rec), hipMemcpyDeviceToHost, c->stream));
-      if (io.members) HIPCHK(hipMemcpyAsync(io.members, d_members, (size_t)n * sizeof(kc_scaf_member), hipMemcpyDeviceToHost, c->stream));
-      if (d_cm) HIPCHK(hipMemcpyAsync(io.ctg_member, d_cm, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-    }
+    KCTRY(seqs.download(c));
+    KCTRY(offsets.download(c));
+    KCTRY(scaf.download(c));
+    KCTRY(members.download(c));
+    KCTRY(cm.download(c));
     HIPCHK(hipStreamSynchronize(c->stream));
   }
   *io.n_scaffolds = n_scaf;
@@ -210,27 +188,16 @@ extern "C" int kc_scaffold(kc_ctx *c, const kc_ctg_link *links, uint64_t n_links
     return KC_ERR_INVALID_ARG;
   }
   if (!c || (n_links && !links)) return KC_ERR_INVALID_ARG;
-  if (on_device && (((uintptr_t)links | (uintptr_t)scaffolds | (uintptr_t)members) & 15)) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_scaffold: a device record array is 16-byte aligned");
-    return KC_ERR_INVALID_ARG;
-  }
+  if (on_device && (((uintptr_t)links | (uintptr_t)scaffolds | (uintptr_t)members) & 15)) return misaligned_records("kc_scaffold");
   if (on_device && ((((uintptr_t)offsets_out) & 7) || (((uintptr_t)ctg_member) & 3))) {
     snprintf(g_last_error, sizeof(g_last_error), "kc_scaffold: device offsets are 8-byte aligned, ctg_member 4-byte");
     return KC_ERR_INVALID_ARG;
   }
-  if (!c->ai_ready) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_scaffold: no contig index (kc_ctg_index_build)");
-    return KC_ERR_STATE;
-  }
+  if (!c->ai_ready) return no_ctg_index("kc_scaffold");
   if (c->ai.n_ctgs == 0 || c->ai.n_ctgs >= (1u << 31)) {
     snprintf(g_last_error, sizeof(g_last_error), "kc_scaffold: %u contigs, oriented node ids are 32-bit (1 .. 2^31 - 1 contigs)", c->ai.n_ctgs);
     return c->ai.n_ctgs ? KC_ERR_CAPACITY : KC_ERR_STATE;
   }
-  HIPCHK(hipSetDevice(c->cfg.device));
-  LassmBufs b;
   const ScafIo io{links, n_links, on_device, seqs_out, capacity, offsets_out, scaffolds, members, ctg_member, n_scaffolds, nbytes_out, stats};
-  const int rc = scaffold_run(c, b, io, *p);
-  if (rc) (void)hipStreamSynchronize(c->stream);
-  b.release();
-  return rc;
+  return call_with_bufs(c, [&](CallBufs &b) { return scaffold_run(c, b, io, *p); });
 }

@@ -1,18 +1,6 @@
 // kc_api_unitig.hpp -- kc_build_unitigs (kernels in kc_unitig.hpp).  Part of kc_api.hip's translation unit, like
 // kc_api_sort.hpp.
 
-// what a call holds until it returns: the scratch, and the unitigs' sums where the caller keeps none
-struct UnitigBufs {
-  uint8_t *scratch = nullptr;
-  uint64_t *sums = nullptr;
-  void release() {
-    if (scratch) (void)hipFree(scratch);
-    if (sums) (void)hipFree(sums);
-    scratch = nullptr;
-    sums = nullptr;
-  }
-};
-
 // rounds of pointer jumping after which a path of up to 2n nodes has been walked: ceil(log2 2n) + 1
 static int unitig_rounds(uint64_t n) {
   int r = 0;
@@ -21,7 +9,7 @@ static int unitig_rounds(uint64_t n) {
 }
 
 template <int NL>
-static int unitig_run(kc_ctx *c, UnitigBufs &b, uint8_t *d_seqs, uint64_t capacity, uint16_t *d_depths, uint64_t *d_offsets,
+static int unitig_run(kc_ctx *c, CallBufs &b, uint8_t *d_seqs, uint64_t capacity, uint16_t *d_depths, uint64_t *d_offsets,
                       uint64_t unitigs_capacity, uint64_t *d_kmer_sums, uint64_t *n_unitigs, uint64_t *nbytes, kc_unitig_stats *stats) {
   KCTRY(ensure_index<NL>(c));
   const uint32_t n = (uint32_t)c->out_n, nn = 2 * n;
@@ -39,12 +27,10 @@ static int unitig_run(kc_ctx *c, UnitigBufs &b, uint8_t *d_seqs, uint64_t capaci
     st = m.take<uint64_t>(UST_COUNT);
     return m.used;
   };
-  HIPCHK(hipMalloc((void **)&b.scratch, layout(nullptr)));
-  layout(b.scratch);
+  KCTRY(b.carve(layout));
   // size .. st are neighbours in the layout
   HIPCHK(hipMemsetAsync(size, 0, (size_t)((uint8_t *)(st + UST_COUNT) - (uint8_t *)size), c->stream));
-  const dim3 per_result((unsigned)(((uint64_t)n + UNITIG_TPB - 1) / UNITIG_TPB)), per_node((unsigned)(((uint64_t)nn + UNITIG_TPB - 1) / UNITIG_TPB)),
-      tpb(UNITIG_TPB);
+  const dim3 per_result = blocks_for(n, UNITIG_TPB), per_node = blocks_for(nn, UNITIG_TPB), tpb(UNITIG_TPB);
   const int rounds = unitig_rounds(n);
   KCTRY(launch_timed(c, KT_UNITIG_LINKS, kc_unitig_links_kernel<NL>, per_result, tpb, 0, (const uint64_t *)c->d_out_keys,
                      (const uint8_t *)c->d_out_left, (const uint8_t *)c->d_out_right, n, c->k, (const uint32_t *)c->d_index, c->index_cap - 1,
@@ -60,8 +46,7 @@ static int unitig_run(kc_ctx *c, UnitigBufs &b, uint8_t *d_seqs, uint64_t capaci
   KCTRY(launch_timed(c, KT_UNITIG_SELECT, kc_unitig_select_kernel, per_node, tpb, 0, rank, (const uint32_t *)next, nn, c->k, size, num, sel, st));
   KCTRY(launch_timed(c, KT_UNITIG_SCAN, kc_scan_kernel<2>, dim3(1), dim3(SCAN_TPB), 0, ScanArrays<2>{{size, num}}, (uint64_t)n, st + UST_TOTALS));
   uint64_t h[UST_COUNT];
-  HIPCHK(hipMemcpyAsync(h, st, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  KCTRY(read_back(c, h, st));
   const uint64_t total = h[UST_TOTALS], nu = h[UST_TOTALS + 1];
   *nbytes = total;
   *n_unitigs = nu;
@@ -80,10 +65,7 @@ static int unitig_run(kc_ctx *c, UnitigBufs &b, uint8_t *d_seqs, uint64_t capaci
     return KC_ERR_CAPACITY;
   }
   uint64_t *sums = d_kmer_sums;
-  if (!sums && d_depths) {
-    HIPCHK(hipMalloc((void **)&b.sums, nu * 8));
-    sums = b.sums;
-  }
+  if (!sums && d_depths) KCTRY(b.alloc(&sums, nu * 8));  // the caller keeps none
   if (sums) HIPCHK(hipMemsetAsync(sums, 0, nu * 8, c->stream));
   KCTRY(launch_timed(c, KT_UNITIG_WRITE, kc_unitig_write_kernel, per_node, tpb, 0, rank, (const uint32_t *)next, (const uint64_t *)c->d_out_keys,
                      c->nl, (const uint16_t *)c->d_out_counts, (const uint8_t *)sel, (const uint64_t *)size, (const uint64_t *)num, nn, c->k, total,
@@ -112,8 +94,8 @@ extern "C" int kc_build_unitigs(kc_ctx *c, uint8_t *d_seqs, uint64_t capacity, u
              (unsigned long long)c->out_n);
     return KC_ERR_CAPACITY;
   }
-  HIPCHK(hipSetDevice(c->cfg.device));
   if (!c->out_n) {
+    HIPCHK(hipSetDevice(c->cfg.device));
     if (d_seqs && d_offsets) {
       HIPCHK(hipMemsetAsync(d_offsets, 0, 8, c->stream));  // offsets[0] = 0: the one entry of no unitigs
       HIPCHK(hipStreamSynchronize(c->stream));
@@ -121,11 +103,9 @@ extern "C" int kc_build_unitigs(kc_ctx *c, uint8_t *d_seqs, uint64_t capacity, u
     return KC_OK;
   }
   KCTRY(kc_sort_results(c, nullptr));  // result order is key order from here on
-  UnitigBufs b;
-  const int rc = with_nl(c, [&](auto nl) {
-    return unitig_run<nl>(c, b, d_seqs, capacity, d_depths, d_offsets, unitigs_capacity, d_kmer_sums, n_unitigs, nbytes, stats);
+  return call_with_bufs(c, [&](CallBufs &b) {
+    return with_nl(c, [&](auto nl) {
+      return unitig_run<nl>(c, b, d_seqs, capacity, d_depths, d_offsets, unitigs_capacity, d_kmer_sums, n_unitigs, nbytes, stats);
+    });
   });
-  if (rc) (void)hipStreamSynchronize(c->stream);
-  b.release();
-  return rc;
 }

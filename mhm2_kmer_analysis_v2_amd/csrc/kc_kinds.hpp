@@ -1,0 +1,158 @@
+// kc_kinds.hpp -- the kinds under which the host times its kernel launches, and the name each is reported under.  One list:
+// the enum and the names come from it, so a kind and its name cannot drift apart.  No HIP in here.
+//
+// Several kinds are one kernel launched by different callers or in different passes; the name in angle brackets says
+// which (kc_align_lengths_kernel<close> is kc_close_gaps' launch of kc_align_lengths_kernel).  The *_scan_kernel names are
+// the uses of the one shared kc_scan_kernel (kc_scan.hpp) and keep the names they were first reported under.
+#pragma once
+
+#define KC_KERNEL_KINDS(X) \
+  X(KT_EXTRACT_INSERT,     "kc_extract_kernel<insert>") \
+  X(KT_EXTRACT_BIN,        "kc_bin_reads_kernel") \
+  X(KT_INSERT_RECORDS,     "kc_insert_records_kernel") \
+  X(KT_FINALIZE,           "kc_finalize_kernel") \
+  X(KT_TILE_FIRST,         "kc_tile_first_kernel") \
+  X(KT_REHASH,             "kc_rehash_kernel") \
+  X(KT_L1_READS,           "kc_l1_reads_kernel") \
+  X(KT_L1_RECORDS,         "kc_l1_records_kernel") \
+  X(KT_L2_SPLIT,           "kc_l2_split_kernel") \
+  X(KT_COUNT_REGIONS,      "kc_count_kernel") \
+  X(KT_FALLBACK,           "kc_flagged_to_table_kernel") \
+  X(KT_SHARD_PACK,         "kc_shard_pack_kernel") \
+  X(KT_L1_READS_UQ,        "kc_l1_reads_kernel<byte-loaded qualities>") \
+  X(KT_L1_READS16,         "kc_l1_reads16_kernel") \
+  X(KT_L2_REC6,            "kc_l2_rec6_kernel") \
+  X(KT_BIN16,              "kc_bin16_kernel") \
+  X(KT_L1_WIRE6,           "kc_l1_wire6_kernel") \
+  X(KT_MERGE_DECIDE,       "kc_merge_decide_kernel") \
+  X(KT_MERGE_DECIDE_LONG,  "kc_merge_decide_kernel<long>") \
+  X(KT_MERGE_SCAN,         "kc_merge_scan_kernel") \
+  X(KT_MERGE_WRITE,        "kc_merge_write_kernel") \
+  X(KT_MERGE_WRITE_LONG,   "kc_merge_write_kernel<long>") \
+  X(KT_FQ_COUNT,           "kc_fq_count_kernel") \
+  X(KT_FQ_SCAN,            "kc_fq_scan_kernel") \
+  X(KT_FQ_INDEX,           "kc_fq_index_kernel") \
+  X(KT_FQ_CHECK,           "kc_fq_check_kernel") \
+  X(KT_FQ_DETAIL,          "kc_fq_detail_kernel") \
+  X(KT_FQ_SUMS,            "kc_fq_sums_kernel") \
+  X(KT_FQ_WRITE_PACKED,    "kc_fq_write_kernel<packed>") \
+  X(KT_FQ_WRITE_PAIRS,     "kc_fq_write_kernel<pairs>") \
+  X(KT_TRIM_SEED,          "kc_trim_seed_kernel") \
+  X(KT_TRIM_ALIGN,         "kc_trim_align_kernel") \
+  X(KT_TRIM_SIZES,         "kc_trim_sizes_kernel") \
+  X(KT_TRIM_SCAN,          "kc_merge_scan_kernel<trim>") \
+  X(KT_TRIM_WRITE,         "kc_trim_write_kernel") \
+  X(KT_SORT_HIST,          "kc_sort_hist_kernel") \
+  X(KT_SORT_HIST_LOAD,     "kc_sort_hist_kernel<load>") \
+  X(KT_SORT_SCAN,          "kc_sort_scan_kernel") \
+  X(KT_SORT_SCATTER,       "kc_sort_scatter_kernel") \
+  X(KT_SORT_GATHER,        "kc_sort_gather_kernel") \
+  X(KT_DUMP_SIZES,         "kc_dump_sizes_kernel") \
+  X(KT_DUMP_SCAN,          "kc_dump_scan_kernel") \
+  X(KT_DUMP_WRITE,         "kc_dump_write_kernel") \
+  X(KT_UNITIG_LINKS,       "kc_unitig_links_kernel") \
+  X(KT_UNITIG_MIN_JUMP,    "kc_unitig_min_jump_kernel") \
+  X(KT_UNITIG_CUT,         "kc_unitig_cut_kernel") \
+  X(KT_UNITIG_RANK_JUMP,   "kc_unitig_rank_jump_kernel") \
+  X(KT_UNITIG_SELECT,      "kc_unitig_select_kernel") \
+  X(KT_UNITIG_SCAN,        "kc_unitig_scan_kernel") \
+  X(KT_UNITIG_WRITE,       "kc_unitig_write_kernel") \
+  X(KT_UNITIG_DEPTH,       "kc_unitig_depth_kernel") \
+  X(KT_ALIGN_CHECK,        "kc_align_check_kernel") \
+  X(KT_ALIGN_INDEX,        "kc_align_index_kernel") \
+  X(KT_ALIGN_SWEEP,        "kc_align_sweep_kernel") \
+  X(KT_ALIGN_LENGTHS,      "kc_align_lengths_kernel") \
+  X(KT_ALIGN_COUNT,        "kc_align_reads_kernel<count>") \
+  X(KT_ALIGN_SCAN,         "kc_align_scan_kernel") \
+  X(KT_ALIGN_WRITE,        "kc_align_reads_kernel<write>") \
+  X(KT_GAP_LENGTHS,        "kc_align_lengths_kernel<gap>") \
+  X(KT_GAP_CHECK,          "kc_gap_check_kernel") \
+  X(KT_GAP_SORT,           "kc_gap_sort_kernel") \
+  X(KT_GAP_DP,             "kc_gap_dp_kernel") \
+  X(KT_DEPTH_CHECK,        "kc_depth_check_kernel") \
+  X(KT_DEPTH_BEST,         "kc_depth_best_kernel") \
+  X(KT_DEPTH_MARK,         "kc_depth_mark_kernel") \
+  X(KT_DEPTH_TILE_SUMS,    "kc_depth_tile_sums_kernel") \
+  X(KT_DEPTH_SCAN,         "kc_depth_scan_kernel") \
+  X(KT_DEPTH_RESCAN,       "kc_depth_rescan_kernel") \
+  X(KT_DEPTH_CTG,          "kc_depth_ctg_kernel") \
+  X(KT_DEPTH_FILL,         "kc_depth_fill_kernel") \
+  X(KT_PAIR_LENGTHS,       "kc_align_lengths_kernel<pair>") \
+  X(KT_PAIR_CHECK,         "kc_depth_check_kernel<pair>") \
+  X(KT_PAIR_BEST,          "kc_depth_best_kernel<pair>") \
+  X(KT_PAIR_CLASSIFY,      "kc_pair_classify_kernel") \
+  X(KT_PAIR_CLASSIFY_LDS,  "kc_pair_classify_kernel<lds>") \
+  X(KT_LASSM_LENGTHS,      "kc_align_lengths_kernel<lassm>") \
+  X(KT_LASSM_CHECK,        "kc_depth_check_kernel<lassm>") \
+  X(KT_LASSM_PAIR_CHECK,   "kc_lassm_pair_check_kernel") \
+  X(KT_LASSM_COUNT,        "kc_lassm_cands_kernel<count>") \
+  X(KT_LASSM_PLAN,         "kc_lassm_plan_kernel") \
+  X(KT_LASSM_SCAN,         "kc_lassm_scan_kernel") \
+  X(KT_LASSM_SCATTER,      "kc_lassm_cands_kernel<write>") \
+  X(KT_LASSM_TEXT,         "kc_lassm_text_kernel") \
+  X(KT_LASSM_WALK,         "kc_lassm_walk_kernel") \
+  X(KT_LASSM_LENS,         "kc_lassm_lens_kernel") \
+  X(KT_LASSM_ENDS,         "kc_lassm_ends_kernel") \
+  X(KT_LASSM_WRITE,        "kc_lassm_write_kernel") \
+  X(KT_LINK_LENGTHS,       "kc_align_lengths_kernel<links>") \
+  X(KT_LINK_CHECK,         "kc_depth_check_kernel<links>") \
+  X(KT_LINK_PAIR_CHECK,    "kc_lassm_pair_check_kernel<links>") \
+  X(KT_LINK_GROUP_COUNT,   "kc_link_group_kernel<count>") \
+  X(KT_LINK_GROUP_FILL,    "kc_link_group_kernel<fill>") \
+  X(KT_LINK_TILE_SCAN,     "kc_link_tile_scan_kernel") \
+  X(KT_LINK_SCAN,          "kc_link_scan_kernel") \
+  X(KT_LINK_CANDS_COUNT,   "kc_link_cands_kernel<count>") \
+  X(KT_LINK_CANDS_WRITE,   "kc_link_cands_kernel<write>") \
+  X(KT_LINK_SORT_HIST,     "kc_sort_hist_kernel<links>") \
+  X(KT_LINK_SORT_SCAN,     "kc_sort_scan_kernel<links>") \
+  X(KT_LINK_SORT_SCATTER,  "kc_sort_scatter_kernel<links>") \
+  X(KT_LINK_HEADS,         "kc_link_heads_kernel") \
+  X(KT_LINK_REDUCE,        "kc_link_reduce_kernel") \
+  X(KT_LINK_EMIT,          "kc_link_emit_kernel") \
+  X(KT_LINK_END_FIRST,     "kc_link_end_first_kernel") \
+  X(KT_SCAF_CHECK,         "kc_scaf_check_kernel") \
+  X(KT_SCAF_END_FIRST,     "kc_link_end_first_kernel<scaffold>") \
+  X(KT_SCAF_CHOOSE,        "kc_scaf_choose_kernel") \
+  X(KT_SCAF_EDGE,          "kc_scaf_edge_kernel") \
+  X(KT_SCAF_NEXT,          "kc_scaf_next_kernel") \
+  X(KT_SCAF_MIN_JUMP,      "kc_unitig_min_jump_kernel<scaffold>") \
+  X(KT_SCAF_CUT,           "kc_unitig_cut_kernel<scaffold>") \
+  X(KT_SCAF_WEIGHT,        "kc_scaf_weight_kernel") \
+  X(KT_SCAF_RANK_JUMP,     "kc_unitig_rank_jump_kernel<scaffold>") \
+  X(KT_SCAF_POS_JUMP,      "kc_unitig_rank_jump_kernel<scaffold pos>") \
+  X(KT_SCAF_SELECT,        "kc_scaf_select_kernel") \
+  X(KT_SCAF_SCAN,          "kc_scaf_scan_kernel") \
+  X(KT_SCAF_MEMBERS,       "kc_scaf_members_kernel") \
+  X(KT_SCAF_RECORDS,       "kc_scaf_records_kernel") \
+  X(KT_SCAF_WRITE,         "kc_scaf_write_kernel") \
+  X(KT_CLOSE_LENGTHS,      "kc_align_lengths_kernel<close>") \
+  X(KT_CLOSE_CHECK,        "kc_depth_check_kernel<close>") \
+  X(KT_CLOSE_CHECK_SCAF,   "kc_close_check_scaf_kernel") \
+  X(KT_CLOSE_CLAIM,        "kc_close_claim_kernel") \
+  X(KT_CLOSE_CHECK_MEMBER, "kc_close_check_member_kernel") \
+  X(KT_CLOSE_GROUP_COUNT,  "kc_link_group_kernel<close count>") \
+  X(KT_CLOSE_GROUP_FILL,   "kc_link_group_kernel<close fill>") \
+  X(KT_CLOSE_TILE_SCAN,    "kc_link_tile_scan_kernel<close>") \
+  X(KT_CLOSE_SCAN,         "kc_close_scan_kernel") \
+  X(KT_CLOSE_ENDS,         "kc_close_ends_kernel") \
+  X(KT_CLOSE_CANDS_COUNT,  "kc_close_cands_kernel<count>") \
+  X(KT_CLOSE_CANDS_WRITE,  "kc_close_cands_kernel<write>") \
+  X(KT_CLOSE_DECIDE,       "kc_close_decide_kernel") \
+  X(KT_CLOSE_PLACE,        "kc_close_place_kernel") \
+  X(KT_CLOSE_VOTE,         "kc_close_vote_kernel") \
+  X(KT_CLOSE_RECORDS,      "kc_close_records_kernel") \
+  X(KT_CLOSE_WRITE,        "kc_close_write_kernel")
+
+enum {
+#define X(kind, name) kind,
+  KC_KERNEL_KINDS(X)
+#undef X
+  KT_COUNT
+};
+
+static const char *const kt_names[] = {
+#define X(kind, name) name,
+    KC_KERNEL_KINDS(X)
+#undef X
+};
+static_assert(sizeof(kt_names) / sizeof(kt_names[0]) == KT_COUNT, "a name for every kind");

@@ -290,6 +290,19 @@ def test_capacity_read_first_and_repeatability():
         assert (rc, na, st0["reads"]) == (0, 0, 0)
 
 
+def test_names_and_launch_counts_in_the_kernel_times():
+    rng = np.random.default_rng(13)
+    contigs, reads = small_case(rng)
+    kc, ix = indexed(21, contigs, time_kernels=True)
+    with kc:
+        kc.kernel_times(clear=True)
+        alns, _, _ = kc.align_reads(*read_arrays(reads))  # a size query and the call
+        assert len(alns) == 4
+        t = kc.kernel_times()
+    want = {"kc_align_lengths_kernel": 2, "kc_align_reads_kernel<count>": 2, "kc_align_scan_kernel": 2, "kc_align_reads_kernel<write>": 1}
+    assert {n: c for n, (c, _) in t.items()} == want
+
+
 def test_state_and_argument_errors():
     import torch
     rng = np.random.default_rng(14)

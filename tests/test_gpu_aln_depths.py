@@ -295,6 +295,17 @@ def test_null_outputs_no_records_host_and_wrapper():
         compare(kc, lens, alns)
 
 
+def test_names_and_launch_counts_in_the_kernel_times():
+    lens, alns = small_case()
+    with lengths_index(lens, time_kernels=True) as kc:
+        kc.kernel_times(clear=True)
+        kc.aln_depths(alns, best_only=True, per_contig=True, nreads=3)  # every optional kernel runs
+        t = kc.kernel_times()
+    want = {"kc_depth_check_kernel": 1, "kc_depth_best_kernel": 1, "kc_depth_mark_kernel": 1, "kc_depth_tile_sums_kernel": 1,
+            "kc_depth_scan_kernel": 1, "kc_depth_rescan_kernel": 1, "kc_depth_ctg_kernel": 1, "kc_depth_fill_kernel": 1}
+    assert {n: c for n, (c, _) in t.items()} == want
+
+
 def test_invalid_records_are_named_and_nothing_is_written():
     lens, alns = small_case()
     good = alns[3]  # contig 0 (300 bases): cstart 200, cstop 300, rstart 0, rstop 100

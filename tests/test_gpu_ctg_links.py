@@ -425,6 +425,22 @@ def test_optional_outputs_capacity_host_arrays_and_the_wrapper():
         assert len(links) == 0 and len(gap) == 0 and not ef.any() and st["links"] == 0
 
 
+def test_names_and_launch_counts_in_the_kernel_times():
+    read_lens, alns, pairs = small_case()  # splints and a span: the sort passes and the reduce kernel run
+    with lengths_index(LENS, time_kernels=True) as kc:
+        kc.kernel_times(clear=True)
+        links, _, st, _ = kc.ctg_links(offsets_of(read_lens), alns, pairs, **KW)
+        assert len(links) == 4 and st["span_cands"] > 0
+        t = kc.kernel_times()
+    # an end's number takes 3 bits: one radix pass a word
+    want = {"kc_align_lengths_kernel<links>": 1, "kc_depth_check_kernel<links>": 1, "kc_lassm_pair_check_kernel<links>": 1,
+            "kc_link_group_kernel<count>": 1, "kc_link_group_kernel<fill>": 1, "kc_link_tile_scan_kernel": 2, "kc_link_scan_kernel": 3,
+            "kc_link_cands_kernel<count>": 1, "kc_link_cands_kernel<write>": 1, "kc_sort_hist_kernel<links>": 2,
+            "kc_sort_scan_kernel<links>": 2, "kc_sort_scatter_kernel<links>": 2, "kc_link_heads_kernel": 1, "kc_link_reduce_kernel": 1,
+            "kc_link_emit_kernel": 1, "kc_link_end_first_kernel": 1}
+    assert {n: c for n, (c, _) in t.items()} == want
+
+
 def test_the_wrapper_calls_once_more_when_four_a_contig_are_too_few():
     lens = [CL] * 12  # room for 4 * 12 + 16 = 64 records; every end linked to every end of the other contigs wants 12 * 11 * 2 * 2
     rows, r = [], 0

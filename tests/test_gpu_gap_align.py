@@ -323,6 +323,18 @@ def test_host_and_device_inputs_and_alignment():
         compare(kc, contigs, reads, alns)
 
 
+def test_names_and_launch_counts_in_the_kernel_times():
+    rng = np.random.default_rng(60)
+    contigs, reads, alns = small_case(rng)
+    with indexed(contigs, time_kernels=True) as kc:
+        kc.kernel_times(clear=True)
+        _, st = kc.align_gapped(*read_arrays(reads), alns)
+        assert st["dp"] > 0
+        t = kc.kernel_times()
+    want = {"kc_align_lengths_kernel<gap>": 1, "kc_gap_check_kernel": 1, "kc_gap_sort_kernel": 1, "kc_gap_dp_kernel": 1}
+    assert {n: c for n, (c, _) in t.items()} == want
+
+
 def test_invalid_records_are_named_and_nothing_is_written():
     rng = np.random.default_rng(61)
     contigs, reads, alns = small_case(rng)

@@ -339,6 +339,20 @@ def test_many_short_contigs_around_a_long_one_and_the_table_budget():
                              "kc_lassm_lens_kernel": 1, "kc_lassm_ends_kernel": 1, "kc_lassm_write_kernel": 1}, (budget, times)
 
 
+def test_names_and_launch_counts_in_the_kernel_times():
+    c = LC.random_case(1, n_ctgs=4, pairs=20)
+    with indexed(c.contigs, 15, time_kernels=True) as kc:
+        kc.kernel_times(clear=True)
+        model = compare(c, k=15, kc=kc, min_mer_len=7, max_walk_len=60, max_insert=300)
+        assert model[3]["ext_bases"] > 0
+        t = kc.kernel_times()
+    want = {"kc_align_lengths_kernel<lassm>": 1, "kc_depth_check_kernel<lassm>": 1, "kc_lassm_pair_check_kernel": 1,
+            "kc_lassm_cands_kernel<count>": 1, "kc_lassm_plan_kernel": 1, "kc_lassm_scan_kernel": 3, "kc_lassm_cands_kernel<write>": 1,
+            "kc_lassm_text_kernel": 1, "kc_lassm_walk_kernel": 1, "kc_lassm_lens_kernel": 1, "kc_lassm_ends_kernel": 1,
+            "kc_lassm_write_kernel": 1}
+    assert {n: launches for n, (launches, _) in t.items()} == want
+
+
 # ---- the protocol -----------------------------------------------------------------------------------------------------
 def test_capacity_size_query_and_optional_outputs():
     c = LC.random_case(6, pairs=60)

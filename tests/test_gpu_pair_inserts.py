@@ -269,6 +269,17 @@ def test_null_outputs_no_records_host_and_wrapper():
         compare(kc, ctg_lens, read_lens[:3] + [1024] + read_lens[4:], alns)
 
 
+def test_names_and_launch_counts_in_the_kernel_times():
+    ctg_lens, read_lens, alns = small_case()
+    with lengths_index(ctg_lens, time_kernels=True) as kc:
+        for max_insert, classify in ((1000, "kc_pair_classify_kernel<lds>"), (LDS_BINS, "kc_pair_classify_kernel")):  # LDS_BINS + 1 bins do not fit
+            kc.kernel_times(clear=True)
+            kc.pair_inserts(offsets_of(read_lens), alns, max_insert=max_insert)
+            t = kc.kernel_times()
+            want = {"kc_align_lengths_kernel<pair>": 1, "kc_depth_check_kernel<pair>": 1, "kc_depth_best_kernel<pair>": 1, classify: 1}
+            assert {n: c for n, (c, _) in t.items()} == want
+
+
 def test_invalid_records_are_named_and_nothing_is_written():
     ctg_lens, read_lens, alns = small_case()
     good = alns[3]  # read 2 of 100 bases on contig 0 (300 bases): cstart 200, cstop 300, rstart 0, rstop 100
