@@ -1142,6 +1142,64 @@ int kc_close_gaps(kc_ctx *ctx, const uint8_t *bases, const uint64_t *offsets, ui
                   const kc_scaffold_rec *scaffolds, uint64_t n_scaffolds, const kc_scaf_member *members, int on_device,
                   const kc_close_params *params, uint8_t *seqs_out, uint64_t capacity, uint64_t *offsets_out, kc_scaffold_rec *scaffolds_out,
                   kc_scaf_member *members_out, kc_closure *closures, uint64_t *nbytes_out, kc_close_stats *stats);
+/* The read pairs regrouped by their home contig: the role of shuffle_reads(qual_offset, packed_reads_list, ctgs),
+ * src/contigging.cpp:128-147, commented out in the proxy.  The reference holds no code for it (no shuffle_reads in src/),
+ * so the rules below are this project's own definition (tests/shuffle_model.py); no parity with
+ * MetaHipMer is claimed.  All quantities are integers; every output is one exact byte string for a given input.
+ *
+ * Input.  Reads 2p and 2p + 1 are mates; bases / quals / offsets: the reads (quals may be NULL, then quals_out is NULL
+ * too); alns: kc_align_gapped's records in any order; pairs: kc_pair_inserts' records for these reads and these records.
+ *
+ * Home.  A pair's candidates are the records its aln0 and aln1 name (0xFFFFFFFF: none).  Without a candidate the pair is
+ * HOMELESS and its home is KC_SHUFFLE_NO_HOME.  Otherwise the chosen record is the first by (greater score, smaller ctg,
+ * smaller cstart, mate 0 before mate 1); its ctg is the pair's HOME, its cstart the pair's ANCHOR.
+ *
+ * Order.  Homed pairs are ordered by (home, anchor, old pair index), homeless pairs by old pair index: one stable radix
+ * sort of a 32-bit permutation by the key home << b | anchor, b the bit length of the longest contig, a homeless pair with
+ * n_ctgs in the home field; the sort runs over the key's key_bits = b + bit length of n_ctgs significant bits only.
+ *
+ * Parts.  With NH homed and NU homeless pairs, part j of `parts` takes the homed pairs of rank
+ * [floor(j NH / parts), floor((j + 1) NH / parts)) and behind them the homeless pairs of rank [floor(j NU / parts),
+ * floor((j + 1) NU / parts)); the new order is part 0, part 1, ...  part_starts[j] = floor(j NH / parts) +
+ * floor(j NU / parts) for j in [0, parts], so part_starts[parts] = the pairs; a part may be empty.  parts = 1: all homed
+ * pairs, then all homeless ones.
+ *
+ * Output, q a new pair index.  order[q]: the old pair index; home[q]: the pair's home; offsets_out: the nreads + 1 offsets
+ * of the reads in new order (mates stay adjacent and keep their order); bases_out / quals_out: the same bytes at the new
+ * offsets; alns_out (may be NULL): alns in the same order with `read` rewritten to the read's new index, so that the
+ * indices in pairs stay valid; pairs_out (may be NULL): pairs_out[q] = pairs[order[q]]; stats (may be NULL): written
+ * once, on success; homed = one_mate + two_same + two_diff, bytes = offsets[nreads].
+ *
+ * Protocol.  Checked in front of ctx, kc_last_error naming the values, each KC_ERR_INVALID_ARG: an odd nreads; parts
+ * outside 1 .. KC_SHUFFLE_MAX_PARTS; a NULL bases_out, offsets_out, order, home or part_starts, or NULL pairs with
+ * nreads > 0; quals and quals_out not both NULL or both given; an output that is an input array.  on_device applies to all
+ * arrays alike; device record arrays (alns, pairs, alns_out, pairs_out) are 16-byte aligned, offsets, offsets_out and
+ * part_starts 8-byte, order and home 4-byte; bases, quals and their outputs may have any alignment.  No index:
+ * KC_ERR_STATE.  2^32 reads or records, or more: KC_ERR_CAPACITY.  A read over KC_ALIGN_MAX_READ_LEN or decreasing
+ * offsets, an invalid record (kc_pair_inserts' validity), a pair that names a record out of range, of another read or of
+ * kind KC_GAP_NONE: KC_ERR_INVALID_ARG, kc_last_error names the lowest bad index; the checks run in the order reads,
+ * records, pairs, each a pass whose verdict is read before anything is stored, so on every error nothing is written
+ * through any pointer.  nreads == 0: KC_OK, offsets_out[0] = 0, part_starts all 0.  The call works before or after
+ * kc_finalize and with rank_n > 1, touches neither the index, the table nor the results, runs on the context's stream
+ * and returns when done; scratch lives for the call only: 36 bytes a pair, 8 a read and 4 for every 4096 bytes of the reads, beside the copies of host arrays
+ * and the outputs' staging for them.
+ */
+#define KC_SHUFFLE_MAX_PARTS 65536
+#define KC_SHUFFLE_NO_HOME 0xFFFFFFFFu
+typedef struct kc_shuffle_stats { /* 80 bytes */
+  uint64_t pairs, homed, homeless;
+  uint64_t one_mate;       /* homed through the only mate that has a best record */
+  uint64_t two_same;       /* both mates have one, on the same contig */
+  uint64_t two_diff;       /* both have one, on different contigs */
+  uint64_t homes;          /* distinct contigs that are some pair's home */
+  uint64_t max_home_pairs; /* the pairs of the home that has the most */
+  uint64_t bytes;          /* offsets[nreads] */
+  uint64_t key_bits;       /* significant bits the sort ran over */
+} kc_shuffle_stats;
+int kc_shuffle_reads(kc_ctx *ctx, const uint8_t *bases, const uint8_t *quals, const uint64_t *offsets, uint64_t nreads,
+                     const kc_gap_aln *alns, uint64_t n_alns, const kc_pair_rec *pairs, int on_device, uint32_t parts,
+                     uint8_t *bases_out, uint8_t *quals_out, uint64_t *offsets_out, uint32_t *order, uint32_t *home,
+                     uint64_t *part_starts, kc_gap_aln *alns_out, kc_pair_rec *pairs_out, kc_shuffle_stats *stats);
 /* KmerDHT::kmer_exists / get_kmer_count / get_local_kmer_counts (src/kcount/kmer_dht.cpp:198-245) in bulk, against the
  * results kept in HBM: nq k-mers of num_longs words each, in either orientation; counts[i] = 0 (and left/right = 0)
  * when the k-mer did not survive.  The index over the results is built on the first call after kc_finalize.

@@ -218,6 +218,15 @@ class kc_close_stats(C.Structure):
 (KC_CLOSE_HEAD, KC_CLOSE_NOT_A_GAP, KC_CLOSE_NO_READS, KC_CLOSE_WEAK, KC_CLOSE_FILLED, KC_CLOSE_ABUT, KC_CLOSE_OVERLAP,
  KC_CLOSE_OVERLAP_REJECTED) = range(8)
 
+
+class kc_shuffle_stats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("pairs", "homed", "homeless", "one_mate", "two_same", "two_diff", "homes", "max_home_pairs", "bytes",
+                                          "key_bits")]
+
+
+KC_SHUFFLE_MAX_PARTS = 65536
+KC_SHUFFLE_NO_HOME = 0xFFFFFFFF
+
 # every symbol include/kcount_mi355.h declares: (restype, argtypes)
 SYMBOLS = {
     "kc_abi_version": (C.c_int, []),
@@ -302,6 +311,9 @@ SYMBOLS = {
     "kc_close_gaps": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int,
                                 C.POINTER(kc_close_params), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                 C.POINTER(C.c_uint64), C.POINTER(kc_close_stats)]),
+    "kc_shuffle_reads": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int, C.c_uint32,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.POINTER(kc_shuffle_stats)]),
     "kc_lookup": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "kc_dump_table": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
     "kc_get_stats": (C.c_int, [C.c_void_p, C.POINTER(kc_stats)]),

@@ -141,7 +141,22 @@
   X(KT_CLOSE_PLACE,        "kc_close_place_kernel") \
   X(KT_CLOSE_VOTE,         "kc_close_vote_kernel") \
   X(KT_CLOSE_RECORDS,      "kc_close_records_kernel") \
-  X(KT_CLOSE_WRITE,        "kc_close_write_kernel")
+  X(KT_CLOSE_WRITE,        "kc_close_write_kernel") \
+  X(KT_SHUF_LENGTHS,       "kc_align_lengths_kernel<shuffle>") \
+  X(KT_SHUF_CHECK,         "kc_depth_check_kernel<shuffle>") \
+  X(KT_SHUF_PAIR_CHECK,    "kc_lassm_pair_check_kernel<shuffle>") \
+  X(KT_SHUF_LONGEST,       "kc_shuf_longest_kernel") \
+  X(KT_SHUF_KEY,           "kc_shuf_key_kernel") \
+  X(KT_SHUF_SORT_HIST,     "kc_sort_hist_kernel<shuffle>") \
+  X(KT_SHUF_SORT_SCAN,     "kc_sort_scan_kernel<shuffle>") \
+  X(KT_SHUF_SORT_SCATTER,  "kc_sort_scatter_kernel<shuffle>") \
+  X(KT_SHUF_PLACE,         "kc_shuf_place_kernel") \
+  X(KT_SHUF_TILE_SCAN,     "kc_link_tile_scan_kernel<shuffle>") \
+  X(KT_SHUF_SCAN,          "kc_shuf_scan_kernel") \
+  X(KT_SHUF_OFFSETS,       "kc_shuf_offsets_kernel") \
+  X(KT_SHUF_GATHER,        "kc_shuf_gather_kernel") \
+  X(KT_SHUF_REMAP,         "kc_shuf_remap_kernel") \
+  X(KT_SHUF_PARTS,         "kc_shuf_parts_kernel")
 
 enum {
 #define X(kind, name) kind,

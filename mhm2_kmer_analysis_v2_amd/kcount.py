@@ -978,6 +978,64 @@ class KmerCounter:
         text = seqs.tobytes().decode()
         return [text[int(offs[i]):int(offs[i + 1]) - 1] for i in range(len(offs) - 1)]
 
+    def shuffle_reads(self, bases, quals, offsets, gap_alns, pairs, parts=1, remap=True):
+        """The read pairs regrouped by their home contig (kc_shuffle_reads): a pair's home is the
+        contig of the better of its mates' best records; homed pairs are ordered by (home, position on it), homeless
+        ones keep their order, and both are dealt evenly over `parts` consecutive parts.  bases / quals / offsets: the
+        reads (2p and 2p + 1 are mates; quals None: none come back); gap_alns align_gapped's records, pairs pair_inserts'.
+        Returns a dict: bases, quals, offsets -- the reads in new order -- order (new pair -> old pair), home (new pair ->
+        contig, KC_SHUFFLE_NO_HOME for none), part_starts (parts + 1 pair indices), gap_alns (the records with their read
+        renumbered) and pairs (in new order), both None without remap, and stats (kc_shuffle_stats as a dict).  Host arrays
+        in give numpy arrays out (GAP_ALN_DTYPE, PAIR_DTYPE records, uint32 order and home, uint64 offsets); device
+        tensors in give device tensors out (uint8 tensors of records, int32 order and home holding the 32 bits, int64
+        offsets and part_starts)."""
+        pa, n_alns, dev_a = self._gap_records(gap_alns)
+        po, dev = _ptr(offsets)
+        nreads = len(offsets) - 1
+        pb, dev_b = _ptr(bases)
+        pq, dev_q = (None, dev) if quals is None else _ptr(quals)
+        pp, dev_p = _ptr(pairs)
+        npairs = pairs.numel() // 16 if dev_p else len(pairs)
+        nbytes = bases.numel() if dev_b else len(bases)
+        if (n_alns and dev_a != dev) or (nbytes and (dev_b != dev or dev_q != dev)) or (npairs and dev_p != dev):
+            raise ValueError("bases, quals, offsets, gap_alns and pairs must all be host arrays or all be device tensors")
+        if npairs != nreads // 2 or (not dev and npairs and (pairs.dtype.itemsize != 16 or not pairs.flags["C_CONTIGUOUS"])):
+            raise ValueError("pairs: a contiguous array of nreads / 2 16-byte records (PAIR_DTYPE)")
+        if quals is not None and (quals.numel() if dev_q and hasattr(quals, "numel") else len(quals)) != nbytes:
+            raise ValueError("quals: as many bytes as bases")
+        st = _lib.kc_shuffle_stats()
+        if dev:
+            import torch
+            dv = "cuda:%d" % self.device
+            out = {"bases": torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dv),
+                   "quals": None if quals is None else torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dv),
+                   "offsets": torch.empty(nreads + 1, dtype=torch.int64, device=dv),
+                   "order": torch.empty(max(npairs, 1), dtype=torch.int32, device=dv),
+                   "home": torch.empty(max(npairs, 1), dtype=torch.int32, device=dv),
+                   "part_starts": torch.empty(parts + 1, dtype=torch.int64, device=dv),
+                   "gap_alns": torch.empty(max(n_alns, 1) * 32, dtype=torch.uint8, device=dv) if remap else None,
+                   "pairs": torch.empty(max(npairs, 1) * 16, dtype=torch.uint8, device=dv) if remap else None}
+            torch.cuda.current_stream(self.device).synchronize()  # the input and the fresh arrays are torch's until now
+        else:
+            out = {"bases": np.zeros(max(nbytes, 1), dtype=np.uint8), "quals": None if quals is None else np.zeros(max(nbytes, 1), dtype=np.uint8),
+                   "offsets": np.zeros(nreads + 1, dtype=np.uint64), "order": np.zeros(max(npairs, 1), dtype=np.uint32),
+                   "home": np.zeros(max(npairs, 1), dtype=np.uint32), "part_starts": np.zeros(parts + 1, dtype=np.uint64),
+                   "gap_alns": np.zeros(max(n_alns, 1), dtype=GAP_ALN_DTYPE) if remap else None,
+                   "pairs": np.zeros(max(npairs, 1), dtype=PAIR_DTYPE) if remap else None}
+        p = {k: _ptr(v)[0] for k, v in out.items()}
+        check(lib().kc_shuffle_reads(self._h, pb if nbytes else None, pq if nbytes else None, po, nreads, pa, n_alns, pp if npairs else None,
+                                     1 if dev else 0, parts, p["bases"], p["quals"] if nbytes or quals is None else None, p["offsets"], p["order"],
+                                     p["home"], p["part_starts"], p["gap_alns"], p["pairs"], C.byref(st)), "kc_shuffle_reads")
+        out["bases"] = out["bases"][:nbytes]
+        if quals is not None:
+            out["quals"] = out["quals"][:nbytes]
+        out["order"], out["home"] = out["order"][:npairs], out["home"][:npairs]
+        if remap:
+            out["gap_alns"] = out["gap_alns"][:n_alns * 32] if dev else out["gap_alns"][:n_alns]
+            out["pairs"] = out["pairs"][:npairs * 16] if dev else out["pairs"][:npairs]
+        out["stats"] = {f: int(getattr(st, f)) for f, _ in _lib.kc_shuffle_stats._fields_}
+        return out
+
     def submit_ctg_block(self, seqs, depths):
         """kc_submit_ctg_block with device tensors (a '_'-joined block and one 16-bit depth per byte), e.g. those of
         unitig_block(); begin_ctg_kmers first."""
