@@ -36,6 +36,108 @@ def _ptr(a):
     return a.ctypes.data, False
 
 
+def _reads(bases, quals, offsets, nreads=None):
+    """The reads of a call -> the addresses of bases, quals (None: none) and offsets, the number of reads (by default
+    what the offsets hold) and whether bases is device memory."""
+    pb, dev = _ptr(bases)
+    n = (len(offsets) - 1) if nreads is None else nreads
+    return pb, _ptr(quals)[0], _ptr(offsets)[0], n, dev
+
+
+def _span(offsets, n):
+    """the bytes of the first n reads, from host or device offsets"""
+    return int(offsets[n]) - int(offsets[0]) if n else 0
+
+
+def _records(name, a, dtype, contiguous=True, required=False):
+    """A record array argument -> (address, or None where there are no records; number of records; on the device).
+    Device records come as a uint8 tensor of count * itemsize bytes; a host array is checked for the item size and for
+    being contiguous (contiguous=False: only the item size).  required: the library wants the array even where it is
+    empty, so it is checked and its address passed as it is."""
+    p, dev = _ptr(a)
+    n = a.numel() // dtype.itemsize if dev else len(a)
+    if not dev and (n or required) and (a.dtype.itemsize != dtype.itemsize or (contiguous and not a.flags["C_CONTIGUOUS"])):
+        raise ValueError("%s: a contiguous array of %d-byte records" % (name, dtype.itemsize))
+    return (p if n or required else None), n, dev
+
+
+def _side(ref, dev, **others):
+    """Which side a call is on: that of its argument `ref`, which is on the device or not (dev).  others: name =
+    (on the device, number of elements) of every other array; one that has elements lies on the same side.  The error
+    names the fewer: the arrays that are not where most of the call's are, or all of them where it is a draw."""
+    sides = {True: [], False: []}
+    sides[bool(dev)].append(ref)
+    for name, (d, n) in others.items():
+        if n:
+            sides[bool(d)].append(name)
+    if sides[True] and sides[False]:
+        few, many = sorted(sides.items(), key=lambda kv: len(kv[1]))
+        if len(few[1]) == len(many[1]):
+            raise ValueError("%s: not on one side; a call's arrays are all host arrays or all device tensors" % ", ".join(few[1] + many[1]))
+        raise ValueError("%s: %s among %s; a call's arrays are all host arrays or all device tensors" % (
+            ", ".join(few[1]), "on the device" if few[0] else "in host memory", "host arrays" if few[0] else "device tensors"))
+    return dev
+
+
+# torch has no unsigned 16-, 32- and 64-bit integers: the signed ones hold the bits
+_TORCH_OF = {"uint8": "uint8", "uint16": "int16", "uint32": "int32", "uint64": "int64"}
+
+
+class _Out:
+    """One output array of a call, of n elements of a record dtype or a scalar dtype, and its address (ptr).  device None:
+    a numpy array of zeros; else the torch device: an uninitialised tensor (zeroed=True: zeros), records as uint8 bytes of
+    n * itemsize.  pad: room for one element where n is 0, so that the library gets an address; an exact array of no
+    elements has torch's address 0 on the device, which the library reads as NULL -- for the seqs of a call, a size query."""
+
+    def __init__(self, device, n, dtype, pad=False, zeroed=False):
+        dtype = np.dtype(dtype)
+        # elements of `a` to one of the n: the bytes of a record on the device, else one
+        self.n, self.size = n, dtype.itemsize if dtype.fields and device is not None else 1
+        m = max(n, 1) if pad else n
+        if device is None:
+            self.a = np.zeros(m, dtype=dtype)
+        else:
+            import torch
+            kind = torch.uint8 if dtype.fields else getattr(torch, _TORCH_OF[dtype.name])
+            self.a = (torch.zeros if zeroed else torch.empty)(m * self.size, dtype=kind, device=device)
+        self.ptr = _ptr(self.a)[0]
+
+    def first(self, n=None):
+        """the first n elements (by default the n it was made for)"""
+        return self.a[:(self.n if n is None else n) * self.size]
+
+
+def _stats_dict(st):
+    """A statistics struct as a dict: integers, lists of integers for array fields, nothing of `reserved`."""
+    values = ((f, getattr(st, f)) for f, _ in st._fields_ if f != "reserved")
+    return {f: [int(x) for x in v] if isinstance(v, C.Array) else int(v) for f, v in values}
+
+
+def _retry_on_capacity(capacity, call, below=None):
+    """call(capacity) allocates that much, calls the library and returns (status, the size the library reported, the
+    array).  Where the guess was too small -- KC_ERR_CAPACITY and a larger size reported (and one below `below`) -- the
+    call is made once more with that size, never a third time."""
+    rc, told, out = call(capacity)
+    if rc == _lib.KC_ERR_CAPACITY and capacity < told and (below is None or told < below):
+        rc, told, out = call(told)  # the size it was told
+    return rc, told, out
+
+
+def _block_strings(seqs, offsets):
+    """A seq block (every sequence followed by '_') and its starts, host arrays or device tensors, as Python strings."""
+    if not isinstance(seqs, np.ndarray):
+        seqs, offsets = seqs.cpu().numpy(), offsets.cpu().numpy()
+    text = seqs.tobytes().decode()
+    return [text[int(offsets[i]):int(offsets[i + 1]) - 1] for i in range(len(offsets) - 1)]
+
+
+def _adapter_counts(fn, *args):
+    """the loader's four counters, which kc_adapters_load and kc_adapters_index return behind their other arguments"""
+    v = [C.c_uint64(0) for _ in range(4)]
+    check(getattr(lib(), fn)(*args, *[C.byref(x) for x in v]), fn)
+    return dict(zip(("n_adapters", "n_short", "n_entries", "n_kmers"), (x.value for x in v)))
+
+
 def _text_on_device(t):
     return hasattr(t, "data_ptr") and bool(t.is_cuda)
 
@@ -155,50 +257,48 @@ class KmerCounter:
             self.nl = lib().kc_num_longs(new_kmer_len)
             self.rec_nl = lib().kc_record_longs(new_kmer_len)
 
+    def _torch_device(self):
+        return "cuda:%d" % self.device
+
+    def _out(self, dev, n, dtype, **kw):
+        """an output array of the call's side (_Out): on this counter's device, or host memory"""
+        return _Out(self._torch_device() if dev else None, n, dtype, **kw)
+
+    def _hand_over(self, dev=True):
+        """The hand-over from torch to the library in a call on the device side: the input and the fresh arrays are
+        torch's until its current stream on this counter's device has nothing more to do with them."""
+        if dev:
+            import torch
+            torch.cuda.current_stream(self.device).synchronize()
+
     def submit_reads(self, bases, quals, offsets, nreads=None):
-        pb, dev = _ptr(bases)
-        pq, _ = _ptr(quals)
-        po, _ = _ptr(offsets)
-        n = (len(offsets) - 1) if nreads is None else nreads
+        pb, pq, po, n, dev = _reads(bases, quals, offsets, nreads)
         check(lib().kc_submit_reads(self._h, pb, pq, po, n, 1 if dev else 0), "kc_submit_reads")
 
     def submit_packed_reads(self, packed, offsets, nreads=None):
         """PackedRead bytes (base | quality<<3, src/packed_reads.cpp:99-126) + offsets."""
-        pp, dev = _ptr(packed)
-        po, _ = _ptr(offsets)
-        n = (len(offsets) - 1) if nreads is None else nreads
+        pp, _, po, n, dev = _reads(packed, None, offsets, nreads)
         check(lib().kc_submit_packed_reads(self._h, pp, po, n, 1 if dev else 0), "kc_submit_packed_reads")
 
     def merge_pairs(self, bases, quals, offsets, npairs=None, min_kmer_len=0):
         """Overlap merge of interleaved pairs on the device (kc_merge_pairs): returns (packed u8, offsets int64) as device
         tensors holding exactly the output, ready for submit_packed_reads, and the counters as a dict.  Host arrays are
         staged; min_kmer_len 0 = this counter's k."""
-        import torch
-        pb, dev = _ptr(bases)
-        pq, _ = _ptr(quals)
-        po, _ = _ptr(offsets)
-        n = (len(offsets) - 1) // 2 if npairs is None else npairs
-        if dev:
-            total = int(offsets[2 * n].item()) - int(offsets[0].item()) if n else 0
-        else:
-            total = int(offsets[2 * n]) - int(offsets[0]) if n else 0
-        d = "cuda:%d" % self.device
-        packed = torch.empty(max(total, 1), dtype=torch.uint8, device=d)
-        outo = torch.empty(2 * n + 1, dtype=torch.int64, device=d)
+        pb, pq, po, nreads, dev = _reads(bases, quals, offsets, None if npairs is None else 2 * npairs)
+        n = nreads // 2
+        total = _span(offsets, 2 * n)
+        packed, outo = self._out(True, total, np.uint8, pad=True), self._out(True, 2 * n + 1, np.uint64)
         nr, nb, st = C.c_uint64(0), C.c_uint64(0), kc_merge_stats()
-        check(lib().kc_merge_pairs(self._h, pb, pq, po, n, 1 if dev else 0, min_kmer_len, packed.data_ptr(), total, outo.data_ptr(),
-                                   2 * n, C.byref(nr), C.byref(nb), C.byref(st)), "kc_merge_pairs")
-        return packed[:nb.value], outo[:nr.value + 1], {f: int(getattr(st, f)) for f, _ in kc_merge_stats._fields_}
+        check(lib().kc_merge_pairs(self._h, pb, pq, po, n, 1 if dev else 0, min_kmer_len, packed.ptr, total, outo.ptr, 2 * n, C.byref(nr),
+                                   C.byref(nb), C.byref(st)), "kc_merge_pairs")
+        return packed.first(nb.value), outo.first(nr.value + 1), _stats_dict(st)
 
     def load_adapters(self, text_or_path, adapter_k=0, blastn_scores=False):
         """Load an adapter set into this counter (kc_adapters_load): FASTA text as bytes, or the path of a FASTA file as
         str.  adapter_k 0 = this counter's k; blastn_scores: align with 2/3/5/2/1 instead of 1/1/1/1/1.  The set stays
         over reset(); loading again replaces it.  Returns the loader's counts."""
         data = _adapter_text(text_or_path)
-        v = [C.c_uint64(0) for _ in range(4)]
-        check(lib().kc_adapters_load(self._h, data, len(data), adapter_k, _lib.KC_ADAPTERS_BLASTN_SCORES if blastn_scores else 0,
-                                     *[C.byref(x) for x in v]), "kc_adapters_load")
-        return dict(zip(("n_adapters", "n_short", "n_entries", "n_kmers"), (x.value for x in v)))
+        return _adapter_counts("kc_adapters_load", self._h, data, len(data), adapter_k, _lib.KC_ADAPTERS_BLASTN_SCORES if blastn_scores else 0)
 
     def clear_adapters(self):
         check(lib().kc_adapters_clear(self._h), "kc_adapters_clear")
@@ -208,68 +308,52 @@ class KmerCounter:
         (2p, 2p+1), or with paired=False Adapters::trim per read.  Returns (bases u8, quals u8, offsets int64) as device
         tensors in the input's layout, ready for merge_pairs or submit_reads, and the counters as a dict.  Host arrays
         are staged."""
-        import torch
-        pb, dev = _ptr(bases)
-        pq, _ = _ptr(quals)
-        po, _ = _ptr(offsets)
-        n = (len(offsets) - 1) if nreads is None else nreads
-        if dev:
-            total = int(offsets[n].item()) - int(offsets[0].item()) if n else 0
-        else:
-            total = int(offsets[n]) - int(offsets[0]) if n else 0
-        d = "cuda:%d" % self.device
-        ob = torch.empty(max(total, 1), dtype=torch.uint8, device=d)
-        oq = torch.empty(max(total, 1), dtype=torch.uint8, device=d)
-        oo = torch.empty(n + 1, dtype=torch.int64, device=d)
+        pb, pq, po, n, dev = _reads(bases, quals, offsets, nreads)
+        total = _span(offsets, n)
+        ob, oq = self._out(True, total, np.uint8, pad=True), self._out(True, total, np.uint8, pad=True)
+        oo = self._out(True, n + 1, np.uint64)
         nb, st = C.c_uint64(0), kc_trim_stats()
-        torch.cuda.current_stream(self.device).synchronize()  # the input and the fresh arrays are torch's until now
-        check(lib().kc_trim_adapters(self._h, pb, pq, po, n, 1 if dev else 0, _lib.KC_TRIM_PAIRED if paired else 0, ob.data_ptr(),
-                                     oq.data_ptr(), total, oo.data_ptr(), C.byref(nb), C.byref(st)), "kc_trim_adapters")
-        return ob[:nb.value], oq[:nb.value], oo, {f: int(getattr(st, f)) for f, _ in kc_trim_stats._fields_}
+        self._hand_over()
+        check(lib().kc_trim_adapters(self._h, pb, pq, po, n, 1 if dev else 0, _lib.KC_TRIM_PAIRED if paired else 0, ob.ptr, oq.ptr, total,
+                                     oo.ptr, C.byref(nb), C.byref(st)), "kc_trim_adapters")
+        return ob.first(nb.value), oq.first(nb.value), oo.a, _stats_dict(st)
 
     def fastq_to_packed(self, text, partial=False):
         """FASTQ text parsed on the device (kc_fastq_to_packed_device): returns (packed u8, offsets int64) as device
         tensors holding exactly kc_fastq_to_packed's output, ready for submit_packed_reads, and with partial=True also
         `consumed`, the byte past the last whole record (only whole records are parsed; the caller carries the tail).
         text: bytes, a numpy uint8 array (copied to the device) or a uint8 device tensor (read in place)."""
-        import torch
         pt, n, dev, keep = _text(text)
-        d = "cuda:%d" % self.device
-        packed = torch.empty(max(n, 1), dtype=torch.uint8, device=d)
-        offs = torch.empty(n // 4 + 2, dtype=torch.int64, device=d)
+        packed, offs = self._out(True, n, np.uint8, pad=True), self._out(True, n // 4 + 2, np.uint64)
         nr, nb, cons = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
-        torch.cuda.current_stream(self.device).synchronize()  # the text and the fresh arrays are torch's until now
-        check(lib().kc_fastq_to_packed_device(self._h, pt, n, 1 if dev else 0, _lib.KC_FASTQ_PARTIAL if partial else 0,
-                                              packed.data_ptr(), n, offs.data_ptr(), n // 4 + 1, C.byref(nr), C.byref(nb),
-                                              C.byref(cons)), "kc_fastq_to_packed_device")
+        self._hand_over()
+        check(lib().kc_fastq_to_packed_device(self._h, pt, n, 1 if dev else 0, _lib.KC_FASTQ_PARTIAL if partial else 0, packed.ptr, n,
+                                              offs.ptr, n // 4 + 1, C.byref(nr), C.byref(nb), C.byref(cons)), "kc_fastq_to_packed_device")
         del keep
-        out = (packed[:nb.value], offs[:nr.value + 1])
+        out = (packed.first(nb.value), offs.first(nr.value + 1))
         return out + (cons.value,) if partial else out
 
     def fastq_pairs(self, text1, text2=None, partial=False):
         """Paired FASTQ text parsed on the device (kc_fastq_pairs_device; text2 None = text1 interleaved): returns
         (bases u8, quals u8, offsets int64) device tensors holding exactly kc_fastq_pairs' output, ready for merge_pairs,
         and with partial=True also (consumed1, consumed2), the bytes of each text taken (consumed2 None for one text)."""
-        import torch
         p1, n1, dev, keep1 = _text(text1)
         p2, n2, _, keep2 = _text(text2) if text2 is not None else (None, 0, dev, None)
         if text2 is not None and _text_on_device(text2) != dev:
             raise ValueError("text1 and text2 must both be host or both be device memory")
-        d = "cuda:%d" % self.device
         if text2 is not None and not p2:  # an empty second file is still a second file: NULL text2 would mean interleaved
-            keep2 = torch.zeros(1, dtype=torch.uint8, device=d) if dev else np.zeros(1, dtype=np.uint8)
-            p2 = keep2.data_ptr() if dev else keep2.ctypes.data
+            keep2 = self._out(dev, 1, np.uint8, zeroed=True)
+            p2 = keep2.ptr
         n = n1 + n2
-        bases = torch.empty(max(n, 1), dtype=torch.uint8, device=d)
-        quals = torch.empty(max(n, 1), dtype=torch.uint8, device=d)
-        offs = torch.empty(n // 4 + 2, dtype=torch.int64, device=d)
+        bases, quals = self._out(True, n, np.uint8, pad=True), self._out(True, n, np.uint8, pad=True)
+        offs = self._out(True, n // 4 + 2, np.uint64)
         nr, nb, c1, c2 = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
-        torch.cuda.current_stream(self.device).synchronize()  # the texts and the fresh arrays are torch's until now
-        check(lib().kc_fastq_pairs_device(self._h, p1, n1, p2, n2, 1 if dev else 0, _lib.KC_FASTQ_PARTIAL if partial else 0,
-                                          bases.data_ptr(), quals.data_ptr(), n, offs.data_ptr(), n // 4 + 1, C.byref(nr),
-                                          C.byref(nb), C.byref(c1), C.byref(c2)), "kc_fastq_pairs_device")
+        self._hand_over()
+        check(lib().kc_fastq_pairs_device(self._h, p1, n1, p2, n2, 1 if dev else 0, _lib.KC_FASTQ_PARTIAL if partial else 0, bases.ptr,
+                                          quals.ptr, n, offs.ptr, n // 4 + 1, C.byref(nr), C.byref(nb), C.byref(c1), C.byref(c2)),
+              "kc_fastq_pairs_device")
         del keep1, keep2
-        out = (bases[:nb.value], quals[:nb.value], offs[:nr.value + 1])
+        out = (bases.first(nb.value), quals.first(nb.value), offs.first(nr.value + 1))
         return out + ((c1.value, None if text2 is None else c2.value),) if partial else out
 
     def submit_fastq(self, path_or_fileobj, block_bytes=1 << 30):
@@ -326,11 +410,8 @@ class KmerCounter:
     def extract_partition(self, bases, quals, offsets, records, seg_capacity, nreads=None):
         """records: device buffer of rank_n*pieces*seg_capacity*unit_words u64 (wire_unit()).  Returns the units of every
         piece, destination after destination."""
-        pb, dev = _ptr(bases)
-        pq, _ = _ptr(quals)
-        po, _ = _ptr(offsets)
+        pb, pq, po, n, dev = _reads(bases, quals, offsets, nreads)
         pr, _ = _ptr(records)
-        n = (len(offsets) - 1) if nreads is None else nreads
         counts = np.zeros(self.rank_n * (self.wire_unit()[2] if self._wire_units else 1), dtype=np.uint64)
         check(lib().kc_extract_partition(self._h, pb, pq, po, n, 1 if dev else 0, pr, seg_capacity, counts.ctypes.data),
               "kc_extract_partition")
@@ -389,11 +470,8 @@ class KmerCounter:
     # ---- the single-pass shard flow (ownership by level-1 bucket) ----
     def shard_extract(self, bases, quals, offsets, segments, seg_words, nreads=None):
         """segments: device buffer of rank_n*seg_words u64.  Returns the words to ship per destination."""
-        pb, dev = _ptr(bases)
-        pq, _ = _ptr(quals)
-        po, _ = _ptr(offsets)
+        pb, pq, po, n, dev = _reads(bases, quals, offsets, nreads)
         ps, _ = _ptr(segments)
-        n = (len(offsets) - 1) if nreads is None else nreads
         words = np.zeros(self.rank_n, dtype=np.uint64)
         check(lib().kc_shard_extract(self._h, pb, pq, po, n, 1 if dev else 0, ps, seg_words, words.ctypes.data), "kc_shard_extract")
         return words
@@ -416,8 +494,8 @@ class KmerCounter:
         p = C.c_void_p(0)
         check(lib().kc_shard_reserve(self._h, int(nwords), C.byref(p)), "kc_shard_reserve")
         if not nwords:
-            return torch.empty(0, dtype=torch.int64, device=device or ("cuda:%d" % self.device))
-        return _DeviceWords(p.value, int(nwords), device or ("cuda:%d" % self.device)).tensor()
+            return torch.empty(0, dtype=torch.int64, device=device or self._torch_device())
+        return _DeviceWords(p.value, int(nwords), device or self._torch_device()).tensor()
 
     def shard_commit(self, segment, nwords):
         ps, _ = _ptr(segment)
@@ -487,7 +565,7 @@ class KmerCounter:
     def stats(self):
         s = kc_stats()
         check(lib().kc_get_stats(self._h, C.byref(s)), "kc_get_stats")
-        return {n: int(getattr(s, n)) for n, _ in kc_stats._fields_}
+        return _stats_dict(s)
 
     def arena_probe_rate(self):
         """TB/s of level 1's write pattern on the level-1 arena this context chose (0.0: no probe ran)."""
@@ -497,10 +575,11 @@ class KmerCounter:
 
     def kernel_times(self, clear=False):
         """{kernel name: (launches, total_ms)} from HIP events on the launch stream (needs time_kernels=True)."""
-        arr = (kc_kernel_time * 128)()  # more than the library has kinds of kernels
         n = C.c_int(0)
-        check(lib().kc_get_kernel_times(self._h, arr, 128, C.byref(n)), "kc_get_kernel_times")
-        out = {arr[i].name.decode(): (int(arr[i].launches), float(arr[i].total_ms)) for i in range(min(n.value, 128))}
+        check(lib().kc_get_kernel_times(self._h, None, 0, C.byref(n)), "kc_get_kernel_times")  # how many entries it has
+        arr = (kc_kernel_time * n.value)()
+        check(lib().kc_get_kernel_times(self._h, arr, len(arr), C.byref(n)), "kc_get_kernel_times")
+        out = {x.name.decode(): (int(x.launches), float(x.total_ms)) for x in arr}
         if clear:
             check(lib().kc_clear_kernel_times(self._h), "kc_clear_kernel_times")
         return out
@@ -529,7 +608,6 @@ class KmerCounter:
     def dump_text(self, first=0, count=None, sort=True):
         """The dump text of results [first, first + count) as bytes, formatted on the device (kc_dump_text_device): what
         "".join(line + "\n" for line in dump_lines()) gives for the whole.  sort=False: the results' current order."""
-        import torch
         r = self.sort_results() if sort else self.finalize()
         if count is None:
             count = int(r.n) - first
@@ -537,28 +615,26 @@ class KmerCounter:
         check(lib().kc_dump_text_device(self._h, first, count, None, 0, C.byref(nb)), "kc_dump_text_device")
         if not nb.value:
             return b""
-        text = torch.empty(nb.value, dtype=torch.uint8, device="cuda:%d" % self.device)
-        torch.cuda.current_stream(self.device).synchronize()  # the fresh array is torch's until now
-        check(lib().kc_dump_text_device(self._h, first, count, text.data_ptr(), nb.value, C.byref(nb)), "kc_dump_text_device")
-        return text.cpu().numpy().tobytes()
+        text = self._out(True, nb.value, np.uint8)
+        self._hand_over()
+        check(lib().kc_dump_text_device(self._h, first, count, text.ptr, nb.value, C.byref(nb)), "kc_dump_text_device")
+        return text.a.cpu().numpy().tobytes()
 
     def _unitigs(self, with_depths, with_sums):
-        import torch
         self.finalize()
         L = lib()
         nu, nb, st = C.c_uint64(0), C.c_uint64(0), kc_unitig_stats()
         check(L.kc_build_unitigs(self._h, None, 0, None, None, 0, None, C.byref(nu), C.byref(nb), C.byref(st)), "kc_build_unitigs")
-        dev = "cuda:%d" % self.device
-        seqs = torch.empty(nb.value, dtype=torch.uint8, device=dev)
-        offsets = torch.zeros(nu.value + 1, dtype=torch.int64, device=dev)
-        depths = torch.empty(nb.value, dtype=torch.int16, device=dev) if with_depths else None
-        sums = torch.empty(nu.value, dtype=torch.int64, device=dev) if with_sums else None
-        torch.cuda.current_stream(self.device).synchronize()  # the fresh arrays are torch's until now
-        check(L.kc_build_unitigs(self._h, seqs.data_ptr(), nb.value, depths.data_ptr() if with_depths else None, offsets.data_ptr(),
-                                 nu.value, sums.data_ptr() if with_sums else None, C.byref(nu), C.byref(nb), C.byref(st)),
-              "kc_build_unitigs")
+        seqs = self._out(True, nb.value, np.uint8)
+        # zeroed: without unitigs seqs has no address, the call is one more size query and offsets[0] is not written
+        offsets = self._out(True, nu.value + 1, np.uint64, zeroed=True)
+        depths = self._out(True, nb.value, np.uint16) if with_depths else None
+        sums = self._out(True, nu.value, np.uint64) if with_sums else None
+        self._hand_over()
+        check(L.kc_build_unitigs(self._h, seqs.ptr, nb.value, depths.ptr if with_depths else None, offsets.ptr, nu.value,
+                                 sums.ptr if with_sums else None, C.byref(nu), C.byref(nb), C.byref(st)), "kc_build_unitigs")
         self._res = None  # the results may have moved (kc_sort_results)
-        return seqs, depths, offsets, sums, {n: int(getattr(st, n)) for n, _ in kc_unitig_stats._fields_}
+        return seqs.a, depths.a if with_depths else None, offsets.a, sums.a if with_sums else None, _stats_dict(st)
 
     def unitigs(self):
         """The unitigs of the results, built on the device (kc_build_unitigs): (seqs, offsets,
@@ -577,26 +653,22 @@ class KmerCounter:
     def unitig_strings(self):
         """Host list of (sequence, kmer_sum), in the output's order: for tests and small inputs."""
         seqs, offsets, sums, _ = self.unitigs()
-        text, offs, ks = seqs.cpu().numpy().tobytes().decode(), offsets.cpu().tolist(), sums.cpu().tolist()
-        return [(text[offs[u]:offs[u + 1] - 1], ks[u]) for u in range(len(ks))]
+        return list(zip(_block_strings(seqs, offsets), sums.cpu().tolist()))
 
     def index_contigs(self, seqs, offsets):
         """Seed index over a block of contigs (kc_ctg_index_build): seqs a uint8 seq block (every
         contig followed by '_'), offsets its len(contigs) + 1 starts as 64-bit integers -- numpy arrays, or device tensors
         as unitigs() returns them.  The counter keeps its own copy; an earlier index is replaced.  Returns
         kc_ctg_index_stats as a dict."""
-        ps, dev = _ptr(seqs)
+        ps, dev_s = _ptr(seqs)
         po, dev_o = _ptr(offsets)
-        if dev != dev_o:
-            raise ValueError("seqs and offsets must both be host arrays or both be device tensors")
+        dev = _side("seqs", dev_s, offsets=(dev_o, True))
         n = len(offsets) - 1
         nbytes = seqs.numel() if dev else len(seqs)
         st = kc_ctg_index_stats()
-        if dev:
-            import torch
-            torch.cuda.current_stream(self.device).synchronize()  # the arrays are torch's until now
+        self._hand_over(dev)
         check(lib().kc_ctg_index_build(self._h, ps if nbytes else None, nbytes, po, n, 1 if dev else 0, C.byref(st)), "kc_ctg_index_build")
-        return {f: int(getattr(st, f)) for f, _ in kc_ctg_index_stats._fields_}
+        return _stats_dict(st)
 
     def index_unitigs(self):
         """unitigs() straight into the seed index, on the device.  Returns kc_ctg_index_stats as a dict."""
@@ -611,32 +683,17 @@ class KmerCounter:
         uint8 ASCII, offsets nreads + 1 64-bit integers.  Returns (alns, read_first, stats): for host arrays alns is a
         numpy structured array (ALN_DTYPE) and read_first a uint64 array; for device tensors alns is a uint8 device tensor
         of 32-byte records and read_first an int64 device tensor.  max_mismatches None keeps every candidate."""
-        pb, dev = _ptr(bases)
-        po, dev_o = _ptr(offsets)
-        n = (len(offsets) - 1) if nreads is None else nreads
-        if n and dev != dev_o:
-            raise ValueError("bases and offsets must both be host arrays or both be device tensors")
-        dev = dev_o
+        pb, _, po, n, dev_b = _reads(bases, None, offsets, nreads)
+        dev = _side("offsets", _ptr(offsets)[1], bases=(dev_b, n))
         mm = _lib.KC_ALIGN_KEEP_ALL if max_mismatches is None else max_mismatches
-        L = lib()
+        head = (self._h, pb, po, n, 1 if dev else 0, seed_space, mm)
         na, st = C.c_uint64(0), kc_align_stats()
-        if dev:
-            import torch
-            torch.cuda.current_stream(self.device).synchronize()  # the input is torch's until now
-        check(L.kc_align_reads(self._h, pb, po, n, 1 if dev else 0, seed_space, mm, None, 0, None, C.byref(na), C.byref(st)), "kc_align_reads")
-        if dev:
-            d = "cuda:%d" % self.device
-            alns = torch.empty(max(na.value, 1) * 32, dtype=torch.uint8, device=d)
-            first = torch.empty(n + 1, dtype=torch.int64, device=d)
-            torch.cuda.current_stream(self.device).synchronize()  # the fresh arrays are torch's until now
-            pa, pf = alns.data_ptr(), first.data_ptr()
-        else:
-            alns = np.zeros(max(na.value, 1), dtype=ALN_DTYPE)
-            first = np.zeros(n + 1, dtype=np.uint64)
-            pa, pf = alns.ctypes.data, first.ctypes.data
-        check(L.kc_align_reads(self._h, pb, po, n, 1 if dev else 0, seed_space, mm, pa, na.value, pf, C.byref(na), C.byref(st)), "kc_align_reads")
-        alns = alns[:na.value * 32] if dev else alns[:na.value]
-        return alns, first, {f: int(getattr(st, f)) for f, _ in kc_align_stats._fields_}
+        self._hand_over(dev)
+        check(lib().kc_align_reads(*head, None, 0, None, C.byref(na), C.byref(st)), "kc_align_reads")
+        alns, first = self._out(dev, na.value, ALN_DTYPE, pad=True), self._out(dev, n + 1, np.uint64)
+        self._hand_over(dev)  # fresh arrays
+        check(lib().kc_align_reads(*head, alns.ptr, na.value, first.ptr, C.byref(na), C.byref(st)), "kc_align_reads")
+        return alns.first(na.value), first.a, _stats_dict(st)
 
     def align_gapped(self, bases, offsets, alns, pad=16, scores=None, always_dp=False):
         """Gapped refinement of align_reads' records (kc_align_gapped): the same reads and the
@@ -644,42 +701,22 @@ class KmerCounter:
         a uint8 tensor of 32-byte records).  scores: (match, mismatch, gap open, gap extend, ambiguity), by default
         BLASTN_ALN_SCORES.  Returns (gap_alns, stats): one record per input record, in the same order -- a structured
         array of GAP_ALN_DTYPE for host arrays, a uint8 device tensor of 32-byte records for device tensors."""
-        pb, dev_b = _ptr(bases)
-        po, dev = _ptr(offsets)
-        pa, dev_a = _ptr(alns)
-        n = len(offsets) - 1
-        n_alns = alns.numel() // 32 if dev_a else len(alns)
-        if (n_alns and dev_a != dev) or (n and len(bases) and dev_b != dev):
-            raise ValueError("bases, offsets and alns must all be host arrays or all be device tensors")
-        if not dev and n_alns and (alns.dtype.itemsize != 32 or not alns.flags["C_CONTIGUOUS"]):
-            raise ValueError("alns: a contiguous array of 32-byte records (ALN_DTYPE)")
+        pb, _, po, n, dev_b = _reads(bases, None, offsets)
+        pa, n_alns, dev_a = _records("alns", alns, ALN_DTYPE)
+        dev = _side("offsets", _ptr(offsets)[1], alns=(dev_a, n_alns), bases=(dev_b, n and len(bases)))
         sc = kc_aln_scores(*(BLASTN_ALN_SCORES if scores is None else scores))
         st = kc_gap_stats()
-        if dev:
-            import torch
-            out = torch.empty(max(n_alns, 1) * 32, dtype=torch.uint8, device="cuda:%d" % self.device)
-            torch.cuda.current_stream(self.device).synchronize()  # the input and the fresh array are torch's until now
-            pout = out.data_ptr()
-        else:
-            out = np.zeros(max(n_alns, 1), dtype=GAP_ALN_DTYPE)
-            pout = out.ctypes.data
-        check(lib().kc_align_gapped(self._h, pb, po, n, pa if n_alns else None, n_alns, 1 if dev else 0, pad, C.byref(sc),
-                                    _lib.KC_GAP_ALWAYS_DP if always_dp else 0, pout, C.byref(st)), "kc_align_gapped")
-        out = out[:n_alns * 32] if dev else out[:n_alns]
-        return out, {f: int(getattr(st, f)) for f, _ in kc_gap_stats._fields_}
+        out = self._out(dev, n_alns, GAP_ALN_DTYPE, pad=True)
+        self._hand_over(dev)
+        check(lib().kc_align_gapped(self._h, pb, po, n, pa, n_alns, 1 if dev else 0, pad, C.byref(sc),
+                                    _lib.KC_GAP_ALWAYS_DP if always_dp else 0, out.ptr, C.byref(st)), "kc_align_gapped")
+        return out.first(), _stats_dict(st)
 
     def contig_index_info(self):
         """(nbytes, n_ctgs) of the kept contig index (kc_ctg_index_info): the sizes of aln_depths' arrays."""
         nb, nc = C.c_uint64(0), C.c_uint64(0)
         check(lib().kc_ctg_index_info(self._h, C.byref(nb), C.byref(nc)), "kc_ctg_index_info")
         return int(nb.value), int(nc.value)
-
-    def _gap_records(self, gap_alns):
-        pa, dev = _ptr(gap_alns)
-        n = gap_alns.numel() // 32 if dev else len(gap_alns)
-        if not dev and n and (gap_alns.dtype.itemsize != 32 or not gap_alns.flags["C_CONTIGUOUS"]):
-            raise ValueError("gap_alns: a contiguous array of 32-byte records (GAP_ALN_DTYPE)")
-        return (pa if n else None), n, dev
 
     def aln_depths(self, gap_alns, min_score=0, min_len=0, edge_clip=0, best_only=False, per_contig=False, nreads=None):
         """Per-base and per-contig depths from align_gapped's records (kc_aln_depths).  Returns
@@ -688,27 +725,17 @@ class KmerCounter:
         records give numpy arrays; a uint8 device tensor of records gives device tensors (depths int16 holding the
         16 bits, ctgs uint8 of 32-byte records).  best_only: only every read's best record counts (nreads: the reads
         the records index)."""
-        pa, n, dev = self._gap_records(gap_alns)
+        pa, n, dev = _records("gap_alns", gap_alns, GAP_ALN_DTYPE)
         if best_only and nreads is None:
             raise ValueError("best_only needs nreads")
         nbytes, n_ctgs = self.contig_index_info()
         flags = (_lib.KC_DEPTH_BEST_ONLY if best_only else 0) | (_lib.KC_DEPTH_PER_CONTIG if per_contig else 0)
         st = kc_depth_stats()
-        if dev:
-            import torch
-            d = "cuda:%d" % self.device
-            depths = torch.empty(max(nbytes, 1), dtype=torch.int16, device=d)
-            ctgs = torch.empty(max(n_ctgs, 1) * 32, dtype=torch.uint8, device=d)
-            torch.cuda.current_stream(self.device).synchronize()  # the input and the fresh arrays are torch's until now
-            pd, pc = depths.data_ptr(), ctgs.data_ptr()
-        else:
-            depths = np.zeros(max(nbytes, 1), dtype=np.uint16)
-            ctgs = np.zeros(max(n_ctgs, 1), dtype=CTG_DEPTH_DTYPE)
-            pd, pc = depths.ctypes.data, ctgs.ctypes.data
-        check(lib().kc_aln_depths(self._h, pa, n, nreads or 0, 1 if dev else 0, min_score, min_len, edge_clip, flags, pd, pc, C.byref(st)),
-              "kc_aln_depths")
-        ctgs = ctgs[:n_ctgs * 32] if dev else ctgs[:n_ctgs]
-        return depths[:nbytes], ctgs, {f: int(getattr(st, f)) for f, _ in kc_depth_stats._fields_}
+        depths, ctgs = self._out(dev, nbytes, np.uint16, pad=True), self._out(dev, n_ctgs, CTG_DEPTH_DTYPE, pad=True)
+        self._hand_over(dev)
+        check(lib().kc_aln_depths(self._h, pa, n, nreads or 0, 1 if dev else 0, min_score, min_len, edge_clip, flags, depths.ptr, ctgs.ptr,
+                                  C.byref(st)), "kc_aln_depths")
+        return depths.first(), ctgs.first(), _stats_dict(st)
 
     def pair_inserts(self, offsets, gap_alns, max_insert=_lib.KC_INSERT_MAX, min_score=0, min_len=0):
         """Every read's best record, every pair's class and the insert-size histogram (kc_pair_inserts; DESIGN.md
@@ -716,34 +743,21 @@ class KmerCounter:
         PAIR_DTYPE record per pair (host) or a uint8 device tensor of 16-byte records, hist an int64 device tensor then.
         stats: kc_insert_stats as a dict, cls a list by KC_PAIR_*, with mean and stddev of the proper pairs' inserts
         (0.0 without any) beside the integers."""
-        pa, n, dev_a = self._gap_records(gap_alns)
-        po, dev = _ptr(offsets)
+        pa, n, dev_a = _records("gap_alns", gap_alns, GAP_ALN_DTYPE)
+        po, dev_o = _ptr(offsets)
+        dev = _side("offsets", dev_o, gap_alns=(dev_a, n))
         nreads = len(offsets) - 1
-        if n and dev_a != dev:
-            raise ValueError("offsets and gap_alns must both be host arrays or both be device tensors")
         st = kc_insert_stats()
-        npairs = nreads // 2
-        if dev:
-            import torch
-            d = "cuda:%d" % self.device
-            hist = torch.empty(max_insert + 1, dtype=torch.int64, device=d)
-            pairs = torch.empty(max(npairs, 1) * 16, dtype=torch.uint8, device=d)
-            torch.cuda.current_stream(self.device).synchronize()  # the input and the fresh arrays are torch's until now
-            ph, pp = hist.data_ptr(), pairs.data_ptr()
-        else:
-            hist = np.zeros(max_insert + 1, dtype=np.uint64)
-            pairs = np.zeros(max(npairs, 1), dtype=PAIR_DTYPE)
-            ph, pp = hist.ctypes.data, pairs.ctypes.data
-        check(lib().kc_pair_inserts(self._h, po, nreads, pa, n, 1 if dev else 0, min_score, min_len, max_insert, ph, pp, C.byref(st)),
-              "kc_pair_inserts")
-        pairs = pairs[:npairs * 16] if dev else pairs[:npairs]
-        out = {"pairs": int(st.pairs), "cls": [int(x) for x in st.cls], "insert_sum": int(st.insert_sum),
-               "insert_sq_sum": int(st.insert_sq_sum), "reads_with_best": int(st.reads_with_best)}
+        hist, pairs = self._out(dev, max_insert + 1, np.uint64), self._out(dev, nreads // 2, PAIR_DTYPE, pad=True)
+        self._hand_over(dev)
+        check(lib().kc_pair_inserts(self._h, po, nreads, pa, n, 1 if dev else 0, min_score, min_len, max_insert, hist.ptr, pairs.ptr,
+                                    C.byref(st)), "kc_pair_inserts")
+        out = _stats_dict(st)
         proper = out["cls"][_lib.KC_PAIR_PROPER]
         out["mean"] = out["insert_sum"] / proper if proper else 0.0
         # the variance from exact integers: n * sum(x^2) - sum(x)^2 >= 0
         out["stddev"] = (proper * out["insert_sq_sum"] - out["insert_sum"] ** 2) ** 0.5 / proper if proper else 0.0
-        return hist, pairs, out
+        return hist.a, pairs.first(), out
 
     def local_assm(self, bases, quals, offsets, gap_alns, pairs, ctg_depths=None, min_mer_len=13, max_mer_len=121, shift=8, max_walk_len=400,
                    max_insert=1000, min_qual=10, hi_qual=20, min_viable=2, viable_permille=200, max_cands=2000, table_budget_mb=0):
@@ -756,53 +770,36 @@ class KmerCounter:
         give numpy arrays out; device tensors in give device tensors out (ends a uint8 tensor of 16-byte records, offsets
         int64).  The block is allocated at the indexed block's size plus a quarter; if that is too small the call is
         made once more with the size it reported."""
-        pa, n_alns, dev_a = self._gap_records(gap_alns)
-        po, dev = _ptr(offsets)
-        nreads = len(offsets) - 1
-        pb, dev_b = _ptr(bases)
-        pq, dev_q = (None, dev) if quals is None else _ptr(quals)
-        pp, dev_p = _ptr(pairs)
-        npairs = pairs.numel() // 16 if dev_p else len(pairs)
-        pc, dev_c = (None, dev) if ctg_depths is None else _ptr(ctg_depths)
+        pa, n_alns, dev_a = _records("gap_alns", gap_alns, GAP_ALN_DTYPE)
+        pb, pq, po, nreads, dev_b = _reads(bases, quals, offsets)
+        pp, npairs, dev_p = _records("pairs", pairs, PAIR_DTYPE)
+        # the one record array whose contiguity has never been looked at, and whose address goes to the library as it is
+        _, n_depths, dev_c = (None, 0, False) if ctg_depths is None else _records("ctg_depths", ctg_depths, CTG_DEPTH_DTYPE, contiguous=False)
+        pc = _ptr(ctg_depths)[0]
         nbytes, n_ctgs = self.contig_index_info()
-        if ((n_alns and dev_a != dev) or (nreads and len(bases) and (dev_b != dev or dev_q != dev)) or (npairs and dev_p != dev) or
-                (n_ctgs and dev_c != dev)):
-            raise ValueError("bases, quals, offsets, gap_alns, pairs and ctg_depths must all be host arrays or all be device tensors")
-        if npairs != nreads // 2 or (not dev and npairs and (pairs.dtype.itemsize != 16 or not pairs.flags["C_CONTIGUOUS"])):
+        n_bases = nreads and len(bases)
+        dev = _side("offsets", _ptr(offsets)[1], gap_alns=(dev_a, n_alns), bases=(dev_b, n_bases),
+                    quals=(_ptr(quals)[1], n_bases and quals is not None), pairs=(dev_p, npairs),
+                    ctg_depths=(dev_c, n_ctgs and ctg_depths is not None))
+        if npairs != nreads // 2:
             raise ValueError("pairs: a contiguous array of nreads / 2 16-byte records (PAIR_DTYPE)")
-        if ctg_depths is not None:
-            if (ctg_depths.numel() // 32 if dev else len(ctg_depths)) != n_ctgs or (not dev and n_ctgs and ctg_depths.dtype.itemsize != 32):
-                raise ValueError("ctg_depths: one 32-byte record (CTG_DEPTH_DTYPE) per indexed contig")
+        if ctg_depths is not None and n_depths != n_ctgs:
+            raise ValueError("ctg_depths: one 32-byte record (CTG_DEPTH_DTYPE) per indexed contig")
         prm = kc_lassm_params(min_mer_len, max_mer_len, shift, max_walk_len, max_insert, min_qual, hi_qual, min_viable, viable_permille,
                               max_cands, table_budget_mb, 0)
         st, nb = kc_lassm_stats(), C.c_uint64(0)
-        if dev:
-            import torch
-            d = "cuda:%d" % self.device
-            offs_out = torch.empty(n_ctgs + 1, dtype=torch.int64, device=d)
-            ends = torch.empty(max(2 * n_ctgs, 1) * 16, dtype=torch.uint8, device=d)
-        else:
-            offs_out = np.zeros(n_ctgs + 1, dtype=np.uint64)
-            ends = np.zeros(max(2 * n_ctgs, 1), dtype=LASSM_END_DTYPE)
-        capacity = nbytes + nbytes // 4
-        for attempt in (0, 1):
-            if dev:
-                seqs = torch.empty(max(capacity, 1), dtype=torch.uint8, device=d)
-                torch.cuda.current_stream(self.device).synchronize()  # the input and the fresh arrays are torch's until now
-                ps, pf, pe = seqs.data_ptr(), offs_out.data_ptr(), ends.data_ptr()
-            else:
-                seqs = np.zeros(max(capacity, 1), dtype=np.uint8)
-                ps, pf, pe = seqs.ctypes.data, offs_out.ctypes.data, ends.ctypes.data
-            rc = lib().kc_local_assm(self._h, pb, pq, po, nreads, pa, n_alns, pp if npairs else None, pc, 1 if dev else 0, C.byref(prm), ps,
-                                     capacity, pf, pe, C.byref(nb), C.byref(st))
-            if rc != _lib.KC_ERR_CAPACITY or attempt or not capacity < nb.value < (1 << 31):
-                break
-            capacity = int(nb.value)  # the size it was told
+        offs_out, ends = self._out(dev, n_ctgs + 1, np.uint64), self._out(dev, 2 * n_ctgs, LASSM_END_DTYPE, pad=True)
+
+        def call(capacity):
+            seqs = self._out(dev, capacity, np.uint8, pad=True)
+            self._hand_over(dev)
+            rc = lib().kc_local_assm(self._h, pb, pq, po, nreads, pa, n_alns, pp, pc, 1 if dev else 0, C.byref(prm), seqs.ptr, capacity,
+                                     offs_out.ptr, ends.ptr, C.byref(nb), C.byref(st))
+            return rc, int(nb.value), seqs
+
+        rc, told, seqs = _retry_on_capacity(nbytes + nbytes // 4, call, below=1 << 31)
         check(rc, "kc_local_assm")
-        ends = ends[:2 * n_ctgs * 16] if dev else ends[:2 * n_ctgs]
-        out = {f: int(getattr(st, f)) for f, _ in kc_lassm_stats._fields_ if f not in ("status", "reserved")}
-        out["status"] = [int(x) for x in st.status]
-        return seqs[:int(nb.value)], offs_out, ends, out
+        return seqs.first(told), offs_out.a, ends.first(), _stats_dict(st)
 
     def ctg_links(self, offsets, gap_alns, pairs=None, insert_avg=300, max_insert=1000, min_score=0, min_len=0, end_slack=5, max_overlap=200,
                   max_splint_gap=100, max_read_alns=8):
@@ -815,47 +812,34 @@ class KmerCounter:
         total (uint64 array / int64 tensor; end 2u is the left end of contig u, 2u + 1 its right end), kc_link_stats as a
         dict, and gap a float64 numpy column: a link's mean splint gap where it has splints, else its mean span gap.  The
         records are allocated at four a contig; if that is too few the call is made once more with the number it reported."""
-        pa, n_alns, dev_a = self._gap_records(gap_alns)
-        po, dev = _ptr(offsets)
+        pa, n_alns, dev_a = _records("gap_alns", gap_alns, GAP_ALN_DTYPE)
+        po, dev_o = _ptr(offsets)
         nreads = len(offsets) - 1
-        pp, dev_p = _ptr(pairs)
-        npairs = 0 if pairs is None else (pairs.numel() // 16 if dev_p else len(pairs))
-        if (n_alns and dev_a != dev) or (npairs and dev_p != dev):
-            raise ValueError("offsets, gap_alns and pairs must all be host arrays or all be device tensors")
-        if pairs is not None and (npairs != nreads // 2 or (not dev and npairs and (pairs.dtype.itemsize != 16 or not pairs.flags["C_CONTIGUOUS"]))):
+        pp, npairs, dev_p = (None, 0, False) if pairs is None else _records("pairs", pairs, PAIR_DTYPE)
+        dev = _side("offsets", dev_o, gap_alns=(dev_a, n_alns), pairs=(dev_p, npairs))
+        if pairs is not None and npairs != nreads // 2:
             raise ValueError("pairs: a contiguous array of nreads / 2 16-byte records (PAIR_DTYPE)")
         _, n_ctgs = self.contig_index_info()
         prm = kc_link_params(min_score, min_len, end_slack, max_overlap, max_splint_gap, insert_avg, max_insert, max_read_alns, 0)
         st, n = kc_link_stats(), C.c_uint64(0)
-        pp = pp if npairs else None
-        if dev:
-            import torch
-            d = "cuda:%d" % self.device
-            end_first = torch.empty(2 * n_ctgs + 1, dtype=torch.int64, device=d)
-        else:
-            end_first = np.zeros(2 * n_ctgs + 1, dtype=np.uint64)
-        capacity = 4 * n_ctgs + 16  # two records an end: a chain of contigs and as much again
-        for attempt in (0, 1):
-            if dev:
-                links = torch.empty(max(capacity, 1) * 48, dtype=torch.uint8, device=d)
-                torch.cuda.current_stream(self.device).synchronize()  # the input and the fresh arrays are torch's until now
-                pl, pe = links.data_ptr(), end_first.data_ptr()
-            else:
-                links = np.zeros(max(capacity, 1), dtype=LINK_DTYPE)
-                pl, pe = links.ctypes.data, end_first.ctypes.data
-            rc = lib().kc_ctg_links(self._h, po, nreads, pa, n_alns, pp, 1 if dev else 0, C.byref(prm), pl, capacity, pe, C.byref(n), C.byref(st))
-            if rc != _lib.KC_ERR_CAPACITY or attempt or not capacity < n.value:
-                break
-            capacity = int(n.value)  # the size it was told
+        end_first = self._out(dev, 2 * n_ctgs + 1, np.uint64)
+
+        def call(capacity):
+            links = self._out(dev, capacity, LINK_DTYPE, pad=True)
+            self._hand_over(dev)
+            rc = lib().kc_ctg_links(self._h, po, nreads, pa, n_alns, pp, 1 if dev else 0, C.byref(prm), links.ptr, capacity, end_first.ptr,
+                                    C.byref(n), C.byref(st))
+            return rc, int(n.value), links
+
+        rc, n_links, links = _retry_on_capacity(4 * n_ctgs + 16, call)  # two records an end: a chain of contigs and as much again
         check(rc, "kc_ctg_links")
-        cap = int(n.value)
-        links = links[:cap * 48] if dev else links[:cap]
+        links = links.first(n_links)
         host = links.cpu().numpy().view(LINK_DTYPE) if dev else links
-        gap = np.zeros(cap, dtype=np.float64)
-        if cap:
+        gap = np.zeros(n_links, dtype=np.float64)
+        if n_links:
             s, m = host["splints"].astype(np.float64), host["spans"].astype(np.float64)
             gap = np.where(s > 0, host["splint_gap_sum"] / np.maximum(s, 1), host["span_gap_sum"] / np.maximum(m, 1))
-        return links, end_first, {f: int(getattr(st, f)) for f, _ in kc_link_stats._fields_ if f != "reserved"}, gap
+        return links, end_first.a, _stats_dict(st), gap
 
     def scaffolds(self, links, min_splints=1, min_spans=2, max_second_permille=0, overlap_slack=0):
         """The scaffolds the links give over the indexed contigs (kc_scaffold): one partner per contig
@@ -866,51 +850,23 @@ class KmerCounter:
         takes as it is, SCAFFOLD_DTYPE and MEMBER_DTYPE records -- numpy for host input; uint8 / int64 device tensors and
         uint8 tensors of 32- and 16-byte records for a device tensor -- and kc_scaf_stats as a dict.  A size query first,
         then the call."""
-        pl, dev = _ptr(links)
-        if dev:
-            n_links = links.numel() // 48
-        else:
-            if len(links) and (links.dtype.itemsize != 48 or not links.flags["C_CONTIGUOUS"]):
-                raise ValueError("links: a contiguous array of 48-byte records (LINK_DTYPE)")
-            n_links = len(links)
-        pl = pl if n_links else None
+        pl, n_links, dev = _records("links", links, LINK_DTYPE)
         _, n_ctgs = self.contig_index_info()
         prm = _lib.kc_scaf_params(min_splints, min_spans, max_second_permille, overlap_slack, 0)
         st, ns, nb = _lib.kc_scaf_stats(), C.c_uint64(0), C.c_uint64(0)
-        if dev:
-            import torch
-            torch.cuda.current_stream(self.device).synchronize()  # the input is torch's until now
-        d = 1 if dev else 0
-        check(lib().kc_scaffold(self._h, pl, n_links, d, C.byref(prm), None, 0, None, None, None, None, C.byref(ns), C.byref(nb), C.byref(st)),
-              "kc_scaffold")
+        head, tail = (self._h, pl, n_links, 1 if dev else 0, C.byref(prm)), (None, C.byref(ns), C.byref(nb), C.byref(st))
+        self._hand_over(dev)
+        check(lib().kc_scaffold(*head, None, 0, None, None, None, *tail), "kc_scaffold")
         n_scaf, nbytes = int(ns.value), int(nb.value)
-        if dev:
-            dv = "cuda:%d" % self.device
-            seqs = torch.empty(nbytes, dtype=torch.uint8, device=dv)
-            offsets = torch.empty(n_scaf + 1, dtype=torch.int64, device=dv)
-            scafs = torch.empty(max(n_scaf, 1) * 32, dtype=torch.uint8, device=dv)
-            members = torch.empty(max(n_ctgs, 1) * 16, dtype=torch.uint8, device=dv)
-            torch.cuda.current_stream(self.device).synchronize()
-            ptrs = (seqs.data_ptr(), offsets.data_ptr(), scafs.data_ptr(), members.data_ptr())
-        else:
-            seqs = np.zeros(nbytes, dtype=np.uint8)
-            offsets = np.zeros(n_scaf + 1, dtype=np.uint64)
-            scafs = np.zeros(max(n_scaf, 1), dtype=SCAFFOLD_DTYPE)
-            members = np.zeros(max(n_ctgs, 1), dtype=MEMBER_DTYPE)
-            ptrs = (seqs.ctypes.data, offsets.ctypes.data, scafs.ctypes.data, members.ctypes.data)
-        check(lib().kc_scaffold(self._h, pl, n_links, d, C.byref(prm), ptrs[0], nbytes, ptrs[1], ptrs[2], ptrs[3], None, C.byref(ns), C.byref(nb),
-                                C.byref(st)), "kc_scaffold")
-        scafs = scafs[:n_scaf * 32] if dev else scafs[:n_scaf]
-        members = members[:n_ctgs * 16] if dev else members[:n_ctgs]
-        return seqs, offsets, scafs, members, {f: int(getattr(st, f)) for f, _ in _lib.kc_scaf_stats._fields_ if f != "reserved"}
+        seqs, offsets = self._out(dev, nbytes, np.uint8), self._out(dev, n_scaf + 1, np.uint64)
+        scafs, members = self._out(dev, n_scaf, SCAFFOLD_DTYPE, pad=True), self._out(dev, n_ctgs, MEMBER_DTYPE, pad=True)
+        self._hand_over(dev)  # fresh arrays
+        check(lib().kc_scaffold(*head, seqs.ptr, nbytes, offsets.ptr, scafs.ptr, members.ptr, *tail), "kc_scaffold")
+        return seqs.a, offsets.a, scafs.first(), members.first(), _stats_dict(st)
 
     def scaffold_strings(self, links, **kw):
         """The scaffolds' texts as Python strings (for tests and small inputs): scaffolds() without its records."""
-        seqs, offsets = self.scaffolds(links, **kw)[:2]
-        if not isinstance(seqs, np.ndarray):
-            seqs, offsets = seqs.cpu().numpy(), offsets.cpu().numpy()
-        text = seqs.tobytes().decode()
-        return [text[int(offsets[i]):int(offsets[i + 1]) - 1] for i in range(len(offsets) - 1)]
+        return _block_strings(*self.scaffolds(links, **kw)[:2])
 
     def close_gaps(self, bases, offsets, gap_alns, scaffolds, members, min_reads=2, min_agree_permille=500, min_score=0, min_len=0, end_slack=5,
                    max_overlap=200, max_splint_gap=100, max_read_alns=8):
@@ -922,61 +878,31 @@ class KmerCounter:
         closures, stats): the seq block index_contigs takes as it is, SCAFFOLD_DTYPE, MEMBER_DTYPE and CLOSURE_DTYPE records
         -- numpy for host input; uint8 / int64 device tensors and uint8 tensors of 32-, 16- and 32-byte records for device
         tensors -- and kc_close_stats as a dict.  A size query first, then the call."""
-        pa, n_alns, dev_a = self._gap_records(gap_alns)
-        pb, dev = _ptr(bases)
-        po, dev_o = _ptr(offsets)
-        ps, dev_s = _ptr(scaffolds)
-        pm, dev_m = _ptr(members)
-        nreads = len(offsets) - 1
-        if dev_o != dev or dev_s != dev or dev_m != dev or (n_alns and dev_a != dev):
-            raise ValueError("bases, offsets, gap_alns, scaffolds and members must all be host arrays or all be device tensors")
-        if dev:
-            n_scaf = scaffolds.numel() // 32
-        else:
-            if scaffolds.dtype.itemsize != 32 or members.dtype.itemsize != 16 or not scaffolds.flags["C_CONTIGUOUS"] or not members.flags["C_CONTIGUOUS"]:
-                raise ValueError("scaffolds, members: contiguous arrays of 32- and 16-byte records (SCAFFOLD_DTYPE, MEMBER_DTYPE)")
-            n_scaf = len(scaffolds)
+        pa, n_alns, dev_a = _records("gap_alns", gap_alns, GAP_ALN_DTYPE)
+        pb, _, po, nreads, dev_b = _reads(bases, None, offsets)
+        # the library takes the scaffolds and the members as they are: they, and the offsets, count even where they are empty
+        ps, n_scaf, dev_s = _records("scaffolds", scaffolds, SCAFFOLD_DTYPE, required=True)
+        pm, n_members, dev_m = _records("members", members, MEMBER_DTYPE, required=True)
+        dev = _side("bases", dev_b, offsets=(_ptr(offsets)[1], True), gap_alns=(dev_a, n_alns), scaffolds=(dev_s, True), members=(dev_m, True))
         _, n_ctgs = self.contig_index_info()
-        if (members.numel() // 16 if dev else len(members)) != n_ctgs:
+        if n_members != n_ctgs:
             raise ValueError("members: one record for each of the %d indexed contigs" % n_ctgs)
         prm = _lib.kc_close_params(min_score, min_len, end_slack, max_overlap, max_splint_gap, min_reads, min_agree_permille, max_read_alns, 0)
         st, nb = _lib.kc_close_stats(), C.c_uint64(0)
-        if dev:
-            import torch
-            torch.cuda.current_stream(self.device).synchronize()  # the input is torch's until now
-        d = 1 if dev else 0
-        head = (self._h, pb, po, nreads, pa, n_alns, ps, n_scaf, pm, d, C.byref(prm))
-        check(lib().kc_close_gaps(*head, None, 0, None, None, None, None, C.byref(nb), C.byref(st)), "kc_close_gaps")
+        head, tail = (self._h, pb, po, nreads, pa, n_alns, ps, n_scaf, pm, 1 if dev else 0, C.byref(prm)), (C.byref(nb), C.byref(st))
+        self._hand_over(dev)
+        check(lib().kc_close_gaps(*head, None, 0, None, None, None, None, *tail), "kc_close_gaps")
         nbytes = int(nb.value)
-        if dev:
-            dv = "cuda:%d" % self.device
-            seqs = torch.empty(nbytes, dtype=torch.uint8, device=dv)
-            offs_out = torch.empty(n_scaf + 1, dtype=torch.int64, device=dv)
-            scafs = torch.empty(max(n_scaf, 1) * 32, dtype=torch.uint8, device=dv)
-            mem = torch.empty(max(n_ctgs, 1) * 16, dtype=torch.uint8, device=dv)
-            clo = torch.empty(max(n_ctgs, 1) * 32, dtype=torch.uint8, device=dv)
-            torch.cuda.current_stream(self.device).synchronize()
-            ptrs = (seqs.data_ptr(), offs_out.data_ptr(), scafs.data_ptr(), mem.data_ptr(), clo.data_ptr())
-        else:
-            seqs = np.zeros(nbytes, dtype=np.uint8)
-            offs_out = np.zeros(n_scaf + 1, dtype=np.uint64)
-            scafs = np.zeros(max(n_scaf, 1), dtype=SCAFFOLD_DTYPE)
-            mem = np.zeros(max(n_ctgs, 1), dtype=MEMBER_DTYPE)
-            clo = np.zeros(max(n_ctgs, 1), dtype=CLOSURE_DTYPE)
-            ptrs = (seqs.ctypes.data, offs_out.ctypes.data, scafs.ctypes.data, mem.ctypes.data, clo.ctypes.data)
-        check(lib().kc_close_gaps(*head, ptrs[0], nbytes, ptrs[1], ptrs[2], ptrs[3], ptrs[4], C.byref(nb), C.byref(st)), "kc_close_gaps")
-        scafs = scafs[:n_scaf * 32] if dev else scafs[:n_scaf]
-        mem = mem[:n_ctgs * 16] if dev else mem[:n_ctgs]
-        clo = clo[:n_ctgs * 32] if dev else clo[:n_ctgs]
-        return seqs, offs_out, scafs, mem, clo, {f: int(getattr(st, f)) for f, _ in _lib.kc_close_stats._fields_}
+        seqs, offs_out = self._out(dev, nbytes, np.uint8), self._out(dev, n_scaf + 1, np.uint64)
+        scafs, mem = self._out(dev, n_scaf, SCAFFOLD_DTYPE, pad=True), self._out(dev, n_ctgs, MEMBER_DTYPE, pad=True)
+        clo = self._out(dev, n_ctgs, CLOSURE_DTYPE, pad=True)
+        self._hand_over(dev)  # fresh arrays
+        check(lib().kc_close_gaps(*head, seqs.ptr, nbytes, offs_out.ptr, scafs.ptr, mem.ptr, clo.ptr, *tail), "kc_close_gaps")
+        return seqs.a, offs_out.a, scafs.first(), mem.first(), clo.first(), _stats_dict(st)
 
     def close_gaps_strings(self, bases, offsets, gap_alns, scaffolds, members, **kw):
         """The closed scaffolds' texts as Python strings (for tests and small inputs): close_gaps() without its records."""
-        seqs, offs = self.close_gaps(bases, offsets, gap_alns, scaffolds, members, **kw)[:2]
-        if not isinstance(seqs, np.ndarray):
-            seqs, offs = seqs.cpu().numpy(), offs.cpu().numpy()
-        text = seqs.tobytes().decode()
-        return [text[int(offs[i]):int(offs[i + 1]) - 1] for i in range(len(offs) - 1)]
+        return _block_strings(*self.close_gaps(bases, offsets, gap_alns, scaffolds, members, **kw)[:2])
 
     def shuffle_reads(self, bases, quals, offsets, gap_alns, pairs, parts=1, remap=True):
         """The read pairs regrouped by their home contig (kc_shuffle_reads): a pair's home is the
@@ -989,51 +915,34 @@ class KmerCounter:
         in give numpy arrays out (GAP_ALN_DTYPE, PAIR_DTYPE records, uint32 order and home, uint64 offsets); device
         tensors in give device tensors out (uint8 tensors of records, int32 order and home holding the 32 bits, int64
         offsets and part_starts)."""
-        pa, n_alns, dev_a = self._gap_records(gap_alns)
-        po, dev = _ptr(offsets)
-        nreads = len(offsets) - 1
-        pb, dev_b = _ptr(bases)
-        pq, dev_q = (None, dev) if quals is None else _ptr(quals)
-        pp, dev_p = _ptr(pairs)
-        npairs = pairs.numel() // 16 if dev_p else len(pairs)
-        nbytes = bases.numel() if dev_b else len(bases)
-        if (n_alns and dev_a != dev) or (nbytes and (dev_b != dev or dev_q != dev)) or (npairs and dev_p != dev):
-            raise ValueError("bases, quals, offsets, gap_alns and pairs must all be host arrays or all be device tensors")
-        if npairs != nreads // 2 or (not dev and npairs and (pairs.dtype.itemsize != 16 or not pairs.flags["C_CONTIGUOUS"])):
+        pa, n_alns, dev_a = _records("gap_alns", gap_alns, GAP_ALN_DTYPE)
+        pb, pq, po, nreads, dev_b = _reads(bases, quals, offsets)
+        pp, npairs, dev_p = _records("pairs", pairs, PAIR_DTYPE)
+        nbytes = len(bases)
+        dev = _side("offsets", _ptr(offsets)[1], gap_alns=(dev_a, n_alns), bases=(dev_b, nbytes),
+                    quals=(_ptr(quals)[1], nbytes and quals is not None), pairs=(dev_p, npairs))
+        if npairs != nreads // 2:
             raise ValueError("pairs: a contiguous array of nreads / 2 16-byte records (PAIR_DTYPE)")
-        if quals is not None and (quals.numel() if dev_q and hasattr(quals, "numel") else len(quals)) != nbytes:
+        if quals is not None and len(quals) != nbytes:
             raise ValueError("quals: as many bytes as bases")
         st = _lib.kc_shuffle_stats()
-        if dev:
-            import torch
-            dv = "cuda:%d" % self.device
-            out = {"bases": torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dv),
-                   "quals": None if quals is None else torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dv),
-                   "offsets": torch.empty(nreads + 1, dtype=torch.int64, device=dv),
-                   "order": torch.empty(max(npairs, 1), dtype=torch.int32, device=dv),
-                   "home": torch.empty(max(npairs, 1), dtype=torch.int32, device=dv),
-                   "part_starts": torch.empty(parts + 1, dtype=torch.int64, device=dv),
-                   "gap_alns": torch.empty(max(n_alns, 1) * 32, dtype=torch.uint8, device=dv) if remap else None,
-                   "pairs": torch.empty(max(npairs, 1) * 16, dtype=torch.uint8, device=dv) if remap else None}
-            torch.cuda.current_stream(self.device).synchronize()  # the input and the fresh arrays are torch's until now
-        else:
-            out = {"bases": np.zeros(max(nbytes, 1), dtype=np.uint8), "quals": None if quals is None else np.zeros(max(nbytes, 1), dtype=np.uint8),
-                   "offsets": np.zeros(nreads + 1, dtype=np.uint64), "order": np.zeros(max(npairs, 1), dtype=np.uint32),
-                   "home": np.zeros(max(npairs, 1), dtype=np.uint32), "part_starts": np.zeros(parts + 1, dtype=np.uint64),
-                   "gap_alns": np.zeros(max(n_alns, 1), dtype=GAP_ALN_DTYPE) if remap else None,
-                   "pairs": np.zeros(max(npairs, 1), dtype=PAIR_DTYPE) if remap else None}
-        p = {k: _ptr(v)[0] for k, v in out.items()}
-        check(lib().kc_shuffle_reads(self._h, pb if nbytes else None, pq if nbytes else None, po, nreads, pa, n_alns, pp if npairs else None,
-                                     1 if dev else 0, parts, p["bases"], p["quals"] if nbytes or quals is None else None, p["offsets"], p["order"],
-                                     p["home"], p["part_starts"], p["gap_alns"], p["pairs"], C.byref(st)), "kc_shuffle_reads")
-        out["bases"] = out["bases"][:nbytes]
-        if quals is not None:
-            out["quals"] = out["quals"][:nbytes]
-        out["order"], out["home"] = out["order"][:npairs], out["home"][:npairs]
-        if remap:
-            out["gap_alns"] = out["gap_alns"][:n_alns * 32] if dev else out["gap_alns"][:n_alns]
-            out["pairs"] = out["pairs"][:npairs * 16] if dev else out["pairs"][:npairs]
-        out["stats"] = {f: int(getattr(st, f)) for f, _ in _lib.kc_shuffle_stats._fields_}
+        # every output that may be empty is padded; the arrays that were not asked for stay None, here and in the result
+        out = {"bases": self._out(dev, nbytes, np.uint8, pad=True),
+               "quals": None if quals is None else self._out(dev, nbytes, np.uint8, pad=True),
+               "offsets": self._out(dev, nreads + 1, np.uint64),
+               "order": self._out(dev, npairs, np.uint32, pad=True),
+               "home": self._out(dev, npairs, np.uint32, pad=True),
+               "part_starts": self._out(dev, parts + 1, np.uint64),
+               "gap_alns": self._out(dev, n_alns, GAP_ALN_DTYPE, pad=True) if remap else None,
+               "pairs": self._out(dev, npairs, PAIR_DTYPE, pad=True) if remap else None}
+        self._hand_over(dev)
+        p = {k: v and v.ptr for k, v in out.items()}
+        if not nbytes:  # no bases at all: the library takes no byte arrays then, in or out
+            pb = pq = p["quals"] = None
+        check(lib().kc_shuffle_reads(self._h, pb, pq, po, nreads, pa, n_alns, pp, 1 if dev else 0, parts, p["bases"], p["quals"], p["offsets"],
+                                     p["order"], p["home"], p["part_starts"], p["gap_alns"], p["pairs"], C.byref(st)), "kc_shuffle_reads")
+        out = {k: v and v.first() for k, v in out.items()}
+        out["stats"] = _stats_dict(st)
         return out
 
     def submit_ctg_block(self, seqs, depths):
@@ -1126,9 +1035,7 @@ def adapters_index(text, adapter_k):
     """Adapter FASTA text (bytes) -> the loader's counts (kc_adapters_index, host only): kept sequences, sequences
     shorter than adapter_k, entries (both orientations) and distinct k-mers."""
     data = _adapter_text(text)
-    v = [C.c_uint64(0) for _ in range(4)]
-    check(lib().kc_adapters_index(data, len(data), adapter_k, *[C.byref(x) for x in v]), "kc_adapters_index")
-    return dict(zip(("n_adapters", "n_short", "n_entries", "n_kmers"), (x.value for x in v)))
+    return _adapter_counts("kc_adapters_index", data, len(data), adapter_k)
 
 
 def fastq_pairs(text1, text2=None):
@@ -1149,6 +1056,26 @@ def fastq_pairs(text1, text2=None):
     return bases[:nb.value], quals[:nb.value], offs
 
 
+def _count_and_sort(kc):
+    """the end of every analyze_kmers flow: flush, then the sorted results and the counter's stats"""
+    kc.flush()
+    res = kc.sorted_results()
+    return res, kc.stats()
+
+
+def _merge_and_count(kc, bases, quals, offsets, min_kmer_len, adapters, blastn_scores, adapter_k):
+    """the paired flows from interleaved reads on: trim where there are adapters, merge, submit the packed reads, count"""
+    tst = None
+    if adapters is not None:
+        kc.load_adapters(adapters, adapter_k or min_kmer_len, blastn_scores)
+        bases, quals, offsets, tst = kc.trim_adapters(bases, quals, offsets, paired=True)
+    packed, offs, mst = kc.merge_pairs(bases, quals, offsets, min_kmer_len=min_kmer_len)
+    if tst is not None:
+        mst["trim"] = tst
+    kc.submit_packed_reads(packed, offs, nreads=mst["out_reads"])
+    return _count_and_sort(kc) + (mst,)
+
+
 def analyze_kmers_paired(kmer_len, qual_offset, bases, quals, offsets, dmin_thres=2, device=0, max_elems=0, tuning=None,
                          min_kmer_len=0, adapters=None, blastn_scores=False, adapter_k=0):
     """merge_reads' pair loop then analyze_kmers for one shard: interleaved pairs are merged on the device
@@ -1157,17 +1084,7 @@ def analyze_kmers_paired(kmer_len, qual_offset, bases, quals, offsets, dmin_thre
     device first (kc_trim_adapters) with k-mers of adapter_k (0: min_kmer_len, else kmer_len), and the merge's
     counters carry the trim's under "trim"."""
     with KmerCounter(kmer_len, qual_offset, dmin_thres, device=device, max_elems=max_elems, tuning=tuning) as kc:
-        tst = None
-        if adapters is not None:
-            kc.load_adapters(adapters, adapter_k or min_kmer_len, blastn_scores)
-            bases, quals, offsets, tst = kc.trim_adapters(bases, quals, offsets, paired=True)
-        packed, offs, mst = kc.merge_pairs(bases, quals, offsets, min_kmer_len=min_kmer_len)
-        if tst is not None:
-            mst["trim"] = tst
-        kc.submit_packed_reads(packed, offs, nreads=mst["out_reads"])
-        kc.flush()
-        res = kc.sorted_results()
-        return res, kc.stats(), mst
+        return _merge_and_count(kc, bases, quals, offsets, min_kmer_len, adapters, blastn_scores, adapter_k)
 
 
 def analyze_kmers_fastq(kmer_len, qual_offset, text, dmin_thres=2, device=0, max_elems=0, tuning=None):
@@ -1176,9 +1093,7 @@ def analyze_kmers_fastq(kmer_len, qual_offset, text, dmin_thres=2, device=0, max
     with KmerCounter(kmer_len, qual_offset, dmin_thres, device=device, max_elems=max_elems, tuning=tuning) as kc:
         packed, offs = kc.fastq_to_packed(text)
         kc.submit_packed_reads(packed, offs, nreads=offs.numel() - 1)
-        kc.flush()
-        res = kc.sorted_results()
-        return res, kc.stats()
+        return _count_and_sort(kc)
 
 
 def analyze_kmers_fastq_paired(kmer_len, qual_offset, text1, text2=None, dmin_thres=2, device=0, max_elems=0, tuning=None,
@@ -1188,23 +1103,11 @@ def analyze_kmers_fastq_paired(kmer_len, qual_offset, text1, text2=None, dmin_th
     adapters: as for analyze_kmers_paired -- parse, trim (kc_trim_adapters), merge and count, all in device memory."""
     with KmerCounter(kmer_len, qual_offset, dmin_thres, device=device, max_elems=max_elems, tuning=tuning) as kc:
         bases, quals, offs = kc.fastq_pairs(text1, text2)
-        tst = None
-        if adapters is not None:
-            kc.load_adapters(adapters, adapter_k or min_kmer_len, blastn_scores)
-            bases, quals, offs, tst = kc.trim_adapters(bases, quals, offs, paired=True)
-        packed, moffs, mst = kc.merge_pairs(bases, quals, offs, min_kmer_len=min_kmer_len)
-        if tst is not None:
-            mst["trim"] = tst
-        kc.submit_packed_reads(packed, moffs, nreads=mst["out_reads"])
-        kc.flush()
-        res = kc.sorted_results()
-        return res, kc.stats(), mst
+        return _merge_and_count(kc, bases, quals, offs, min_kmer_len, adapters, blastn_scores, adapter_k)
 
 
 def analyze_kmers(kmer_len, qual_offset, bases, quals, offsets, dmin_thres=2, device=0, max_elems=0, tuning=None):
     """analyze_kmers (src/kcount/kcount.cpp:142-161) for one shard: returns sorted results and stats."""
     with KmerCounter(kmer_len, qual_offset, dmin_thres, device=device, max_elems=max_elems, tuning=tuning) as kc:
         kc.submit_reads(bases, quals, offsets)
-        kc.flush()
-        res = kc.sorted_results()
-        return res, kc.stats()
+        return _count_and_sort(kc)
