@@ -45,55 +45,7 @@ using namespace kc;
 
 static thread_local char g_last_error[512] = "";
 
-static int hip_fail(hipError_t e, const char *what, int line) {
-  snprintf(g_last_error, sizeof(g_last_error), "%s failed at kc_api.hip:%d: %s", what, line, hipGetErrorString(e));
-  return e == hipErrorOutOfMemory ? KC_ERR_OUT_OF_MEMORY : KC_ERR_HIP;
-}
-
-#define HIPCHK(call)                                          \
-  do {                                                        \
-    hipError_t e_ = (call);                                   \
-    if (e_ != hipSuccess) return hip_fail(e_, #call, __LINE__); \
-  } while (0)
-
-// ---- small host helpers the context itself needs ------------------------------------------------
-// a device scratch buffer that only ever grows: reserve() frees and allocates again when it is too small (the contents
-// are lost then) and leaves {nullptr, 0} behind when the allocation fails
-struct DevBuf {
-  uint8_t *p;
-  size_t cap;  // bytes
-  hipError_t release() {
-    const hipError_t e = p ? hipFree(p) : hipSuccess;
-    if (e == hipSuccess) p = nullptr, cap = 0;
-    return e;
-  }
-  int reserve(size_t bytes) {
-    if (bytes <= cap) return KC_OK;
-    HIPCHK(release());
-    HIPCHK(hipMalloc((void **)&p, bytes));
-    cap = bytes;
-    return KC_OK;
-  }
-  template <class T> T *as() const { return (T *)p; }
-};
-
-// Bump carver over one scratch allocation, every piece aligned to 256 bytes.  A layout is a few lines that name its
-// pieces; they run twice, on Carver{nullptr} for the size (`used`) and on Carver{base} for the pointers.
-struct Carver {
-  uint8_t *base;
-  size_t used;
-  template <class T> T *take(size_t n) {
-    T *p = (T *)((uintptr_t)base + used);
-    used += (n * sizeof(T) + 255) & ~size_t(255);
-    return p;
-  }
-};
-
-#define KCTRY(call)           \
-  do {                        \
-    const int rc_ = (call);   \
-    if (rc_) return rc_;      \
-  } while (0)
+#include "kc_api_mem.hpp"  // owners of device and pinned memory, HIPCHK / KCTRY, the call frame
 
 // ---- kernel timing kinds and their reported names: kc_kinds.hpp -------------------------------------
 struct kt_pending {
@@ -110,21 +62,21 @@ struct kc_ctx {
   int nl_ext;  // the reference's width of the same k-mer (kc_num_longs): results, dumps, lookups
   hipStream_t own_stream, stream;
   // table arena: keys then vals
-  uint8_t *arena;
-  size_t arena_bytes;
+  DevBuf arena;
   uint64_t capacity;
   Table table;
-  uint64_t *d_ctrs;
-  uint64_t *h_ctrs;  // pinned mirror
-  uint64_t *d_tile_first;
-  uint64_t *d_out_plan;  // hole-closing plan + per-workgroup tails of the block-wise result output
-  size_t tile_first_cap;
+  Dev<uint64_t> d_ctrs;
+  Pin<uint64_t> h_ctrs;  // pinned mirror
+  Dev<uint64_t> d_tile_first;
+  Dev<uint64_t> d_out_plan;  // hole-closing plan + per-workgroup tails of the block-wise result output
   // staging for host-resident input (single slot: the '_'-joined blocks of kc_submit_seq_block)
   DevBuf stage_bases, stage_quals, stage_offsets;
   // host-resident reads: two device slots and two pinned host slots, copies on a stream of their own (host_pipe_*)
   struct {
-    uint8_t *d_bases[2], *d_quals[2], *h_bases[2], *h_quals[2];
-    uint64_t *d_offs[2], *h_offs[2];
+    Dev<uint8_t> d_bases[2], d_quals[2];
+    Pin<uint8_t> h_bases[2], h_quals[2];
+    Dev<uint64_t> d_offs[2];
+    Pin<uint64_t> h_offs[2];
     hipEvent_t copied[2], consumed[2], half[2];
     uint32_t lead_b[2], lead_q[2];  // bytes in front of a slot's first read (the copy started on a page boundary of the source)
     bool used[2];
@@ -133,40 +85,42 @@ struct kc_ctx {
     bool ready;
   } hp;
   // results
-  uint64_t *d_out_keys;
-  uint64_t *d_out_keys_ext;  // the results' keys at the reference's width, where that differs (made by kc_finalize)
-  uint16_t *d_out_counts;
-  uint8_t *d_out_left, *d_out_right;
-  uint64_t out_cap, out_n;
+  Dev<uint64_t> d_out_keys;
+  Dev<uint64_t> d_out_keys_ext;  // the results' keys at the reference's width, where that differs (made by kc_finalize)
+  Dev<uint16_t> d_out_counts;
+  Dev<uint8_t> d_out_left, d_out_right;
+  uint64_t out_cap, out_n;  // entries the four arrays have room for, and hold
   bool finalized;
   bool sorted;  // kc_sort_results has put the results in key order (cleared with `finalized`)
   DevBuf dump_tiles;  // kc_dump_text_device: per-tile bytes, then offsets, and the total
-  uint32_t *d_index;  // lookup index over the results (built on first kc_lookup)
-  uint64_t index_cap;
+  Dev<uint32_t> d_index;  // lookup index over the results (built on first kc_lookup)
+  uint64_t index_cap;     // its slots, a power of two: the kernels' mask
   // the contig pass (kc_ctg.hpp): a table of the contigs' k-mers, merged into the results by kc_finalize
-  Table ctg_table;
+  Dev<uint64_t> ctg_keys;
+  Dev<uint32_t> ctg_vals;
+  Table ctg_table;  // over the two; keys == nullptr: no contig pass has begun
   uint64_t ctg_cap;
-  uint64_t *d_ctg_status;  // [0] a character outside the alphabet was seen, [1] entries
+  Dev<uint64_t> d_ctg_status;  // [0] a character outside the alphabet was seen, [1] entries
   uint64_t ctg_attempted, ctg_new;
   // the contigs' seed index (kc_ctg_index_build, kc_align.hpp): slots, 32-bit offsets and the block in one allocation; it
   // belongs to a pass, like the contig table (kc_reset drops it)
-  uint8_t *d_ai;
+  DevBuf d_ai;
   AlignIndex ai;
   uint64_t ai_nbytes;  // the block's bytes (kc_ctg_index_info)
   bool ai_ready;
   double arena_probe_tbps;  // rate of level 1's write pattern on the arena pick_fast_arena chose (0: no probe ran)
-  kc_synth_table *d_synth;
+  Dev<kc_synth_table> d_synth;
   // scratch of the reference-wire entry points (kc_build_supermers, kc_submit_packed_supermers)
   DevBuf sm_bytes;        // block / unpacked block
   DevBuf sm_packed;       // packed block / packed supermers
   DevBuf sm_targets;      // int32_t
   DevBuf sm_out;          // SupermerInfo
-  uint32_t *d_sm_ctr;     // n_out, n_kmers, too_long, + a u64 "bad character" flag behind them
+  Dev<uint32_t> d_sm_ctr; // n_out, n_kmers, too_long, + a u64 "bad character" flag behind them
   // scratch of kc_merge_pairs: per-pair decisions and sizes, the long-pair list, per-tile sums, statistics
   DevBuf mg;
   // the adapter set (kc_adapters_load, kc_trim.hpp): slots, records, entry offsets and entry bytes in one allocation;
   // it belongs to the context, not to a pass (kc_reset keeps it)
-  uint8_t *d_ad;
+  DevBuf d_ad;
   bool ad_loaded;
   int ad_k, ad_blastn;
   uint32_t ad_entries, ad_lg_slots;
@@ -188,25 +142,24 @@ struct kc_ctx {
   bool started;       // something was submitted since create/reset
   Geom gm;
   BucketBufs bb;
-  // arrays of an earlier geometry of this context (another k of a sweep), kept so that a later one can take them over
-  // instead of allocating again: [i] pairs with the i-th pointer of BucketBufs (bk_slots)
-  struct { void *p; size_t bytes; } bk_pool[13];
-  size_t bk_held[13];    // bytes behind the pointers bb holds now
+  // the arrays behind bb's pointers, and those of an earlier geometry of this context (another k of a sweep), kept so that
+  // a later one can take them over instead of allocating again: [i] is the array bk_init takes as its i-th
+  DevBuf bk_mem[13], bk_pool[13];
   // what the host knows without asking the device (a question is a device-to-host copy and a wait for the stream: the
   // host pipe asked twice per block, and its copies stood still meanwhile)
   uint64_t expect_host;  // == the device's CTR_EXPECT whenever expect_host_ok
   bool expect_host_ok;
   uint64_t ovf1_ub;      // upper bound of the records in the level-1 overflow list: positions launched since it was last read
   bool inc_on;           // level 2 has begun in instalments (kc_l2_split_kernel<..., INC>): bb.done1 / used2 / cnt2 carry its state
-  uint64_t *d_cb, *h_cb;
+  Dev<uint64_t> d_cb;
+  Pin<uint64_t> h_cb;
   bool bk_spilled;       // earlier buffer-fulls of this pass were counted and merged into the global table (bk_spill_pass)
   bool wire6;            // KC_FLAG_WIRE_UNITS and a geometry of six-byte records: kc_extract_partition / kc_insert_records speak kc_wire6.hpp's units
-  uint64_t *d_w6cur;     // ... the sender's cursors, one per (destination, piece); h_w6cur: their host copy
+  Dev<uint64_t> d_w6cur; // ... the sender's cursors, one per (destination, piece); h_w6cur: their host copy
   uint64_t h_w6cur[WIRE6_MAX_SHARDS << WIRE6_MAX_LG_PIECES];
   bool l1_dropped;       // earlier buffer-fulls of this pass went through level 2 and left level 1 (bk_light_spill): level 2 holds them
   uint64_t l2_held;      // ... that many records (an upper bound)
-  uint8_t *d_l2snap;     // level 2's state before a launch that cannot be run again as a whole pass (l2_snapshot)
-  size_t l2snap_bytes;
+  DevBuf d_l2snap;       // level 2's state before a launch that cannot be run again as a whole pass (l2_snapshot)
   uint64_t l2_per_bucket;  // records every bucket's part of the level-2 arena has room for while level 2 runs in instalments
   uint64_t expect_base;  // CTR_EXPECT when the buffer was last emptied: what is buffered now is CTR_EXPECT - expect_base
   uint64_t expect_prev;  // CTR_EXPECT after the previous block
@@ -216,27 +169,30 @@ struct kc_ctx {
   int num_cus;
   // shard flow (kc_shard.hpp): ownership by level-1 bucket
   struct ShardExtent {
-    uint64_t *p;
-    uint64_t cap, used;  // words
+    Dev<uint64_t> mem;
+    uint64_t used;  // words
+    uint64_t words() const { return mem.cap / 8; }
   };
   struct {
     bool flow;         // this pass runs the shard flow (kc_shard_extract / kc_shard_commit were used)
     bool extracting;   // inside kc_shard_extract: level 1 keeps every k-mer, whoever owns it
-    uint64_t *d_plan;  // off[PMAX], totals[SHARD_MAX], flags[SHARD_MAX], loose[SHARD_MAX], wtotals[SHARD_MAX]
-    uint64_t *h_plan;  // pinned mirror of totals, flags, loose, wtotals (+ SHARD_MAX header words)
+    Dev<uint64_t> d_plan;  // off[PMAX], totals[SHARD_MAX], flags[SHARD_MAX], loose[SHARD_MAX], wtotals[SHARD_MAX]
+    Pin<uint64_t> h_plan;  // pinned mirror of totals, flags, loose, wtotals (+ SHARD_MAX header words)
     uint32_t F;        // flat sources (received segments) of this pass
     uint32_t nbo;      // buckets this shard owns (row length of d_cnt / d_at)
-    uint32_t *d_cnt;   // [FLAT_MAX][nbo]
-    uint64_t *d_at;    // [FLAT_MAX][nbo]
+    Dev<uint32_t> d_cnt;   // [FLAT_MAX][nbo]
+    Dev<uint64_t> d_at;    // [FLAT_MAX][nbo]
     uint64_t sent, received;  // records, this pass
   } sh;
   std::vector<ShardExtent> sh_extents;  // where received segments live until the regions are built (kc_shard_reserve)
 };
 
+static hipStream_t ctx_stream(const kc_ctx *c) { return c->stream; }
+static int ctx_device(const kc_ctx *c) { return c->cfg.device; }
+
 // ---- kernel timing (HIP events on the launch stream) --------------------------------------------
 static void bk_free(kc_ctx *c, bool keep);
 static void host_pipe_free(kc_ctx *c);
-static void shard_free(kc_ctx *c);
 
 struct KernelTimer {
   kc_ctx *c;
@@ -334,8 +290,8 @@ static uint64_t next_pow2(uint64_t v) {
 static size_t table_bytes_for(uint64_t capacity, int nl) { return (size_t)capacity * ((size_t)nl * 8 + 36); }
 
 static void carve_table(kc_ctx *c) {
-  c->table.keys = (uint64_t *)c->arena;
-  c->table.vals = (uint32_t *)(c->arena + (size_t)c->capacity * c->nl * 8);
+  c->table.keys = c->arena.as<uint64_t>();
+  c->table.vals = (uint32_t *)(c->arena.p + (size_t)c->capacity * c->nl * 8);
   c->table.mask = c->capacity - 1;
 }
 
@@ -353,12 +309,11 @@ static int sync_ctrs(kc_ctx *c) {
 
 template <int NL>
 static int grow_table_nl(kc_ctx *c, uint64_t new_capacity) {
-  uint8_t *na = nullptr;
-  size_t nb = table_bytes_for(new_capacity, NL);
-  HIPCHK(hipMalloc((void **)&na, nb));
+  DevBuf na;  // the old arena goes with it, once the entries have moved
+  KCTRY(na.reserve(table_bytes_for(new_capacity, NL)));
   Table nt;
-  nt.keys = (uint64_t *)na;
-  nt.vals = (uint32_t *)(na + (size_t)new_capacity * NL * 8);
+  nt.keys = na.as<uint64_t>();
+  nt.vals = (uint32_t *)(na.p + (size_t)new_capacity * NL * 8);
   nt.mask = new_capacity - 1;
   HIPCHK(hipMemsetAsync(nt.keys, 0xFF, (size_t)new_capacity * NL * 8, c->stream));
   HIPCHK(hipMemsetAsync(nt.vals, 0, (size_t)new_capacity * 36, c->stream));
@@ -369,9 +324,7 @@ static int grow_table_nl(kc_ctx *c, uint64_t new_capacity) {
   }
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(c->stream));
-  HIPCHK(hipFree(c->arena));
-  c->arena = na;
-  c->arena_bytes = nb;
+  c->arena.swap(na);
   c->capacity = new_capacity;
   c->table = nt;
   return KC_OK;
@@ -390,16 +343,6 @@ static int ensure_room(kc_ctx *c, uint64_t incoming) {
   uint64_t cap = c->capacity;
   while ((double)need > 0.9 * (double)cap) cap <<= 1;
   if (cap != c->capacity) return grow_table(c, cap);
-  return KC_OK;
-}
-
-static int ensure_tile_first(kc_ctx *c, size_t ntiles) {
-  if (ntiles <= c->tile_first_cap) return KC_OK;
-  if (c->d_tile_first) HIPCHK(hipFree(c->d_tile_first));
-  c->d_tile_first = nullptr;
-  c->tile_first_cap = 0;
-  HIPCHK(hipMalloc((void **)&c->d_tile_first, ntiles * 8));
-  c->tile_first_cap = ntiles;
   return KC_OK;
 }
 
@@ -504,14 +447,13 @@ static int create_impl(kc_ctx *c) {
   c->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
   // the global table starts small: on the bucketed path it only ever holds the regions that did not fit
   c->capacity = 1ULL << 16;
-  c->arena_bytes = table_bytes_for(c->capacity, c->nl);
-  HIPCHK(hipMalloc((void **)&c->arena, c->arena_bytes));
+  KCTRY(c->arena.reserve(table_bytes_for(c->capacity, c->nl)));
   carve_table(c);
-  HIPCHK(hipMalloc((void **)&c->d_ctrs, CTR_COUNT * 8));
-  HIPCHK(hipHostMalloc((void **)&c->h_ctrs, CTR_COUNT * 8, hipHostMallocDefault));
+  KCTRY(c->d_ctrs.reserve(CTR_COUNT * 8));
+  KCTRY(c->h_ctrs.reserve(CTR_COUNT * 8));
   HIPCHK(hipMemsetAsync(c->d_ctrs, 0, CTR_COUNT * 8, c->stream));
-  HIPCHK(hipMalloc((void **)&c->d_cb, CB_COUNT * 8));
-  HIPCHK(hipHostMalloc((void **)&c->h_cb, CB_COUNT * 8, hipHostMallocDefault));
+  KCTRY(c->d_cb.reserve(CB_COUNT * 8));
+  KCTRY(c->h_cb.reserve(CB_COUNT * 8));
   HIPCHK(hipMemsetAsync(c->d_cb, 0, CB_COUNT * 8, c->stream));
   memset(c->h_cb, 0, CB_COUNT * 8);
   int rc = clear_table(c);
@@ -550,67 +492,41 @@ extern "C" kc_ctx *kc_create(const kc_config *cfg, int *status) {
 }
 
 static void free_index(kc_ctx *c) {
-  if (c->d_index) (void)hipFree(c->d_index);
-  c->d_index = nullptr;
+  (void)c->d_index.release();
   c->index_cap = 0;
 }
 
 static void free_ctg(kc_ctx *c) {
-  if (c->ctg_table.keys) (void)hipFree(c->ctg_table.keys);
-  if (c->ctg_table.vals) (void)hipFree(c->ctg_table.vals);
-  if (c->d_ctg_status) (void)hipFree(c->d_ctg_status);
+  (void)c->ctg_keys.release();
+  (void)c->ctg_vals.release();
+  (void)c->d_ctg_status.release();
   memset(&c->ctg_table, 0, sizeof(c->ctg_table));
-  c->d_ctg_status = nullptr;
   c->ctg_cap = c->ctg_attempted = c->ctg_new = 0;
 }
 
 static void free_align_index(kc_ctx *c) {
-  if (c->d_ai) (void)hipFree(c->d_ai);
-  c->d_ai = nullptr;
+  (void)c->d_ai.release();
   memset(&c->ai, 0, sizeof(c->ai));
   c->ai_ready = false;
 }
 
 static void free_results(kc_ctx *c) {
   free_index(c);
-  if (c->d_out_keys) (void)hipFree(c->d_out_keys);
-  if (c->d_out_keys_ext) (void)hipFree(c->d_out_keys_ext);
-  c->d_out_keys_ext = nullptr;
-  if (c->d_out_counts) (void)hipFree(c->d_out_counts);
-  if (c->d_out_left) (void)hipFree(c->d_out_left);
-  if (c->d_out_right) (void)hipFree(c->d_out_right);
-  c->d_out_keys = nullptr;
-  c->d_out_counts = nullptr;
-  c->d_out_left = c->d_out_right = nullptr;
+  (void)c->d_out_keys.release();
+  (void)c->d_out_keys_ext.release();
+  (void)c->d_out_counts.release();
+  (void)c->d_out_left.release();
+  (void)c->d_out_right.release();
   c->out_cap = c->out_n = 0;
 }
 
+// the context's memory goes with its owners
 extern "C" void kc_destroy(kc_ctx *c) {
   if (!c) return;
   (void)hipSetDevice(c->cfg.device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   drain_kernel_times(c);
-  free_results(c);
-  if (c->arena) (void)hipFree(c->arena);
-  if (c->d_ctrs) (void)hipFree(c->d_ctrs);
-  if (c->d_w6cur) (void)hipFree(c->d_w6cur);
-  if (c->d_l2snap) (void)hipFree(c->d_l2snap);
-  if (c->h_ctrs) (void)hipHostFree(c->h_ctrs);
-  if (c->d_tile_first) (void)hipFree(c->d_tile_first);
-  if (c->d_out_plan) (void)hipFree(c->d_out_plan);
-  for (DevBuf *b : {&c->stage_bases, &c->stage_quals, &c->stage_offsets, &c->sm_bytes, &c->sm_packed, &c->sm_targets, &c->sm_out,
-                    &c->mg, &c->tr, &c->fq_text, &c->fq_tiles, &c->fq_recs, &c->dump_tiles})
-    (void)b->release();
-  if (c->d_synth) (void)hipFree(c->d_synth);
-  if (c->d_sm_ctr) (void)hipFree(c->d_sm_ctr);
-  if (c->d_ad) (void)hipFree(c->d_ad);
-  host_pipe_free(c);
-  free_ctg(c);
-  free_align_index(c);
-  bk_free(c, false);
-  shard_free(c);
-  if (c->d_cb) (void)hipFree(c->d_cb);
-  if (c->h_cb) (void)hipHostFree(c->h_cb);
+  host_pipe_free(c);  // its events and streams
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
   delete c;
 }
@@ -629,22 +545,10 @@ static void shard_reset(kc_ctx *c, bool geometry_changes) {
   c->sh.sent = c->sh.received = 0;
   for (auto &e : c->sh_extents) e.used = 0;
   if (geometry_changes) {
-    if (c->sh.d_cnt) (void)hipFree(c->sh.d_cnt);
-    if (c->sh.d_at) (void)hipFree(c->sh.d_at);
-    c->sh.d_cnt = nullptr;
-    c->sh.d_at = nullptr;
+    (void)c->sh.d_cnt.release();
+    (void)c->sh.d_at.release();
     c->sh.nbo = 0;
   }
-}
-
-static void shard_free(kc_ctx *c) {
-  shard_reset(c, true);
-  for (auto &e : c->sh_extents)
-    if (e.p) (void)hipFree(e.p);
-  c->sh_extents.clear();
-  if (c->sh.d_plan) (void)hipFree(c->sh.d_plan);
-  if (c->sh.h_plan) (void)hipHostFree(c->sh.h_plan);
-  c->sh.d_plan = c->sh.h_plan = nullptr;
 }
 
 // Level 1 empty: every chain, every writer's arena whole, nothing on its overflow list (whose counter, CB_OVF1, is
@@ -691,11 +595,10 @@ extern "C" int kc_reset(kc_ctx *c, int new_k) {
   c->cfg.kmer_len = new_k;
   c->nl = kc_record_longs(new_k);
   c->nl_ext = kc_num_longs(new_k);
-  if (c->d_out_keys_ext) (void)hipFree(c->d_out_keys_ext);
-  c->d_out_keys_ext = nullptr;
+  (void)c->d_out_keys_ext.release();
   // re-carve the same arena for the new word count: largest power of two that fits
   uint64_t cap = 1;
-  while (table_bytes_for(cap << 1, c->nl) <= c->arena_bytes) cap <<= 1;
+  while (table_bytes_for(cap << 1, c->nl) <= c->arena.cap) cap <<= 1;
   c->capacity = cap;
   carve_table(c);
   HIPCHK(hipMemsetAsync(c->d_ctrs, 0, CTR_COUNT * 8, c->stream));
@@ -731,35 +634,14 @@ static uint32_t count_smax(int nl) {
   }
 }
 
-// the pointers of BucketBufs, in the order of kc_ctx::bk_pool
-static void bk_slots(BucketBufs &b, void ***out) {
-  void **ptrs[13] = {(void **)&b.rec1, (void **)&b.chain1, (void **)&b.cnt1, (void **)&b.used1, (void **)&b.rec2, (void **)&b.chain2,
-                     (void **)&b.cnt2, (void **)&b.base2, (void **)&b.flag, (void **)&b.ovf1, (void **)&b.ovf2, (void **)&b.done1,
-                     (void **)&b.used2};
-  for (int i = 0; i < 13; i++) out[i] = ptrs[i];
-}
-
 // Give up the current geometry.  keep: its arrays stay with the context (kc_reset to another k, kc_set_tuning) and the
 // next geometry takes over every one that is large enough -- BASELINE config 5's sweep k = 21, 33, 55, 77 keeps its
 // arenas resident in HBM: they are allocated once per record width at most, and a width seen before allocates nothing.
 static void bk_free(kc_ctx *c, bool keep = false) {
-  void **slot[13];
-  bk_slots(c->bb, slot);
   for (int i = 0; i < 13; i++) {
-    void *p = *slot[i];
-    if (p && keep && c->bk_held[i] > c->bk_pool[i].bytes) {  // the larger of the two stays
-      if (c->bk_pool[i].p) (void)hipFree(c->bk_pool[i].p);
-      c->bk_pool[i].p = p;
-      c->bk_pool[i].bytes = c->bk_held[i];
-    } else if (p) {
-      (void)hipFree(p);
-    }
-    if (!keep && c->bk_pool[i].p) {
-      (void)hipFree(c->bk_pool[i].p);
-      c->bk_pool[i].p = nullptr;
-      c->bk_pool[i].bytes = 0;
-    }
-    c->bk_held[i] = 0;
+    if (keep && c->bk_mem[i].cap > c->bk_pool[i].cap) c->bk_pool[i] = std::move(c->bk_mem[i]);  // the larger of the two stays
+    (void)c->bk_mem[i].release();
+    if (!keep) (void)c->bk_pool[i].release();
   }
   memset(&c->bb, 0, sizeof(c->bb));
   c->bk_ready = false;
@@ -770,22 +652,12 @@ static void bk_free(kc_ctx *c, bool keep = false) {
 // `bytes` of device memory for the i-th array of the bucket buffers: what the context kept from an earlier geometry
 // when that is large enough (*reused), else a fresh allocation
 static int bk_take(kc_ctx *c, int i, void **out, size_t bytes, bool *reused = nullptr) {
-  if (reused) *reused = false;
-  if (c->bk_pool[i].p && c->bk_pool[i].bytes >= bytes) {
-    *out = c->bk_pool[i].p;
-    c->bk_held[i] = c->bk_pool[i].bytes;
-    c->bk_pool[i].p = nullptr;
-    c->bk_pool[i].bytes = 0;
-    if (reused) *reused = true;
-    return KC_OK;
-  }
-  if (c->bk_pool[i].p) {  // too small: make room for its successor
-    (void)hipFree(c->bk_pool[i].p);
-    c->bk_pool[i].p = nullptr;
-    c->bk_pool[i].bytes = 0;
-  }
-  HIPCHK(hipMalloc(out, bytes));
-  c->bk_held[i] = bytes;
+  const bool fits = c->bk_pool[i].p && c->bk_pool[i].cap >= bytes;
+  if (reused) *reused = fits;
+  if (fits) c->bk_mem[i] = std::move(c->bk_pool[i]);
+  (void)c->bk_pool[i].release();  // too small: make room for its successor
+  KCTRY(c->bk_mem[i].reserve(bytes));
+  *out = c->bk_mem[i].p;
   return KC_OK;
 }
 
@@ -986,6 +858,8 @@ static int bk_init(kc_ctx *c) {
     const char *pe = getenv("KC_ARENA_PROBE");
     if (!rc && !(pe && pe[0] == '0') && rec1_bytes >= ((size_t)1 << 30) && !rec1_reused) {
       rc = pick_fast_arena(c, &b.rec1, rec1_bytes, g.G, "level 1");
+      c->bk_mem[0].forget();  // the probe has freed what it did not choose
+      if (b.rec1) c->bk_mem[0].p = reinterpret_cast<uint8_t *>(b.rec1), c->bk_mem[0].cap = rec1_bytes;
     }
     if (!rc) rc = bk_take(c, 1, (void **)&b.chain1, nseg * g.L1MAX * 4);
     if (!rc) rc = bk_take(c, 2, (void **)&b.cnt1, nseg * 4);
@@ -1283,18 +1157,17 @@ static int bk_l2_reserve(kc_ctx *c, uint64_t need) {
   const uint64_t pb = c->inc_on ? std::max<uint64_t>(2 * pb_now, pb_need) : pb_need;
   const uint64_t a2 = (uint64_t)g.P1 * ((pb + CH2 - 1) / CH2 + g.P2) + 16;
   if (a2 >= (1ULL << 32)) return KC_ERR_OUT_OF_MEMORY;
-  uint64_t *bigger = nullptr;
+  DevBuf bigger;  // the old arena goes with it, once the parts have moved
   const size_t bytes = (size_t)a2 * CH2 * 4;
   size_t free_b = 0, total_b = 0;
-  if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b < bytes + ((size_t)4 << 30) || hipMalloc((void **)&bigger, bytes) != hipSuccess) {
+  if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b < bytes + ((size_t)4 << 30) || bigger.reserve(bytes)) {
     (void)hipGetLastError();
     return KC_ERR_OUT_OF_MEMORY;
   }
   if (c->inc_on) {
-    uint32_t *nb = nullptr;
-    if (hipMalloc((void **)&nb, ((size_t)g.P1 + 1) * 4) != hipSuccess) {
+    Dev<uint32_t> nb;
+    if (nb.reserve(((size_t)g.P1 + 1) * 4)) {
       (void)hipGetLastError();
-      (void)hipFree(bigger);
       return KC_ERR_OUT_OF_MEMORY;
     }
     BucketBufs tmp = c->bb;
@@ -1303,21 +1176,16 @@ static int bk_l2_reserve(kc_ctx *c, uint64_t need) {
     memset(&fs, 0, sizeof(fs));
     hipLaunchKernelGGL(kc_bucket_prefix_kernel, dim3(1), dim3(WGB), 0, c->stream, c->gm, tmp, fs, c->d_cb, pb);
     hipLaunchKernelGGL(kc_l2_grow_kernel, dim3(g.P1), dim3(WGB), 0, c->stream, c->gm, reinterpret_cast<const uint32_t *>(c->bb.rec2),
-                       reinterpret_cast<uint32_t *>(bigger), c->bb.base2, nb, c->bb.used2, c->bb.chain2, c->bb.cnt2);
+                       bigger.as<uint32_t>(), c->bb.base2, nb, c->bb.used2, c->bb.chain2, c->bb.cnt2);
     c->num_gpu_calls += 2;
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(c->bb.base2, nb, ((size_t)g.P1 + 1) * 4, hipMemcpyDeviceToDevice, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(nb);
-    if (e != hipSuccess) {
-      (void)hipFree(bigger);
-      return hip_fail(e, "bk_l2_reserve", __LINE__);
-    }
+    if (e != hipSuccess) return HIP_FAIL(e, "bk_l2_reserve");
   }
-  HIPCHK(hipFree(c->bb.rec2));
-  c->bk_bytes += bytes - c->bk_held[4];
-  c->bb.rec2 = bigger;
-  c->bk_held[4] = bytes;
+  c->bk_bytes += bytes - c->bk_mem[4].cap;
+  c->bk_mem[4].swap(bigger);
+  c->bb.rec2 = c->bk_mem[4].as<uint64_t>();
   c->gm.A2 = (uint32_t)a2;
   c->l2_per_bucket = pb;
   return KC_OK;
@@ -1327,19 +1195,18 @@ static int bk_l2_reserve(kc_ctx *c, uint64_t need) {
 static int grow_ovf2(kc_ctx *c, uint64_t records, uint64_t keep) {
   if (records <= c->bb.ovf2_cap) return KC_OK;
   const size_t w = (size_t)c->nl * 8;
-  uint64_t *bigger = nullptr;
-  if (hipMalloc((void **)&bigger, records * w) != hipSuccess) {
+  DevBuf bigger;  // the old list goes with it, once its entries are copied
+  if (bigger.reserve(records * w)) {
     (void)hipGetLastError();
     snprintf(g_last_error, sizeof(g_last_error), "no memory for a region overflow list of %llu records", (unsigned long long)records);
     return KC_ERR_OUT_OF_MEMORY;
   }
-  if (keep) HIPCHK(hipMemcpyAsync(bigger, c->bb.ovf2, keep * w, hipMemcpyDeviceToDevice, c->stream));
+  if (keep) HIPCHK(hipMemcpyAsync(bigger.p, c->bb.ovf2, keep * w, hipMemcpyDeviceToDevice, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
-  HIPCHK(hipFree(c->bb.ovf2));
   c->bk_bytes += (records - c->bb.ovf2_cap) * w;
-  c->bb.ovf2 = bigger;
+  c->bk_mem[10].swap(bigger);
+  c->bb.ovf2 = c->bk_mem[10].as<uint64_t>();
   c->bb.ovf2_cap = records;
-  c->bk_held[10] = records * w;
   return KC_OK;
 }
 
@@ -1349,15 +1216,8 @@ static int l2_snapshot(kc_ctx *c, bool restore) {
   const Geom &g = c->gm;
   void *const part[4] = {c->bb.cnt2, c->bb.used2, c->bb.done1, c->d_cb + CB_OVF2};
   const size_t bytes[4] = {(size_t)g.P1 * g.P2 * 4, (size_t)g.P1 * 4, (size_t)g.G * g.P1 * 4, 8};
-  const size_t need = bytes[0] + bytes[1] + bytes[2] + bytes[3];
-  if (!restore && c->l2snap_bytes < need) {
-    if (c->d_l2snap) HIPCHK(hipFree(c->d_l2snap));
-    c->d_l2snap = nullptr;
-    c->l2snap_bytes = 0;
-    HIPCHK(hipMalloc((void **)&c->d_l2snap, need));
-    c->l2snap_bytes = need;
-  }
-  uint8_t *s = c->d_l2snap;
+  if (!restore) KCTRY(c->d_l2snap.reserve(bytes[0] + bytes[1] + bytes[2] + bytes[3]));
+  uint8_t *s = c->d_l2snap.p;
   for (int i = 0; i < 4; s += bytes[i], i++)
     HIPCHK(hipMemcpyAsync(restore ? part[i] : s, restore ? s : part[i], bytes[i], hipMemcpyDeviceToDevice, c->stream));
   if (restore) HIPCHK(hipMemsetAsync(c->d_cb + CB_FATAL, 0, 8, c->stream));
@@ -1537,7 +1397,7 @@ static int bk_move_flagged(kc_ctx *c) {
 }
 
 // entries of the LDS-counted regions, unfiltered: two passes (size, then write)
-static int bk_dump(kc_ctx *c, uint64_t **dk, uint16_t **dc, uint16_t **de, uint64_t *n_regions) {
+static int bk_dump(kc_ctx *c, CallBufs &b, uint64_t **dk, uint16_t **dc, uint16_t **de, uint64_t *n_regions) {
   int rc = bk_build_regions(c);
   if (rc) return rc;
   uint64_t cap = 0;
@@ -1560,9 +1420,9 @@ static int bk_dump(kc_ctx *c, uint64_t **dk, uint16_t **dc, uint16_t **de, uint6
     if (pass == 0) {
       cap = c->h_cb[CB_DUMP];
       if (!cap) break;
-      HIPCHK(hipMalloc((void **)dk, cap * c->nl * 8));
-      HIPCHK(hipMalloc((void **)dc, cap * 2));
-      HIPCHK(hipMalloc((void **)de, cap * 16));
+      KCTRY(b.alloc(dk, cap * c->nl * 8));
+      KCTRY(b.alloc(dc, cap * 2));
+      KCTRY(b.alloc(de, cap * 16));
     }
   }
   *n_regions = cap;
@@ -1577,7 +1437,8 @@ static int bk_spill_pass(kc_ctx *c) {
   uint64_t *dk = nullptr;
   uint16_t *dc = nullptr, *de = nullptr;
   uint64_t n = 0;
-  int rc = bk_dump(c, &dk, &dc, &de, &n);  // regions built, entries listed, flagged regions and overflow records to the table
+  CallBufs b;  // the entries, until the stream has merged them
+  int rc = bk_dump(c, b, &dk, &dc, &de, &n);  // regions built, entries listed, flagged regions and overflow records to the table
   if (!rc && n) {
     rc = ensure_room(c, n);
     if (!rc) {
@@ -1590,9 +1451,7 @@ static int bk_spill_pass(kc_ctx *c) {
     }
   }
   if (hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = KC_ERR_HIP;
-  if (dk) (void)hipFree(dk);
-  if (dc) (void)hipFree(dc);
-  if (de) (void)hipFree(de);
+  b.release();
   if (!rc) rc = bk_empty_level1(c);
   if (!rc) rc = bk_empty_level2(c);
   if (rc) return rc;
@@ -1772,8 +1631,7 @@ static int run_extract_device(kc_ctx *c, const uint8_t *bases, const uint8_t *qu
       if (rc) return rc;
     }
     if (fmt != FMT_SEQBLOCK) {
-      int rc = ensure_tile_first(c, nt);
-      if (rc) return rc;
+      KCTRY(c->d_tile_first.reserve(nt * 8));
       {
         KernelTimer kt(c, KT_TILE_FIRST);
         hipLaunchKernelGGL(kc_tile_first_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, c->stream, d_offsets, nreads,
@@ -1850,19 +1708,25 @@ static size_t host_block_bytes() {
 static void host_pipe_free(kc_ctx *c) {
   auto &h = c->hp;
   for (int s = 0; s < 2; s++) {
-    if (h.d_bases[s]) (void)hipFree(h.d_bases[s]);
-    if (h.d_quals[s]) (void)hipFree(h.d_quals[s]);
-    if (h.d_offs[s]) (void)hipFree(h.d_offs[s]);
-    if (h.h_bases[s]) (void)hipHostFree(h.h_bases[s]);
-    if (h.h_quals[s]) (void)hipHostFree(h.h_quals[s]);
-    if (h.h_offs[s]) (void)hipHostFree(h.h_offs[s]);
-    if (h.copied[s]) (void)hipEventDestroy(h.copied[s]);
-    if (h.consumed[s]) (void)hipEventDestroy(h.consumed[s]);
-    if (h.half[s]) (void)hipEventDestroy(h.half[s]);
+    (void)h.d_bases[s].release();
+    (void)h.d_quals[s].release();
+    (void)h.d_offs[s].release();
+    (void)h.h_bases[s].release();
+    (void)h.h_quals[s].release();
+    (void)h.h_offs[s].release();
+    for (hipEvent_t *e : {&h.copied[s], &h.consumed[s], &h.half[s]}) {
+      if (*e) (void)hipEventDestroy(*e);
+      *e = nullptr;
+    }
+    h.lead_b[s] = h.lead_q[s] = 0;
+    h.used[s] = false;
   }
-  if (h.copy_stream) (void)hipStreamDestroy(h.copy_stream);
-  if (h.copy_stream2) (void)hipStreamDestroy(h.copy_stream2);
-  memset(&h, 0, sizeof(h));
+  for (hipStream_t *st : {&h.copy_stream, &h.copy_stream2}) {
+    if (*st) (void)hipStreamDestroy(*st);
+    *st = nullptr;
+  }
+  h.cap_bytes = h.cap_reads = 0;
+  h.ready = false;
 }
 
 static int host_pipe_init(kc_ctx *c, size_t bytes, size_t reads, bool pinned_source) {
@@ -1873,13 +1737,13 @@ static int host_pipe_init(kc_ctx *c, size_t bytes, size_t reads, bool pinned_sou
   HIPCHK(hipStreamCreateWithFlags(&h.copy_stream2, hipStreamNonBlocking));
   for (int s = 0; s < 2; s++) {
     HIPCHK(hipEventCreateWithFlags(&h.half[s], hipEventDisableTiming));
-    HIPCHK(hipMalloc((void **)&h.d_bases[s], bytes + 4096 + 64));  // (+ a page: copies start page-aligned in the source)
-    HIPCHK(hipMalloc((void **)&h.d_quals[s], bytes + 4096 + 64));
-    HIPCHK(hipMalloc((void **)&h.d_offs[s], (reads + 1) * 8));
-    HIPCHK(hipHostMalloc((void **)&h.h_offs[s], (reads + 1) * 8, hipHostMallocDefault));
+    KCTRY(h.d_bases[s].reserve(bytes + 4096 + 64));  // (+ a page: copies start page-aligned in the source)
+    KCTRY(h.d_quals[s].reserve(bytes + 4096 + 64));
+    KCTRY(h.d_offs[s].reserve((reads + 1) * 8));
+    KCTRY(h.h_offs[s].reserve((reads + 1) * 8));
     if (!pinned_source) {
-      HIPCHK(hipHostMalloc((void **)&h.h_bases[s], bytes, hipHostMallocDefault));
-      HIPCHK(hipHostMalloc((void **)&h.h_quals[s], bytes, hipHostMallocDefault));
+      KCTRY(h.h_bases[s].reserve(bytes));
+      KCTRY(h.h_quals[s].reserve(bytes));
     }
     HIPCHK(hipEventCreateWithFlags(&h.copied[s], hipEventDisableTiming));
     HIPCHK(hipEventCreateWithFlags(&h.consumed[s], hipEventDisableTiming));
@@ -1988,7 +1852,7 @@ static int submit_host_reads(kc_ctx *c, const uint8_t *bases, const uint8_t *qua
     if (h.used[s]) HIPCHK(hipEventSynchronize(h.consumed[s]));  // the kernels of two blocks ago have read slot s
     const uint64_t nb = offsets[b.r1] - offsets[b.r0], nr = b.r1 - b.r0;
     // the block's offsets as they are (a plain copy, a few threads); the device makes them relative to the block
-    parallel_copy(reinterpret_cast<uint8_t *>(h.h_offs[s]), reinterpret_cast<const uint8_t *>(offsets + b.r0), (nr + 1) * 8);
+    parallel_copy(h.h_offs[s].p, reinterpret_cast<const uint8_t *>(offsets + b.r0), (nr + 1) * 8);
     const uint8_t *sb = bases + offsets[b.r0], *sq = with_quals ? quals + offsets[b.r0] : nullptr;
     if (!pinned) {
       parallel_copy(h.h_bases[s], sb, nb);
@@ -2145,7 +2009,7 @@ extern "C" int kc_build_supermers(kc_ctx *c, const char *seqs, uint64_t len, int
   KCTRY(c->sm_out.reserve((size_t)std::max<uint32_t>(capacity, 1) * sizeof(SupermerInfo)));
   KCTRY(c->sm_packed.reserve((size_t)(len + 1) / 2));
   if (!on_device) KCTRY(c->sm_bytes.reserve((size_t)len));
-  if (!c->d_sm_ctr) HIPCHK(hipMalloc((void **)&c->d_sm_ctr, 32));
+  KCTRY(c->d_sm_ctr.reserve(32));
   HIPCHK(hipMemsetAsync(c->d_sm_ctr, 0, 32, c->stream));
   const uint8_t *d = (const uint8_t *)seqs;
   if (!on_device) {
@@ -2189,7 +2053,7 @@ extern "C" int kc_submit_packed_supermers(kc_ctx *c, const uint8_t *packed, uint
   HIPCHK(hipStreamSynchronize(c->stream));
   KCTRY(c->sm_bytes.reserve((size_t)len * 2));
   if (!on_device) KCTRY(c->sm_packed.reserve((size_t)len));
-  if (!c->d_sm_ctr) HIPCHK(hipMalloc((void **)&c->d_sm_ctr, 32));
+  KCTRY(c->d_sm_ctr.reserve(32));
   HIPCHK(hipMemsetAsync(c->d_sm_ctr, 0, 32, c->stream));
   const uint8_t *d = packed;
   if (!on_device) {
@@ -2216,7 +2080,7 @@ static int bin_begin(kc_ctx *c) {
   }
   HIPCHK(hipMemsetAsync(c->d_ctrs + CTR_OVERFLOW, 0, (1 + 64) * 8, c->stream));
   if (c->wire6) {
-    if (!c->d_w6cur) HIPCHK(hipMalloc((void **)&c->d_w6cur, sizeof(c->h_w6cur)));
+    KCTRY(c->d_w6cur.reserve(sizeof(c->h_w6cur)));
     HIPCHK(hipMemsetAsync(c->d_w6cur, 0, sizeof(c->h_w6cur), c->stream));
   }
   return KC_OK;
@@ -2335,21 +2199,18 @@ extern "C" int kc_insert_records(kc_ctx *c, const uint64_t *d_records, uint64_t 
     }
   }
   if (w6) {  // the context has left the bucketed path: back to k-mer records for the global table
-    uint64_t *tmp = nullptr;
-    HIPCHK(hipMalloc((void **)&tmp, (n + 1) * 8));
-    int rc = KC_OK;
-    unsigned long long h_n = 0;
-    if (hipMemsetAsync(tmp + n, 0, 8, c->stream) != hipSuccess) rc = KC_ERR_HIP;
-    if (!rc) {
+    return call_with_bufs(c, [&](CallBufs &b) {
+      uint64_t *tmp, h_n = 0;
+      KCTRY(b.alloc(&tmp, (n + 1) * 8));
+      HIPCHK(hipMemsetAsync(tmp + n, 0, 8, c->stream));
       hipLaunchKernelGGL(kc_wire6_expand_kernel, dim3((unsigned)std::min<uint64_t>((n + TPB - 1) / TPB, 256 * 32)), dim3(TPB), 0, c->stream,
                          reinterpret_cast<const uint8_t *>(d_records), n, c->gm, tmp, (unsigned long long *)(tmp + n));
       c->num_gpu_calls++;
-      if (hipMemcpyAsync(&h_n, tmp + n, 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) rc = KC_ERR_HIP;
-    }
-    if (!rc && h_n) rc = table_insert_records(c, tmp, h_n, 1u);
-    if (hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = KC_ERR_HIP;
-    (void)hipFree(tmp);
-    return rc;
+      KCTRY(read_back(c, &h_n, tmp + n, 1));
+      if (h_n) KCTRY(table_insert_records(c, tmp, h_n, 1u));
+      HIPCHK(hipStreamSynchronize(c->stream));  // the table has taken the records
+      return (int)KC_OK;
+    });
   }
   return table_insert_records(c, d_records, n, 1u);
 }
@@ -2450,10 +2311,8 @@ static uint64_t shard_signature(const kc_ctx *c) {
 }
 
 static int shard_init(kc_ctx *c) {
-  if (c->sh.d_plan) return KC_OK;
-  HIPCHK(hipMalloc((void **)&c->sh.d_plan, ((size_t)PMAX + 4 * SHARD_MAX) * 8));
-  HIPCHK(hipHostMalloc((void **)&c->sh.h_plan, (size_t)5 * SHARD_MAX * 8, hipHostMallocDefault));
-  return KC_OK;
+  KCTRY(c->sh.d_plan.reserve(((size_t)PMAX + 4 * SHARD_MAX) * 8));
+  return c->sh.h_plan.reserve((size_t)5 * SHARD_MAX * 8);
 }
 
 // checks and set-up shared by the two forms of kc_shard_extract
@@ -2588,8 +2447,8 @@ extern "C" int kc_shard_reserve(kc_ctx *c, uint64_t nwords, uint64_t **d_dst) {
   HIPCHK(hipSetDevice(c->cfg.device));
   const uint64_t need = (nwords + 1) & ~1ULL;  // 16-byte granules
   for (auto &e : c->sh_extents) {
-    if (e.cap - e.used >= need) {
-      *d_dst = e.p + e.used;
+    if (e.words() - e.used >= need) {
+      *d_dst = e.mem + e.used;
       e.used += need;
       return KC_OK;
     }
@@ -2598,12 +2457,10 @@ extern "C" int kc_shard_reserve(kc_ctx *c, uint64_t nwords, uint64_t **d_dst) {
   // what this call needs
   const uint64_t bcap = c->cfg.max_kmers_buffered ? c->cfg.max_kmers_buffered : (1ULL << 26);
   kc_ctx::ShardExtent e;
-  e.cap = std::max<uint64_t>(need, std::max<uint64_t>(bcap * (uint64_t)c->nl / 8, 1ULL << 17));
+  KCTRY(e.mem.reserve((size_t)std::max<uint64_t>(need, std::max<uint64_t>(bcap * (uint64_t)c->nl / 8, 1ULL << 17)) * 8));
   e.used = need;
-  e.p = nullptr;
-  HIPCHK(hipMalloc((void **)&e.p, (size_t)e.cap * 8));
-  c->sh_extents.push_back(e);
-  *d_dst = e.p;
+  *d_dst = e.mem;
+  c->sh_extents.push_back(std::move(e));
   return KC_OK;
 }
 
@@ -2615,7 +2472,7 @@ extern "C" int kc_shard_commit(kc_ctx *c, const uint64_t *d_segment, uint64_t nw
   if (n < 2 || !bk_active(c)) return KC_ERR_STATE;
   if (c->started && !c->sh.flow) return KC_ERR_STATE;
   bool inside = false;
-  for (auto &e : c->sh_extents) inside |= d_segment >= e.p && d_segment + nwords <= e.p + e.used;
+  for (auto &e : c->sh_extents) inside |= d_segment >= e.mem && d_segment + nwords <= e.mem + e.used;
   if (!inside) {
     snprintf(g_last_error, sizeof(g_last_error), "kc_shard_commit: the segment does not lie in memory handed out by kc_shard_reserve");
     return KC_ERR_INVALID_ARG;
@@ -2665,12 +2522,10 @@ extern "C" int kc_shard_commit(kc_ctx *c, const uint64_t *d_segment, uint64_t nw
     return KC_ERR_CAPACITY;
   }
   if (c->sh.nbo != nbo || !c->sh.d_cnt) {  // first segment for this geometry
-    if (c->sh.d_cnt) (void)hipFree(c->sh.d_cnt);
-    if (c->sh.d_at) (void)hipFree(c->sh.d_at);
-    c->sh.d_cnt = nullptr;
-    c->sh.d_at = nullptr;
-    HIPCHK(hipMalloc((void **)&c->sh.d_cnt, (size_t)FLAT_MAX * nbo * 4));
-    HIPCHK(hipMalloc((void **)&c->sh.d_at, (size_t)FLAT_MAX * nbo * 8));
+    (void)c->sh.d_cnt.release();
+    (void)c->sh.d_at.release();
+    KCTRY(c->sh.d_cnt.reserve((size_t)FLAT_MAX * nbo * 4));
+    KCTRY(c->sh.d_at.reserve((size_t)FLAT_MAX * nbo * 8));
     c->sh.nbo = nbo;
   }
   c->sh.flow = true;
@@ -2751,36 +2606,41 @@ static int alloc_results(kc_ctx *c, uint64_t cap) {
     return KC_OK;
   }
   free_results(c);
-  HIPCHK(hipMalloc((void **)&c->d_out_keys, cap * c->nl * 8));
-  HIPCHK(hipMalloc((void **)&c->d_out_counts, cap * 2));
-  HIPCHK(hipMalloc((void **)&c->d_out_left, cap));
-  HIPCHK(hipMalloc((void **)&c->d_out_right, cap));
+  KCTRY(c->d_out_keys.reserve(cap * c->nl * 8));
+  KCTRY(c->d_out_counts.reserve(cap * 2));
+  KCTRY(c->d_out_left.reserve(cap));
+  KCTRY(c->d_out_right.reserve(cap));
   c->out_cap = cap;
   return KC_OK;
 }
 
-// make room for `need` results, keeping the first `keep` already written
+// make room for `need` results, keeping the first `keep` already written: the old arrays go when the new ones are filled
 static int grow_results(kc_ctx *c, uint64_t need, uint64_t keep) {
   if (need <= c->out_cap) return KC_OK;
-  uint64_t *k0 = c->d_out_keys;
-  uint16_t *c0 = c->d_out_counts;
-  uint8_t *l0 = c->d_out_left, *r0 = c->d_out_right;
-  c->d_out_keys = nullptr;
-  c->d_out_counts = nullptr;
-  c->d_out_left = c->d_out_right = nullptr;
-  int rc = alloc_results(c, need);
-  if (!rc && keep) {
-    HIPCHK(hipMemcpyAsync(c->d_out_keys, k0, keep * c->nl * 8, hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->d_out_counts, c0, keep * 2, hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->d_out_left, l0, keep, hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->d_out_right, r0, keep, hipMemcpyDeviceToDevice, c->stream));
+  Dev<uint64_t> k0;
+  Dev<uint16_t> c0;
+  Dev<uint8_t> l0, r0;
+  KCTRY(k0.reserve(need * c->nl * 8));
+  KCTRY(c0.reserve(need * 2));
+  KCTRY(l0.reserve(need));
+  KCTRY(r0.reserve(need));
+  if (keep) {
+    HIPCHK(hipMemcpyAsync(k0, c->d_out_keys, keep * c->nl * 8, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c0, c->d_out_counts, keep * 2, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(l0, c->d_out_left, keep, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(r0, c->d_out_right, keep, hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
   }
-  if (k0) (void)hipFree(k0);
-  if (c0) (void)hipFree(c0);
-  if (l0) (void)hipFree(l0);
-  if (r0) (void)hipFree(r0);
-  return rc;
+  free_index(c);
+  (void)c->d_out_keys_ext.release();
+  c->d_out_keys.swap(k0);
+  c->d_out_counts.swap(c0);
+  c->d_out_left.swap(l0);
+  c->d_out_right.swap(r0);
+  c->out_cap = need;
+  c->out_n = 0;
+  (void)k0.release(), (void)c0.release(), (void)l0.release(), (void)r0.release();  // the old arrays, keys first as ever
+  return KC_OK;
 }
 
 // S7/S8 over the global table, appended to the result arrays at ctrs[CTR_OUT]
@@ -2821,9 +2681,7 @@ static int bk_finalize(kc_ctx *c) {
     block = 64;
     while (block < 8192u && (uint64_t)block * 2 * max_wg * 4 <= cap) block *= 2;
   }
-  if (block && !c->d_out_plan) {
-    HIPCHK(hipMalloc((void **)&c->d_out_plan, (PLAN_WORDS + 4 * (size_t)max_wg) * 8));
-  }
+  if (block) KCTRY(c->d_out_plan.reserve((PLAN_WORDS + 4 * (size_t)max_wg) * 8));
   // a workgroup holds at most two blocks that are not full, each a multiple of `block` that covers a region table
   const uint64_t slack = block ? 2 * (((uint64_t)c->gm.S + block - 1) / block * block) * max_wg : 0;
   cap += slack;
@@ -2922,9 +2780,7 @@ extern "C" int kc_finalize(kc_ctx *c, kc_result *out) {
       if (rc) return rc;
     }
     if (c->nl != c->nl_ext) {  // k % 32 in {30, 31}: the caller sees the reference's width
-      if (c->d_out_keys_ext) HIPCHK(hipFree(c->d_out_keys_ext));
-      c->d_out_keys_ext = nullptr;
-      HIPCHK(hipMalloc((void **)&c->d_out_keys_ext, std::max<uint64_t>(c->out_n, 1) * c->nl_ext * 8));
+      KCTRY(c->d_out_keys_ext.reserve(std::max<uint64_t>(c->out_n, 1) * c->nl_ext * 8));
       if (c->out_n) {
         hipLaunchKernelGGL(kc_rewidth_keys_kernel, dim3((unsigned)((c->out_n + 255) / 256)), dim3(256), 0, c->stream, c->d_out_keys,
                            c->d_out_keys_ext, c->out_n, c->nl, c->nl_ext);
@@ -2969,104 +2825,83 @@ extern "C" int kc_copy_results_entries(kc_ctx *c, uint64_t *keys, kc_count_exts 
   static_assert(sizeof(kc_count_exts) == 8, "kc_count_exts is one 8-byte word");
   if (!c) return KC_ERR_INVALID_ARG;
   if (!c->finalized) return KC_ERR_STATE;
-  HIPCHK(hipSetDevice(c->cfg.device));
   const uint64_t n = c->out_n;
-  if (!n) return KC_OK;
-  if (keys) HIPCHK(hipMemcpy(keys, c->nl != c->nl_ext ? c->d_out_keys_ext : c->d_out_keys, n * c->nl_ext * 8, hipMemcpyDeviceToHost));
-  if (vals) {
-    uint64_t *d_vals = nullptr;
-    HIPCHK(hipMalloc((void **)&d_vals, n * 8));
-    hipLaunchKernelGGL(kc_pack_count_exts_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->d_out_counts, c->d_out_left,
-                       c->d_out_right, n, d_vals);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess) e = hipMemcpy(vals, d_vals, n * 8, hipMemcpyDeviceToHost);
-    (void)hipFree(d_vals);
-    if (e != hipSuccess) return hip_fail(e, "kc_copy_results_entries", __LINE__);
-  }
-  return KC_OK;
+  return call_with_bufs(c, [&](CallBufs &b) {
+    if (!n) return (int)KC_OK;
+    if (keys) HIPCHK(hipMemcpy(keys, c->nl != c->nl_ext ? c->d_out_keys_ext : c->d_out_keys, n * c->nl_ext * 8, hipMemcpyDeviceToHost));
+    if (vals) {
+      uint64_t *d_vals;
+      KCTRY(b.alloc(&d_vals, n * 8));
+      hipLaunchKernelGGL(kc_pack_count_exts_kernel, blocks_for(n), dim3(256), 0, c->stream, c->d_out_counts, c->d_out_left, c->d_out_right, n,
+                         d_vals);
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipStreamSynchronize(c->stream));
+      HIPCHK(hipMemcpy(vals, d_vals, n * 8, hipMemcpyDeviceToHost));
+    }
+    return (int)KC_OK;
+  });
 }
 
 // n keys from a device array of the library's width to a host array of the reference's width
-static int keys_to_host(kc_ctx *c, uint64_t *h_dst, const uint64_t *d_src, uint64_t n) {
+static int keys_to_host(kc_ctx *c, CallBufs &b, uint64_t *h_dst, const uint64_t *d_src, uint64_t n) {
   if (!n) return KC_OK;
-  if (c->nl == c->nl_ext) {
-    HIPCHK(hipMemcpy(h_dst, d_src, n * c->nl * 8, hipMemcpyDeviceToHost));
-    return KC_OK;
+  if (c->nl != c->nl_ext) {
+    uint64_t *tmp;
+    KCTRY(b.alloc(&tmp, n * c->nl_ext * 8));
+    hipLaunchKernelGGL(kc_rewidth_keys_kernel, blocks_for(n), dim3(256), 0, c->stream, d_src, tmp, n, c->nl, c->nl_ext);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->stream));
+    d_src = tmp;
   }
-  uint64_t *tmp = nullptr;
-  HIPCHK(hipMalloc((void **)&tmp, n * c->nl_ext * 8));
-  hipLaunchKernelGGL(kc_rewidth_keys_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, d_src, tmp, n, c->nl, c->nl_ext);
-  hipError_t e = hipStreamSynchronize(c->stream);
-  if (e == hipSuccess) e = hipMemcpy(h_dst, tmp, n * c->nl_ext * 8, hipMemcpyDeviceToHost);
-  (void)hipFree(tmp);
-  if (e != hipSuccess) return hip_fail(e, "keys_to_host", __LINE__);
+  HIPCHK(hipMemcpy(h_dst, d_src, n * c->nl_ext * 8, hipMemcpyDeviceToHost));
   return KC_OK;
 }
 
 extern "C" int kc_dump_table(kc_ctx *c, uint64_t *keys, uint16_t *counts, uint16_t *exts, uint64_t *n_out) {
   if (!c || !n_out) return KC_ERR_INVALID_ARG;
-  HIPCHK(hipSetDevice(c->cfg.device));
-  int rc = sync_ctrs(c);
-  if (rc) return rc;
-  if (c->h_ctrs[CTR_BAD_BASE]) return KC_ERR_BAD_BASE;
-  uint64_t *rk = nullptr;
-  uint16_t *rc16 = nullptr, *re = nullptr;
-  uint64_t nreg = 0;
-  if (c->bk_ready && !c->table_mode && c->bk_spilled) {  // one k-mer, one entry: what is buffered joins the table first
-    rc = bk_spill_pass(c);
-    if (rc) return rc;
-    rc = sync_ctrs(c);
-    if (rc) return rc;
-  } else if (c->bk_ready && !c->table_mode) {
-    rc = bk_dump(c, &rk, &rc16, &re, &nreg);
-    if (rc) return rc;
-    rc = sync_ctrs(c);
-    if (rc) return rc;
-  }
-  const uint64_t ntab = c->h_ctrs[CTR_ENTRIES];
-  const uint64_t n = nreg + ntab;
-  *n_out = n;
-  if (!keys || !n) {
-    if (rk) (void)hipFree(rk);
-    if (rc16) (void)hipFree(rc16);
-    if (re) (void)hipFree(re);
-    return KC_OK;
-  }
-  if (nreg) {
-    rc = keys_to_host(c, keys, rk, nreg);
-    if (rc) return rc;
-    HIPCHK(hipMemcpy(counts, rc16, nreg * 2, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(exts, re, nreg * 16, hipMemcpyDeviceToHost));
-    (void)hipFree(rk);
-    (void)hipFree(rc16);
-    (void)hipFree(re);
-  }
-  if (ntab) {
-    uint64_t *dk = nullptr, *dcur = nullptr;
-    uint16_t *dc = nullptr, *de = nullptr;
-    HIPCHK(hipMalloc((void **)&dk, ntab * c->nl * 8));
-    HIPCHK(hipMalloc((void **)&dc, ntab * 2));
-    HIPCHK(hipMalloc((void **)&de, ntab * 16));
-    HIPCHK(hipMalloc((void **)&dcur, 8));
-    HIPCHK(hipMemsetAsync(dcur, 0, 8, c->stream));
-    const unsigned nblk = (unsigned)((c->capacity + 255) / 256);
-    with_nl(c, [&](auto nl) {
-      hipLaunchKernelGGL(kc_dump_kernel<nl>, dim3(nblk), dim3(256), 0, c->stream, c->table, c->capacity, dk, dc, de, dcur);
-    });
-    c->num_gpu_calls++;
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(c->stream));
-    rc = keys_to_host(c, keys + nreg * c->nl_ext, dk, ntab);
-    if (rc) return rc;
-    HIPCHK(hipMemcpy(counts + nreg, dc, ntab * 2, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(exts + nreg * 8, de, ntab * 16, hipMemcpyDeviceToHost));
-    (void)hipFree(dk);
-    (void)hipFree(dc);
-    (void)hipFree(de);
-    (void)hipFree(dcur);
-  }
-  return KC_OK;
+  return call_with_bufs(c, [&](CallBufs &b) {
+    KCTRY(sync_ctrs(c));
+    if (c->h_ctrs[CTR_BAD_BASE]) return (int)KC_ERR_BAD_BASE;
+    uint64_t *rk = nullptr;
+    uint16_t *rc16 = nullptr, *re = nullptr;
+    uint64_t nreg = 0;
+    if (c->bk_ready && !c->table_mode && c->bk_spilled) {  // one k-mer, one entry: what is buffered joins the table first
+      KCTRY(bk_spill_pass(c));
+      KCTRY(sync_ctrs(c));
+    } else if (c->bk_ready && !c->table_mode) {
+      KCTRY(bk_dump(c, b, &rk, &rc16, &re, &nreg));
+      KCTRY(sync_ctrs(c));
+    }
+    const uint64_t ntab = c->h_ctrs[CTR_ENTRIES];
+    const uint64_t n = nreg + ntab;
+    *n_out = n;
+    if (!keys || !n) return (int)KC_OK;
+    if (nreg) {
+      KCTRY(keys_to_host(c, b, keys, rk, nreg));
+      HIPCHK(hipMemcpy(counts, rc16, nreg * 2, hipMemcpyDeviceToHost));
+      HIPCHK(hipMemcpy(exts, re, nreg * 16, hipMemcpyDeviceToHost));
+      b.release();  // the regions' entries have arrived: their arrays go before the table's are made
+    }
+    if (ntab) {
+      uint64_t *dk, *dcur;
+      uint16_t *dc, *de;
+      KCTRY(b.alloc(&dk, ntab * c->nl * 8));
+      KCTRY(b.alloc(&dc, ntab * 2));
+      KCTRY(b.alloc(&de, ntab * 16));
+      KCTRY(b.alloc(&dcur, 8));
+      HIPCHK(hipMemsetAsync(dcur, 0, 8, c->stream));
+      with_nl(c, [&](auto nl) {
+        hipLaunchKernelGGL(kc_dump_kernel<nl>, blocks_for(c->capacity), dim3(256), 0, c->stream, c->table, c->capacity, dk, dc, de, dcur);
+      });
+      c->num_gpu_calls++;
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipStreamSynchronize(c->stream));
+      KCTRY(keys_to_host(c, b, keys + nreg * c->nl_ext, dk, ntab));
+      HIPCHK(hipMemcpy(counts + nreg, dc, ntab * 2, hipMemcpyDeviceToHost));
+      HIPCHK(hipMemcpy(exts + nreg * 8, de, ntab * 16, hipMemcpyDeviceToHost));
+    }
+    return (int)KC_OK;
+  });
 }
 
 extern "C" int kc_get_stats(kc_ctx *c, kc_stats *o) {
@@ -3086,7 +2921,7 @@ extern "C" int kc_get_stats(kc_ctx *c, kc_stats *o) {
   o->num_dropped = 0;
   o->capacity = c->capacity;
   o->num_gpu_calls = c->num_gpu_calls;
-  o->table_bytes = c->arena_bytes + c->bk_bytes;
+  o->table_bytes = c->arena.cap + c->bk_bytes;
   return KC_OK;
 }
 
@@ -3113,7 +2948,7 @@ static int ensure_index(kc_ctx *c) {
       return KC_ERR_CAPACITY;
     }
     uint64_t cap = next_pow2(std::max<uint64_t>(1024, c->out_n * 2));
-    HIPCHK(hipMalloc((void **)&c->d_index, cap * 4));
+    KCTRY(c->d_index.reserve(cap * 4));
     c->index_cap = cap;
     HIPCHK(hipMemsetAsync(c->d_index, 0, cap * 4, c->stream));
     if (c->out_n) {
@@ -3142,39 +2977,37 @@ static int lookup_t(kc_ctx *c, const uint64_t *dq, uint64_t nq, uint16_t *dc, ui
 extern "C" int kc_lookup(kc_ctx *c, const uint64_t *queries, uint64_t nq, int on_device, uint16_t *counts, uint8_t *left, uint8_t *right) {
   if (!c || (nq && (!queries || !counts))) return KC_ERR_INVALID_ARG;
   if (!c->finalized) return KC_ERR_STATE;
-  HIPCHK(hipSetDevice(c->cfg.device));
-  const uint64_t *dq = queries;
-  uint64_t *sq = nullptr;
-  uint16_t *dc = counts;
-  uint8_t *dl = left, *dr = right;
-  uint64_t *wq = nullptr;  // the queries at the library's width, where that differs from the caller's
-  if (!on_device && nq) {
-    HIPCHK(hipMalloc((void **)&sq, nq * c->nl_ext * 8 + nq * 4));
-    HIPCHK(hipMemcpyAsync(sq, queries, nq * c->nl_ext * 8, hipMemcpyHostToDevice, c->stream));
-    dq = sq;
-    dc = (uint16_t *)(sq + nq * c->nl_ext);
-    dl = (uint8_t *)(dc + nq);
-    dr = dl + nq;
-  }
-  if (c->nl != c->nl_ext && nq) {
-    HIPCHK(hipMalloc((void **)&wq, nq * c->nl * 8));
-    hipLaunchKernelGGL(kc_rewidth_keys_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, c->stream, dq, wq, nq, c->nl_ext, c->nl);
-    HIPCHK(hipGetLastError());
-    dq = wq;
-  }
-  int rc = with_nl(c, [&](auto nl) { return lookup_t<nl>(c, dq, nq, dc, dl, dr); });
-  if (!rc && !on_device && nq) {
-    HIPCHK(hipStreamSynchronize(c->stream));
-    HIPCHK(hipMemcpy(counts, dc, nq * 2, hipMemcpyDeviceToHost));
-    if (left) HIPCHK(hipMemcpy(left, dl, nq, hipMemcpyDeviceToHost));
-    if (right) HIPCHK(hipMemcpy(right, dr, nq, hipMemcpyDeviceToHost));
-  }
-  if (wq) {
-    (void)hipStreamSynchronize(c->stream);
-    (void)hipFree(wq);
-  }
-  if (sq) (void)hipFree(sq);
-  return rc;
+  return call_with_bufs(c, [&](CallBufs &b) {
+    const uint64_t *dq = queries;
+    uint16_t *dc = counts;
+    uint8_t *dl = left, *dr = right;
+    if (!on_device && nq) {  // the queries, and behind them the answers
+      uint64_t *sq;
+      KCTRY(b.alloc(&sq, nq * c->nl_ext * 8 + nq * 4));
+      HIPCHK(hipMemcpyAsync(sq, queries, nq * c->nl_ext * 8, hipMemcpyHostToDevice, c->stream));
+      dq = sq;
+      dc = (uint16_t *)(sq + nq * c->nl_ext);
+      dl = (uint8_t *)(dc + nq);
+      dr = dl + nq;
+    }
+    if (c->nl != c->nl_ext && nq) {  // the queries at the library's width, where that differs from the caller's
+      uint64_t *wq;
+      KCTRY(b.alloc(&wq, nq * c->nl * 8));
+      hipLaunchKernelGGL(kc_rewidth_keys_kernel, blocks_for(nq), dim3(256), 0, c->stream, dq, wq, nq, c->nl_ext, c->nl);
+      HIPCHK(hipGetLastError());
+      dq = wq;
+    }
+    KCTRY(with_nl(c, [&](auto nl) { return lookup_t<nl>(c, dq, nq, dc, dl, dr); }));
+    if (!on_device && nq) {
+      HIPCHK(hipStreamSynchronize(c->stream));
+      HIPCHK(hipMemcpy(counts, dc, nq * 2, hipMemcpyDeviceToHost));
+      if (left) HIPCHK(hipMemcpy(left, dl, nq, hipMemcpyDeviceToHost));
+      if (right) HIPCHK(hipMemcpy(right, dr, nq, hipMemcpyDeviceToHost));
+    } else if (c->nl != c->nl_ext && nq) {
+      HIPCHK(hipStreamSynchronize(c->stream));  // the lookup has read the widened queries
+    }
+    return (int)KC_OK;
+  });
 }
 
 #include "kc_api_call.hpp"  // what the entry points below share
@@ -3196,9 +3029,11 @@ extern "C" int kc_begin_ctg_kmers(kc_ctx *c, uint64_t max_ctg_kmers) {
   HIPCHK(hipSetDevice(c->cfg.device));
   free_ctg(c);
   const uint64_t cap = next_pow2(std::max<uint64_t>(1024, 2 * max_ctg_kmers));
-  HIPCHK(hipMalloc((void **)&c->ctg_table.keys, cap * (size_t)c->nl * 8));
-  HIPCHK(hipMalloc((void **)&c->ctg_table.vals, cap * 2 * 4));
-  HIPCHK(hipMalloc((void **)&c->d_ctg_status, 4 * 8));
+  KCTRY(c->ctg_keys.reserve(cap * (size_t)c->nl * 8));
+  KCTRY(c->ctg_vals.reserve(cap * 2 * 4));
+  KCTRY(c->d_ctg_status.reserve(4 * 8));
+  c->ctg_table.keys = c->ctg_keys;
+  c->ctg_table.vals = c->ctg_vals;
   HIPCHK(hipMemsetAsync(c->ctg_table.keys, 0xFF, cap * (size_t)c->nl * 8, c->stream));
   HIPCHK(hipMemsetAsync(c->ctg_table.vals, 0, cap * 2 * 4, c->stream));
   HIPCHK(hipMemsetAsync(c->d_ctg_status, 0, 4 * 8, c->stream));
@@ -3211,75 +3046,68 @@ extern "C" int kc_submit_ctg_block(kc_ctx *c, const char *seqs, const uint16_t *
   if (!c || (len && (!seqs || !depths))) return KC_ERR_INVALID_ARG;
   if (c->finalized || !c->ctg_table.keys) return KC_ERR_STATE;  // kc_begin_ctg_kmers first
   if (!len) return KC_OK;
-  HIPCHK(hipSetDevice(c->cfg.device));
-  const uint8_t *d_seqs = reinterpret_cast<const uint8_t *>(seqs);
-  const uint16_t *d_depths = depths;
-  uint8_t *tmp = nullptr;
-  if (!on_device) {
-    HIPCHK(hipMalloc((void **)&tmp, len * 3 + 16));
-    HIPCHK(hipMemcpyAsync(tmp, seqs, len, hipMemcpyHostToDevice, c->stream));
-    uint16_t *td = reinterpret_cast<uint16_t *>(tmp + ((len + 15) & ~(uint64_t)15));
-    HIPCHK(hipMemcpyAsync(td, depths, len * 2, hipMemcpyHostToDevice, c->stream));
-    d_seqs = tmp;
-    d_depths = td;
-  }
-  // which k-mers this context keeps: everything as one rank; as one of several, what the read path keeps there
-  CtgOwn own;
-  memset(&own, 0, sizeof(own));
-  own.mode = CTG_OWN_ALL;
-  own.rank_me = (uint32_t)c->cfg.rank_me;
-  own.rank_n = (uint32_t)c->cfg.rank_n;
-  int rc = KC_OK;
-  if (c->cfg.rank_n > 1) {
-    if (c->sh.flow || (c->cfg.flags & KC_FLAG_SHARD_BUCKETS)) {  // the shard flow: the owner of the k-mer's level-1 bucket
-      rc = bk_active(c) ? bk_init(c) : KC_ERR_STATE;
-      own.mode = CTG_OWN_BUCKET;
-      own.gm = c->gm;
-      own.own_lo = shard_first_bucket((uint32_t)c->cfg.rank_me, c->gm.P1, (uint32_t)c->cfg.rank_n);
-      own.own_hi = shard_first_bucket((uint32_t)c->cfg.rank_me + 1, c->gm.P1, (uint32_t)c->cfg.rank_n);
-    } else {
-      if ((c->cfg.flags & KC_FLAG_WIRE_UNITS) && bk_active(c)) rc = bk_init(c);  // the geometry decides (kc_partition_owner)
-      if (c->wire6) {  // the records flow with wire units: the owner kc_extract_partition sends the k-mer to
-        own.mode = CTG_OWN_WIRE6;
+  return call_with_bufs(c, [&](CallBufs &b) {
+    const uint8_t *d_seqs = reinterpret_cast<const uint8_t *>(seqs);
+    const uint16_t *d_depths = depths;
+    if (!on_device) {
+      uint8_t *tmp;
+      KCTRY(b.alloc(&tmp, len * 3 + 16));
+      HIPCHK(hipMemcpyAsync(tmp, seqs, len, hipMemcpyHostToDevice, c->stream));
+      uint16_t *td = reinterpret_cast<uint16_t *>(tmp + ((len + 15) & ~(uint64_t)15));
+      HIPCHK(hipMemcpyAsync(td, depths, len * 2, hipMemcpyHostToDevice, c->stream));
+      d_seqs = tmp;
+      d_depths = td;
+    }
+    // which k-mers this context keeps: everything as one rank; as one of several, what the read path keeps there
+    CtgOwn own;
+    memset(&own, 0, sizeof(own));
+    own.mode = CTG_OWN_ALL;
+    own.rank_me = (uint32_t)c->cfg.rank_me;
+    own.rank_n = (uint32_t)c->cfg.rank_n;
+    if (c->cfg.rank_n > 1) {
+      if (c->sh.flow || (c->cfg.flags & KC_FLAG_SHARD_BUCKETS)) {  // the shard flow: the owner of the k-mer's level-1 bucket
+        KCTRY(bk_active(c) ? bk_init(c) : KC_ERR_STATE);
+        own.mode = CTG_OWN_BUCKET;
         own.gm = c->gm;
+        own.own_lo = shard_first_bucket((uint32_t)c->cfg.rank_me, c->gm.P1, (uint32_t)c->cfg.rank_n);
+        own.own_hi = shard_first_bucket((uint32_t)c->cfg.rank_me + 1, c->gm.P1, (uint32_t)c->cfg.rank_n);
       } else {
-        own.mode = (c->cfg.flags & KC_FLAG_REFERENCE_OWNER) ? CTG_OWN_REFERENCE : CTG_OWN_HASH;
+        if ((c->cfg.flags & KC_FLAG_WIRE_UNITS) && bk_active(c)) KCTRY(bk_init(c));  // the geometry decides (kc_partition_owner)
+        if (c->wire6) {  // the records flow with wire units: the owner kc_extract_partition sends the k-mer to
+          own.mode = CTG_OWN_WIRE6;
+          own.gm = c->gm;
+        } else {
+          own.mode = (c->cfg.flags & KC_FLAG_REFERENCE_OWNER) ? CTG_OWN_REFERENCE : CTG_OWN_HASH;
+        }
       }
     }
-  }
-  // A launch may add as many distinct k-mers as it has positions: it gets no more positions than the table has room for
-  // below three quarters, so that a probe always ends at an empty slot (an estimate that is too low -- the driver passes
-  // the reference's -- must end in KC_ERR_CAPACITY, not in a kernel that never returns).
-  hipError_t e = hipSuccess;
-  uint64_t st[2] = {0, c->ctg_new};
-  for (uint64_t p0 = 0; rc == KC_OK && p0 < len;) {
-    const uint64_t limit = c->ctg_cap / 4 * 3;
-    if (st[1] >= limit) {
-      snprintf(g_last_error, sizeof(g_last_error), "contig pass: %llu distinct k-mers fill the table kc_begin_ctg_kmers made (%llu slots)",
-               (unsigned long long)st[1], (unsigned long long)c->ctg_cap);
-      rc = KC_ERR_CAPACITY;
-      break;
+    // A launch may add as many distinct k-mers as it has positions: it gets no more positions than the table has room for
+    // below three quarters, so that a probe always ends at an empty slot (an estimate that is too low -- the driver passes
+    // the reference's -- must end in KC_ERR_CAPACITY, not in a kernel that never returns).
+    uint64_t st[2] = {0, c->ctg_new};
+    for (uint64_t p0 = 0; p0 < len;) {
+      const uint64_t limit = c->ctg_cap / 4 * 3;
+      if (st[1] >= limit) {
+        snprintf(g_last_error, sizeof(g_last_error), "contig pass: %llu distinct k-mers fill the table kc_begin_ctg_kmers made (%llu slots)",
+                 (unsigned long long)st[1], (unsigned long long)c->ctg_cap);
+        return (int)KC_ERR_CAPACITY;
+      }
+      const uint64_t p1 = std::min<uint64_t>(len, p0 + (limit - st[1]));
+      const unsigned nblk = (unsigned)((p1 - p0 + 255) / 256);
+      with_nl(c, [&](auto nl) {
+        hipLaunchKernelGGL(kc_ctg_insert_kernel<nl>, dim3(nblk), dim3(256), 0, c->stream, d_seqs, d_depths, p0, p1, len, c->k, c->ctg_table,
+                           c->d_ctg_status, own);
+      });
+      c->num_gpu_calls++;
+      HIPCHK(hipGetLastError());
+      KCTRY(read_back(c, st, c->d_ctg_status));
+      c->ctg_new = st[1];
+      p0 = p1;
     }
-    const uint64_t p1 = std::min<uint64_t>(len, p0 + (limit - st[1]));
-    const unsigned nblk = (unsigned)((p1 - p0 + 255) / 256);
-    with_nl(c, [&](auto nl) {
-      hipLaunchKernelGGL(kc_ctg_insert_kernel<nl>, dim3(nblk), dim3(256), 0, c->stream, d_seqs, d_depths, p0, p1, len, c->k, c->ctg_table,
-                         c->d_ctg_status, own);
-    });
-    c->num_gpu_calls++;
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(st, c->d_ctg_status, 16, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) break;
-    c->ctg_new = st[1];
-    p0 = p1;
-  }
-  if (tmp) (void)hipFree(tmp);
-  if (e != hipSuccess) return hip_fail(e, "kc_submit_ctg_block", __LINE__);
-  if (rc) return rc;
-  if (st[0]) return KC_ERR_BAD_BASE;
-  c->ctg_attempted += len;
-  return KC_OK;
+    if (st[0]) return (int)KC_ERR_BAD_BASE;
+    c->ctg_attempted += len;
+    return (int)KC_OK;
+  });
 }
 
 extern "C" int kc_arena_probe_rate(kc_ctx *c, double *tbps) {
@@ -3316,11 +3144,11 @@ static int ctg_merge_t(kc_ctx *c) {
     if (pass == 0) {
       if (got[0] == n_res) return KC_OK;  // nothing to add
       // (the index stays valid: it points at the first n_res entries, which keep their places)
-      uint32_t *index = c->d_index;
+      Dev<uint32_t> index;
       const uint64_t icap = c->index_cap;
-      c->d_index = nullptr;
+      index.swap(c->d_index);
       rc = grow_results(c, got[0], n_res);
-      c->d_index = index;
+      index.swap(c->d_index);
       c->index_cap = icap;
       if (rc) return rc;
       c->out_n = n_res;
@@ -3455,16 +3283,11 @@ extern "C" int kc_synth_reads_device(kc_ctx *c, const kc_synth_params *p, uint64
     delete t;
     return rc;
   }
-  if (!c->d_synth) {
-    hipError_t e = hipMalloc((void **)&c->d_synth, sizeof(kc_synth_table));
-    if (e != hipSuccess) {
-      delete t;
-      return hip_fail(e, "hipMalloc(synth table)", __LINE__);
-    }
-  }
-  hipError_t e = hipMemcpy(c->d_synth, t, sizeof(kc_synth_table), hipMemcpyHostToDevice);
+  rc = c->d_synth.reserve(sizeof(kc_synth_table));
+  const hipError_t e = rc ? hipSuccess : hipMemcpy(c->d_synth, t, sizeof(kc_synth_table), hipMemcpyHostToDevice);
   delete t;
-  if (e != hipSuccess) return hip_fail(e, "hipMemcpy(synth table)", __LINE__);
+  if (rc) return rc;
+  if (e != hipSuccess) return HIP_FAIL(e, "hipMemcpy(synth table)");
   const uint64_t nquads = nreads * ((p->read_len + 3) / 4);
   unsigned nblk = (unsigned)std::min<uint64_t>((nquads + 255) / 256, 256 * 64);
   if (!nblk) nblk = 1;

@@ -95,8 +95,7 @@ extern "C" int kc_ctg_index_build(kc_ctx *c, const uint8_t *seqs, uint64_t nbyte
     KCTRY(with_nl(c, [&](auto nl) { return ctg_index_run<nl>(c, b, seqs, nbytes, offsets, n_ctgs, on_device, ix, stats); }));
     // only now: had it failed, the earlier index, if any, would answer as before
     free_align_index(c);
-    c->d_ai = (uint8_t *)ix.slots;  // the table is the front of the index's allocation, which the context keeps
-    b.disown(c->d_ai);
+    b.hand_over(ix.slots, c->d_ai);  // the table is the front of the index's allocation, which the context keeps
     c->ai = ix;
     c->ai_nbytes = nbytes;
     c->ai_ready = true;

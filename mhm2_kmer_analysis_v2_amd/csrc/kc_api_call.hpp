@@ -1,8 +1,6 @@
-// kc_api_call.hpp -- what the contig pass's entry points share on the host: the owner of a call's device memory and the
-// call's frame, arrays that come from the host or the device, reads back from the device, the checks on reads, records
-// and pairs, the two-level scan.  Part of kc_api.hip's translation unit, ahead of kc_api_sort.hpp.
-
-static dim3 blocks_for(uint64_t n, unsigned tpb = 256) { return dim3((unsigned)((n + tpb - 1) / tpb)); }
+// kc_api_call.hpp -- what the contig pass's entry points share on the host beyond kc_api_mem.hpp: the reads a host caller
+// passes, the checks on reads, records and pairs, the two-level scan.  Part of kc_api.hip's translation unit, ahead of
+// kc_api_sort.hpp.
 
 static int no_ctg_index(const char *who) {
   snprintf(g_last_error, sizeof(g_last_error), "%s: no contig index (kc_ctg_index_build)", who);
@@ -14,86 +12,10 @@ static int misaligned_records(const char *who) {
   return KC_ERR_INVALID_ARG;
 }
 
-// ---- a call's device memory ------------------------------------------------------------------------------------------
-// The allocations a call holds until it returns.
-struct CallBufs {
-  std::vector<void *> held;
-  // *p: `bytes` of device memory, or nullptr for none
-  template <class T> int alloc(T **p, size_t bytes) {
-    *p = nullptr;
-    if (!bytes) return KC_OK;
-    HIPCHK(hipMalloc((void **)p, bytes));
-    held.push_back(*p);
-    return KC_OK;
-  }
-  // one allocation for a Carver layout: the layout runs on nullptr for the size and on the allocation for the pointers, so
-  // it sets every pointer in either run and reads none that the first run left
-  template <class L> int carve(L &&layout) {
-    uint8_t *base;
-    KCTRY(alloc(&base, layout((uint8_t *)nullptr)));
-    layout(base);
-    return KC_OK;
-  }
-  // the caller keeps p beyond the call
-  void disown(void *p) { held.erase(std::remove(held.begin(), held.end(), p), held.end()); }
-  void release() {
-    for (void *p : held) (void)hipFree(p);
-    held.clear();
-  }
-};
-
-// The frame of an entry point behind its host-side checks: body(CallBufs &) runs on the context's device; if it fails the
-// stream is drained before the memory goes, so that no kernel still runs in it.
-template <class F> static int call_with_bufs(kc_ctx *c, F &&body) {
-  HIPCHK(hipSetDevice(c->cfg.device));
-  CallBufs b;
-  const int rc = body(b);
-  if (rc) (void)hipStreamSynchronize(c->stream);
-  b.release();
-  return rc;
-}
-
-// ---- arrays that are the host's or the device's ----------------------------------------------------------------------
-// An input of `bytes` bytes as the kernels read it (d).  A device caller's array is read where it is; a host caller's gets
-// room in the layout that calls reserve() and is copied there by upload() (`filled` false: there is nothing to copy).
-template <class D> struct StagedIn {
-  const void *src;
-  bool dev;
-  size_t bytes;
-  bool filled;
-  D *d;
-  StagedIn(const void *src_, bool dev_, size_t bytes_, bool filled_ = true)
-      : src(src_), dev(dev_), bytes(bytes_), filled(filled_), d(dev_ ? (D *)const_cast<void *>(src_) : nullptr) {}
-  void reserve(Carver &m, bool want = true) {
-    if (!dev && want) d = m.take<D>(bytes / sizeof(D));
-  }
-  int upload(kc_ctx *c) const {
-    if (!dev && d && filled && bytes) HIPCHK(hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, c->stream));
-    return KC_OK;
-  }
-};
-
 // the reads' nreads + 1 offsets: no reads, nothing to copy
 static StagedIn<uint64_t> staged_offsets(const uint64_t *offsets, uint64_t nreads, bool dev) {
   return {offsets, dev, (size_t)(nreads + 1) * 8, nreads != 0};
 }
-
-// An optional output of `bytes` bytes as the kernels write it (d): nullptr where the caller passed none or the call's
-// results do not fit.  A device caller's array is written where it is; a host caller's gets room in the layout that calls
-// reserve() and is copied out by download(), which the caller's stream synchronisation completes.
-template <class D> struct StagedOut {
-  void *dst;
-  bool dev;
-  size_t bytes;
-  D *d = nullptr;
-  void reserve(Carver &m, bool fits = true) {
-    if (dst && fits) d = dev ? (D *)dst : m.take<D>(bytes / sizeof(D));
-  }
-  int download(kc_ctx *c) const {
-    if (!dev && dst && d && bytes) HIPCHK(hipMemcpyAsync(dst, d, bytes, hipMemcpyDeviceToHost, c->stream));
-    return KC_OK;
-  }
-};
 
 // A host caller's read bytes in an allocation of their own, made once the lengths are checked so that no unchecked offset
 // sizes it: the reads are the first `last` bytes.
@@ -104,16 +26,6 @@ static int upload_reads(kc_ctx *c, CallBufs &b, const uint8_t *bases, uint64_t l
   *d_bases = p;
   return KC_OK;
 }
-
-// ---- reads back from the device ----------------------------------------------------------------------------------------
-// n words to the host, and the stream drained: copies queued before it arrive with it
-static int read_back(kc_ctx *c, uint64_t *h, const uint64_t *d, size_t n) {
-  HIPCHK(hipMemcpyAsync(h, d, n * 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return KC_OK;
-}
-
-template <size_t N> static int read_back(kc_ctx *c, uint64_t (&h)[N], const uint64_t *d) { return read_back(c, h, d, N); }
 
 // The verdict of a check kernel that leaves the lowest bad index in *d_bad (all ones: none).  fmt starts with %s for `who`
 // and %llu for the index; `more` are what else it takes.

@@ -648,8 +648,7 @@ extern "C" int kc_adapters_clear(kc_ctx *c) {
   if (!c) return KC_ERR_INVALID_ARG;
   HIPCHK(hipSetDevice(c->cfg.device));
   HIPCHK(hipStreamSynchronize(c->stream));
-  if (c->d_ad) HIPCHK(hipFree(c->d_ad));
-  c->d_ad = nullptr;
+  HIPCHK(c->d_ad.release());
   c->ad_recs = c->ad_ent_off = nullptr;
   c->ad_bytes = nullptr;
   c->ad_loaded = false;
@@ -696,8 +695,8 @@ extern "C" int kc_adapters_load(kc_ctx *c, const char *text, uint64_t len, int a
     return m.used;
   };
   KCTRY(kc_adapters_clear(c));  // loading again replaces the set
-  HIPCHK(hipMalloc((void **)&c->d_ad, layout(nullptr)));
-  layout(c->d_ad);
+  KCTRY(c->d_ad.reserve(layout(nullptr)));
+  layout(c->d_ad.p);
   HIPCHK(hipMemcpy(d_slots, slots.data(), slots.size() * sizeof(TrSlot), hipMemcpyHostToDevice));
   if (!recs.empty()) HIPCHK(hipMemcpy(d_recs, recs.data(), recs.size() * 4, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(d_ent, ent_off.data(), ent_off.size() * 4, hipMemcpyHostToDevice));
@@ -754,7 +753,7 @@ extern "C" int kc_trim_adapters(kc_ctx *c, const uint8_t *bases, const uint8_t *
   a.gap_open = c->ad_blastn ? 5 : 1;
   a.gap_ext = c->ad_blastn ? 2 : 1;
   a.amb = 1;
-  a.slots = (const TrSlot *)c->d_ad;
+  a.slots = c->d_ad.as<const TrSlot>();
   a.lg_slots = c->ad_lg_slots;
   a.slot_mask = (1u << c->ad_lg_slots) - 1u;
   a.recs = c->ad_recs;

@@ -15,31 +15,23 @@ static std::vector<SortPass> sort_passes(int k, int nl_ext) {
   return v;
 }
 
-// what a call of kc_sort_results holds until it has succeeded: the fresh arrays and the scratch
-struct SortBufs {
-  uint64_t *keys = nullptr, *ext = nullptr;
-  uint16_t *counts = nullptr;
-  uint8_t *left = nullptr, *right = nullptr;
-  uint8_t *scratch = nullptr;
-  void release() {
-    for (void *p : {(void *)keys, (void *)ext, (void *)counts, (void *)left, (void *)right, (void *)scratch})
-      if (p) (void)hipFree(p);
-    keys = ext = nullptr;
-    counts = nullptr;
-    left = right = scratch = nullptr;
-  }
+// the results in key order in fresh arrays of the call's (ext: the keys at the reference's width, where that differs)
+struct Sorted {
+  uint64_t *keys, *ext;
+  uint16_t *counts;
+  uint8_t *left, *right;
 };
 
-static int sort_run(kc_ctx *c, SortBufs &b) {
+static int sort_run(kc_ctx *c, CallBufs &cb, Sorted &b) {
   const uint64_t n = c->out_n;
   const uint64_t ntiles = (n + SORT_TILE - 1) / SORT_TILE;
   const uint64_t ncnt = ntiles * SORT_DIGITS;
   const bool two = c->nl != c->nl_ext;
-  HIPCHK(hipMalloc((void **)&b.keys, n * c->nl * 8));
-  if (two) HIPCHK(hipMalloc((void **)&b.ext, n * c->nl_ext * 8));
-  HIPCHK(hipMalloc((void **)&b.counts, n * 2));
-  HIPCHK(hipMalloc((void **)&b.left, n));
-  HIPCHK(hipMalloc((void **)&b.right, n));
+  KCTRY(cb.alloc(&b.keys, n * c->nl * 8));
+  KCTRY(cb.alloc(&b.ext, two ? n * c->nl_ext * 8 : 0));
+  KCTRY(cb.alloc(&b.counts, n * 2));
+  KCTRY(cb.alloc(&b.left, n));
+  KCTRY(cb.alloc(&b.right, n));
   uint64_t *kbuf[2], *cnt, *total;
   uint32_t *ibuf[2];
   auto layout = [&](uint8_t *base) {
@@ -52,8 +44,7 @@ static int sort_run(kc_ctx *c, SortBufs &b) {
     total = m.take<uint64_t>(1);
     return m.used;
   };
-  HIPCHK(hipMalloc((void **)&b.scratch, layout(nullptr)));
-  layout(b.scratch);
+  KCTRY(cb.carve(layout));
   // the order is that of the keys at the reference's width: its words are the first nl_ext of the library's
   const uint64_t *keys = c->d_out_keys;
   const uint32_t *perm = nullptr;  // the identity until the first pass has run
@@ -109,22 +100,18 @@ extern "C" int kc_sort_results(kc_ctx *c, kc_result *out) {
                (unsigned long long)c->out_n);
       return KC_ERR_CAPACITY;
     }
-    HIPCHK(hipSetDevice(c->cfg.device));
-    SortBufs b;
-    const int rc = sort_run(c, b);
-    if (rc) {  // the unsorted results are as they were
-      (void)hipStreamSynchronize(c->stream);
-      b.release();
-      return rc;
-    }
-    free_index(c);  // it holds positions: the next kc_lookup builds it over the new order
-    std::swap(c->d_out_keys, b.keys);
-    if (b.ext) std::swap(c->d_out_keys_ext, b.ext);
-    std::swap(c->d_out_counts, b.counts);
-    std::swap(c->d_out_left, b.left);
-    std::swap(c->d_out_right, b.right);
-    c->out_cap = c->out_n;
-    b.release();  // the old arrays and the scratch
+    KCTRY(call_with_bufs(c, [&](CallBufs &cb) {
+      Sorted b;
+      KCTRY(sort_run(c, cb, b));  // had it failed, the unsorted results would be as they were
+      free_index(c);  // it holds positions: the next kc_lookup builds it over the new order
+      cb.hand_over(b.keys, c->d_out_keys);  // the old arrays go
+      if (b.ext) cb.hand_over(b.ext, c->d_out_keys_ext);
+      cb.hand_over(b.counts, c->d_out_counts);
+      cb.hand_over(b.left, c->d_out_left);
+      cb.hand_over(b.right, c->d_out_right);
+      c->out_cap = c->out_n;
+      return (int)KC_OK;
+    }));
   }
   c->sorted = true;
   if (out) fill_result(c, out);

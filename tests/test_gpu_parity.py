@@ -314,7 +314,9 @@ def _reads_for_overflow(seed=21, n=1200):
     return random_reads(rng, n, min_len=40, max_len=160, genome_len=4000)
 
 
-@pytest.mark.parametrize("k", [13, 21, 51])  # k=13: compact records with these small power-of-two fan-outs
+# k=13: compact records with these small power-of-two fan-outs; k=31, 63: the record is a word wider than the dump's keys,
+# so the regions' entries and the table's both take the re-width copy of kc_dump_table
+@pytest.mark.parametrize("k", [13, 21, 31, 51, 63])
 @pytest.mark.parametrize("tuning", [
     dict(writers=2, p1=2, p2=4, slots=4096, chunk1=16, chain1_max=8, ovf_capacity=1 << 20),   # level-1 chains overflow
     dict(writers=2, p1=2, p2=4, slots=4096, chunk1=16, arena1=20, ovf_capacity=1 << 20),      # a writer's arena runs out
