@@ -1200,6 +1200,87 @@ int kc_shuffle_reads(kc_ctx *ctx, const uint8_t *bases, const uint8_t *quals, co
                      const kc_gap_aln *alns, uint64_t n_alns, const kc_pair_rec *pairs, int on_device, uint32_t parts,
                      uint8_t *bases_out, uint8_t *quals_out, uint64_t *offsets_out, uint32_t *order, uint32_t *home,
                      uint64_t *part_starts, kc_gap_aln *alns_out, kc_pair_rec *pairs_out, kc_shuffle_stats *stats);
+/* The end of the assembly: which contigs are printed, in which order, the figures everybody quotes, and the FASTA text.
+ * The roles of ctgs.dump_contigs(fname, min_ctg_print_len, prefix), src/main.cpp:262 and src/contigging.cpp:115,180, and of
+ * ctgs.print_stats(min_ctg_len), src/contigging.cpp:184 and src/main.cpp:266, all commented out in the proxy.  The
+ * reference holds no Contigs class, so the rules below are this project's own definition (DESIGN.md section 23,
+ * tests/asm_model.py); no parity with MetaHipMer is claimed.  All quantities are integers; every output is one exact byte
+ * string for a given input.
+ *
+ * Both calls take a seq block exactly as kc_ctg_index_build takes it: seqs / nbytes / offsets / n_ctgs, every contig
+ * followed by '_', upper-case A C G T N, offsets[0] = 0, offsets[n_ctgs] = nbytes; empty contigs are allowed; 2^31 bytes
+ * or more: KC_ERR_CAPACITY.  on_device applies to all arrays of a call alike (params is always the host's); device
+ * offsets are 8-byte aligned, order 4-byte, seqs and text may have any alignment.  Neither call needs the contig index,
+ * the table or the results; both work before or after kc_finalize and with rank_n > 1, run on the context's stream,
+ * return when their work is done, keep no state in the context and free their scratch with the call.  The ranges of the
+ * parameters are checked in front of ctx, kc_last_error naming the values.  On every error nothing is written through
+ * any pointer.
+ *
+ * kc_ctg_select.  A contig is SELECTED iff its length, without the separator, is >= min_len.  order (may be NULL; room
+ * for n_ctgs entries, of which the first *n_selected are written) receives the selected contigs' block indices: in block
+ * order, or with KC_ASM_BY_LENGTH by length, longest first, equal lengths by smaller index first.  Unknown flags or
+ * non-zero reserved words: KC_ERR_INVALID_ARG.  The block is checked as kc_ctg_index_build checks it, with the same
+ * verdicts (KC_ERR_BAD_BASE; KC_ERR_INVALID_ARG for offsets that do not match the separators), read before anything is
+ * stored.  *n_selected and *stats (may be NULL) are always written on success.
+ *
+ * Statistics.  contigs, bases: the whole block, without separators.  selected, sel_bases; a, c, g, t, n: byte counts
+ * over the selected contigs.  n_runs: positions p of a selected contig with seqs[p] == 'N' and (p == 0 or
+ * seqs[p - 1] != 'N'): a run that ends one contig and a run that begins the next are two runs, the '_' between them is
+ * not N.  longest, shortest: over the selected contigs, both 0 without any.  With the selected lengths in descending
+ * order l_1 >= l_2 >= ..., their prefix sums S_i and total T: Lx is the smallest i with 100 S_i >= x T, Nx = l_Lx, both 0
+ * when nothing is selected (n50, l50, n90, l90).  ge_count[j], ge_bases[j]: the selected contigs of length >=
+ * KC_ASM_CLASSES[j] and their bases.  key_bits: the significant bits the sort ran over, those of longest - shortest (the
+ * sort is a stable radix sort of a 32-bit permutation by the key longest - length; it always runs, Nx needs it).
+ * Scratch: 45 bytes a contig and 4 for every 4096 bytes of the block, beside the copies of host arrays.
+ *
+ * kc_fasta_text.  line_width is 0 or 1 .. 65535, prefix_len at most KC_FASTA_MAX_PREFIX, every prefix byte 0x21 .. 0x7E,
+ * flags and the reserved words zero; written and total are required.  order == NULL: all contigs in block order, n_order
+ * must then equal n_ctgs; entries may repeat; an entry >= n_ctgs is KC_ERR_INVALID_ARG and kc_last_error names the lowest
+ * bad index.  The offsets are checked contig by contig (offsets[0] == 0, strictly increasing, offsets[n_ctgs] == nbytes,
+ * a '_' in front of each): KC_ERR_INVALID_ARG.  The alphabet is NOT checked, that is kc_ctg_select's job: bytes are
+ * copied as they are.
+ *
+ * The text.  For j = 0 .. n_order - 1, u = order[j]: '>' prefix u-in-decimal '\n', then the contig's bytes in lines of
+ * line_width, each followed by '\n'; line_width 0: one line.  max(1, ceil(len / line_width)) lines: an empty contig gives
+ * one empty line.  A record is 1 + prefix_len + digits(u) + 1 + len + lines bytes.  line_width 0 with the prefix
+ * "scaffold_" is dump_contigs' format.
+ *
+ * The window.  The call writes bytes [first_byte, min(total, first_byte + capacity)) of the whole text to text; *written
+ * receives the window's size, *total the size of the whole text, on every success.  text == NULL: a size query, 0 written.
+ * first_byte > total: KC_ERR_INVALID_ARG (kc_last_error names the total); first_byte == total: KC_OK, 0 written.  The
+ * windows of any partition of [0, total), laid end to end, are the whole text: a text of any size streams through a
+ * buffer of the caller's choosing, whatever the longest contig.  The records' starts are recomputed on every call, at 8
+ * bytes (scratch and traffic) per order entry, so choose windows far larger than that: megabytes, not records.
+ */
+#define KC_ASM_BY_LENGTH 1u
+#define KC_ASM_CLASSES {1000u, 5000u, 10000u, 25000u, 50000u}
+#define KC_FASTA_MAX_PREFIX 32
+typedef struct kc_asm_params { /* 32 bytes */
+  uint32_t min_len;
+  uint32_t flags;
+  uint32_t reserved[6]; /* zero */
+} kc_asm_params;
+typedef struct kc_asm_stats { /* 256 bytes */
+  uint64_t contigs, bases;
+  uint64_t selected, sel_bases;
+  uint64_t a, c, g, t, n;
+  uint64_t n_runs;
+  uint64_t longest, shortest;
+  uint64_t n50, l50, n90, l90;
+  uint64_t ge_count[5], ge_bases[5];
+  uint64_t key_bits;
+  uint64_t reserved[5]; /* zero */
+} kc_asm_stats;
+typedef struct kc_fasta_params { /* 64 bytes */
+  uint32_t line_width, prefix_len, flags, reserved0;
+  char prefix[32];
+  uint32_t reserved[4]; /* zero */
+} kc_fasta_params;
+int kc_ctg_select(kc_ctx *ctx, const uint8_t *seqs, uint64_t nbytes, const uint64_t *offsets, uint64_t n_ctgs, int on_device,
+                  const kc_asm_params *params, uint32_t *order, uint64_t *n_selected, kc_asm_stats *stats);
+int kc_fasta_text(kc_ctx *ctx, const uint8_t *seqs, uint64_t nbytes, const uint64_t *offsets, uint64_t n_ctgs, const uint32_t *order,
+                  uint64_t n_order, int on_device, const kc_fasta_params *params, uint64_t first_byte, uint8_t *text, uint64_t capacity,
+                  uint64_t *written, uint64_t *total);
 /* KmerDHT::kmer_exists / get_kmer_count / get_local_kmer_counts (src/kcount/kmer_dht.cpp:198-245) in bulk, against the
  * results kept in HBM: nq k-mers of num_longs words each, in either orientation; counts[i] = 0 (and left/right = 0)
  * when the k-mer did not survive.  The index over the results is built on the first call after kc_finalize.

@@ -8,4 +8,4 @@ fallback: without the built library or without a GPU every call fails loudly.
 """
 from ._lib import KcError, lib, lib_path  # noqa: F401
 from .kcount import (KmerCounter, adapters_index, analyze_kmers, analyze_kmers_fastq, analyze_kmers_fastq_paired,  # noqa: F401
-                     analyze_kmers_paired, fastq_pairs, fastq_to_packed, synth_params, synth_reads_host)
+                     analyze_kmers_paired, fastq_pairs, fastq_to_packed, format_assembly_stats, synth_params, synth_reads_host)

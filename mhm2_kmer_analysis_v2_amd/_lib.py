@@ -227,6 +227,26 @@ class kc_shuffle_stats(C.Structure):
 KC_SHUFFLE_MAX_PARTS = 65536
 KC_SHUFFLE_NO_HOME = 0xFFFFFFFF
 
+
+class kc_asm_params(C.Structure):
+    _fields_ = [("min_len", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 6)]
+
+
+class kc_asm_stats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("contigs", "bases", "selected", "sel_bases", "a", "c", "g", "t", "n", "n_runs", "longest", "shortest",
+                                          "n50", "l50", "n90", "l90")] + [("ge_count", C.c_uint64 * 5), ("ge_bases", C.c_uint64 * 5),
+                                                                         ("key_bits", C.c_uint64), ("reserved", C.c_uint64 * 5)]
+
+
+class kc_fasta_params(C.Structure):
+    _fields_ = [("line_width", C.c_uint32), ("prefix_len", C.c_uint32), ("flags", C.c_uint32), ("reserved0", C.c_uint32), ("prefix", C.c_char * 32),
+                ("reserved", C.c_uint32 * 4)]
+
+
+KC_ASM_BY_LENGTH = 1
+KC_ASM_CLASSES = (1000, 5000, 10000, 25000, 50000)
+KC_FASTA_MAX_PREFIX = 32
+
 # every symbol include/kcount_mi355.h declares: (restype, argtypes)
 SYMBOLS = {
     "kc_abi_version": (C.c_int, []),
@@ -314,6 +334,10 @@ SYMBOLS = {
     "kc_shuffle_reads": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int, C.c_uint32,
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.POINTER(kc_shuffle_stats)]),
+    "kc_ctg_select": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.POINTER(kc_asm_params), C.c_void_p,
+                                C.POINTER(C.c_uint64), C.POINTER(kc_asm_stats)]),
+    "kc_fasta_text": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int,
+                                C.POINTER(kc_fasta_params), C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "kc_lookup": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "kc_dump_table": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
     "kc_get_stats": (C.c_int, [C.c_void_p, C.POINTER(kc_stats)]),

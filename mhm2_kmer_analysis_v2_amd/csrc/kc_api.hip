@@ -40,6 +40,7 @@
 #include "kc_scaffold.hpp"
 #include "kc_close.hpp"
 #include "kc_shuffle.hpp"
+#include "kc_asm.hpp"
 
 using namespace kc;
 
@@ -3021,6 +3022,7 @@ extern "C" int kc_lookup(kc_ctx *c, const uint64_t *queries, uint64_t nq, int on
 #include "kc_api_scaffold.hpp"  // kc_scaffold
 #include "kc_api_close.hpp"  // kc_close_gaps
 #include "kc_api_shuffle.hpp"  // kc_shuffle_reads
+#include "kc_api_asm.hpp"  // kc_ctg_select, kc_fasta_text
 
 // ---- the contig pass (kc_ctg.hpp) ----------------------------------------------------------------------------------
 extern "C" int kc_begin_ctg_kmers(kc_ctx *c, uint64_t max_ctg_kmers) {

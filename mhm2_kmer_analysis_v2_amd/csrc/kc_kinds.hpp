@@ -2,7 +2,8 @@
 // the enum and the names come from it, so a kind and its name cannot drift apart.  No HIP in here.
 //
 // Several kinds are one kernel launched by different callers or in different passes; the name in angle brackets says
-// which (kc_align_lengths_kernel<close> is kc_close_gaps' launch of kc_align_lengths_kernel).  The *_scan_kernel names are
+// which (kc_align_lengths_kernel<close> is kc_close_gaps' launch of kc_align_lengths_kernel,
+// <assembly> kc_ctg_select's, <fasta> kc_fasta_text's).  The *_scan_kernel names are
 // the uses of the one shared kc_scan_kernel (kc_scan.hpp) and keep the names they were first reported under.
 #pragma once
 
@@ -156,7 +157,28 @@
   X(KT_SHUF_OFFSETS,       "kc_shuf_offsets_kernel") \
   X(KT_SHUF_GATHER,        "kc_shuf_gather_kernel") \
   X(KT_SHUF_REMAP,         "kc_shuf_remap_kernel") \
-  X(KT_SHUF_PARTS,         "kc_shuf_parts_kernel")
+  X(KT_SHUF_PARTS,         "kc_shuf_parts_kernel") \
+  X(KT_ASM_CHECK,          "kc_align_check_kernel<assembly>") \
+  X(KT_ASM_LENS,           "kc_asm_lens_kernel") \
+  X(KT_ASM_TILE_SCAN,      "kc_link_tile_scan_kernel<assembly>") \
+  X(KT_ASM_SCAN,           "kc_asm_scan_kernel") \
+  X(KT_ASM_COMPACT,        "kc_asm_compact_kernel") \
+  X(KT_ASM_SORT_HIST,      "kc_sort_hist_kernel<assembly>") \
+  X(KT_ASM_SORT_SCAN,      "kc_sort_scan_kernel<assembly>") \
+  X(KT_ASM_SORT_SCATTER,   "kc_sort_scatter_kernel<assembly>") \
+  X(KT_ASM_SORTED,         "kc_asm_sorted_kernel") \
+  X(KT_ASM_LEN_TILE_SCAN,  "kc_link_tile_scan_kernel<assembly lengths>") \
+  X(KT_ASM_LEN_SCAN,       "kc_asm_scan_kernel<lengths>") \
+  X(KT_ASM_NX,             "kc_asm_nx_kernel") \
+  X(KT_ASM_SPANS,          "kc_asm_spans_kernel") \
+  X(KT_ASM_COMP,           "kc_asm_comp_kernel") \
+  X(KT_ASM_TEXT_CHECK,     "kc_asm_text_check_kernel") \
+  X(KT_ASM_SIZES,          "kc_asm_sizes_kernel") \
+  X(KT_ASM_TEXT_TILE_SCAN, "kc_link_tile_scan_kernel<fasta>") \
+  X(KT_ASM_TEXT_SCAN,      "kc_asm_scan_kernel<fasta>") \
+  X(KT_ASM_STARTS,         "kc_asm_starts_kernel") \
+  X(KT_ASM_TEXT_SPANS,     "kc_asm_spans_kernel<fasta>") \
+  X(KT_ASM_WRITE,          "kc_asm_write_kernel")
 
 enum {
 #define X(kind, name) kind,

@@ -15,6 +15,8 @@
                                                       .sort_results()          kc_sort_results
                                                       .dump_text(...)          kc_dump_text_device
   (traverse_debruijn_graph: commented out there)      .unitigs()               kc_build_unitigs
+  (ctgs.print_stats: commented out there)             .select_contigs(...)     kc_ctg_select
+  (ctgs.dump_contigs: commented out there)            .write_fasta(...)        kc_fasta_text
 """
 import ctypes as C
 
@@ -945,6 +947,89 @@ class KmerCounter:
         out["stats"] = _stats_dict(st)
         return out
 
+    def _block(self, seqs, offsets, **others):
+        """A seq block argument -> (address of seqs or None, bytes, address of offsets, contigs, on the device)."""
+        ps, dev_s = _ptr(seqs)
+        po, dev_o = _ptr(offsets)
+        dev = _side("seqs", dev_s, offsets=(dev_o, True), **others)
+        nbytes = seqs.numel() if dev else len(seqs)
+        return (ps if nbytes else None), nbytes, po, len(offsets) - 1, dev
+
+    def select_contigs(self, seqs, offsets, min_len=0, by_length=False):
+        """Which contigs of a seq block are printed, in which order, and the assembly's statistics (kc_ctg_select; DESIGN.md
+        section 23): a contig is selected iff it has at least min_len bases; order holds the selected contigs' block
+        indices, in block order or, with by_length, longest first and equal lengths by index.  seqs / offsets: numpy
+        arrays or device tensors, as index_contigs takes them.  Returns (order, stats): order a uint32 numpy array, or an
+        int32 device tensor holding the 32 bits, and kc_asm_stats as a dict (N50, L50, the length classes, the Ns)."""
+        ps, nbytes, po, n, dev = self._block(seqs, offsets)
+        prm = _lib.kc_asm_params(min_len, _lib.KC_ASM_BY_LENGTH if by_length else 0)
+        order = self._out(dev, n, np.uint32, pad=True)
+        st, nsel = _lib.kc_asm_stats(), C.c_uint64(0)
+        self._hand_over(dev)
+        check(lib().kc_ctg_select(self._h, ps, nbytes, po, n, 1 if dev else 0, C.byref(prm), order.ptr, C.byref(nsel), C.byref(st)), "kc_ctg_select")
+        return order.first(int(nsel.value)), _stats_dict(st)
+
+    def _fasta_call(self, seqs, offsets, order, prefix, line_width):
+        """what the windows of one text share: call(first_byte, address, capacity) -> (written, total), and the side"""
+        p_order, dev_o = _ptr(order)
+        n_order = 0 if order is None else (order.numel() if dev_o else len(order))
+        if order is not None and not dev_o and (order.dtype.itemsize != 4 or not order.flags["C_CONTIGUOUS"]):
+            raise ValueError("order: a contiguous array of 32-bit indices")
+        ps, nbytes, po, n, dev = self._block(seqs, offsets, order=(dev_o, n_order))
+        prefix = prefix.encode() if isinstance(prefix, str) else bytes(prefix)
+        prm = _lib.kc_fasta_params(line_width, len(prefix), 0, 0, prefix[:_lib.KC_FASTA_MAX_PREFIX])
+        if order is None:
+            n_order = n
+
+        def call(first_byte, text, capacity):
+            written, total = C.c_uint64(0), C.c_uint64(0)
+            if order is not None and not n_order:  # an empty selection: an empty text (an empty array has no address to pass)
+                return 0, 0
+            check(lib().kc_fasta_text(self._h, ps, nbytes, po, n, p_order, n_order, 1 if dev else 0, C.byref(prm), first_byte, text,
+                                      capacity, C.byref(written), C.byref(total)), "kc_fasta_text")
+            return int(written.value), int(total.value)
+
+        return call, dev
+
+    def fasta_text(self, seqs, offsets, order=None, prefix="scaffold_", line_width=0, first_byte=0, capacity=None):
+        """The FASTA text of a seq block's contigs, formatted on the device (kc_fasta_text), as bytes:
+        for every entry u of order (None: all contigs in block order; select_contigs' order as it comes) the record
+        ">" prefix u "\\n" and the contig in lines of line_width bases (0: one line, dump_contigs' format).  first_byte /
+        capacity: bytes [first_byte, first_byte + capacity) of the whole text only (capacity None: to its end)."""
+        call, dev = self._fasta_call(seqs, offsets, order, prefix, line_width)
+        self._hand_over(dev)
+        _, total = call(first_byte, None, 0)
+        want = total - first_byte if capacity is None else min(capacity, total - first_byte)
+        if want <= 0:
+            return b""
+        text = self._out(dev, want, np.uint8)
+        self._hand_over(dev)
+        written, _ = call(first_byte, text.ptr, want)
+        out = text.first(written)
+        return (out.cpu().numpy() if dev else out).tobytes()
+
+    def write_fasta(self, path_or_fileobj, seqs, offsets, order=None, prefix="scaffold_", line_width=0, window_bytes=256 << 20):
+        """fasta_text() streamed to a file: the text goes through one buffer of window_bytes, window after window, each
+        written to the file object (a path is opened "wb"; compression and the file itself stay with the caller's file
+        object).  Returns the text's bytes.  The records' starts are recomputed for every window: keep windows large."""
+        if window_bytes < 1:
+            raise ValueError("window_bytes: at least 1")
+        if isinstance(path_or_fileobj, (str, bytes)) or hasattr(path_or_fileobj, "__fspath__"):
+            with open(path_or_fileobj, "wb") as f:
+                return self.write_fasta(f, seqs, offsets, order, prefix, line_width, window_bytes)
+        call, dev = self._fasta_call(seqs, offsets, order, prefix, line_width)
+        self._hand_over(dev)
+        _, total = call(0, None, 0)
+        text = self._out(dev, min(window_bytes, total), np.uint8)
+        self._hand_over(dev)
+        first = 0
+        while first < total:
+            written, _ = call(first, text.ptr, text.n)
+            out = text.first(written)
+            path_or_fileobj.write((out.cpu().numpy() if dev else out).tobytes())
+            first += written
+        return total
+
     def submit_ctg_block(self, seqs, depths):
         """kc_submit_ctg_block with device tensors (a '_'-joined block and one 16-bit depth per byte), e.g. those of
         unitig_block(); begin_ctg_kmers first."""
@@ -1003,6 +1088,24 @@ CLOSURE_DTYPE = np.dtype([("cands", "<u4"), ("reads", "<u4"), ("old_join", "<i4"
                           ("status", "u1"), ("pad", "u1", (3,)), ("reserved", "<u4")])
 BLASTN_ALN_SCORES = (2, 3, 5, 2, 1)
 ALTERNATE_ALN_SCORES = (1, 1, 1, 1, 1)
+
+
+def format_assembly_stats(stats, min_len):
+    """The few lines print_stats(min_ctg_len) would log, from select_contigs' stats."""
+    tot = max(stats["sel_bases"], 1)
+    lines = ["Assembly statistics (contig lengths >= %d)" % min_len,
+             "    Number of contigs:       %d" % stats["selected"],
+             "    Total assembled length:  %d" % stats["sel_bases"],
+             "    Number of Ns/100kbp:     %.2f (%d)" % (stats["n"] * 100000.0 / tot, stats["n"]),
+             "    Runs of Ns:              %d" % stats["n_runs"],
+             "    Max. contig length:      %d" % stats["longest"],
+             "    Min. contig length:      %d" % stats["shortest"],
+             "    N50 / L50:               %d / %d" % (stats["n50"], stats["l50"]),
+             "    N90 / L90:               %d / %d" % (stats["n90"], stats["l90"]),
+             "    Contig lengths:"]
+    for c, n, b in zip(_lib.KC_ASM_CLASSES, stats["ge_count"], stats["ge_bases"]):
+        lines.append("        >= %-7d %10d contigs %14d bases (%.1f%%)" % (c, n, b, 100.0 * b / tot))
+    return "\n".join(lines) + "\n"
 
 
 def kmer_to_string(words, k):
