@@ -1281,6 +1281,99 @@ int kc_ctg_select(kc_ctx *ctx, const uint8_t *seqs, uint64_t nbytes, const uint6
 int kc_fasta_text(kc_ctx *ctx, const uint8_t *seqs, uint64_t nbytes, const uint64_t *offsets, uint64_t n_ctgs, const uint32_t *order,
                   uint64_t n_order, int on_device, const kc_fasta_params *params, uint64_t first_byte, uint8_t *text, uint64_t capacity,
                   uint64_t *written, uint64_t *total);
+/* FASTA text -> a seq block, on the device: the inverse of kc_fasta_text, and the contig side's twin of
+ * kc_fastq_to_packed_device.  It takes up what dump_contigs / --checkpoint wrote (src/contigging.cpp:82,115,177-180,
+ * src/main.cpp:262), or somebody else's assembly: line-wrapped, lower-case, IUPAC codes, CRLF.  The reference holds no
+ * Contigs::load_contigs, so the rules below are this project's own definition (DESIGN.md section 24,
+ * tests/fasta_in_model.py); no parity with MetaHipMer is claimed.  All quantities are integers; every output is one exact
+ * byte string for a given input.
+ *
+ * Lines, as in kc_fastq_to_packed: a line ends at '\n', the last line may lack it.  Trailing '\r', ' ' and '\t' are not part
+ * of a line.  Positions in the text are 64-bit; a text may exceed 2^32 bytes.
+ *
+ * Records.  A line whose first byte is '>' is a header and begins a record.  Empty lines (after stripping) are ignored
+ * everywhere.  A record's sequence is the concatenation of its non-header lines up to the next header or the end of the
+ * text.  A header with no sequence gives an empty contig.  A non-empty non-header line in front of the first header is a
+ * structural error; its position is that of its first byte.
+ *
+ * Alphabet: kc_fastq_to_packed's table (PackedRead, src/packed_reads.cpp:99-124).  A C G T are copied as they are, a c g t
+ * become upper case, N n U R Y K M S W B D H V become N.  Every other byte inside a sequence line is a bad base; interior
+ * white space counts.  With KC_FASTA_STRICT everything but A C G T N is a bad base.
+ *
+ * Errors.  The error at the smallest text position wins, whichever kind it is (at one position, the structural one).  A
+ * sequence before the first header: KC_ERR_INVALID_ARG, kc_last_error "fasta: line L: sequence before the first header".
+ * A bad base: KC_ERR_BAD_BASE, kc_last_error "fasta: line L column C: byte 0xHH is not a base".  L and C are 1-based, C
+ * counts bytes from the line's start.  A format error wins over KC_ERR_CAPACITY.  On every error nothing is written through
+ * any output pointer: the validation runs before any store to the caller's arrays.
+ *
+ * Output.  seqs: the block, *nbytes bytes, every contig followed by '_' (room for seqs_capacity bytes).  offsets:
+ * *n_ctgs + 1 entries, offsets[0] = 0 (room for ctgs_capacity + 1).  depths (may be NULL; room for seqs_capacity entries):
+ * one uint16 per byte of the block, the record's depth on its bases and 0 on its separator, exactly what
+ * kc_submit_ctg_block(..., on_device = 1) takes.  recs (may be NULL; room for ctgs_capacity): one kc_fasta_rec per contig.
+ * A block of 2^31 bytes or more is KC_ERR_CAPACITY, as every consumer of a block says.  NULL seqs or offsets is a size
+ * query: KC_OK, nothing written but the totals.  Arrays that are too small: KC_ERR_CAPACITY, nothing written but the
+ * totals.  *n_ctgs, *nbytes, *consumed (may be NULL) and *stats (may be NULL) receive the totals on success and on
+ * KC_ERR_CAPACITY.
+ *
+ * kc_fasta_rec.  hdr_pos: the text position of the '>'.  hdr_len: the stripped header's length including '>'.  seq_lines:
+ * the record's non-empty sequence lines.  flags: KC_FASTA_HAS_ID, KC_FASTA_HAS_DEPTH, KC_FASTA_LOWERED (a byte of acgtn
+ * was seen in the record), KC_FASTA_RECODED (a byte of URYKMSWBDHV was seen).  The header parse looks at the first
+ * KC_FASTA_HDR_SCAN = 256 bytes of the stripped header only; a token that does not end inside them (at a blank or at the
+ * header's end) is absent.  The first token is the run of bytes other than ' ' and '\t' right after '>'.  id is the value
+ * of the maximal run of decimal digits at the first token's end, present iff that run has 1 to 18 digits; otherwise id = 0
+ * and the flag is clear.  The second token follows the white space.  The depth is present iff the whole second token is 1
+ * to 9 digits, optionally followed by '.' and any number of digits: depth = min(65535, integer part + (first fractional
+ * digit >= '5')).  Otherwise depth = params->default_depth and the flag is clear.  kc_fasta_text's own ">scaffold_17" gives
+ * id 17, so text written by this library comes back with its block indices; MetaHipMer's ">Contig123 17.4" gives id 123,
+ * depth 17.
+ *
+ * KC_FASTA_PARTIAL.  The text is a prefix of a longer input, and only whole records count: a record is whole iff another
+ * header begins behind it inside the text.  *consumed is the position of the last '>' at a line's start, 0 when there is
+ * none (KC_OK with 0 contigs).  The call equals the flag-free call on text[0, *consumed) in status, outputs, error text
+ * and statistics; an error at or behind *consumed is not reported.  Without the flag *consumed = len.  A caller streams a
+ * file by carrying the tail into the next call and making the last call without the flag.
+ *
+ * Parameters: flags, default_depth (0 .. 65535), reserved words zero.  Unknown flags, non-zero reserved words, a
+ * default_depth out of range and NULL n_ctgs / nbytes / params are KC_ERR_INVALID_ARG, refused in front of ctx with
+ * kc_last_error naming the value.  Statistics: lines, empty_lines (after stripping), records, empty_records, bases (the
+ * block without separators), lowered and recoded (bytes of acgtn / of URYKMSWBDHV), longest (contig), with_id, with_depth.
+ *
+ * on_device = 1: the text is read in place from device memory and all output arrays are device pointers (offsets and recs
+ * 8-byte aligned, depths 2-byte; text and seqs may have any alignment).  on_device = 0: the text is host memory, staged in
+ * one copy, and the outputs are host arrays.  The call needs neither table, results nor index, works in any state and
+ * with rank_n > 1, runs on the context's stream, returns when its work is done, keeps nothing in the context and frees
+ * its scratch: 24 bytes a line and 8 a '\n', 52 a record, 8 for every 4096 bytes of text and of block and for every 64 KiB
+ * of text, beside the copies of host arrays.
+ */
+#define KC_FASTA_PARTIAL 1u
+#define KC_FASTA_STRICT 2u
+#define KC_FASTA_HDR_SCAN 256
+#define KC_FASTA_HAS_ID 1u
+#define KC_FASTA_HAS_DEPTH 2u
+#define KC_FASTA_LOWERED 4u
+#define KC_FASTA_RECODED 8u
+typedef struct kc_fasta_in_params { /* 32 bytes */
+  uint32_t flags;
+  uint32_t default_depth;
+  uint32_t reserved[6]; /* zero */
+} kc_fasta_in_params;
+typedef struct kc_fasta_in_stats { /* 128 bytes */
+  uint64_t lines, empty_lines;
+  uint64_t records, empty_records;
+  uint64_t bases, lowered, recoded;
+  uint64_t longest;
+  uint64_t with_id, with_depth;
+  uint64_t reserved[6]; /* zero */
+} kc_fasta_in_stats;
+typedef struct kc_fasta_rec { /* 32 bytes */
+  uint64_t hdr_pos;
+  uint32_t hdr_len, seq_lines;
+  uint64_t id;
+  uint32_t depth, flags;
+} kc_fasta_rec;
+int kc_fasta_to_block(kc_ctx *ctx, const uint8_t *text, uint64_t len, int on_device, const kc_fasta_in_params *params, uint8_t *seqs,
+                      uint64_t seqs_capacity, uint64_t *offsets, uint64_t ctgs_capacity, uint16_t *depths, kc_fasta_rec *recs,
+                      uint64_t *n_ctgs, uint64_t *nbytes, uint64_t *consumed, kc_fasta_in_stats *stats);
 /* KmerDHT::kmer_exists / get_kmer_count / get_local_kmer_counts (src/kcount/kmer_dht.cpp:198-245) in bulk, against the
  * results kept in HBM: nq k-mers of num_longs words each, in either orientation; counts[i] = 0 (and left/right = 0)
  * when the k-mer did not survive.  The index over the results is built on the first call after kc_finalize.

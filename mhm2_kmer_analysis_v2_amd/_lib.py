@@ -247,6 +247,29 @@ KC_ASM_BY_LENGTH = 1
 KC_ASM_CLASSES = (1000, 5000, 10000, 25000, 50000)
 KC_FASTA_MAX_PREFIX = 32
 
+
+class kc_fasta_in_params(C.Structure):
+    _fields_ = [("flags", C.c_uint32), ("default_depth", C.c_uint32), ("reserved", C.c_uint32 * 6)]
+
+
+class kc_fasta_in_stats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("lines", "empty_lines", "records", "empty_records", "bases", "lowered", "recoded", "longest", "with_id",
+                                          "with_depth")] + [("reserved", C.c_uint64 * 6)]
+
+
+class kc_fasta_rec(C.Structure):
+    _fields_ = [("hdr_pos", C.c_uint64), ("hdr_len", C.c_uint32), ("seq_lines", C.c_uint32), ("id", C.c_uint64), ("depth", C.c_uint32),
+                ("flags", C.c_uint32)]
+
+
+KC_FASTA_PARTIAL = 1
+KC_FASTA_STRICT = 2
+KC_FASTA_HDR_SCAN = 256
+KC_FASTA_HAS_ID = 1
+KC_FASTA_HAS_DEPTH = 2
+KC_FASTA_LOWERED = 4
+KC_FASTA_RECODED = 8
+
 # every symbol include/kcount_mi355.h declares: (restype, argtypes)
 SYMBOLS = {
     "kc_abi_version": (C.c_int, []),
@@ -338,6 +361,9 @@ SYMBOLS = {
                                 C.POINTER(C.c_uint64), C.POINTER(kc_asm_stats)]),
     "kc_fasta_text": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int,
                                 C.POINTER(kc_fasta_params), C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "kc_fasta_to_block": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.POINTER(kc_fasta_in_params), C.c_void_p, C.c_uint64, C.c_void_p,
+                                    C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                    C.POINTER(kc_fasta_in_stats)]),
     "kc_lookup": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "kc_dump_table": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
     "kc_get_stats": (C.c_int, [C.c_void_p, C.POINTER(kc_stats)]),

@@ -41,6 +41,7 @@
 #include "kc_close.hpp"
 #include "kc_shuffle.hpp"
 #include "kc_asm.hpp"
+#include "kc_fasta_in.hpp"
 
 using namespace kc;
 
@@ -3023,6 +3024,7 @@ extern "C" int kc_lookup(kc_ctx *c, const uint64_t *queries, uint64_t nq, int on
 #include "kc_api_close.hpp"  // kc_close_gaps
 #include "kc_api_shuffle.hpp"  // kc_shuffle_reads
 #include "kc_api_asm.hpp"  // kc_ctg_select, kc_fasta_text
+#include "kc_api_fasta_in.hpp"  // kc_fasta_to_block
 
 // ---- the contig pass (kc_ctg.hpp) ----------------------------------------------------------------------------------
 extern "C" int kc_begin_ctg_kmers(kc_ctx *c, uint64_t max_ctg_kmers) {

@@ -3,7 +3,7 @@
 //
 // Several kinds are one kernel launched by different callers or in different passes; the name in angle brackets says
 // which (kc_align_lengths_kernel<close> is kc_close_gaps' launch of kc_align_lengths_kernel,
-// <assembly> kc_ctg_select's, <fasta> kc_fasta_text's).  The *_scan_kernel names are
+// <assembly> kc_ctg_select's, <fasta> kc_fasta_text's, <fasta in> kc_fasta_to_block's).  The *_scan_kernel names are
 // the uses of the one shared kc_scan_kernel (kc_scan.hpp) and keep the names they were first reported under.
 #pragma once
 
@@ -178,7 +178,20 @@
   X(KT_ASM_TEXT_SCAN,      "kc_asm_scan_kernel<fasta>") \
   X(KT_ASM_STARTS,         "kc_asm_starts_kernel") \
   X(KT_ASM_TEXT_SPANS,     "kc_asm_spans_kernel<fasta>") \
-  X(KT_ASM_WRITE,          "kc_asm_write_kernel")
+  X(KT_ASM_WRITE,          "kc_asm_write_kernel") \
+  X(KT_FA_COUNT,           "kc_fq_count_kernel<fasta in>") \
+  X(KT_FA_SCAN,            "kc_fq_scan_kernel<fasta in>") \
+  X(KT_FA_INDEX,           "kc_fq_index_kernel<fasta in>") \
+  X(KT_FA_LINES,           "kc_fa_lines_kernel") \
+  X(KT_FA_TILE_SCAN,       "kc_link_tile_scan_kernel<fasta in>") \
+  X(KT_FA_LINE_SCAN,       "kc_fa_scan_kernel") \
+  X(KT_FA_STARTS,          "kc_fa_starts_kernel") \
+  X(KT_FA_SPANS,           "kc_fa_spans_kernel") \
+  X(KT_FA_CHECK,           "kc_fa_check_kernel") \
+  X(KT_FA_DETAIL,          "kc_fa_detail_kernel") \
+  X(KT_FA_RECS,            "kc_fa_recs_kernel") \
+  X(KT_FA_BLOCK_SPANS,     "kc_fa_spans_kernel<block>") \
+  X(KT_FA_WRITE,           "kc_fa_write_kernel")
 
 enum {
 #define X(kind, name) kind,

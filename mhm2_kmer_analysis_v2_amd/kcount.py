@@ -17,6 +17,7 @@
   (traverse_debruijn_graph: commented out there)      .unitigs()               kc_build_unitigs
   (ctgs.print_stats: commented out there)             .select_contigs(...)     kc_ctg_select
   (ctgs.dump_contigs: commented out there)            .write_fasta(...)        kc_fasta_text
+  (options.ctgs_fname / --checkpoint: likewise)       .load_contigs(...)       kc_fasta_to_block
 """
 import ctypes as C
 
@@ -1030,6 +1031,84 @@ class KmerCounter:
             first += written
         return total
 
+    def fasta_to_block(self, text, partial=False, strict=False, default_depth=0, with_depths=False, with_records=True):
+        """FASTA text parsed on the device into a seq block (kc_fasta_to_block), the inverse of
+        fasta_text: line-wrapped or not, lower case and IUPAC codes recoded (strict: refused), CRLF and trailing blanks
+        stripped.  text: bytes, a numpy uint8 array (staged) or a uint8 device tensor (read in place); the result lies on
+        the side the text came from.  Returns a dict: seqs (every contig followed by '_'), offsets (contigs + 1), depths
+        (with_depths: one uint16 per byte, the header's depth or default_depth on the bases, what submit_ctg_block takes;
+        else None), records (with_records: FASTA_REC_DTYPE per contig, a uint8 tensor of 32-byte records on the device; else
+        None), consumed and stats.  partial: the text is a prefix of a longer one, only the records in front of its last
+        header are parsed and `consumed` is that header's position; the caller carries the tail."""
+        if not 0 <= default_depth <= 65535:
+            raise ValueError("default_depth: 0 .. 65535")
+        pt, n, dev, keep = _text(text)
+        dev = _side("text", dev)
+        prm = _lib.kc_fasta_in_params((_lib.KC_FASTA_PARTIAL if partial else 0) | (_lib.KC_FASTA_STRICT if strict else 0), default_depth)
+        seqs = self._out(dev, n, np.uint8, pad=True)  # a header gives a byte and is one at least, a base gives one
+        depths = self._out(dev, n, np.uint16, pad=True) if with_depths else None
+        nc, nb, cons, st = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), _lib.kc_fasta_in_stats()
+
+        def call(capacity):
+            offs = self._out(dev, capacity + 1, np.uint64)
+            recs = self._out(dev, capacity, FASTA_REC_DTYPE, pad=True) if with_records else None
+            self._hand_over(dev)
+            rc = lib().kc_fasta_to_block(self._h, pt, n, 1 if dev else 0, C.byref(prm), seqs.ptr, n, offs.ptr, capacity, depths and depths.ptr,
+                                         recs and recs.ptr, C.byref(nc), C.byref(nb), C.byref(cons), C.byref(st))
+            return rc, int(nc.value), (offs, recs)
+
+        rc, _, (offs, recs) = _retry_on_capacity(n // 64 + 16, call)
+        check(rc, "kc_fasta_to_block")
+        del keep
+        c, b = int(nc.value), int(nb.value)
+        return {"seqs": seqs.first(b), "offsets": offs.first(c + 1), "depths": depths and depths.first(b), "records": recs and recs.first(c),
+                "consumed": int(cons.value), "stats": _stats_dict(st)}
+
+    def load_contigs(self, path_or_fileobj, window_bytes=256 << 20, strict=False, default_depth=0, with_depths=False, with_records=True):
+        """fasta_to_block() streamed from a file (a path is opened "rb"; decompression stays with the caller's file
+        object): the text goes through one device buffer of window_bytes with partial=True, the unfinished tail carried
+        into the next window, the window doubled when it holds no whole record, the last call without the flag.  Returns
+        fasta_to_block's dict for the whole file as device tensors: one block, the offsets rebased, hdr_pos as file
+        positions, the stats summed (longest: the maximum), consumed the file's bytes.  An error in any window raises and
+        returns nothing."""
+        import torch
+        if window_bytes < 1:
+            raise ValueError("window_bytes: at least 1")
+        if not 0 <= default_depth <= 65535:
+            raise ValueError("default_depth: 0 .. 65535")
+        if isinstance(path_or_fileobj, (str, bytes)) or hasattr(path_or_fileobj, "__fspath__"):
+            with open(path_or_fileobj, "rb") as f:
+                return self.load_contigs(f, window_bytes, strict, default_depth, with_depths, with_records)
+        kw = dict(strict=strict, default_depth=default_depth, with_depths=with_depths, with_records=with_records)
+        window = self._out(True, window_bytes, np.uint8)
+        parts, stats, tail, pos, nbytes = [], None, b"", 0, 0  # pos: the file position of the window's first byte
+        while True:
+            while len(tail) >= window.n:  # a record longer than the window
+                window = self._out(True, 2 * window.n, np.uint8)
+            chunk = path_or_fileobj.read(window.n - len(tail))
+            buf = bytearray(tail)  # (writable: torch takes no read-only memory)
+            buf += chunk
+            text = window.first(len(buf))
+            if buf:
+                text.copy_(torch.from_numpy(np.frombuffer(buf, dtype=np.uint8)))
+            r = self.fasta_to_block(text, partial=bool(chunk), **kw)
+            used = r["consumed"]
+            if r["offsets"].numel() > 1:
+                if with_records:
+                    r["records"].view(torch.int64).view(-1, 4)[:, 0] += pos
+                parts.append((r["seqs"], r["offsets"][1:] + nbytes, r["depths"], r["records"]))
+                nbytes += r["seqs"].numel()
+            st = r["stats"]
+            stats = st if stats is None else {k: max(v, st[k]) if k == "longest" else v + st[k] for k, v in stats.items()}
+            pos += used
+            tail = buf[used:]
+            if not chunk:
+                break
+        cat = lambda j, dtype: torch.cat([p[j] for p in parts]) if parts else torch.zeros(0, dtype=dtype, device=self._torch_device())  # noqa: E731
+        zero = torch.zeros(1, dtype=torch.int64, device=self._torch_device())
+        return {"seqs": cat(0, torch.uint8), "offsets": torch.cat([zero] + [p[1] for p in parts]), "depths": cat(2, torch.int16) if with_depths else None,
+                "records": cat(3, torch.uint8) if with_records else None, "consumed": pos, "stats": stats}
+
     def submit_ctg_block(self, seqs, depths):
         """kc_submit_ctg_block with device tensors (a '_'-joined block and one 16-bit depth per byte), e.g. those of
         unitig_block(); begin_ctg_kmers first."""
@@ -1086,6 +1165,8 @@ MEMBER_DTYPE = np.dtype([("ctg", "<u4"), ("join", "<i4"), ("out_pos", "<u4"), ("
 # kc_close_gaps' record of a member's join (kc_closure, 32 bytes)
 CLOSURE_DTYPE = np.dtype([("cands", "<u4"), ("reads", "<u4"), ("old_join", "<i4"), ("new_join", "<i4"), ("fill_pos", "<u4"), ("disputed", "<u4"),
                           ("status", "u1"), ("pad", "u1", (3,)), ("reserved", "<u4")])
+# kc_fasta_to_block's record of a contig (kc_fasta_rec, 32 bytes)
+FASTA_REC_DTYPE = np.dtype([("hdr_pos", "<u8"), ("hdr_len", "<u4"), ("seq_lines", "<u4"), ("id", "<u8"), ("depth", "<u4"), ("flags", "<u4")])
 BLASTN_ALN_SCORES = (2, 3, 5, 2, 1)
 ALTERNATE_ALN_SCORES = (1, 1, 1, 1, 1)
 
