@@ -187,7 +187,9 @@ class ParseAndPackDriver {
   // parse_and_pack.cpp:338: {time in the driver's functions, time in device calls}
   std::tuple<double, double> get_elapsed_times() { return {t_func, t_kernel}; }
 
-  const uint64_t *records() const { return d_records; }  // device pointer
+  // device pointer; rewritten (or freed and grown) by the next process_seq_block: whoever reads the records on another
+  // stream has to be done by then (HashTableDriver::insert_records is when it returns)
+  const uint64_t *records() const { return d_records; }
   uint64_t segment_capacity() const { return seg_capacity; }
   int record_longs() const { return rec_longs; }
   const std::vector<uint64_t> &counts() const { return h_counts; }
@@ -349,10 +351,13 @@ class HashTableDriver {
     elem_buff += '_';
     stats.attempted++;
   }
-  // records that another shard's ParseAndPackDriver binned for this shard (device pointer)
+  // records that another shard's ParseAndPackDriver binned for this shard (device pointer).  They have been read when
+  // this returns: kc_insert_records may leave its kernel running on this context's stream, and the sender's next
+  // process_seq_block writes the same segments from a stream of its own (or frees them), so the wait is here
   void insert_records(const uint64_t *d_records, uint64_t n) {
     StopWatch sw;
     check(kc_insert_records(ctx, d_records, n), "kc_insert_records");
+    check(kc_flush(ctx), "kc_flush");
     num_gpu_calls++;
     t_insert += sw.stop();
   }
@@ -403,10 +408,11 @@ class HashTableDriver {
   void get_elapsed_time(double &insert_time, double &kernel_time) {
     insert_time = t_insert;
     kernel_time = 0;
-    kc_kernel_time kt[16];
-    int n = 0;
-    if (kc_get_kernel_times(ctx, kt, 16, &n) == KC_OK)
-      for (int i = 0; i < n && i < 16; i++) kernel_time += kt[i].total_ms * 1e-3;
+    int n = 0;  // kinds of kernel the context has launched: kc_kinds.hpp lists more than any fixed few
+    if (kc_get_kernel_times(ctx, nullptr, 0, &n) != KC_OK || n <= 0) return;
+    std::vector<kc_kernel_time> kt(n);
+    if (kc_get_kernel_times(ctx, kt.data(), n, &n) == KC_OK)
+      for (int i = 0; i < n && i < (int)kt.size(); i++) kernel_time += kt[i].total_ms * 1e-3;
   }
   int64_t get_capacity() {
     kc_stats st;

@@ -187,6 +187,7 @@ static_assert(sizeof(count_t) == 4 && sizeof(ext_count_t) == 2, "counter types")
 template int surface<32>(int, int, int, int, int, const string &, vector<Entry> &);
 template int surface<64>(int, int, int, int, int, const string &, vector<Entry> &);
 template int surface<96>(int, int, int, int, int, const string &, vector<Entry> &);
+template int surface<128>(int, int, int, int, int, const string &, vector<Entry> &);
 
 #ifndef SURFACE_REFERENCE
 int main(int argc, char **argv) {
@@ -197,8 +198,11 @@ int main(int argc, char **argv) {
   m = m < 15 ? 15 : m > 27 ? 27 : m;
   if (m > k) m = k;
   vector<Entry> result;
-  const int rc = k < 32 ? surface<32>(0, 3, k, 33, m, block, result) : k < 64 ? surface<64>(0, 3, k, 33, m, block, result)
-                                                                             : surface<96>(0, 3, k, 33, m, block, result);
+  // MAX_K as the reference's build picks it for this k: one more word at k = 32, 64 and 96
+  const int rc = k < 32   ? surface<32>(0, 3, k, 33, m, block, result)
+                 : k < 64 ? surface<64>(0, 3, k, 33, m, block, result)
+                 : k < 96 ? surface<96>(0, 3, k, 33, m, block, result)
+                          : surface<128>(0, 3, k, 33, m, block, result);
   if (rc) return rc;
   vector<string> out;
   for (auto &e : result) out.push_back(e.kmer + " " + to_string(e.count) + " " + e.left + " " + e.right);

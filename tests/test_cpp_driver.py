@@ -159,12 +159,12 @@ def test_integration_md_alias_block_is_the_one_the_surface_test_compiles():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("k", [21, 51, 77])
+@pytest.mark.parametrize("k", [21, 51, 77, 99, 125])
 def test_driver_surface_runs_like_kcount_gpu_cpp(tmp_path, k):
     """the surface program run once: three target ranks, the reference's own sequence of calls, result = the oracle's"""
     exe = build_surface(tmp_path)
     rng = np.random.default_rng(79 + k)
-    reads, quals = random_reads(rng, 500, min_len=25, max_len=160, genome_len=1800)
+    reads, quals = random_reads(rng, 500, min_len=25, max_len=160 if k <= 77 else k + 110, genome_len=1800)  # (k = 99, 125: surface<128>)
     masked = ["".join(c.lower() if ord(x) < 33 + 20 else c for c, x in zip(r, q)) for r, q in zip(reads, quals)]
     out = subprocess.run([exe, str(k)], input="\n".join(masked) + "\n", capture_output=True, text=True, check=True).stdout
     (keys, counts, left, right), st = O.count_reads(reads, quals, k=k)

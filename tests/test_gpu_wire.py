@@ -32,7 +32,7 @@ def unpack(seq):
     return "".join(TO_BASE[b >> 4] + TO_BASE[b & 15] for b in seq)
 
 
-@pytest.mark.parametrize("k,nranks", [(21, 5), (33, 3), (51, 8), (77, 2)])
+@pytest.mark.parametrize("k,nranks", [(21, 5), (33, 3), (51, 8), (77, 2), (99, 4), (125, 6)])
 def test_supermers_and_round_trip(k, nranks):
     rng = np.random.default_rng(200 + k)
     reads, quals = random_reads(rng, 1200, min_len=k - 4, max_len=k + 110, genome_len=3000, n_rate=0.004)
@@ -144,3 +144,58 @@ def test_wire_kernels_on_odd_addresses_and_lengths(k):
     for r in res:
         for g, w in zip(r, want):
             assert g.shape == w.shape and (g == w).all()
+
+
+SUPERMER_DTYPE = np.dtype([("target", np.int32), ("offset", np.int32), ("len", np.uint16), ("pad", np.uint16)])
+
+
+def test_supermer_length_limit():
+    """A supermer's length travels in 16 bits: with one rank a read of 65535 bases is the one supermer
+    (0, 0, 65535), as the oracle says; one base more is KC_ERR_INVALID_ARG with the limit in kc_last_error, and the context
+    builds the first block as before afterwards."""
+    k = 21
+    rng = np.random.default_rng(65535)
+    read = "".join(rng.choice(list("ACGT"), size=65536))
+    o = O.Oracle(k, nranks=1, nthreads=1)
+    assert o.supermers(read[:65535]) == [(0, 0, 65535)]
+    o.close()
+    with pkg.KmerCounter(k, rank_me=0, rank_n=1) as kc:
+        for _ in range(2):
+            targets, offsets, lens, nvalid, packed = kc.build_supermers(read[:65535].encode())
+            assert (targets.tolist(), offsets.tolist(), lens.tolist()) == ([0], [0], [65535]) and nvalid == 65535 - k - 1
+            assert unpack(packed.tobytes())[:65535] == read[:65535]
+            with pytest.raises(pkg.KcError) as e:
+                kc.build_supermers(read.encode())
+            assert e.value.status == -1  # KC_ERR_INVALID_ARG
+            assert "65535" in pkg.lib().kc_last_error().decode()
+
+
+def test_supermer_capacity():
+    """room for one supermer less than there are: KC_ERR_CAPACITY, *n_out is the number needed, nothing is written behind
+    `capacity`; the call with that much room equals the oracle"""
+    import ctypes as C
+    k, nranks = 33, 3
+    rng = np.random.default_rng(2033)
+    reads, quals = random_reads(rng, 60, min_len=k - 2, max_len=k + 90, genome_len=2000, n_rate=0.004)
+    masked = ["".join(c.lower() if ord(x) < 33 + 20 else c for c, x in zip(r, q)) for r, q in zip(reads, quals)]
+    block = ("_".join(masked) + "_").encode()
+    o = O.Oracle(k, nranks=nranks, nthreads=1)
+    want, at = set(), 0
+    for m in masked:
+        for t, st, ln in o.supermers(m):
+            want.add((t, at + st, ln))
+        at += len(m) + 1
+    o.close()
+    need = len(want)
+    blk = np.frombuffer(block, dtype=np.uint8)
+    assert need > 64  # more than one wave's worth of starts
+    with pkg.KmerCounter(k, rank_me=0, rank_n=nranks) as kc:
+        out = np.frombuffer(bytearray(b"\xAB" * (SUPERMER_DTYPE.itemsize * (need + 8))), dtype=SUPERMER_DTYPE)
+        n, nk = C.c_uint32(0), C.c_uint32(0)
+        rc = pkg.lib().kc_build_supermers(kc._h, blk.ctypes.data, len(blk), 0, out.ctypes.data, need - 1, C.byref(n), C.byref(nk), None)
+        assert rc == -6 and n.value == need  # KC_ERR_CAPACITY
+        assert (out[need - 1:].view(np.uint8) == 0xAB).all()
+        rc = pkg.lib().kc_build_supermers(kc._h, blk.ctypes.data, len(blk), 0, out.ctypes.data, need, C.byref(n), C.byref(nk), None)
+        assert rc == 0 and n.value == need and nk.value == sum(ln - k - 1 for _, _, ln in want)
+        assert set(zip(out["target"][:need].tolist(), out["offset"][:need].tolist(), out["len"][:need].tolist())) == want
+        assert (out[need:].view(np.uint8) == 0xAB).all()
