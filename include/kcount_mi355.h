@@ -1374,6 +1374,65 @@ typedef struct kc_fasta_rec { /* 32 bytes */
 int kc_fasta_to_block(kc_ctx *ctx, const uint8_t *text, uint64_t len, int on_device, const kc_fasta_in_params *params, uint8_t *seqs,
                       uint64_t seqs_capacity, uint64_t *offsets, uint64_t ctgs_capacity, uint16_t *depths, kc_fasta_rec *recs,
                       uint64_t *n_ctgs, uint64_t *nbytes, uint64_t *consumed, kc_fasta_in_stats *stats);
+/* Reads -> FASTQ text, on the device: the inverse of kc_fastq_pairs / kc_fastq_to_packed, and the read side's twin of
+ * kc_fasta_text.  It plays the role of merge_reads' --dump-merged hand-over (src/merge_reads.cpp:335-340,379-382,635-647):
+ * "@r<id>/1", sequence, "+", qualities.  The reference also writes " #<original name>" behind the name; this library
+ * keeps no names, so the rules below are this project's own definition (tests/fastq_out_model.py);
+ * no parity with MetaHipMer's files beyond the four-line records and the r<id>/<mate> names is claimed.
+ *
+ * Input.  The reads lie as everywhere in the front end: read r is [offsets[r], offsets[r + 1]) of bases and of quals,
+ * no separators, offsets[0] == 0.  Without KC_FASTQ_OUT_PACKED both arrays are ASCII (kc_fastq_pairs' and
+ * kc_shuffle_reads' output).  With it quals must be NULL and bases holds the read cache's byte per base (kc_merge_pairs'
+ * and kc_fastq_to_packed's output): the base is "ACGTN"[b & 7], N for the codes 5 to 7, the quality the byte
+ * (b >> 3) + qual_offset of the context.  on_device applies to all arrays alike; device offsets and ids are 8-byte
+ * aligned, order 4-byte; bases, quals and text may have any alignment.
+ *
+ * The text.  For j = 0 .. n_order - 1, i = order[j], or i = j when order is NULL (n_order must then equal nreads):
+ *   '@' prefix number(i) [ "/1" | "/2" ] '\n' bases '\n' '+' '\n' qualities '\n'
+ * number(i) = ids ? ids[i] : first_id + (PAIRED ? i - (i & 1) : i), in decimal: the reference's r0/1 r0/2 r2/1 r2/2 for
+ * the prefix "r".  The suffix is there only with KC_FASTQ_OUT_PAIRED and follows the parity of i; order may hold the even
+ * reads only, which is how the mate-1 file of a pair of files is written.  Entries of order may repeat.  An empty read
+ * gives two empty lines (kc_fastq_pairs takes that).  A record is 6 + prefix_len + digits + (PAIRED ? 2 : 0) + 2 len bytes.
+ *
+ * The window: kc_fasta_text's contract.  The call writes bytes [first_byte, min(total, first_byte + capacity)) of the whole
+ * text to text; *written and *total are set on every success.  text == NULL: a size query.  first_byte > total:
+ * KC_ERR_INVALID_ARG (kc_last_error names the total); first_byte == total: KC_OK, 0 written.  The windows of any partition
+ * of [0, total), laid end to end, are the whole text.  All positions are 64-bit.  The records' starts are recomputed on
+ * every call, at 8 bytes per order entry: choose windows of megabytes.
+ *
+ * Errors.  On every error nothing is written through any pointer.  In front of ctx, kc_last_error naming the value,
+ * KC_ERR_INVALID_ARG: unknown flags, non-zero reserved words, prefix_len > KC_FASTQ_OUT_MAX_PREFIX, a prefix byte outside
+ * 0x21 .. 0x7E, PACKED with quals, no PACKED without quals where nreads > 0, NULL written / total / params, order == NULL
+ * with n_order != nreads; KC_ERR_CAPACITY: nreads or n_order of 2^32 or more.  Behind ctx and in front of the first
+ * store: PAIRED with an odd nreads is KC_ERR_INVALID_ARG; offsets that do not start at 0 or decrease are
+ * KC_ERR_INVALID_ARG; a read of 2^32 bytes or more is KC_ERR_CAPACITY; an order[j] >= nreads is KC_ERR_INVALID_ARG and
+ * kc_last_error names the lowest such j; a number over 9 999 999 999 999 999 (sixteen digits, what a 64-bit BCD word
+ * carries) is KC_ERR_INVALID_ARG, naming the lowest j.
+ *
+ * KC_FASTQ_OUT_CHECK.  Every base and quality byte of every read that order names (every call checks them all, whatever
+ * the window: check with the size query, then stream without the flag) must be 0x21 .. 0x7E in ASCII reads -- the text
+ * would not parse back otherwise -- and every code b & 7 must be <= 4 in packed reads.  The first offending byte is
+ * KC_ERR_BAD_BASE: first in (j, bases before qualities, position); kc_last_error names j, the read, the position and the
+ * byte.  A bad byte in a read that order leaves out is no error.  Without the flag bytes are copied or decoded as they are.
+ *
+ * The call needs neither table, results nor index, works in any state and with rank_n > 1, runs on the context's stream,
+ * returns when its work is done, keeps nothing in the context and frees its scratch: 8 bytes an order entry, with CHECK
+ * and an order 4 a read, 4 for every 4096 bytes of the window, beside the copies of host arrays.
+ */
+#define KC_FASTQ_OUT_PACKED 1u  /* bases holds the read cache's packed bytes, quals is NULL */
+#define KC_FASTQ_OUT_PAIRED 2u  /* reads 2p and 2p+1 are mates: names end in "/1" and "/2" */
+#define KC_FASTQ_OUT_CHECK  4u  /* validate every byte before the first store */
+#define KC_FASTQ_OUT_MAX_PREFIX 32
+typedef struct kc_fastq_out_params { /* 64 bytes */
+  uint32_t flags, prefix_len;
+  uint64_t first_id;
+  char prefix[32];
+  uint32_t reserved[4]; /* zero */
+} kc_fastq_out_params;
+int kc_fastq_text(kc_ctx *ctx, const uint8_t *bases, const uint8_t *quals, const uint64_t *offsets, uint64_t nreads,
+                  const uint32_t *order, uint64_t n_order, const uint64_t *ids, int on_device,
+                  const kc_fastq_out_params *params, uint64_t first_byte, uint8_t *text, uint64_t capacity,
+                  uint64_t *written, uint64_t *total);
 /* KmerDHT::kmer_exists / get_kmer_count / get_local_kmer_counts (src/kcount/kmer_dht.cpp:198-245) in bulk, against the
  * results kept in HBM: nq k-mers of num_longs words each, in either orientation; counts[i] = 0 (and left/right = 0)
  * when the k-mer did not survive.  The index over the results is built on the first call after kc_finalize.

@@ -270,6 +270,16 @@ KC_FASTA_HAS_DEPTH = 2
 KC_FASTA_LOWERED = 4
 KC_FASTA_RECODED = 8
 
+
+class kc_fastq_out_params(C.Structure):
+    _fields_ = [("flags", C.c_uint32), ("prefix_len", C.c_uint32), ("first_id", C.c_uint64), ("prefix", C.c_char * 32), ("reserved", C.c_uint32 * 4)]
+
+
+KC_FASTQ_OUT_PACKED = 1
+KC_FASTQ_OUT_PAIRED = 2
+KC_FASTQ_OUT_CHECK = 4
+KC_FASTQ_OUT_MAX_PREFIX = 32
+
 # every symbol include/kcount_mi355.h declares: (restype, argtypes)
 SYMBOLS = {
     "kc_abi_version": (C.c_int, []),
@@ -364,6 +374,8 @@ SYMBOLS = {
     "kc_fasta_to_block": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.POINTER(kc_fasta_in_params), C.c_void_p, C.c_uint64, C.c_void_p,
                                     C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                     C.POINTER(kc_fasta_in_stats)]),
+    "kc_fastq_text": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int,
+                                C.POINTER(kc_fastq_out_params), C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "kc_lookup": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "kc_dump_table": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
     "kc_get_stats": (C.c_int, [C.c_void_p, C.POINTER(kc_stats)]),

@@ -42,6 +42,7 @@
 #include "kc_shuffle.hpp"
 #include "kc_asm.hpp"
 #include "kc_fasta_in.hpp"
+#include "kc_fastq_out.hpp"
 
 using namespace kc;
 
@@ -3024,6 +3025,7 @@ extern "C" int kc_lookup(kc_ctx *c, const uint64_t *queries, uint64_t nq, int on
 #include "kc_api_close.hpp"  // kc_close_gaps
 #include "kc_api_shuffle.hpp"  // kc_shuffle_reads
 #include "kc_api_asm.hpp"  // kc_ctg_select, kc_fasta_text
+#include "kc_api_fastq_out.hpp"  // kc_fastq_text
 #include "kc_api_fasta_in.hpp"  // kc_fasta_to_block
 
 // ---- the contig pass (kc_ctg.hpp) ----------------------------------------------------------------------------------

@@ -3,7 +3,7 @@
 //
 // Several kinds are one kernel launched by different callers or in different passes; the name in angle brackets says
 // which (kc_align_lengths_kernel<close> is kc_close_gaps' launch of kc_align_lengths_kernel,
-// <assembly> kc_ctg_select's, <fasta> kc_fasta_text's, <fasta in> kc_fasta_to_block's).  The *_scan_kernel names are
+// <assembly> kc_ctg_select's, <fasta> kc_fasta_text's, <fasta in> kc_fasta_to_block's, <fastq out> kc_fastq_text's).  The *_scan_kernel names are
 // the uses of the one shared kc_scan_kernel (kc_scan.hpp) and keep the names they were first reported under.
 #pragma once
 
@@ -191,7 +191,16 @@
   X(KT_FA_DETAIL,          "kc_fa_detail_kernel") \
   X(KT_FA_RECS,            "kc_fa_recs_kernel") \
   X(KT_FA_BLOCK_SPANS,     "kc_fa_spans_kernel<block>") \
-  X(KT_FA_WRITE,           "kc_fa_write_kernel")
+  X(KT_FA_WRITE,           "kc_fa_write_kernel") \
+  X(KT_RTEXT_CHECK,        "kc_rtext_check_kernel") \
+  X(KT_RTEXT_BYTES,        "kc_rtext_bytes_kernel") \
+  X(KT_RTEXT_DETAIL,       "kc_rtext_detail_kernel") \
+  X(KT_RTEXT_SIZES,        "kc_rtext_sizes_kernel") \
+  X(KT_RTEXT_TILE_SCAN,    "kc_link_tile_scan_kernel<fastq out>") \
+  X(KT_RTEXT_SCAN,         "kc_asm_scan_kernel<fastq out>") \
+  X(KT_RTEXT_STARTS,       "kc_rtext_starts_kernel") \
+  X(KT_RTEXT_SPANS,        "kc_asm_spans_kernel<fastq out>") \
+  X(KT_RTEXT_WRITE,        "kc_rtext_write_kernel")
 
 enum {
 #define X(kind, name) kind,

@@ -6,6 +6,7 @@
   Adapters ctor + load_adapter_seqs (adapters.cpp)   .load_adapters(...)      kc_adapters_load
   Adapters::trim_pair / trim (adapters.cpp:171-273)  .trim_adapters(...)      kc_trim_adapters
   merge_reads' pair loop (merge_reads.cpp:469-648)   .merge_pairs(...)        kc_merge_pairs
+  merge_reads' --dump-merged (merge_reads.cpp:635)   .write_fastq(...)        kc_fastq_text
   KmerDHT ctor -> HashTableInserter::init             KmerCounter(k, ...)      kc_create
   count_kmers: per read quality-mask + process_seq    .submit_reads(...)       kc_submit_reads
   kmer_dht->flush_updates()                           .flush()                 kc_flush
@@ -1030,6 +1031,106 @@ class KmerCounter:
             path_or_fileobj.write((out.cpu().numpy() if dev else out).tobytes())
             first += written
         return total
+
+    def _fastq_call(self, bases, quals, offsets, order, ids, prefix, paired, first_id, nreads):
+        """what the windows of one FASTQ text share: call(first_byte, address, capacity, check) -> (written, total), and the side"""
+        pb, dev_b = _ptr(bases)
+        pq, dev_q = _ptr(quals)
+        po, dev_o = _ptr(offsets)
+        p_order, dev_r = _ptr(order)
+        p_ids, dev_i = _ptr(ids)
+        n = (len(offsets) - 1) if nreads is None else nreads
+        n_order = n if order is None else (order.numel() if dev_r else len(order))
+        if order is not None and not dev_r and (order.dtype.itemsize != 4 or not order.flags["C_CONTIGUOUS"]):
+            raise ValueError("order: a contiguous array of 32-bit indices")
+        if ids is not None and not dev_i and (ids.dtype.itemsize != 8 or not ids.flags["C_CONTIGUOUS"]):
+            raise ValueError("ids: a contiguous array of 64-bit numbers")
+        nbytes = bases.numel() if dev_b else len(bases)
+        dev = _side("bases", dev_b, quals=(dev_q, 0 if quals is None else nbytes), offsets=(dev_o, True),
+                    order=(dev_r, 0 if order is None else n_order), ids=(dev_i, 0 if ids is None else n))
+        keep = None
+        if quals is not None and not pq:  # reads without a byte: an empty array has no address, and NULL would mean packed
+            keep = self._out(dev, 1, np.uint8, zeroed=True)
+            pq = keep.ptr
+        prefix = prefix.encode() if isinstance(prefix, str) else bytes(prefix)
+        flags = (_lib.KC_FASTQ_OUT_PACKED if quals is None else 0) | (_lib.KC_FASTQ_OUT_PAIRED if paired else 0)
+        prm = _lib.kc_fastq_out_params(flags, len(prefix), first_id, prefix[:_lib.KC_FASTQ_OUT_MAX_PREFIX])
+
+        def call(first_byte, text, capacity, check=False, _keep=keep):
+            written, total = C.c_uint64(0), C.c_uint64(0)
+            if order is not None and not n_order:  # an empty selection: an empty text (an empty array has no address to pass)
+                return 0, 0
+            prm.flags = flags | (_lib.KC_FASTQ_OUT_CHECK if check else 0)
+            _lib.check(lib().kc_fastq_text(self._h, pb if nbytes else None, pq, po, n, p_order, n_order, p_ids, 1 if dev else 0, C.byref(prm),
+                                           first_byte, text, capacity, C.byref(written), C.byref(total)), "kc_fastq_text")
+            return int(written.value), int(total.value)
+
+        return call, dev
+
+    def fastq_text(self, bases, quals, offsets, order=None, ids=None, prefix="r", paired=False, first_id=0, check=False, first_byte=0,
+                   capacity=None, nreads=None):
+        """The FASTQ text of reads, formatted on the device (kc_fastq_text), as bytes: for every entry i
+        of order (None: all reads) the record "@" prefix number "\\n" bases "\\n+\\n" qualities "\\n", number = ids[i], or
+        first_id + i without ids.  bases / quals / offsets: the front end's layout, numpy arrays or device tensors;
+        quals=None: bases holds packed reads (merge_pairs', fastq_to_packed's output).  paired: reads 2p and 2p+1 are mates,
+        both numbered first_id + 2p, their names end in "/1" and "/2" (merge_reads' --dump-merged naming).  check: refuse
+        bytes that would not parse back (KC_ERR_BAD_BASE).  first_byte / capacity: bytes [first_byte, first_byte + capacity)
+        of the whole text only (capacity None: to its end)."""
+        call, dev = self._fastq_call(bases, quals, offsets, order, ids, prefix, paired, first_id, nreads)
+        self._hand_over(dev)
+        _, total = call(first_byte, None, 0, check)
+        want = total - first_byte if capacity is None else min(capacity, total - first_byte)
+        if want <= 0:
+            return b""
+        text = self._out(dev, want, np.uint8)
+        self._hand_over(dev)
+        written, _ = call(first_byte, text.ptr, want)
+        out = text.first(written)
+        return (out.cpu().numpy() if dev else out).tobytes()
+
+    def write_fastq(self, path_or_fileobj, bases, quals, offsets, order=None, ids=None, prefix="r", paired=False, first_id=0, check=False,
+                    nreads=None, window_bytes=256 << 20):
+        """fastq_text() streamed to a file: the text goes through one buffer of window_bytes, window after window, each
+        written to the file object (a path is opened "wb"; compression and the file itself stay with the caller's file
+        object).  check is made once, in front of the first window.  Returns the text's bytes.  The records' starts are
+        recomputed for every window: keep windows large."""
+        if window_bytes < 1:
+            raise ValueError("window_bytes: at least 1")
+        if isinstance(path_or_fileobj, (str, bytes)) or hasattr(path_or_fileobj, "__fspath__"):
+            with open(path_or_fileobj, "wb") as f:
+                return self.write_fastq(f, bases, quals, offsets, order, ids, prefix, paired, first_id, check, nreads, window_bytes)
+        call, dev = self._fastq_call(bases, quals, offsets, order, ids, prefix, paired, first_id, nreads)
+        self._hand_over(dev)
+        _, total = call(0, None, 0, check)
+        text = self._out(dev, min(window_bytes, total), np.uint8)
+        self._hand_over(dev)
+        first = 0
+        while first < total:
+            written, _ = call(first, text.ptr, text.n)
+            out = text.first(written)
+            path_or_fileobj.write((out.cpu().numpy() if dev else out).tobytes())
+            first += written
+        return total
+
+    def write_fastq_pairs(self, path1, path2, bases, quals, offsets, ids=None, prefix="r", first_id=0, check=False, first_pair=0, npairs=None,
+                          window_bytes=256 << 20):
+        """Interleaved pairs as a pair of FASTQ files: mates 1 (the even reads) go to path1 and mates 2 to path2, both
+        under the pair's number with "/1" and "/2" (write_fastq with paired=True and order = the even / the odd reads).
+        first_pair / npairs: pairs [first_pair, first_pair + npairs) only (npairs None: to the last), so that one part of
+        shuffle_reads (part_starts) goes to files of its own.  Returns both texts' bytes."""
+        total_pairs = (len(offsets) - 1) // 2
+        npairs = total_pairs - first_pair if npairs is None else npairs
+        if first_pair < 0 or npairs < 0 or first_pair + npairs > total_pairs:
+            raise ValueError("pairs [%d, %d) of %d" % (first_pair, first_pair + npairs, total_pairs))
+        dev = _ptr(bases)[1]
+        sizes = []
+        for mate, path in enumerate((path1, path2)):
+            order = np.arange(2 * first_pair + mate, 2 * (first_pair + npairs), 2, dtype=np.uint32)
+            if dev:
+                import torch
+                order = torch.from_numpy(order.view(np.int32)).to(self._torch_device())
+            sizes.append(self.write_fastq(path, bases, quals, offsets, order, ids, prefix, True, first_id, check, 2 * total_pairs, window_bytes))
+        return tuple(sizes)
 
     def fasta_to_block(self, text, partial=False, strict=False, default_depth=0, with_depths=False, with_records=True):
         """FASTA text parsed on the device into a seq block (kc_fasta_to_block), the inverse of
