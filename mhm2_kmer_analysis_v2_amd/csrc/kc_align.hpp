@@ -14,6 +14,7 @@
 // Which position a repeated slot keeps depends on arrival order and is never read; whether a slot is repeated does not.
 #pragma once
 #include "kc_common.hpp"
+#include "kc_kit.hpp"
 
 namespace kc {
 
@@ -39,8 +40,6 @@ struct AlignIndex {
   uint64_t mask;          // slots - 1
   uint32_t n_ctgs;
 };
-
-__device__ __forceinline__ uint32_t wave_count(bool p) { return (uint32_t)__popcll(__ballot(p)); }
 
 // A C G T in upper case only: a contig's N is no base here, and '_' ends every window
 __device__ __forceinline__ bool ai_is_acgt_upper(uint32_t c) { return c == 'A' || c == 'C' || c == 'G' || c == 'T'; }
@@ -176,10 +175,7 @@ __global__ void kc_align_lengths_kernel(const uint64_t *offsets, uint64_t nreads
     len = bad ? 0 : b - a;
   }
   if (bad) atomicMin((unsigned long long *)&st[ALS_BAD_READ], (unsigned long long)r);
-  for (int o = 32; o > 0; o >>= 1) {
-    const uint64_t t = __shfl_xor(len, o);
-    len = t > len ? t : len;
-  }
+  len = wave_max(len);
   if ((threadIdx.x & 63) == 0 && len) atomicMax((unsigned long long *)&st[ALS_MAX_LEN], (unsigned long long)len);
 }
 
@@ -273,11 +269,7 @@ __global__ void __launch_bounds__(ALIGN_TPB) kc_align_reads_kernel(AlignIndex ix
           break;
         }
         hit = true;
-        uint32_t lo = 0, hi = ix.n_ctgs - 1u;  // the contig: the last one that starts at or before pos
-        while (lo < hi) {
-          const uint32_t mid = lo + (hi - lo + 1u) / 2u;
-          if (ix.offs[mid] <= pos) lo = mid; else hi = mid - 1u;
-        }
+        const uint32_t lo = find_le(ix.offs, 0u, ix.n_ctgs - 1u, pos);  // the contig: the last one that starts at or before pos
         const int64_t j = (int64_t)pos - (int64_t)ix.offs[lo];
         const int64_t d = j - (orient ? (int64_t)(L - (uint32_t)k - p) : (int64_t)p);
         c = ((uint64_t)lo << 33) | ((uint64_t)(orient ? 1u : 0u) << 32) | (uint64_t)(uint32_t)(d + ALIGN_D_BIAS);
@@ -299,10 +291,7 @@ __global__ void __launch_bounds__(ALIGN_TPB) kc_align_reads_kernel(AlignIndex ix
     uint64_t m = cand[0];
 #pragma unroll
     for (int j = 1; j < WPL; j++) m = cand[j] < m ? cand[j] : m;
-    for (int o = 32; o > 0; o >>= 1) {
-      const uint64_t t = __shfl_xor(m, o);
-      m = t < m ? t : m;
-    }
+    m = wave_min(m);
     if (m == ALIGN_NO_CAND) break;
     uint32_t votes = 0;
 #pragma unroll

@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include <math.h>
+#include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -470,10 +471,8 @@ extern "C" kc_ctx *kc_create(const kc_config *cfg, int *status) {
   kc_ctx *c = nullptr;
   if (!cfg || cfg->rank_n < 1 || cfg->rank_n > 64 || cfg->rank_me < 0 || cfg->rank_me >= cfg->rank_n) st = KC_ERR_INVALID_ARG;
   if (!st) st = check_k(cfg->kmer_len);
-  if (!st && (cfg->device < 0 || cfg->device >= kc_device_count())) {
-    st = KC_ERR_NO_DEVICE;
-    snprintf(g_last_error, sizeof(g_last_error), "device %d requested, %d visible", cfg->device, kc_device_count());
-  }
+  if (!st && (cfg->device < 0 || cfg->device >= kc_device_count()))
+    st = fail(KC_ERR_NO_DEVICE, "device %d requested, %d visible", cfg->device, kc_device_count());
   if (!st) {
     c = new (std::nothrow) kc_ctx();
     if (!c) st = KC_ERR_OUT_OF_MEMORY;
@@ -744,8 +743,7 @@ static int pick_fast_arena(kc_ctx *c, uint64_t **arena, size_t bytes, uint32_t G
   (void)hipEventDestroy(e0);
   (void)hipEventDestroy(e1);
   if (!rc && !*arena) rc = KC_ERR_OUT_OF_MEMORY;
-  if (rc) snprintf(g_last_error, sizeof(g_last_error), "choosing the %s arena failed", what);
-  return rc;
+  return rc ? fail(rc, "choosing the %s arena failed", what) : KC_OK;
 }
 
 constexpr double KC_MAX_REGION_LOAD = 0.72;  // highest mean load of the region tables bk_init plans with
@@ -911,8 +909,7 @@ static int bk_ovf1_room(kc_ctx *c, uint64_t want, uint64_t *room) {
   int rc = sync_cb(c);
   if (rc) return rc;
   if (c->h_cb[CB_FATAL] & ~(c->inc_on ? (uint64_t)FATAL_OVF2 : 0ULL)) {  // (an instalment's full second list is bk_level2_pass' business)
-    snprintf(g_last_error, sizeof(g_last_error), "k-mer buffer: records were lost (fatal bits %llu)", (unsigned long long)c->h_cb[CB_FATAL]);
-    return KC_ERR_CAPACITY;
+    return fail(KC_ERR_CAPACITY, "k-mer buffer: records were lost (fatal bits %llu)", (unsigned long long)c->h_cb[CB_FATAL]);
   }
   uint64_t used = std::min<uint64_t>(c->h_cb[CB_OVF1], c->bb.ovf1_cap);
   // (inside a kc_shard_extract the list also holds records of other shards, which must not reach this shard's table: the
@@ -1201,8 +1198,7 @@ static int grow_ovf2(kc_ctx *c, uint64_t records, uint64_t keep) {
   DevBuf bigger;  // the old list goes with it, once its entries are copied
   if (bigger.reserve(records * w)) {
     (void)hipGetLastError();
-    snprintf(g_last_error, sizeof(g_last_error), "no memory for a region overflow list of %llu records", (unsigned long long)records);
-    return KC_ERR_OUT_OF_MEMORY;
+    return fail(KC_ERR_OUT_OF_MEMORY, "no memory for a region overflow list of %llu records", (unsigned long long)records);
   }
   if (keep) HIPCHK(hipMemcpyAsync(bigger.p, c->bb.ovf2, keep * w, hipMemcpyDeviceToDevice, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
@@ -1260,8 +1256,7 @@ static int bk_level2_pass(kc_ctx *c, bool instalment) {
   if (rc) return rc;
   const uint64_t fatal0 = c->h_cb[CB_FATAL];
   if ((fatal0 & ~(uint64_t)FATAL_OVF2) || (fatal0 && c->l1_dropped)) {  // (never a snapshot of a counter larger than its list)
-    snprintf(g_last_error, sizeof(g_last_error), "k-mer buffer: records were lost (fatal bits %llu)", (unsigned long long)fatal0);
-    return KC_ERR_CAPACITY;
+    return fail(KC_ERR_CAPACITY, "k-mer buffer: records were lost (fatal bits %llu)", (unsigned long long)fatal0);
   }
   // the list takes what an instalment's heavy regions spill: at least half of it free, or it grows
   if (instalment && c->h_cb[CB_OVF2] * 2 > c->bb.ovf2_cap) {
@@ -1281,11 +1276,9 @@ static int bk_level2_pass(kc_ctx *c, bool instalment) {
     if (rc) return rc;
     const uint64_t fatal = c->h_cb[CB_FATAL], asked = c->h_cb[CB_OVF2];
     if (!fatal) return KC_OK;
-    if (fatal != FATAL_OVF2 || attempt > 0) {
-      snprintf(g_last_error, sizeof(g_last_error), "k-mer buffer: records were lost %s (fatal bits %llu)",
-               instalment ? "in an instalment of level 2" : "building the regions", (unsigned long long)fatal);
-      return KC_ERR_CAPACITY;
-    }
+    if (fatal != FATAL_OVF2 || attempt > 0)
+      return fail(KC_ERR_CAPACITY, "k-mer buffer: records were lost %s (fatal bits %llu)",
+                  instalment ? "in an instalment of level 2" : "building the regions", (unsigned long long)fatal);
     if (c->l1_dropped) {
       rc = grow_ovf2(c, asked + asked / 16 + 4096, listed);
       if (!rc) rc = l2_snapshot(c, true);
@@ -1376,10 +1369,7 @@ static int bk_move_flagged(kc_ctx *c) {
   c->num_gpu_calls++;
   int rc = sync_cb(c);
   if (rc) return rc;
-  if (c->h_cb[CB_FATAL]) {
-    snprintf(g_last_error, sizeof(g_last_error), "region overflow list exhausted: raise max_kmers_buffered");
-    return KC_ERR_CAPACITY;
-  }
+  if (c->h_cb[CB_FATAL]) return fail(KC_ERR_CAPACITY, "region overflow list exhausted: raise max_kmers_buffered");
   const uint64_t nflag = c->h_cb[CB_FLAGGED_RECS], n2 = std::min<uint64_t>(c->h_cb[CB_OVF2], c->bb.ovf2_cap);
   if (nflag) {
     rc = ensure_room(c, nflag + n2);
@@ -1500,8 +1490,7 @@ static int bk_drain_to_table(kc_ctx *c) {
   rc = sync_cb(c);
   if (rc) return rc;
   if (c->h_cb[CB_FATAL] & ~(c->inc_on ? (uint64_t)FATAL_OVF2 : 0ULL)) {  // (what instalments of level 2 made is dropped here anyway)
-    snprintf(g_last_error, sizeof(g_last_error), "k-mer buffer overflow lists exhausted: raise max_kmers_buffered");
-    return KC_ERR_CAPACITY;
+    return fail(KC_ERR_CAPACITY, "k-mer buffer overflow lists exhausted: raise max_kmers_buffered");
   }
   rc = ensure_room(c, c->h_ctrs[CTR_INSERTED]);
   if (rc) return rc;
@@ -1608,11 +1597,10 @@ static int run_extract_device(kc_ctx *c, const uint8_t *bases, const uint8_t *qu
       chunk_tiles = std::min<uint64_t>(chunk_tiles, (1ULL << 28) / span);
     }
     uint64_t nt = std::min<uint64_t>(chunk_tiles, ((uint64_t)(end - p0) + span - 1) / span);
-    if (bk && over_capacity && c->sh.flow) {
-      snprintf(g_last_error, sizeof(g_last_error), "shard flow: more k-mers than max_kmers_buffered (%llu): raise it, or use kc_extract_partition / kc_insert_records",
-               (unsigned long long)c->bk_capacity);
-      return KC_ERR_CAPACITY;
-    }
+    if (bk && over_capacity && c->sh.flow)
+      return fail(KC_ERR_CAPACITY,
+                  "shard flow: more k-mers than max_kmers_buffered (%llu): raise it, or use kc_extract_partition / kc_insert_records",
+                  (unsigned long long)c->bk_capacity);
     if (bk && over_capacity) {
       int rc = bk_drain_to_table(c);  // out of buffer room: this and every later chunk take the table path
       if (rc) return rc;
@@ -1625,8 +1613,7 @@ static int run_extract_device(kc_ctx *c, const uint8_t *bases, const uint8_t *qu
       nt = std::max<uint64_t>(1, std::min<uint64_t>(nt, room / span));
       c->ovf1_ub += nt * span;  // what this launch can add to the list at most
       if (room < span) {  // a list smaller than one super-tile (test geometries only): nothing is bounded by it
-        snprintf(g_last_error, sizeof(g_last_error), "overflow list smaller than one tile of %llu positions: raise ovf_capacity", (unsigned long long)span);
-        return KC_ERR_CAPACITY;
+        return fail(KC_ERR_CAPACITY, "overflow list smaller than one tile of %llu positions: raise ovf_capacity", (unsigned long long)span);
       }
     }
     if (mode == MODE_INSERT && !bk) {
@@ -2032,16 +2019,10 @@ extern "C" int kc_build_supermers(kc_ctx *c, const char *seqs, uint64_t len, int
   HIPCHK(hipMemcpyAsync(h, c->d_sm_ctr, 24, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   if (h[4] | h[5]) return KC_ERR_BAD_BASE;
-  if (h[2]) {
-    snprintf(g_last_error, sizeof(g_last_error), "a supermer is longer than 65535 characters");
-    return KC_ERR_INVALID_ARG;
-  }
+  if (h[2]) return fail(KC_ERR_INVALID_ARG, "a supermer is longer than 65535 characters");
   *n_out = h[0];
   if (num_valid_kmers) *num_valid_kmers = h[1];
-  if (h[0] > capacity) {
-    snprintf(g_last_error, sizeof(g_last_error), "%u supermers, room for %u", h[0], capacity);
-    return KC_ERR_CAPACITY;
-  }
+  if (h[0] > capacity) return fail(KC_ERR_CAPACITY, "%u supermers, room for %u", h[0], capacity);
   if (h[0]) HIPCHK(hipMemcpy(out, c->sm_out.as<SupermerInfo>(), (size_t)h[0] * sizeof(kc_supermer), hipMemcpyDeviceToHost));
   if (packed_out) HIPCHK(hipMemcpy(packed_out, c->sm_packed.p, (size_t)(len + 1) / 2, hipMemcpyDeviceToHost));
   return KC_OK;
@@ -2101,11 +2082,9 @@ static int bin_end(kc_ctx *c, uint64_t *d_records, uint64_t seg_capacity, uint64
   if (rc) return rc;
   for (uint32_t j = 0; j < np; j++) h_counts[j] = c->wire6 ? c->h_w6cur[j] / WIRE6_UNIT_RECORDS : c->h_ctrs[CTR_BIN0 + j];
   if (c->h_ctrs[CTR_BAD_BASE]) return KC_ERR_BAD_BASE;
-  if (c->h_ctrs[CTR_OVERFLOW]) {
-    snprintf(g_last_error, sizeof(g_last_error), "a shard segment is too small: raise seg_capacity (%llu %s)", (unsigned long long)seg_capacity,
-             c->wire6 ? "units of four records per piece" : "records");
-    return KC_ERR_CAPACITY;
-  }
+  if (c->h_ctrs[CTR_OVERFLOW])
+    return fail(KC_ERR_CAPACITY, "a shard segment is too small: raise seg_capacity (%llu %s)", (unsigned long long)seg_capacity,
+                c->wire6 ? "units of four records per piece" : "records");
   return KC_OK;
 }
 
@@ -2175,17 +2154,11 @@ extern "C" int kc_insert_records(kc_ctx *c, const uint64_t *d_records, uint64_t 
         rc = bk_ovf1_room(c, n - done, &room);
         if (rc) return rc;
         uint64_t m = std::min<uint64_t>(n - done, room);
-        if (!m) {
-          snprintf(g_last_error, sizeof(g_last_error), "overflow list has no room: raise ovf_capacity");
-          return KC_ERR_CAPACITY;
-        }
+        if (!m) return fail(KC_ERR_CAPACITY, "overflow list has no room: raise ovf_capacity");
         c->ovf1_ub += m;
         if (w6) {
           if (m < n - done) m &= ~(uint64_t)(WIRE6_UNIT_RECORDS - 1);  // pieces of whole units
-          if (!m) {
-            snprintf(g_last_error, sizeof(g_last_error), "overflow list has no room: raise ovf_capacity");
-            return KC_ERR_CAPACITY;
-          }
+          if (!m) return fail(KC_ERR_CAPACITY, "overflow list has no room: raise ovf_capacity");
           rc = launch_l1_wire6(c, reinterpret_cast<const uint8_t *>(d_records) + done * 6, 0, 1, &m);
           if (rc) return rc;
           HIPCHK(hipGetLastError());
@@ -2325,21 +2298,15 @@ static int shard_extract_begin(kc_ctx *c, uint64_t *d_segments, uint64_t seg_wor
   if (n > 1 && (!d_segments || seg_words < SHARD_HDR + PMAX / 2)) return KC_ERR_INVALID_ARG;
   for (uint32_t d = 0; d < n; d++) h_words[d] = 0;
   if (c->finalized || c->bk_level2) return KC_ERR_STATE;
-  if (!bk_active(c)) {
-    snprintf(g_last_error, sizeof(g_last_error), "the shard flow needs the bucketed path (this context is on the global table): use kc_extract_partition / kc_insert_records");
-    return KC_ERR_STATE;
-  }
-  if (n > 1 && c->started && !c->sh.flow) {
-    snprintf(g_last_error, sizeof(g_last_error), "this pass already took k-mers by hash ownership (kc_submit_* / kc_insert_records): kc_reset first");
-    return KC_ERR_STATE;
-  }
+  if (!bk_active(c))
+    return fail(KC_ERR_STATE,
+                "the shard flow needs the bucketed path (this context is on the global table): use kc_extract_partition / kc_insert_records");
+  if (n > 1 && c->started && !c->sh.flow)
+    return fail(KC_ERR_STATE, "this pass already took k-mers by hash ownership (kc_submit_* / kc_insert_records): kc_reset first");
   HIPCHK(hipSetDevice(c->cfg.device));
   int rc = bk_init(c);
   if (rc) return rc;
-  if (n > c->gm.P1) {
-    snprintf(g_last_error, sizeof(g_last_error), "more shards (%u) than level-1 buckets (%u)", n, c->gm.P1);
-    return KC_ERR_INVALID_ARG;
-  }
+  if (n > c->gm.P1) return fail(KC_ERR_INVALID_ARG, "more shards (%u) than level-1 buckets (%u)", n, c->gm.P1);
   return KC_OK;
 }
 
@@ -2368,10 +2335,7 @@ static int shard_extract_pack(kc_ctx *c, bool anything, uint64_t *d_segments, ui
   // what found no room at level 1: this shard's own to its table, the rest behind the buckets of its destination
   rc = sync_cb(c);
   if (rc) return rc;
-  if (c->h_cb[CB_FATAL]) {
-    snprintf(g_last_error, sizeof(g_last_error), "k-mer buffer: records were lost (fatal bits %llu)", (unsigned long long)c->h_cb[CB_FATAL]);
-    return KC_ERR_CAPACITY;
-  }
+  if (c->h_cb[CB_FATAL]) return fail(KC_ERR_CAPACITY, "k-mer buffer: records were lost (fatal bits %llu)", (unsigned long long)c->h_cb[CB_FATAL]);
   const uint64_t n1 = std::min<uint64_t>(c->h_cb[CB_OVF1], c->bb.ovf1_cap);
   if (n1) {
     rc = ensure_room(c, n1);
@@ -2399,11 +2363,9 @@ static int shard_extract_pack(kc_ctx *c, bool anything, uint64_t *d_segments, ui
   bool patched = false;
   for (uint32_t d = 0; d < n; d++) {
     if (d == me) continue;
-    if (h_flags[d]) {
-      snprintf(g_last_error, sizeof(g_last_error), "the segment of shard %u is too small: %llu records (+ %llu loose) do not fit %llu words", d,
-               (unsigned long long)h_totals[d], (unsigned long long)h_loose[d], (unsigned long long)seg_words);
-      return KC_ERR_CAPACITY;
-    }
+    if (h_flags[d])
+      return fail(KC_ERR_CAPACITY, "the segment of shard %u is too small: %llu records (+ %llu loose) do not fit %llu words", d,
+                  (unsigned long long)h_totals[d], (unsigned long long)h_loose[d], (unsigned long long)seg_words);
     const uint32_t nb = shard_first_bucket(d + 1, c->gm.P1, n) - shard_first_bucket(d, c->gm.P1, n);
     h_words[d] = shard_header_words(nb) + h_wtotals[d] + h_loose[d] * (uint64_t)c->nl;  // (five bytes a record in the compact wire form)
     if (h_loose[d]) {
@@ -2476,10 +2438,7 @@ extern "C" int kc_shard_commit(kc_ctx *c, const uint64_t *d_segment, uint64_t nw
   if (c->started && !c->sh.flow) return KC_ERR_STATE;
   bool inside = false;
   for (auto &e : c->sh_extents) inside |= d_segment >= e.mem && d_segment + nwords <= e.mem + e.used;
-  if (!inside) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_shard_commit: the segment does not lie in memory handed out by kc_shard_reserve");
-    return KC_ERR_INVALID_ARG;
-  }
+  if (!inside) return fail(KC_ERR_INVALID_ARG, "kc_shard_commit: the segment does not lie in memory handed out by kc_shard_reserve");
   HIPCHK(hipSetDevice(c->cfg.device));
   int rc = bk_init(c);
   if (rc) return rc;
@@ -2496,8 +2455,7 @@ extern "C" int kc_shard_commit(kc_ctx *c, const uint64_t *d_segment, uint64_t nw
   const uint32_t wire = (uint32_t)(hdr[3] >> 56);
   if (hdr[0] != shard_signature(c) || nb != nbo || wire != shard_wire_of(c->gm) ||
       shard_header_words(nb) + rec_words + loose * (uint64_t)c->nl != nwords) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_shard_commit: not a segment for this shard (made by a context with another k, geometry or shard count?)");
-    return KC_ERR_INVALID_ARG;
+    return fail(KC_ERR_INVALID_ARG, "kc_shard_commit: not a segment for this shard (made by a context with another k, geometry or shard count?)");
   }
   {
     // the per-bucket counts must add up to the records the header announces: level 2 takes every bucket's address from
@@ -2509,21 +2467,15 @@ extern "C" int kc_shard_commit(kc_ctx *c, const uint64_t *d_segment, uint64_t nw
       sum += v;
       wsum += shard_bucket_words(v, (uint32_t)c->nl, wire);
     }
-    if (sum != nrec || wsum != rec_words) {
-      snprintf(g_last_error, sizeof(g_last_error),
-               "kc_shard_commit: the segment's bucket counts add up to %llu records in %llu words, its header says %llu in %llu",
-               (unsigned long long)sum, (unsigned long long)wsum, (unsigned long long)nrec, (unsigned long long)rec_words);
-      return KC_ERR_INVALID_ARG;
-    }
+    if (sum != nrec || wsum != rec_words)
+      return fail(KC_ERR_INVALID_ARG,
+                  "kc_shard_commit: the segment's bucket counts add up to %llu records in %llu words, its header says %llu in %llu",
+                  (unsigned long long)sum, (unsigned long long)wsum, (unsigned long long)nrec, (unsigned long long)rec_words);
   }
-  if (c->sh.F >= std::min<uint32_t>(FLAT_MAX, GMAX - c->gm.G)) {
-    snprintf(g_last_error, sizeof(g_last_error), "shard flow: %u segments received in one pass is the limit: use larger blocks", c->sh.F);
-    return KC_ERR_CAPACITY;
-  }
-  if (c->h_ctrs[CTR_INSERTED] + nrec + loose > c->bk_capacity) {
-    snprintf(g_last_error, sizeof(g_last_error), "shard flow: this shard would hold more k-mers than max_kmers_buffered (%llu)", (unsigned long long)c->bk_capacity);
-    return KC_ERR_CAPACITY;
-  }
+  if (c->sh.F >= std::min<uint32_t>(FLAT_MAX, GMAX - c->gm.G))
+    return fail(KC_ERR_CAPACITY, "shard flow: %u segments received in one pass is the limit: use larger blocks", c->sh.F);
+  if (c->h_ctrs[CTR_INSERTED] + nrec + loose > c->bk_capacity)
+    return fail(KC_ERR_CAPACITY, "shard flow: this shard would hold more k-mers than max_kmers_buffered (%llu)", (unsigned long long)c->bk_capacity);
   if (c->sh.nbo != nbo || !c->sh.d_cnt) {  // first segment for this geometry
     (void)c->sh.d_cnt.release();
     (void)c->sh.d_at.release();
@@ -2727,18 +2679,12 @@ static int bk_finalize(kc_ctx *c) {
       // every block ever taken must lie inside the arrays, or entries were dropped: run again with enough room
       if (c->h_cb[CB_OUT_RESERVED] <= c->out_cap) break;
       cap = c->h_ctrs[CTR_OUT] + slack;
-      if (attempt == 2) {
-        snprintf(g_last_error, sizeof(g_last_error), "result arrays still too small after three passes (%llu entries)", (unsigned long long)cap);
-        return KC_ERR_CAPACITY;
-      }
+      if (attempt == 2) return fail(KC_ERR_CAPACITY, "result arrays still too small after three passes (%llu entries)", (unsigned long long)cap);
       continue;
     }
     if (c->h_ctrs[CTR_OUT] <= c->out_cap) break;
     cap = c->h_ctrs[CTR_OUT];  // the pass only counted past the end: run it again with exactly enough room
-    if (attempt == 2) {
-      snprintf(g_last_error, sizeof(g_last_error), "result arrays still too small after three passes (%llu entries)", (unsigned long long)cap);
-      return KC_ERR_CAPACITY;
-    }
+    if (attempt == 2) return fail(KC_ERR_CAPACITY, "result arrays still too small after three passes (%llu entries)", (unsigned long long)cap);
   }
   rc = bk_move_flagged(c);
   if (rc) return rc;
@@ -2946,10 +2892,7 @@ extern "C" int kc_set_tuning(kc_ctx *c, const kc_tuning *t) {
 template <int NL>
 static int ensure_index(kc_ctx *c) {
   if (!c->d_index) {
-    if (c->out_n >= 0xFFFFFFFFull) {
-      snprintf(g_last_error, sizeof(g_last_error), "the lookup index holds at most 2^32 - 1 results");
-      return KC_ERR_CAPACITY;
-    }
+    if (c->out_n >= 0xFFFFFFFFull) return fail(KC_ERR_CAPACITY, "the lookup index holds at most 2^32 - 1 results");
     uint64_t cap = next_pow2(std::max<uint64_t>(1024, c->out_n * 2));
     KCTRY(c->d_index.reserve(cap * 4));
     c->index_cap = cap;
@@ -3093,11 +3036,9 @@ extern "C" int kc_submit_ctg_block(kc_ctx *c, const char *seqs, const uint16_t *
     uint64_t st[2] = {0, c->ctg_new};
     for (uint64_t p0 = 0; p0 < len;) {
       const uint64_t limit = c->ctg_cap / 4 * 3;
-      if (st[1] >= limit) {
-        snprintf(g_last_error, sizeof(g_last_error), "contig pass: %llu distinct k-mers fill the table kc_begin_ctg_kmers made (%llu slots)",
-                 (unsigned long long)st[1], (unsigned long long)c->ctg_cap);
-        return (int)KC_ERR_CAPACITY;
-      }
+      if (st[1] >= limit)
+        return fail((int)KC_ERR_CAPACITY, "contig pass: %llu distinct k-mers fill the table kc_begin_ctg_kmers made (%llu slots)",
+                    (unsigned long long)st[1], (unsigned long long)c->ctg_cap);
       const uint64_t p1 = std::min<uint64_t>(len, p0 + (limit - st[1]));
       const unsigned nblk = (unsigned)((p1 - p0 + 255) / 256);
       with_nl(c, [&](auto nl) {

@@ -37,15 +37,10 @@ static int ctg_index_run(kc_ctx *c, CallBufs &b, const uint8_t *seqs, uint64_t n
                      (const uint64_t *)d_in_offs, n_ctgs, d_offs, d_status));
   uint64_t h[AIS_COUNT];
   KCTRY(read_back(c, h, d_status));
-  if (h[AIS_BAD_BASE]) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_ctg_index_build: a byte outside ACGTN and '_' in the block");
-    return KC_ERR_BAD_BASE;
-  }
-  if (h[AIS_BAD_OFFSETS] || h[AIS_SEPARATORS] != n_ctgs) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_ctg_index_build: the offsets of %llu contigs do not match the block's %llu separators",
-             (unsigned long long)n_ctgs, (unsigned long long)h[AIS_SEPARATORS]);
-    return KC_ERR_INVALID_ARG;
-  }
+  if (h[AIS_BAD_BASE]) return fail(KC_ERR_BAD_BASE, "kc_ctg_index_build: a byte outside ACGTN and '_' in the block");
+  if (h[AIS_BAD_OFFSETS] || h[AIS_SEPARATORS] != n_ctgs)
+    return fail(KC_ERR_INVALID_ARG, "kc_ctg_index_build: the offsets of %llu contigs do not match the block's %llu separators",
+                (unsigned long long)n_ctgs, (unsigned long long)h[AIS_SEPARATORS]);
   if (nbytes) {
     KCTRY(launch_timed(c, KT_ALIGN_INDEX, kc_align_index_kernel<NL>, blocks_for(nbytes), tpb, 0, (const uint8_t *)d_seqs, (uint32_t)nbytes, c->k,
                        d_slots, cap - 1, d_status));
@@ -79,15 +74,11 @@ extern "C" int kc_ctg_index_build(kc_ctx *c, const uint8_t *seqs, uint64_t nbyte
                                   kc_ctg_index_stats *stats) {
   if (!c || !offsets || (nbytes && !seqs)) return KC_ERR_INVALID_ARG;
   if (stats) memset(stats, 0, sizeof(*stats));
-  if (nbytes >= (1ull << 31)) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_ctg_index_build: a block of %llu bytes, slots hold 32-bit positions (fewer than 2^31 bytes)",
-             (unsigned long long)nbytes);
-    return KC_ERR_CAPACITY;
-  }
+  if (nbytes >= (1ull << 31))
+    return fail(KC_ERR_CAPACITY, "kc_ctg_index_build: a block of %llu bytes, slots hold 32-bit positions (fewer than 2^31 bytes)",
+                (unsigned long long)nbytes);
   if (n_ctgs > nbytes) {  // every contig has its separator
-    snprintf(g_last_error, sizeof(g_last_error), "kc_ctg_index_build: %llu contigs in %llu bytes", (unsigned long long)n_ctgs,
-             (unsigned long long)nbytes);
-    return KC_ERR_INVALID_ARG;
+    return fail(KC_ERR_INVALID_ARG, "kc_ctg_index_build: %llu contigs in %llu bytes", (unsigned long long)n_ctgs, (unsigned long long)nbytes);
   }
   return call_with_bufs(c, [&](CallBufs &b) {
     AlignIndex ix;
@@ -163,11 +154,8 @@ static int align_run(kc_ctx *c, CallBufs &b, const uint8_t *bases, const uint64_
     stats->perfect = h[ALS_PERFECT];
   }
   if (!alns) return KC_OK;  // a size query
-  if (total > capacity) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_align_reads: %llu alignments, the array holds %llu", (unsigned long long)total,
-             (unsigned long long)capacity);
-    return KC_ERR_CAPACITY;
-  }
+  if (total > capacity)
+    return fail(KC_ERR_CAPACITY, "kc_align_reads: %llu alignments, the array holds %llu", (unsigned long long)total, (unsigned long long)capacity);
   uint4 *d_alns = (uint4 *)alns;
   if (!on_device) KCTRY(b.alloc(&d_alns, total * sizeof(kc_read_aln)));
   if (total) KCTRY(pass(KT_ALIGN_WRITE, d_alns));

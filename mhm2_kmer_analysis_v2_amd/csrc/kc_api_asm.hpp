@@ -15,14 +15,10 @@ static_assert(sizeof(asm_hdr_classes) == sizeof(asm_classes) && sizeof(asm_class
 // what both calls ask of a block's arguments behind the context
 static int asm_block_args(const char *who, const uint8_t *seqs, uint64_t nbytes, const uint64_t *offsets, uint64_t n_ctgs) {
   if (!offsets || (nbytes && !seqs)) return KC_ERR_INVALID_ARG;
-  if (nbytes >= (1ull << 31)) {
-    snprintf(g_last_error, sizeof(g_last_error), "%s: a block of %llu bytes, positions take 31 bits (fewer than 2^31 bytes)", who,
-             (unsigned long long)nbytes);
-    return KC_ERR_CAPACITY;
-  }
+  if (nbytes >= (1ull << 31))
+    return fail(KC_ERR_CAPACITY, "%s: a block of %llu bytes, positions take 31 bits (fewer than 2^31 bytes)", who, (unsigned long long)nbytes);
   if (n_ctgs > nbytes) {  // every contig has its separator
-    snprintf(g_last_error, sizeof(g_last_error), "%s: %llu contigs in %llu bytes", who, (unsigned long long)n_ctgs, (unsigned long long)nbytes);
-    return KC_ERR_INVALID_ARG;
+    return fail(KC_ERR_INVALID_ARG, "%s: %llu contigs in %llu bytes", who, (unsigned long long)n_ctgs, (unsigned long long)nbytes);
   }
   return KC_OK;
 }
@@ -71,15 +67,10 @@ static int asm_select_run(kc_ctx *c, CallBufs &b, const uint8_t *seqs, uint64_t 
                      (const uint64_t *)offs.d, n_ctgs, d_offs32, d_ais));
   uint64_t ha[AIS_COUNT];
   KCTRY(read_back(c, ha, d_ais));
-  if (ha[AIS_BAD_BASE]) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_ctg_select: a byte outside ACGTN and '_' in the block");
-    return KC_ERR_BAD_BASE;
-  }
-  if (ha[AIS_BAD_OFFSETS] || ha[AIS_SEPARATORS] != n_ctgs) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_ctg_select: the offsets of %llu contigs do not match the block's %llu separators",
-             (unsigned long long)n_ctgs, (unsigned long long)ha[AIS_SEPARATORS]);
-    return KC_ERR_INVALID_ARG;
-  }
+  if (ha[AIS_BAD_BASE]) return fail(KC_ERR_BAD_BASE, "kc_ctg_select: a byte outside ACGTN and '_' in the block");
+  if (ha[AIS_BAD_OFFSETS] || ha[AIS_SEPARATORS] != n_ctgs)
+    return fail(KC_ERR_INVALID_ARG, "kc_ctg_select: the offsets of %llu contigs do not match the block's %llu separators", (unsigned long long)n_ctgs,
+                (unsigned long long)ha[AIS_SEPARATORS]);
   const dim3 tpb(ASM_TPB);
   uint64_t h[AS_COUNT];
   memset(h, 0, sizeof(h));
@@ -166,21 +157,13 @@ extern "C" int kc_ctg_select(kc_ctx *c, const uint8_t *seqs, uint64_t nbytes, co
                              const kc_asm_params *p, uint32_t *order, uint64_t *n_selected, kc_asm_stats *stats) {
   // the ranges come before the context so that they can be checked where there is no device
   if (!p || !n_selected) return KC_ERR_INVALID_ARG;
-  if (p->flags & ~KC_ASM_BY_LENGTH) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_ctg_select: unknown flags 0x%x", p->flags & ~KC_ASM_BY_LENGTH);
-    return KC_ERR_INVALID_ARG;
-  }
+  if (p->flags & ~KC_ASM_BY_LENGTH) return fail(KC_ERR_INVALID_ARG, "kc_ctg_select: unknown flags 0x%x", p->flags & ~KC_ASM_BY_LENGTH);
   for (int i = 0; i < 6; i++)
-    if (p->reserved[i]) {
-      snprintf(g_last_error, sizeof(g_last_error), "kc_ctg_select: reserved[%d] is %u, not zero", i, p->reserved[i]);
-      return KC_ERR_INVALID_ARG;
-    }
+    if (p->reserved[i]) return fail(KC_ERR_INVALID_ARG, "kc_ctg_select: reserved[%d] is %u, not zero", i, p->reserved[i]);
   if (!c) return KC_ERR_INVALID_ARG;
   KCTRY(asm_block_args("kc_ctg_select", seqs, nbytes, offsets, n_ctgs));
-  if (on_device && (((uintptr_t)offsets & 7) || ((uintptr_t)order & 3))) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_ctg_select: device offsets are 8-byte aligned, order 4-byte");
-    return KC_ERR_INVALID_ARG;
-  }
+  if (on_device && (((uintptr_t)offsets & 7) || ((uintptr_t)order & 3)))
+    return fail(KC_ERR_INVALID_ARG, "kc_ctg_select: device offsets are 8-byte aligned, order 4-byte");
   return call_with_bufs(c, [&](CallBufs &b) { return asm_select_run(c, b, seqs, nbytes, offsets, n_ctgs, on_device, *p, order, n_selected, stats); });
 }
 
@@ -228,16 +211,11 @@ static int asm_text_run(kc_ctx *c, CallBufs &b, const uint8_t *seqs, uint64_t nb
   KCTRY(launch_timed(c, KT_ASM_TEXT_CHECK, kc_asm_text_check_kernel, blocks_for(std::max(n_ctgs + 1, n_order), ASM_TPB), tpb, 0, a));
   uint64_t h[AT_COUNT];
   KCTRY(read_back(c, h, a.st));
-  if (h[AT_BAD_OFFSETS]) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_fasta_text: the offsets of %llu contigs do not match the block's separators",
-             (unsigned long long)n_ctgs);
-    return KC_ERR_INVALID_ARG;
-  }
-  if (h[AT_BAD_ORDER] != ~0ull) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_fasta_text: order[%llu] names no contig (%llu contigs)", (unsigned long long)h[AT_BAD_ORDER],
-             (unsigned long long)n_ctgs);
-    return KC_ERR_INVALID_ARG;
-  }
+  if (h[AT_BAD_OFFSETS])
+    return fail(KC_ERR_INVALID_ARG, "kc_fasta_text: the offsets of %llu contigs do not match the block's separators", (unsigned long long)n_ctgs);
+  if (h[AT_BAD_ORDER] != ~0ull)
+    return fail(KC_ERR_INVALID_ARG, "kc_fasta_text: order[%llu] names no contig (%llu contigs)", (unsigned long long)h[AT_BAD_ORDER],
+                (unsigned long long)n_ctgs);
   // ---- the records' starts and the total
   uint64_t all = 0;
   if (n_order) {
@@ -246,11 +224,9 @@ static int asm_text_run(kc_ctx *c, CallBufs &b, const uint8_t *seqs, uint64_t nb
     KCTRY(launch_timed(c, KT_ASM_STARTS, kc_asm_starts_kernel, blocks_for(n_order + 1, ASM_TPB), tpb, 0, a));
     KCTRY(read_back(c, &all, a.st + AT_TOTAL, 1));
   }
-  if (first_byte > all) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_fasta_text: first_byte %llu is behind the text's %llu bytes", (unsigned long long)first_byte,
-             (unsigned long long)all);
-    return KC_ERR_INVALID_ARG;
-  }
+  if (first_byte > all)
+    return fail(KC_ERR_INVALID_ARG, "kc_fasta_text: first_byte %llu is behind the text's %llu bytes", (unsigned long long)first_byte,
+                (unsigned long long)all);
   const uint64_t n = text ? std::min(all - first_byte, capacity) : 0;
   if (n) {
     // ---- the window
@@ -279,47 +255,26 @@ extern "C" int kc_fasta_text(kc_ctx *c, const uint8_t *seqs, uint64_t nbytes, co
                              uint64_t *written, uint64_t *total) {
   // the ranges come before the context so that they can be checked where there is no device
   if (!p) return KC_ERR_INVALID_ARG;
-  if (p->line_width > 65535) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_fasta_text: line_width %u over 65535", p->line_width);
-    return KC_ERR_INVALID_ARG;
-  }
-  if (p->prefix_len > KC_FASTA_MAX_PREFIX) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_fasta_text: prefix_len %u over %d", p->prefix_len, KC_FASTA_MAX_PREFIX);
-    return KC_ERR_INVALID_ARG;
-  }
+  if (p->line_width > 65535) return fail(KC_ERR_INVALID_ARG, "kc_fasta_text: line_width %u over 65535", p->line_width);
+  if (p->prefix_len > KC_FASTA_MAX_PREFIX)
+    return fail(KC_ERR_INVALID_ARG, "kc_fasta_text: prefix_len %u over %d", p->prefix_len, KC_FASTA_MAX_PREFIX);
   for (uint32_t i = 0; i < p->prefix_len; i++)
-    if ((uint8_t)p->prefix[i] < 0x21 || (uint8_t)p->prefix[i] > 0x7E) {
-      snprintf(g_last_error, sizeof(g_last_error), "kc_fasta_text: prefix[%u] is 0x%02x, outside 0x21 .. 0x7e", i, (unsigned)(uint8_t)p->prefix[i]);
-      return KC_ERR_INVALID_ARG;
-    }
-  if (p->flags) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_fasta_text: unknown flags 0x%x", p->flags);
-    return KC_ERR_INVALID_ARG;
-  }
-  if (p->reserved0 || p->reserved[0] || p->reserved[1] || p->reserved[2] || p->reserved[3]) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_fasta_text: reserved words %u %u %u %u %u, not zero", p->reserved0, p->reserved[0], p->reserved[1],
-             p->reserved[2], p->reserved[3]);
-    return KC_ERR_INVALID_ARG;
-  }
-  if (!written || !total) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_fasta_text: %s is NULL", written ? "total" : "written");
-    return KC_ERR_INVALID_ARG;
-  }
-  if (!order && n_order != n_ctgs) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_fasta_text: order is NULL and n_order %llu is not the %llu contigs", (unsigned long long)n_order,
-             (unsigned long long)n_ctgs);
-    return KC_ERR_INVALID_ARG;
-  }
+    if ((uint8_t)p->prefix[i] < 0x21 || (uint8_t)p->prefix[i] > 0x7E)
+      return fail(KC_ERR_INVALID_ARG, "kc_fasta_text: prefix[%u] is 0x%02x, outside 0x21 .. 0x7e", i, (unsigned)(uint8_t)p->prefix[i]);
+  if (p->flags) return fail(KC_ERR_INVALID_ARG, "kc_fasta_text: unknown flags 0x%x", p->flags);
+  if (p->reserved0 || p->reserved[0] || p->reserved[1] || p->reserved[2] || p->reserved[3])
+    return fail(KC_ERR_INVALID_ARG, "kc_fasta_text: reserved words %u %u %u %u %u, not zero", p->reserved0, p->reserved[0], p->reserved[1],
+                p->reserved[2], p->reserved[3]);
+  if (!written || !total) return fail(KC_ERR_INVALID_ARG, "kc_fasta_text: %s is NULL", written ? "total" : "written");
+  if (!order && n_order != n_ctgs)
+    return fail(KC_ERR_INVALID_ARG, "kc_fasta_text: order is NULL and n_order %llu is not the %llu contigs", (unsigned long long)n_order,
+                (unsigned long long)n_ctgs);
   if (!c) return KC_ERR_INVALID_ARG;
   KCTRY(asm_block_args("kc_fasta_text", seqs, nbytes, offsets, n_ctgs));
-  if (on_device && (((uintptr_t)offsets & 7) || ((uintptr_t)order & 3))) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_fasta_text: device offsets are 8-byte aligned, order 4-byte");
-    return KC_ERR_INVALID_ARG;
-  }
-  if (n_order > 0xFFFFFFFFull) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_fasta_text: %llu records, the window's table holds 32-bit record indices", (unsigned long long)n_order);
-    return KC_ERR_CAPACITY;
-  }
+  if (on_device && (((uintptr_t)offsets & 7) || ((uintptr_t)order & 3)))
+    return fail(KC_ERR_INVALID_ARG, "kc_fasta_text: device offsets are 8-byte aligned, order 4-byte");
+  if (n_order > 0xFFFFFFFFull)
+    return fail(KC_ERR_CAPACITY, "kc_fasta_text: %llu records, the window's table holds 32-bit record indices", (unsigned long long)n_order);
   return call_with_bufs(c, [&](CallBufs &b) {
     return asm_text_run(c, b, seqs, nbytes, offsets, n_ctgs, order, n_order, on_device, *p, first_byte, text, capacity, written, total);
   });

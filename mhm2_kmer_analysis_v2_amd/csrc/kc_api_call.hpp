@@ -3,13 +3,11 @@
 // kc_api_sort.hpp.
 
 static int no_ctg_index(const char *who) {
-  snprintf(g_last_error, sizeof(g_last_error), "%s: no contig index (kc_ctg_index_build)", who);
-  return KC_ERR_STATE;
+  return fail(KC_ERR_STATE, "%s: no contig index (kc_ctg_index_build)", who);
 }
 
 static int misaligned_records(const char *who) {
-  snprintf(g_last_error, sizeof(g_last_error), "%s: a device record array is 16-byte aligned", who);
-  return KC_ERR_INVALID_ARG;
+  return fail(KC_ERR_INVALID_ARG, "%s: a device record array is 16-byte aligned", who);
 }
 
 // the reads' nreads + 1 offsets: no reads, nothing to copy
@@ -33,8 +31,7 @@ template <class... A> static int lowest_bad(kc_ctx *c, const uint64_t *d_bad, co
   uint64_t bad = ~0ull;
   KCTRY(read_back(c, &bad, d_bad, 1));
   if (bad == ~0ull) return KC_OK;
-  snprintf(g_last_error, sizeof(g_last_error), fmt, who, (unsigned long long)bad, more...);
-  return KC_ERR_INVALID_ARG;
+  return fail(KC_ERR_INVALID_ARG, fmt, who, (unsigned long long)bad, more...);
 }
 
 // ---- the checks on reads, records and pairs: nothing has been stored when one returns ----------------------------------
@@ -54,11 +51,9 @@ static int check_read_lengths(kc_ctx *c, int kind, const char *who, const uint64
     HIPCHK(hipMemcpyAsync(h + ALS_BAD_READ, d_als + ALS_BAD_READ, 8, hipMemcpyDeviceToHost, c->stream));
   if (last) HIPCHK(hipMemcpyAsync(last, d_offs + nreads, 8, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
-  if (h[ALS_BAD_READ] != ~0ull) {
-    snprintf(g_last_error, sizeof(g_last_error), "%s: read %llu is longer than %d bases, or its offsets decrease", who,
-             (unsigned long long)h[ALS_BAD_READ], KC_ALIGN_MAX_READ_LEN);
-    return KC_ERR_INVALID_ARG;
-  }
+  if (h[ALS_BAD_READ] != ~0ull)
+    return fail(KC_ERR_INVALID_ARG, "%s: read %llu is longer than %d bases, or its offsets decrease", who, (unsigned long long)h[ALS_BAD_READ],
+                KC_ALIGN_MAX_READ_LEN);
   if (max_len) *max_len = h[ALS_MAX_LEN];
   return KC_OK;
 }

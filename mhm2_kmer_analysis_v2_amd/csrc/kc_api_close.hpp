@@ -170,10 +170,8 @@ static int close_run(kc_ctx *c, CallBufs &b, const CloseIo &io, const kc_close_p
   HIPCHK(hipMemcpyAsync(h, st, sizeof(h), hipMemcpyDeviceToHost, c->stream));
   KCTRY(read_back(c, hl, a.st));
   const uint64_t total = h[CLS_SEG_TOTAL], fill_total = h[CLS_FILL_TOTAL];
-  if (total >= (1ull << 31)) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_close_gaps: the scaffolds are %llu bytes, a block holds fewer than 2^31", (unsigned long long)total);
-    return KC_ERR_CAPACITY;
-  }
+  if (total >= (1ull << 31))
+    return fail(KC_ERR_CAPACITY, "kc_close_gaps: the scaffolds are %llu bytes, a block holds fewer than 2^31", (unsigned long long)total);
   const bool fits = io.seqs_out && io.capacity >= total;
   const bool want_recs = fits && io.scaffolds_out != nullptr;
   uint8_t *buf = nullptr;
@@ -241,11 +239,8 @@ static int close_run(kc_ctx *c, CallBufs &b, const CloseIo &io, const kc_close_p
     s.disputed_cols = h[CLS_DISPUTED];
     *io.stats = s;
   }
-  if (io.seqs_out && !fits) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_close_gaps: %llu bytes, the array holds %llu", (unsigned long long)total,
-             (unsigned long long)io.capacity);
-    return KC_ERR_CAPACITY;
-  }
+  if (io.seqs_out && !fits)
+    return fail(KC_ERR_CAPACITY, "kc_close_gaps: %llu bytes, the array holds %llu", (unsigned long long)total, (unsigned long long)io.capacity);
   return KC_OK;
 }
 
@@ -256,53 +251,28 @@ extern "C" int kc_close_gaps(kc_ctx *c, const uint8_t *bases, const uint64_t *of
                              kc_close_stats *stats) {
   // the ranges come before the context so that they can be checked where there is no device
   if (!p || !nbytes_out) return KC_ERR_INVALID_ARG;
-  if (p->end_slack > KC_LINK_MAX_SLACK) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_close_gaps: end_slack %u over %d", p->end_slack, KC_LINK_MAX_SLACK);
-    return KC_ERR_INVALID_ARG;
-  }
-  if (p->max_overlap > KC_LINK_MAX_OVERLAP || p->max_splint_gap > KC_LINK_MAX_SLACK) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_close_gaps: max_overlap %u over %d or max_splint_gap %u over %d", p->max_overlap,
-             KC_LINK_MAX_OVERLAP, p->max_splint_gap, KC_LINK_MAX_SLACK);
-    return KC_ERR_INVALID_ARG;
-  }
-  if (p->min_reads < 1) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_close_gaps: min_reads %u below 1", p->min_reads);
-    return KC_ERR_INVALID_ARG;
-  }
-  if (p->min_agree_permille > 1000) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_close_gaps: min_agree_permille %u over 1000", p->min_agree_permille);
-    return KC_ERR_INVALID_ARG;
-  }
-  if (p->max_read_alns < 2 || p->max_read_alns > KC_LINK_MAX_READ_ALNS) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_close_gaps: max_read_alns %u outside 2 .. %d", (unsigned)p->max_read_alns,
-             KC_LINK_MAX_READ_ALNS);
-    return KC_ERR_INVALID_ARG;
-  }
-  if (p->flags) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_close_gaps: unknown flags 0x%x", (unsigned)p->flags);
-    return KC_ERR_INVALID_ARG;
-  }
+  if (p->end_slack > KC_LINK_MAX_SLACK) return fail(KC_ERR_INVALID_ARG, "kc_close_gaps: end_slack %u over %d", p->end_slack, KC_LINK_MAX_SLACK);
+  if (p->max_overlap > KC_LINK_MAX_OVERLAP || p->max_splint_gap > KC_LINK_MAX_SLACK)
+    return fail(KC_ERR_INVALID_ARG, "kc_close_gaps: max_overlap %u over %d or max_splint_gap %u over %d", p->max_overlap, KC_LINK_MAX_OVERLAP,
+                p->max_splint_gap, KC_LINK_MAX_SLACK);
+  if (p->min_reads < 1) return fail(KC_ERR_INVALID_ARG, "kc_close_gaps: min_reads %u below 1", p->min_reads);
+  if (p->min_agree_permille > 1000) return fail(KC_ERR_INVALID_ARG, "kc_close_gaps: min_agree_permille %u over 1000", p->min_agree_permille);
+  if (p->max_read_alns < 2 || p->max_read_alns > KC_LINK_MAX_READ_ALNS)
+    return fail(KC_ERR_INVALID_ARG, "kc_close_gaps: max_read_alns %u outside 2 .. %d", (unsigned)p->max_read_alns, KC_LINK_MAX_READ_ALNS);
+  if (p->flags) return fail(KC_ERR_INVALID_ARG, "kc_close_gaps: unknown flags 0x%x", (unsigned)p->flags);
   if (!c || (nreads && (!offsets || !bases)) || (n_alns && !alns) || !scaffolds || !members || nreads > 0xFFFFFFFFull) return KC_ERR_INVALID_ARG;
   if (on_device && (((uintptr_t)alns | (uintptr_t)scaffolds | (uintptr_t)members | (uintptr_t)scaffolds_out | (uintptr_t)members_out |
                      (uintptr_t)closures) & 15))
     return misaligned_records("kc_close_gaps");
-  if (on_device && (((uintptr_t)offsets | (uintptr_t)offsets_out) & 7)) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_close_gaps: device offsets are 8-byte aligned");
-    return KC_ERR_INVALID_ARG;
-  }
+  if (on_device && (((uintptr_t)offsets | (uintptr_t)offsets_out) & 7))
+    return fail(KC_ERR_INVALID_ARG, "kc_close_gaps: device offsets are 8-byte aligned");
   if (!c->ai_ready) return no_ctg_index("kc_close_gaps");
-  if (c->ai.n_ctgs == 0 || c->ai.n_ctgs >= (1u << 31)) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_close_gaps: %u contigs, oriented node ids are 32-bit (1 .. 2^31 - 1 contigs)", c->ai.n_ctgs);
-    return c->ai.n_ctgs ? KC_ERR_CAPACITY : KC_ERR_STATE;
-  }
-  if (n_alns > 0xFFFFFFFFull) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_close_gaps: %llu records, a join counts its candidates in 32 bits", (unsigned long long)n_alns);
-    return KC_ERR_CAPACITY;
-  }
-  if (n_scaffolds == 0) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_close_gaps: scaffold 0 is invalid (no scaffolds over %u contigs)", c->ai.n_ctgs);
-    return KC_ERR_INVALID_ARG;
-  }
+  if (c->ai.n_ctgs == 0 || c->ai.n_ctgs >= (1u << 31))
+    return fail(c->ai.n_ctgs ? KC_ERR_CAPACITY : KC_ERR_STATE, "kc_close_gaps: %u contigs, oriented node ids are 32-bit (1 .. 2^31 - 1 contigs)",
+                c->ai.n_ctgs);
+  if (n_alns > 0xFFFFFFFFull)
+    return fail(KC_ERR_CAPACITY, "kc_close_gaps: %llu records, a join counts its candidates in 32 bits", (unsigned long long)n_alns);
+  if (n_scaffolds == 0) return fail(KC_ERR_INVALID_ARG, "kc_close_gaps: scaffold 0 is invalid (no scaffolds over %u contigs)", c->ai.n_ctgs);
   const CloseIo io{bases,    offsets,     nreads,        alns,        n_alns,   scaffolds,  n_scaffolds, members, on_device,
                    seqs_out, capacity,    offsets_out,   scaffolds_out, members_out, closures, nbytes_out,  stats};
   return call_with_bufs(c, [&](CallBufs &b) { return close_run(c, b, io, *p); });

@@ -99,22 +99,14 @@ static int depth_run(kc_ctx *c, CallBufs &b, const kc_gap_aln *alns, uint64_t n_
 extern "C" int kc_aln_depths(kc_ctx *c, const kc_gap_aln *alns, uint64_t n_alns, uint64_t nreads, int on_device, uint32_t min_score,
                              uint32_t min_len, uint32_t edge_clip, uint32_t flags, uint16_t *depths, kc_ctg_depth *ctgs, kc_depth_stats *stats) {
   // the ranges come before the context so that they can be checked where there is no device
-  if (edge_clip > KC_DEPTH_MAX_EDGE || (flags & ~(KC_DEPTH_BEST_ONLY | KC_DEPTH_PER_CONTIG))) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_aln_depths: edge_clip %u over %d or unknown flags 0x%x", edge_clip, KC_DEPTH_MAX_EDGE, flags);
-    return KC_ERR_INVALID_ARG;
-  }
+  if (edge_clip > KC_DEPTH_MAX_EDGE || (flags & ~(KC_DEPTH_BEST_ONLY | KC_DEPTH_PER_CONTIG)))
+    return fail(KC_ERR_INVALID_ARG, "kc_aln_depths: edge_clip %u over %d or unknown flags 0x%x", edge_clip, KC_DEPTH_MAX_EDGE, flags);
   if (!c || (n_alns && !alns)) return KC_ERR_INVALID_ARG;
   if (on_device && (((uintptr_t)alns | (uintptr_t)ctgs) & 15)) return misaligned_records("kc_aln_depths");
-  if (on_device && ((uintptr_t)depths & 1)) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_aln_depths: a device depth array is 2-byte aligned");
-    return KC_ERR_INVALID_ARG;
-  }
+  if (on_device && ((uintptr_t)depths & 1)) return fail(KC_ERR_INVALID_ARG, "kc_aln_depths: a device depth array is 2-byte aligned");
   if (!c->ai_ready) return no_ctg_index("kc_aln_depths");
-  if (n_alns > 0xFFFFFFFFull) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_aln_depths: %llu records, a depth and a best record's index hold 32 bits",
-             (unsigned long long)n_alns);
-    return KC_ERR_CAPACITY;
-  }
+  if (n_alns > 0xFFFFFFFFull)
+    return fail(KC_ERR_CAPACITY, "kc_aln_depths: %llu records, a depth and a best record's index hold 32 bits", (unsigned long long)n_alns);
   return call_with_bufs(c, [&](CallBufs &b) {
     return depth_run(c, b, alns, n_alns, nreads, on_device, min_score, min_len, edge_clip, flags, depths, ctgs, stats);
   });
@@ -183,26 +175,17 @@ extern "C" int kc_pair_inserts(kc_ctx *c, const uint64_t *offsets, uint64_t nrea
                                uint32_t min_score, uint32_t min_len, uint32_t max_insert, uint64_t *hist, kc_pair_rec *pairs,
                                kc_insert_stats *stats) {
   // the ranges come before the context so that they can be checked where there is no device
-  if (max_insert < 1 || max_insert > KC_INSERT_MAX) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_pair_inserts: max_insert %u outside 1 .. %d", max_insert, KC_INSERT_MAX);
-    return KC_ERR_INVALID_ARG;
-  }
-  if (nreads & 1) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_pair_inserts: %llu reads are no pairs (reads 2p and 2p + 1 are mates)",
-             (unsigned long long)nreads);
-    return KC_ERR_INVALID_ARG;
-  }
+  if (max_insert < 1 || max_insert > KC_INSERT_MAX)
+    return fail(KC_ERR_INVALID_ARG, "kc_pair_inserts: max_insert %u outside 1 .. %d", max_insert, KC_INSERT_MAX);
+  if (nreads & 1)
+    return fail(KC_ERR_INVALID_ARG, "kc_pair_inserts: %llu reads are no pairs (reads 2p and 2p + 1 are mates)", (unsigned long long)nreads);
   if (!c || (nreads && !offsets) || (n_alns && !alns) || nreads > 0xFFFFFFFFull) return KC_ERR_INVALID_ARG;
   if (on_device && (((uintptr_t)alns | (uintptr_t)pairs) & 15)) return misaligned_records("kc_pair_inserts");
-  if (on_device && (((uintptr_t)offsets | (uintptr_t)hist) & 7)) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_pair_inserts: device offsets and bins are 8-byte aligned");
-    return KC_ERR_INVALID_ARG;
-  }
+  if (on_device && (((uintptr_t)offsets | (uintptr_t)hist) & 7))
+    return fail(KC_ERR_INVALID_ARG, "kc_pair_inserts: device offsets and bins are 8-byte aligned");
   if (!c->ai_ready) return no_ctg_index("kc_pair_inserts");
-  if (n_alns > 0xFFFFFFFFull) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_pair_inserts: %llu records, a best record's index holds 32 bits", (unsigned long long)n_alns);
-    return KC_ERR_CAPACITY;
-  }
+  if (n_alns > 0xFFFFFFFFull)
+    return fail(KC_ERR_CAPACITY, "kc_pair_inserts: %llu records, a best record's index holds 32 bits", (unsigned long long)n_alns);
   return call_with_bufs(c, [&](CallBufs &b) {
     return pair_run(c, b, offsets, nreads, alns, n_alns, on_device, min_score, min_len, max_insert, hist, pairs, stats);
   });

@@ -113,13 +113,10 @@ static int fasta_in_run(kc_ctx *c, CallBufs &b, const uint8_t *text, uint64_t le
   if (a.n_ctgs) KCTRY(launch_timed(c, KT_FA_RECS, kc_fa_recs_kernel, blocks_for(a.n_ctgs, FA_TPB), tpb, 0, a));
   KCTRY(read_back(c, h, st));
   if (h[FAS_KEY] != ~0ull) {
-    if (h[FAS_KEY] & 1) {
-      snprintf(g_last_error, sizeof(g_last_error), "fasta: line %llu column %llu: byte 0x%02x is not a base", (unsigned long long)h[FAS_ERR_LINE],
-               (unsigned long long)h[FAS_ERR_COL], (unsigned)h[FAS_ERR_BYTE]);
-      return KC_ERR_BAD_BASE;
-    }
-    snprintf(g_last_error, sizeof(g_last_error), "fasta: line %llu: sequence before the first header", (unsigned long long)h[FAS_ERR_LINE]);
-    return KC_ERR_INVALID_ARG;
+    if (h[FAS_KEY] & 1)
+      return fail(KC_ERR_BAD_BASE, "fasta: line %llu column %llu: byte 0x%02x is not a base", (unsigned long long)h[FAS_ERR_LINE],
+                  (unsigned long long)h[FAS_ERR_COL], (unsigned)h[FAS_ERR_BYTE]);
+    return fail(KC_ERR_INVALID_ARG, "fasta: line %llu: sequence before the first header", (unsigned long long)h[FAS_ERR_LINE]);
   }
   // ---- the totals
   *n_ctgs = a.n_ctgs;
@@ -140,17 +137,13 @@ static int fasta_in_run(kc_ctx *c, CallBufs &b, const uint8_t *text, uint64_t le
     s.with_depth = h[FAS_WITH_DEPTH];
     *stats = s;
   }
-  if (a.nbytes >= (1ull << 31)) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_fasta_to_block: a block of %llu bytes, positions take 31 bits (fewer than 2^31 bytes)",
-             (unsigned long long)a.nbytes);
-    return KC_ERR_CAPACITY;
-  }
+  if (a.nbytes >= (1ull << 31))
+    return fail(KC_ERR_CAPACITY, "kc_fasta_to_block: a block of %llu bytes, positions take 31 bits (fewer than 2^31 bytes)",
+                (unsigned long long)a.nbytes);
   if (!seqs || !offsets) return KC_OK;  // a size query
-  if (a.nbytes > seqs_capacity || a.n_ctgs > ctgs_capacity) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_fasta_to_block: %llu contigs in %llu bytes do not fit the arrays", (unsigned long long)a.n_ctgs,
-             (unsigned long long)a.nbytes);
-    return KC_ERR_CAPACITY;
-  }
+  if (a.nbytes > seqs_capacity || a.n_ctgs > ctgs_capacity)
+    return fail(KC_ERR_CAPACITY, "kc_fasta_to_block: %llu contigs in %llu bytes do not fit the arrays", (unsigned long long)a.n_ctgs,
+                (unsigned long long)a.nbytes);
   // ---- the block
   StagedOut<uint8_t> out{seqs, dev, (size_t)a.nbytes};
   StagedOut<uint16_t> dep{depths, dev, (size_t)a.nbytes * 2};
@@ -186,28 +179,15 @@ extern "C" int kc_fasta_to_block(kc_ctx *c, const uint8_t *text, uint64_t len, i
                                  uint64_t seqs_capacity, uint64_t *offsets, uint64_t ctgs_capacity, uint16_t *depths, kc_fasta_rec *recs, uint64_t *n_ctgs,
                                  uint64_t *nbytes, uint64_t *consumed, kc_fasta_in_stats *stats) {
   // the ranges come before the context so that they can be checked where there is no device
-  if (!p || !n_ctgs || !nbytes) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_fasta_to_block: %s is NULL", !p ? "params" : !n_ctgs ? "n_ctgs" : "nbytes");
-    return KC_ERR_INVALID_ARG;
-  }
-  if (p->flags & ~(KC_FASTA_PARTIAL | KC_FASTA_STRICT)) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_fasta_to_block: unknown flags 0x%x", p->flags & ~(KC_FASTA_PARTIAL | KC_FASTA_STRICT));
-    return KC_ERR_INVALID_ARG;
-  }
-  if (p->default_depth > 65535) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_fasta_to_block: default_depth %u over 65535", p->default_depth);
-    return KC_ERR_INVALID_ARG;
-  }
+  if (!p || !n_ctgs || !nbytes) return fail(KC_ERR_INVALID_ARG, "kc_fasta_to_block: %s is NULL", !p ? "params" : !n_ctgs ? "n_ctgs" : "nbytes");
+  if (p->flags & ~(KC_FASTA_PARTIAL | KC_FASTA_STRICT))
+    return fail(KC_ERR_INVALID_ARG, "kc_fasta_to_block: unknown flags 0x%x", p->flags & ~(KC_FASTA_PARTIAL | KC_FASTA_STRICT));
+  if (p->default_depth > 65535) return fail(KC_ERR_INVALID_ARG, "kc_fasta_to_block: default_depth %u over 65535", p->default_depth);
   for (int i = 0; i < 6; i++)
-    if (p->reserved[i]) {
-      snprintf(g_last_error, sizeof(g_last_error), "kc_fasta_to_block: reserved[%d] is %u, not zero", i, p->reserved[i]);
-      return KC_ERR_INVALID_ARG;
-    }
+    if (p->reserved[i]) return fail(KC_ERR_INVALID_ARG, "kc_fasta_to_block: reserved[%d] is %u, not zero", i, p->reserved[i]);
   if (!c || (len && !text)) return KC_ERR_INVALID_ARG;
-  if (on_device && (((uintptr_t)offsets & 7) || ((uintptr_t)recs & 7) || ((uintptr_t)depths & 1))) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_fasta_to_block: device offsets and recs are 8-byte aligned, depths 2-byte");
-    return KC_ERR_INVALID_ARG;
-  }
+  if (on_device && (((uintptr_t)offsets & 7) || ((uintptr_t)recs & 7) || ((uintptr_t)depths & 1)))
+    return fail(KC_ERR_INVALID_ARG, "kc_fasta_to_block: device offsets and recs are 8-byte aligned, depths 2-byte");
   return call_with_bufs(c, [&](CallBufs &b) {
     return fasta_in_run(c, b, text, len, on_device, *p, seqs, seqs_capacity, offsets, ctgs_capacity, depths, recs, n_ctgs, nbytes, consumed, stats);
   });

@@ -8,10 +8,8 @@ static int rtext_run(kc_ctx *c, CallBufs &b, const uint8_t *bases, const uint8_t
                      uint64_t n_order, const uint64_t *ids, int on_device, const kc_fastq_out_params &prm, uint64_t first_byte, uint8_t *text,
                      uint64_t capacity, uint64_t *written, uint64_t *total) {
   const bool dev = on_device != 0, packed = (prm.flags & KC_FASTQ_OUT_PACKED) != 0, check = (prm.flags & KC_FASTQ_OUT_CHECK) != 0;
-  if ((prm.flags & KC_FASTQ_OUT_PAIRED) && (nreads & 1)) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_fastq_text: KC_FASTQ_OUT_PAIRED with %llu reads, an odd number", (unsigned long long)nreads);
-    return KC_ERR_INVALID_ARG;
-  }
+  if ((prm.flags & KC_FASTQ_OUT_PAIRED) && (nreads & 1))
+    return fail(KC_ERR_INVALID_ARG, "kc_fastq_text: KC_FASTQ_OUT_PAIRED with %llu reads, an odd number", (unsigned long long)nreads);
   const uint64_t tiles = (n_order + LINK_SCAN_TILE - 1) / LINK_SCAN_TILE;
   RtextArgs a;
   memset(&a, 0, sizeof(a));
@@ -59,27 +57,15 @@ static int rtext_run(kc_ctx *c, CallBufs &b, const uint8_t *bases, const uint8_t
     if (nreads) HIPCHK(hipMemcpyAsync(&last, offs.d + nreads, 8, hipMemcpyDeviceToHost, c->stream));
     KCTRY(read_back(c, h, a.st));
   }
-  if (h[RT_BAD_OFFSETS]) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_fastq_text: the offsets of %llu reads do not start at 0 or decrease", (unsigned long long)nreads);
-    return KC_ERR_INVALID_ARG;
-  }
-  if (h[RT_TOO_LONG]) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_fastq_text: a read of 2^32 bytes or more, positions in a read take 32 bits");
-    return KC_ERR_CAPACITY;
-  }
-  if (h[RT_BAD_ORDER] != ~0ull) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_fastq_text: order[%llu] names no read (%llu reads)", (unsigned long long)h[RT_BAD_ORDER],
-             (unsigned long long)nreads);
-    return KC_ERR_INVALID_ARG;
-  }
-  if (h[RT_BAD_NUMBER] != ~0ull) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_fastq_text: the number of record %llu has more than 16 digits", (unsigned long long)h[RT_BAD_NUMBER]);
-    return KC_ERR_INVALID_ARG;
-  }
-  if (last && !bases) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_fastq_text: bases is NULL and the reads hold %llu bytes", (unsigned long long)last);
-    return KC_ERR_INVALID_ARG;
-  }
+  if (h[RT_BAD_OFFSETS])
+    return fail(KC_ERR_INVALID_ARG, "kc_fastq_text: the offsets of %llu reads do not start at 0 or decrease", (unsigned long long)nreads);
+  if (h[RT_TOO_LONG]) return fail(KC_ERR_CAPACITY, "kc_fastq_text: a read of 2^32 bytes or more, positions in a read take 32 bits");
+  if (h[RT_BAD_ORDER] != ~0ull)
+    return fail(KC_ERR_INVALID_ARG, "kc_fastq_text: order[%llu] names no read (%llu reads)", (unsigned long long)h[RT_BAD_ORDER],
+                (unsigned long long)nreads);
+  if (h[RT_BAD_NUMBER] != ~0ull)
+    return fail(KC_ERR_INVALID_ARG, "kc_fastq_text: the number of record %llu has more than 16 digits", (unsigned long long)h[RT_BAD_NUMBER]);
+  if (last && !bases) return fail(KC_ERR_INVALID_ARG, "kc_fastq_text: bases is NULL and the reads hold %llu bytes", (unsigned long long)last);
   // ---- the reads, sized by checked offsets
   a.nbytes = last;
   a.bases = bases;
@@ -94,10 +80,9 @@ static int rtext_run(kc_ctx *c, CallBufs &b, const uint8_t *bases, const uint8_t
     if (h[RT_BAD_J] != ~0ull) {
       KCTRY(launch_timed(c, KT_RTEXT_DETAIL, kc_rtext_detail_kernel, dim3(1), tpb, 0, a, h[RT_BAD_J]));
       KCTRY(read_back(c, h, a.st));
-      snprintf(g_last_error, sizeof(g_last_error), "kc_fastq_text: record %llu (read %u): %s %llu is 0x%02x, %s", (unsigned long long)h[RT_BAD_J], (unsigned)h[RT_BAD_READ],
-               (h[RT_BAD_KEY] >> 32) ? "quality" : "base", (unsigned long long)(h[RT_BAD_KEY] & 0xFFFFFFFFull), (unsigned)h[RT_BAD_BYTE],
-               packed ? "a code over 4" : "outside 0x21 .. 0x7e");
-      return KC_ERR_BAD_BASE;
+      return fail(KC_ERR_BAD_BASE, "kc_fastq_text: record %llu (read %u): %s %llu is 0x%02x, %s", (unsigned long long)h[RT_BAD_J],
+                  (unsigned)h[RT_BAD_READ], (h[RT_BAD_KEY] >> 32) ? "quality" : "base", (unsigned long long)(h[RT_BAD_KEY] & 0xFFFFFFFFull),
+                  (unsigned)h[RT_BAD_BYTE], packed ? "a code over 4" : "outside 0x21 .. 0x7e");
     }
   }
   // ---- the records' starts and the total
@@ -108,11 +93,9 @@ static int rtext_run(kc_ctx *c, CallBufs &b, const uint8_t *bases, const uint8_t
     KCTRY(launch_timed(c, KT_RTEXT_STARTS, kc_rtext_starts_kernel, blocks_for(n_order + 1, RTEXT_TPB), tpb, 0, a));
     KCTRY(read_back(c, &all, a.st + RT_TOTAL, 1));
   }
-  if (first_byte > all) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_fastq_text: first_byte %llu is behind the text's %llu bytes", (unsigned long long)first_byte,
-             (unsigned long long)all);
-    return KC_ERR_INVALID_ARG;
-  }
+  if (first_byte > all)
+    return fail(KC_ERR_INVALID_ARG, "kc_fastq_text: first_byte %llu is behind the text's %llu bytes", (unsigned long long)first_byte,
+                (unsigned long long)all);
   const uint64_t n = text ? std::min(all - first_byte, capacity) : 0;
   if (n) {
     // ---- the window
@@ -141,55 +124,28 @@ extern "C" int kc_fastq_text(kc_ctx *c, const uint8_t *bases, const uint8_t *qua
                              uint64_t capacity, uint64_t *written, uint64_t *total) {
   // the ranges come before the context so that they can be checked where there is no device
   constexpr uint32_t known = KC_FASTQ_OUT_PACKED | KC_FASTQ_OUT_PAIRED | KC_FASTQ_OUT_CHECK;
-  if (!p || !written || !total) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_fastq_text: %s is NULL", !p ? "params" : !written ? "written" : "total");
-    return KC_ERR_INVALID_ARG;
-  }
-  if (p->flags & ~known) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_fastq_text: unknown flags 0x%x", p->flags & ~known);
-    return KC_ERR_INVALID_ARG;
-  }
+  if (!p || !written || !total) return fail(KC_ERR_INVALID_ARG, "kc_fastq_text: %s is NULL", !p ? "params" : !written ? "written" : "total");
+  if (p->flags & ~known) return fail(KC_ERR_INVALID_ARG, "kc_fastq_text: unknown flags 0x%x", p->flags & ~known);
   for (int i = 0; i < 4; i++)
-    if (p->reserved[i]) {
-      snprintf(g_last_error, sizeof(g_last_error), "kc_fastq_text: reserved[%d] is %u, not zero", i, p->reserved[i]);
-      return KC_ERR_INVALID_ARG;
-    }
-  if (p->prefix_len > KC_FASTQ_OUT_MAX_PREFIX) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_fastq_text: prefix_len %u over %d", p->prefix_len, KC_FASTQ_OUT_MAX_PREFIX);
-    return KC_ERR_INVALID_ARG;
-  }
+    if (p->reserved[i]) return fail(KC_ERR_INVALID_ARG, "kc_fastq_text: reserved[%d] is %u, not zero", i, p->reserved[i]);
+  if (p->prefix_len > KC_FASTQ_OUT_MAX_PREFIX)
+    return fail(KC_ERR_INVALID_ARG, "kc_fastq_text: prefix_len %u over %d", p->prefix_len, KC_FASTQ_OUT_MAX_PREFIX);
   for (uint32_t i = 0; i < p->prefix_len; i++)
-    if ((uint8_t)p->prefix[i] < 0x21 || (uint8_t)p->prefix[i] > 0x7E) {
-      snprintf(g_last_error, sizeof(g_last_error), "kc_fastq_text: prefix[%u] is 0x%02x, outside 0x21 .. 0x7e", i, (unsigned)(uint8_t)p->prefix[i]);
-      return KC_ERR_INVALID_ARG;
-    }
-  if ((p->flags & KC_FASTQ_OUT_PACKED) && quals) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_fastq_text: KC_FASTQ_OUT_PACKED and quals is not NULL");
-    return KC_ERR_INVALID_ARG;
-  }
-  if (!(p->flags & KC_FASTQ_OUT_PACKED) && !quals && nreads) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_fastq_text: quals is NULL for %llu reads without KC_FASTQ_OUT_PACKED", (unsigned long long)nreads);
-    return KC_ERR_INVALID_ARG;
-  }
-  if (!order && n_order != nreads) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_fastq_text: order is NULL and n_order %llu is not the %llu reads", (unsigned long long)n_order,
-             (unsigned long long)nreads);
-    return KC_ERR_INVALID_ARG;
-  }
-  if (nreads > 0xFFFFFFFFull || n_order > 0xFFFFFFFFull) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_fastq_text: %llu reads and %llu records, read and record indices take 32 bits",
-             (unsigned long long)nreads, (unsigned long long)n_order);
-    return KC_ERR_CAPACITY;
-  }
+    if ((uint8_t)p->prefix[i] < 0x21 || (uint8_t)p->prefix[i] > 0x7E)
+      return fail(KC_ERR_INVALID_ARG, "kc_fastq_text: prefix[%u] is 0x%02x, outside 0x21 .. 0x7e", i, (unsigned)(uint8_t)p->prefix[i]);
+  if ((p->flags & KC_FASTQ_OUT_PACKED) && quals) return fail(KC_ERR_INVALID_ARG, "kc_fastq_text: KC_FASTQ_OUT_PACKED and quals is not NULL");
+  if (!(p->flags & KC_FASTQ_OUT_PACKED) && !quals && nreads)
+    return fail(KC_ERR_INVALID_ARG, "kc_fastq_text: quals is NULL for %llu reads without KC_FASTQ_OUT_PACKED", (unsigned long long)nreads);
+  if (!order && n_order != nreads)
+    return fail(KC_ERR_INVALID_ARG, "kc_fastq_text: order is NULL and n_order %llu is not the %llu reads", (unsigned long long)n_order,
+                (unsigned long long)nreads);
+  if (nreads > 0xFFFFFFFFull || n_order > 0xFFFFFFFFull)
+    return fail(KC_ERR_CAPACITY, "kc_fastq_text: %llu reads and %llu records, read and record indices take 32 bits", (unsigned long long)nreads,
+                (unsigned long long)n_order);
   if (!c) return KC_ERR_INVALID_ARG;
-  if (nreads && !offsets) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_fastq_text: offsets is NULL for %llu reads", (unsigned long long)nreads);
-    return KC_ERR_INVALID_ARG;
-  }
-  if (on_device && (((uintptr_t)offsets & 7) || ((uintptr_t)ids & 7) || ((uintptr_t)order & 3))) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_fastq_text: device offsets and ids are 8-byte aligned, order 4-byte");
-    return KC_ERR_INVALID_ARG;
-  }
+  if (nreads && !offsets) return fail(KC_ERR_INVALID_ARG, "kc_fastq_text: offsets is NULL for %llu reads", (unsigned long long)nreads);
+  if (on_device && (((uintptr_t)offsets & 7) || ((uintptr_t)ids & 7) || ((uintptr_t)order & 3)))
+    return fail(KC_ERR_INVALID_ARG, "kc_fastq_text: device offsets and ids are 8-byte aligned, order 4-byte");
   return call_with_bufs(c, [&](CallBufs &b) {
     return rtext_run(c, b, bases, quals, offsets, nreads, order, n_order, ids, on_device, *p, first_byte, text, capacity, written, total);
   });

@@ -35,23 +35,14 @@ static int fq_next(FqCursor &f, uint64_t *sb, uint64_t *qb, uint64_t *sl) {
   uint64_t b0, e0, b1, e1, b2, e2, b3, e3;
   if (!next_line(b0, e0)) return 0;
   if (e0 == b0 && f.pos >= len) return 0;  // a final empty line
-  if (!next_line(b1, e1) || !next_line(b2, e2) || !next_line(b3, e3)) {
-    snprintf(g_last_error, sizeof(g_last_error), "FASTQ ends inside the record that starts at line %llu", (unsigned long long)(f.line_no - (f.line_no - 1) % 4));
-    return KC_ERR_INVALID_ARG;
-  }
-  if (e0 == b0 || text[b0] != '@') {
-    snprintf(g_last_error, sizeof(g_last_error), "Invalid FASTQ: expected read name (@) at line %llu", (unsigned long long)(f.line_no - 3));
-    return KC_ERR_INVALID_ARG;
-  }
-  if (e2 == b2 || text[b2] != '+') {
-    snprintf(g_last_error, sizeof(g_last_error), "Invalid FASTQ: expected '+' at line %llu", (unsigned long long)(f.line_no - 1));
-    return KC_ERR_INVALID_ARG;
-  }
-  if (e1 - b1 != e3 - b3) {
-    snprintf(g_last_error, sizeof(g_last_error), "Invalid FASTQ: sequence length %llu != %llu quals length at line %llu",
-             (unsigned long long)(e1 - b1), (unsigned long long)(e3 - b3), (unsigned long long)(f.line_no - 2));
-    return KC_ERR_INVALID_ARG;
-  }
+  if (!next_line(b1, e1) || !next_line(b2, e2) || !next_line(b3, e3))
+    return fail(KC_ERR_INVALID_ARG, "FASTQ ends inside the record that starts at line %llu", (unsigned long long)(f.line_no - (f.line_no - 1) % 4));
+  if (e0 == b0 || text[b0] != '@')
+    return fail(KC_ERR_INVALID_ARG, "Invalid FASTQ: expected read name (@) at line %llu", (unsigned long long)(f.line_no - 3));
+  if (e2 == b2 || text[b2] != '+') return fail(KC_ERR_INVALID_ARG, "Invalid FASTQ: expected '+' at line %llu", (unsigned long long)(f.line_no - 1));
+  if (e1 - b1 != e3 - b3)
+    return fail(KC_ERR_INVALID_ARG, "Invalid FASTQ: sequence length %llu != %llu quals length at line %llu", (unsigned long long)(e1 - b1),
+                (unsigned long long)(e3 - b3), (unsigned long long)(f.line_no - 2));
   *sb = b1;
   *qb = b3;
   *sl = e1 - b1;
@@ -75,11 +66,9 @@ extern "C" int kc_fastq_to_packed(const char *text, uint64_t len, int qual_offse
     const bool room = fits && packed && offsets && nr < reads_capacity && nb + sl <= packed_capacity;
     for (uint64_t i = 0; i < sl; i++) {
       const uint8_t cb = code[(uint8_t)text[b1 + i]];
-      if (cb == 255) {
-        snprintf(g_last_error, sizeof(g_last_error), "Illegal char in comp nucleotide (int=%d) at line %llu", (int)(uint8_t)text[b1 + i],
-                 (unsigned long long)(f.line_no - 2));
-        return KC_ERR_BAD_BASE;
-      }
+      if (cb == 255)
+        return fail(KC_ERR_BAD_BASE, "Illegal char in comp nucleotide (int=%d) at line %llu", (int)(uint8_t)text[b1 + i],
+                    (unsigned long long)(f.line_no - 2));
       if (room) {
         int q = (int)(uint8_t)text[b3 + i] - qual_offset;
         if (q > 31) q = 31;
@@ -93,10 +82,8 @@ extern "C" int kc_fastq_to_packed(const char *text, uint64_t len, int qual_offse
   }
   *nreads = nr;
   *nbytes = nb;
-  if (!fits && (nr || nb)) {
-    snprintf(g_last_error, sizeof(g_last_error), "%llu reads with %llu bases do not fit the arrays", (unsigned long long)nr, (unsigned long long)nb);
-    return KC_ERR_CAPACITY;
-  }
+  if (!fits && (nr || nb))
+    return fail(KC_ERR_CAPACITY, "%llu reads with %llu bases do not fit the arrays", (unsigned long long)nr, (unsigned long long)nb);
   return KC_OK;
 }
 
@@ -116,28 +103,21 @@ extern "C" int kc_fastq_pairs(const char *text1, uint64_t len1, const char *text
     const int r = fq_next(fc, &b1, &b3, &sl);
     if (r < 0) return r;
     if (r == 0) {
-      if (two && (nr & 1)) {
-        snprintf(g_last_error, sizeof(g_last_error), "the second file ends after %llu records, the first has more", (unsigned long long)(nr / 2));
-        return KC_ERR_INVALID_ARG;
-      }
+      if (two && (nr & 1))
+        return fail(KC_ERR_INVALID_ARG, "the second file ends after %llu records, the first has more", (unsigned long long)(nr / 2));
       if (two) {  // the first file ended: the second must end too
         uint64_t x, y, z;
         const int r2 = fq_next(f[1], &x, &y, &z);
         if (r2 < 0) return r2;
-        if (r2 > 0) {
-          snprintf(g_last_error, sizeof(g_last_error), "the first file ends after %llu records, the second has more", (unsigned long long)(nr / 2));
-          return KC_ERR_INVALID_ARG;
-        }
+        if (r2 > 0) return fail(KC_ERR_INVALID_ARG, "the first file ends after %llu records, the second has more", (unsigned long long)(nr / 2));
       }
       break;
     }
     const bool room = fits && bases && quals && offsets && nr < reads_capacity && nb + sl <= capacity;
     for (uint64_t i = 0; i < sl; i++) {
-      if (code[(uint8_t)fc.text[b1 + i]] == 255) {
-        snprintf(g_last_error, sizeof(g_last_error), "Illegal char in comp nucleotide (int=%d) at line %llu of file %d",
-                 (int)(uint8_t)fc.text[b1 + i], (unsigned long long)(fc.line_no - 2), two ? (int)(nr & 1) + 1 : 1);
-        return KC_ERR_BAD_BASE;
-      }
+      if (code[(uint8_t)fc.text[b1 + i]] == 255)
+        return fail(KC_ERR_BAD_BASE, "Illegal char in comp nucleotide (int=%d) at line %llu of file %d", (int)(uint8_t)fc.text[b1 + i],
+                    (unsigned long long)(fc.line_no - 2), two ? (int)(nr & 1) + 1 : 1);
     }
     if (room) {
       memcpy(bases + nb, fc.text + b1, sl);
@@ -149,16 +129,11 @@ extern "C" int kc_fastq_pairs(const char *text1, uint64_t len1, const char *text
     nr++;
     if (room) offsets[nr] = nb;
   }
-  if (nr & 1) {
-    snprintf(g_last_error, sizeof(g_last_error), "an interleaved file of %llu records: pairs need an even count", (unsigned long long)nr);
-    return KC_ERR_INVALID_ARG;
-  }
+  if (nr & 1) return fail(KC_ERR_INVALID_ARG, "an interleaved file of %llu records: pairs need an even count", (unsigned long long)nr);
   *nreads = nr;
   *nbytes = nb;
-  if (!fits && (nr || nb)) {
-    snprintf(g_last_error, sizeof(g_last_error), "%llu reads with %llu bases do not fit the arrays", (unsigned long long)nr, (unsigned long long)nb);
-    return KC_ERR_CAPACITY;
-  }
+  if (!fits && (nr || nb))
+    return fail(KC_ERR_CAPACITY, "%llu reads with %llu bases do not fit the arrays", (unsigned long long)nr, (unsigned long long)nb);
   return KC_OK;
 }
 
@@ -321,38 +296,33 @@ static FqWalk fq_walk(const uint64_t h_ctl[2][FQC_N], const uint64_t nrec[2], in
   const uint64_t *k = h_ctl[evf];
   const uint64_t r = two > 0 ? g >> 1 : g;  // the record of file evf
   if (ev == EV_BASE) {
-    w.status = KC_ERR_BAD_BASE;
     if (two < 0) {
-      snprintf(g_last_error, sizeof(g_last_error), "Illegal char in comp nucleotide (int=%d) at line %llu", (int)k[FQC_BYTE],
-               (unsigned long long)(4 * r + 2));
+      w.status = fail(KC_ERR_BAD_BASE, "Illegal char in comp nucleotide (int=%d) at line %llu", (int)k[FQC_BYTE], (unsigned long long)(4 * r + 2));
       w.part_rec = g;
       w.part_len = k[FQC_POS];
     } else {
-      snprintf(g_last_error, sizeof(g_last_error), "Illegal char in comp nucleotide (int=%d) at line %llu of file %d", (int)k[FQC_BYTE],
-               (unsigned long long)(4 * r + 2), evf + 1);
+      w.status = fail(KC_ERR_BAD_BASE, "Illegal char in comp nucleotide (int=%d) at line %llu of file %d", (int)k[FQC_BYTE],
+                      (unsigned long long)(4 * r + 2), evf + 1);
     }
   } else if (ev == EV_END && two > 0 && evf == 1) {
-    w.status = KC_ERR_INVALID_ARG;
-    snprintf(g_last_error, sizeof(g_last_error), "the second file ends after %llu records, the first has more", (unsigned long long)t[1]);
+    w.status = fail(KC_ERR_INVALID_ARG, "the second file ends after %llu records, the first has more", (unsigned long long)t[1]);
   } else if (ev == EV_END && two > 0 && t[1] > t[0]) {  // file 1 ended; file 2's next record is sound
-    w.status = KC_ERR_INVALID_ARG;
-    snprintf(g_last_error, sizeof(g_last_error), "the first file ends after %llu records, the second has more", (unsigned long long)t[0]);
+    w.status = fail(KC_ERR_INVALID_ARG, "the first file ends after %llu records, the second has more", (unsigned long long)t[0]);
   } else if (ev == EV_STRUCT || (ev == EV_END && two > 0 && serr[1] && t[1] == t[0])) {
     int fi = ev == EV_STRUCT ? evf : 1;  // (or file 2's record after file 1's end is malformed)
     const uint64_t *kk = h_ctl[fi];
     const unsigned long long rr = (unsigned long long)t[fi];
-    w.status = KC_ERR_INVALID_ARG;
+    const int e = KC_ERR_INVALID_ARG;
     switch ((int)kk[FQC_KIND]) {
-      case FQK_TRUNCATED: snprintf(g_last_error, sizeof(g_last_error), "FASTQ ends inside the record that starts at line %llu", 4 * rr + 1); break;
-      case FQK_NAME: snprintf(g_last_error, sizeof(g_last_error), "Invalid FASTQ: expected read name (@) at line %llu", 4 * rr + 1); break;
-      case FQK_PLUS: snprintf(g_last_error, sizeof(g_last_error), "Invalid FASTQ: expected '+' at line %llu", 4 * rr + 3); break;
+      case FQK_TRUNCATED: w.status = fail(e, "FASTQ ends inside the record that starts at line %llu", 4 * rr + 1); break;
+      case FQK_NAME: w.status = fail(e, "Invalid FASTQ: expected read name (@) at line %llu", 4 * rr + 1); break;
+      case FQK_PLUS: w.status = fail(e, "Invalid FASTQ: expected '+' at line %llu", 4 * rr + 3); break;
       default:
-        snprintf(g_last_error, sizeof(g_last_error), "Invalid FASTQ: sequence length %llu != %llu quals length at line %llu",
-                 (unsigned long long)kk[FQC_A], (unsigned long long)kk[FQC_B], 4 * rr + 2);
+        w.status = fail(e, "Invalid FASTQ: sequence length %llu != %llu quals length at line %llu", (unsigned long long)kk[FQC_A],
+                        (unsigned long long)kk[FQC_B], 4 * rr + 2);
     }
   } else if (two == 0 && (g & 1)) {
-    w.status = KC_ERR_INVALID_ARG;
-    snprintf(g_last_error, sizeof(g_last_error), "an interleaved file of %llu records: pairs need an even count", (unsigned long long)g);
+    w.status = fail(KC_ERR_INVALID_ARG, "an interleaved file of %llu records: pairs need an even count", (unsigned long long)g);
   }
   return w;
 }
@@ -390,10 +360,8 @@ static int fq_write(kc_ctx *c, const FqJob &j, const FqWalk &w, uint8_t *d_packe
   *nreads = nr;
   *nbytes = nb;
   const bool fits = arrays && nr <= reads_capacity && nb <= capacity;
-  if (!fits && (nr || nb)) {
-    snprintf(g_last_error, sizeof(g_last_error), "%llu reads with %llu bases do not fit the arrays", (unsigned long long)nr, (unsigned long long)nb);
-    return KC_ERR_CAPACITY;
-  }
+  if (!fits && (nr || nb))
+    return fail(KC_ERR_CAPACITY, "%llu reads with %llu bases do not fit the arrays", (unsigned long long)nr, (unsigned long long)nb);
   return KC_OK;
 }
 
@@ -499,15 +467,9 @@ extern "C" int kc_merge_pairs(kc_ctx *c, const uint8_t *bases, const uint8_t *qu
     HIPCHK(hipMemcpyAsync(ctl, a.ctl, sizeof(ctl), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
   }
-  if (ctl[MG_CTL_ERR] & MG_ERR_BASE) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_merge_pairs: a read holds a byte outside ACGTN/acgtn/IUPAC");
-    return KC_ERR_BAD_BASE;
-  }
-  if (ctl[MG_CTL_ERR]) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_merge_pairs: a quality outside [qual_offset, qual_offset + 80] or a mate longer than %d",
-             MG_MAX_LEN);
-    return KC_ERR_INVALID_ARG;
-  }
+  if (ctl[MG_CTL_ERR] & MG_ERR_BASE) return fail(KC_ERR_BAD_BASE, "kc_merge_pairs: a read holds a byte outside ACGTN/acgtn/IUPAC");
+  if (ctl[MG_CTL_ERR])
+    return fail(KC_ERR_INVALID_ARG, "kc_merge_pairs: a quality outside [qual_offset, qual_offset + 80] or a mate longer than %d", MG_MAX_LEN);
   KCTRY(launch_timed(c, KT_MERGE_SCAN, kc_scan_kernel<2>, dim3(1), dim3(SCAN_TPB), 0, ScanArrays<2>{{a.tile_bytes, a.tile_reads}}, ntiles,
                      a.totals));
   uint64_t tot[2], hs[MG_SLOTS * MGS_N];
@@ -528,9 +490,7 @@ extern "C" int kc_merge_pairs(kc_ctx *c, const uint8_t *bases, const uint8_t *qu
   if (stats) *stats = ms;
   if (!d_packed || !d_out_offsets || tot[0] > packed_capacity || tot[1] > reads_capacity) {
     if (!tot[0] && !tot[1]) return KC_OK;
-    snprintf(g_last_error, sizeof(g_last_error), "%llu merged reads with %llu bases do not fit the arrays", (unsigned long long)tot[1],
-             (unsigned long long)tot[0]);
-    return KC_ERR_CAPACITY;
+    return fail(KC_ERR_CAPACITY, "%llu merged reads with %llu bases do not fit the arrays", (unsigned long long)tot[1], (unsigned long long)tot[0]);
   }
   KCTRY(launch_timed(c, KT_MERGE_WRITE, kc_merge_write_kernel, dim3((unsigned)ntiles), dim3(64 * MG_WAVES), 0, a));
   if (nlong) KCTRY(launch_timed(c, KT_MERGE_WRITE_LONG, kc_merge_write_long_kernel, dim3(nlong), dim3(64), lbytes, a, lcap));
@@ -569,10 +529,7 @@ static bool adapters_revcomp(const std::string &s, std::string &rc) {
 // Adapters::load_adapter_seqs (src/adapters.cpp:48-146) on a text in memory
 static int adapters_build(const char *text, uint64_t len, int k, HostAdapters &h) {
   if (k < 1 || (len && !text)) return KC_ERR_INVALID_ARG;
-  if (k > TR_MAX_K) {
-    snprintf(g_last_error, sizeof(g_last_error), "adapter_k %d is above MAX_ADAPTER_K = %d", k, TR_MAX_K);
-    return KC_ERR_UNSUPPORTED_K;
-  }
+  if (k > TR_MAX_K) return fail(KC_ERR_UNSUPPORTED_K, "adapter_k %d is above MAX_ADAPTER_K = %d", k, TR_MAX_K);
   uint64_t lineno = 0;
   for (uint64_t p = 0; p < len;) {  // getline: a last line without '\n' counts, nothing after the last '\n' does not
     const char *nl = (const char *)memchr(text + p, '\n', len - p);
@@ -583,20 +540,13 @@ static int adapters_build(const char *text, uint64_t len, int k, HostAdapters &h
       if (n < (uint64_t)k) {
         h.n_short++;
       } else {
-        if (n > (uint64_t)TR_MAX_ENTRY_LEN) {
-          snprintf(g_last_error, sizeof(g_last_error), "adapter of %llu bases in line %llu: at most %d", (unsigned long long)n,
-                   (unsigned long long)lineno, TR_MAX_ENTRY_LEN);
-          return KC_ERR_INVALID_ARG;
-        }
-        if (h.entries.size() + 2 > (size_t)TR_MAX_ENTRIES) {
-          snprintf(g_last_error, sizeof(g_last_error), "more than %d adapter sequences", TR_MAX_ENTRIES / 2);
-          return KC_ERR_INVALID_ARG;
-        }
+        if (n > (uint64_t)TR_MAX_ENTRY_LEN)
+          return fail(KC_ERR_INVALID_ARG, "adapter of %llu bases in line %llu: at most %d", (unsigned long long)n, (unsigned long long)lineno,
+                      TR_MAX_ENTRY_LEN);
+        if (h.entries.size() + 2 > (size_t)TR_MAX_ENTRIES) return fail(KC_ERR_INVALID_ARG, "more than %d adapter sequences", TR_MAX_ENTRIES / 2);
         std::string s(text + p, (size_t)n), rc;
-        if (!adapters_revcomp(s, rc)) {
-          snprintf(g_last_error, sizeof(g_last_error), "adapter in line %llu holds a byte revcomp does not take", (unsigned long long)lineno);
-          return KC_ERR_BAD_BASE;
-        }
+        if (!adapters_revcomp(s, rc))
+          return fail(KC_ERR_BAD_BASE, "adapter in line %llu holds a byte revcomp does not take", (unsigned long long)lineno);
         h.entries.push_back(std::move(s));
         h.entries.push_back(std::move(rc));
       }
@@ -718,14 +668,8 @@ extern "C" int kc_trim_adapters(kc_ctx *c, const uint8_t *bases, const uint8_t *
                                 uint64_t *d_out_offsets, uint64_t *nbytes, kc_trim_stats *stats) {
   if (!c || !nbytes || (flags & ~KC_TRIM_PAIRED) || (nreads && (!bases || !quals || !offsets))) return KC_ERR_INVALID_ARG;
   const int paired = (flags & KC_TRIM_PAIRED) ? 1 : 0;
-  if (paired && (nreads & 1)) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_trim_adapters: KC_TRIM_PAIRED with an odd number of reads");
-    return KC_ERR_INVALID_ARG;
-  }
-  if (!c->ad_loaded) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_trim_adapters: no adapter set is loaded (kc_adapters_load)");
-    return KC_ERR_STATE;
-  }
+  if (paired && (nreads & 1)) return fail(KC_ERR_INVALID_ARG, "kc_trim_adapters: KC_TRIM_PAIRED with an odd number of reads");
+  if (!c->ad_loaded) return fail(KC_ERR_STATE, "kc_trim_adapters: no adapter set is loaded (kc_adapters_load)");
   HIPCHK(hipSetDevice(c->cfg.device));
   kc_trim_stats ts;
   memset(&ts, 0, sizeof(ts));
@@ -782,10 +726,7 @@ extern "C" int kc_trim_adapters(kc_ctx *c, const uint8_t *bases, const uint8_t *
   uint32_t ctl[TR_CTL_N];
   HIPCHK(hipMemcpyAsync(ctl, a.ctl, sizeof(ctl), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
-  if (ctl[TR_CTL_ERR]) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_trim_adapters: a read longer than %d, or offsets that decrease", MG_MAX_LEN);
-    return KC_ERR_INVALID_ARG;
-  }
+  if (ctl[TR_CTL_ERR]) return fail(KC_ERR_INVALID_ARG, "kc_trim_adapters: a read longer than %d, or offsets that decrease", MG_MAX_LEN);
   if (const uint32_t nlist = ctl[TR_CTL_NLIST]) {
     const unsigned grid = (unsigned)std::min<uint64_t>(nlist, (uint64_t)c->num_cus * 32);
     KCTRY(launch_timed(c, KT_TRIM_ALIGN, kc_trim_align_kernel, dim3(grid), dim3(64), 0, a, nlist));
@@ -804,11 +745,8 @@ extern "C" int kc_trim_adapters(kc_ctx *c, const uint8_t *bases, const uint8_t *
   ts.out_bases = tot[0];
   *nbytes = tot[0];
   if (stats) *stats = ts;
-  if (!d_out_bases || !d_out_quals || !d_out_offsets || tot[0] > capacity) {
-    snprintf(g_last_error, sizeof(g_last_error), "%llu trimmed reads with %llu bases do not fit the arrays", (unsigned long long)nreads,
-             (unsigned long long)tot[0]);
-    return KC_ERR_CAPACITY;
-  }
+  if (!d_out_bases || !d_out_quals || !d_out_offsets || tot[0] > capacity)
+    return fail(KC_ERR_CAPACITY, "%llu trimmed reads with %llu bases do not fit the arrays", (unsigned long long)nreads, (unsigned long long)tot[0]);
   KCTRY(launch_timed(c, KT_TRIM_WRITE, kc_trim_write_kernel, dim3((unsigned)ntiles), dim3(TR_TILE), 0, a));
   HIPCHK(hipStreamSynchronize(c->stream));
   return KC_OK;

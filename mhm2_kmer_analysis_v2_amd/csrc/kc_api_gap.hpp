@@ -54,11 +54,9 @@ static int gap_run(kc_ctx *c, CallBufs &b, const uint8_t *bases, const uint64_t 
   KCTRY(launch_timed(c, KT_GAP_CHECK, kc_gap_check_kernel, blocks_for(n_alns), dim3(256), 0, a));
   uint64_t h[GPS_COUNT];
   KCTRY(read_back(c, h, d_st));
-  if (h[GPS_BAD] != ~0ull) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_align_gapped: record %llu is not one kc_align_reads emits for these reads and this index",
-             (unsigned long long)h[GPS_BAD]);
-    return KC_ERR_INVALID_ARG;
-  }
+  if (h[GPS_BAD] != ~0ull)
+    return fail(KC_ERR_INVALID_ARG, "kc_align_gapped: record %llu is not one kc_align_reads emits for these reads and this index",
+                (unsigned long long)h[GPS_BAD]);
   // a wave per record, or a few records a wave once every compute unit is full
   auto waves_grid = [](uint64_t n) { return dim3((unsigned)std::min<uint64_t>((n + GAP_WAVES - 1) / GAP_WAVES, 4096)); };
   KCTRY(launch_timed(c, KT_GAP_SORT, kc_gap_sort_kernel, waves_grid(n_alns), dim3(GAP_TPB), 0, a));
@@ -99,24 +97,18 @@ extern "C" int kc_align_gapped(kc_ctx *c, const uint8_t *bases, const uint64_t *
   // the ranges come before the context so that they can be checked where there is no device
   if (!scores || !out) return KC_ERR_INVALID_ARG;
   if (scores->match < 1 || scores->match > 9 || scores->mismatch > 9 || scores->ambiguity > 9 || scores->gap_ext < 1 ||
-      scores->gap_ext > scores->gap_open || scores->gap_open > 9) {
-    snprintf(g_last_error, sizeof(g_last_error),
-             "kc_align_gapped: scores %u %u %u %u %u outside 1 <= match <= 9, mismatch, ambiguity <= 9, 1 <= gap_ext <= gap_open <= 9",
-             scores->match, scores->mismatch, scores->gap_open, scores->gap_ext, scores->ambiguity);
-    return KC_ERR_INVALID_ARG;
-  }
-  if (pad > KC_GAP_MAX_PAD || (flags & ~KC_GAP_ALWAYS_DP)) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_align_gapped: pad %u over %d or unknown flags 0x%x", pad, KC_GAP_MAX_PAD, flags);
-    return KC_ERR_INVALID_ARG;
-  }
+      scores->gap_ext > scores->gap_open || scores->gap_open > 9)
+    return fail(KC_ERR_INVALID_ARG,
+                "kc_align_gapped: scores %u %u %u %u %u outside 1 <= match <= 9, mismatch, ambiguity <= 9, 1 <= gap_ext <= gap_open <= 9",
+                scores->match, scores->mismatch, scores->gap_open, scores->gap_ext, scores->ambiguity);
+  if (pad > KC_GAP_MAX_PAD || (flags & ~KC_GAP_ALWAYS_DP))
+    return fail(KC_ERR_INVALID_ARG, "kc_align_gapped: pad %u over %d or unknown flags 0x%x", pad, KC_GAP_MAX_PAD, flags);
   if (!c) return KC_ERR_INVALID_ARG;
   if ((nreads && !offsets) || (n_alns && !alns) || nreads > 0xFFFFFFFFull) return KC_ERR_INVALID_ARG;
   if (on_device && (((uintptr_t)alns | (uintptr_t)out) & 15)) return misaligned_records("kc_align_gapped");
   if (!c->ai_ready) return no_ctg_index("kc_align_gapped");
-  if (n_alns > 0xFFFFFFFFull) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_align_gapped: %llu records, the list holds 32-bit indices", (unsigned long long)n_alns);
-    return KC_ERR_CAPACITY;
-  }
+  if (n_alns > 0xFFFFFFFFull)
+    return fail(KC_ERR_CAPACITY, "kc_align_gapped: %llu records, the list holds 32-bit indices", (unsigned long long)n_alns);
   if (!n_alns) {
     if (stats) memset(stats, 0, sizeof(*stats));
     return KC_OK;

@@ -157,10 +157,8 @@ static int lassm_run(kc_ctx *c, CallBufs &b, const LassmIo &io, const kc_lassm_p
   HIPCHK(hipMemcpyAsync(a.newoff + n_ctgs, a.st + LS_OUT_TOTAL, 8, hipMemcpyDeviceToDevice, c->stream));
   KCTRY(read_back(c, h, a.st));
   const uint64_t total = h[LS_OUT_TOTAL];
-  if (total >= (1ull << 31)) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_local_assm: a block of %llu bytes, a block holds fewer than 2^31", (unsigned long long)total);
-    return KC_ERR_CAPACITY;
-  }
+  if (total >= (1ull << 31))
+    return fail(KC_ERR_CAPACITY, "kc_local_assm: a block of %llu bytes, a block holds fewer than 2^31", (unsigned long long)total);
   kc_lassm_stats st;
   memset(&st, 0, sizeof(st));
   st.ends = n_ends;
@@ -175,9 +173,8 @@ static int lassm_run(kc_ctx *c, CallBufs &b, const LassmIo &io, const kc_lassm_p
     *io.nbytes_out = total;
     if (io.stats) *io.stats = st;
     if (!io.seqs_out) return KC_OK;
-    snprintf(g_last_error, sizeof(g_last_error), "kc_local_assm: a block of %llu bytes, the array holds %llu", (unsigned long long)total,
-             (unsigned long long)io.capacity);
-    return KC_ERR_CAPACITY;
+    return fail(KC_ERR_CAPACITY, "kc_local_assm: a block of %llu bytes, the array holds %llu", (unsigned long long)total,
+                (unsigned long long)io.capacity);
   }
   // ---- assemble
   uint8_t *d_out = io.seqs_out;
@@ -200,53 +197,30 @@ extern "C" int kc_local_assm(kc_ctx *c, const uint8_t *bases, const uint8_t *qua
                              uint64_t *nbytes_out, kc_lassm_stats *stats) {
   // the ranges come before the context so that they can be checked where there is no device
   if (!p || !nbytes_out) return KC_ERR_INVALID_ARG;
-  if (p->min_mer_len < 4 || p->min_mer_len > p->max_mer_len || p->max_mer_len > KC_LASSM_MAX_MER_LEN || p->shift < 1 || p->shift > 64) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_local_assm: mer lengths %u .. %u by %u outside 4 <= min <= max <= %d, 1 <= shift <= 64",
-             p->min_mer_len, p->max_mer_len, p->shift, KC_LASSM_MAX_MER_LEN);
-    return KC_ERR_INVALID_ARG;
-  }
-  if (p->max_walk_len < 1 || p->max_walk_len > KC_LASSM_MAX_WALK) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_local_assm: max_walk_len %u outside 1 .. %d", p->max_walk_len, KC_LASSM_MAX_WALK);
-    return KC_ERR_INVALID_ARG;
-  }
-  if (p->max_insert < 1 || p->max_insert > KC_INSERT_MAX) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_local_assm: max_insert %u outside 1 .. %d", p->max_insert, KC_INSERT_MAX);
-    return KC_ERR_INVALID_ARG;
-  }
-  if (p->min_qual > p->hi_qual || p->hi_qual > 93) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_local_assm: qualities %u %u outside min_qual <= hi_qual <= 93", p->min_qual, p->hi_qual);
-    return KC_ERR_INVALID_ARG;
-  }
-  if (p->min_viable < 1 || p->viable_permille > 1000) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_local_assm: min_viable %u under 1 or viable_permille %u over 1000", p->min_viable,
-             p->viable_permille);
-    return KC_ERR_INVALID_ARG;
-  }
-  if (p->max_cands < 1 || p->max_cands > KC_LASSM_MAX_CANDS) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_local_assm: max_cands %u outside 1 .. %u", p->max_cands, KC_LASSM_MAX_CANDS);
-    return KC_ERR_INVALID_ARG;
-  }
-  if (p->flags) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_local_assm: unknown flags 0x%x", p->flags);
-    return KC_ERR_INVALID_ARG;
-  }
-  if (nreads & 1) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_local_assm: %llu reads are no pairs (reads 2p and 2p + 1 are mates)",
-             (unsigned long long)nreads);
-    return KC_ERR_INVALID_ARG;
-  }
+  if (p->min_mer_len < 4 || p->min_mer_len > p->max_mer_len || p->max_mer_len > KC_LASSM_MAX_MER_LEN || p->shift < 1 || p->shift > 64)
+    return fail(KC_ERR_INVALID_ARG, "kc_local_assm: mer lengths %u .. %u by %u outside 4 <= min <= max <= %d, 1 <= shift <= 64", p->min_mer_len,
+                p->max_mer_len, p->shift, KC_LASSM_MAX_MER_LEN);
+  if (p->max_walk_len < 1 || p->max_walk_len > KC_LASSM_MAX_WALK)
+    return fail(KC_ERR_INVALID_ARG, "kc_local_assm: max_walk_len %u outside 1 .. %d", p->max_walk_len, KC_LASSM_MAX_WALK);
+  if (p->max_insert < 1 || p->max_insert > KC_INSERT_MAX)
+    return fail(KC_ERR_INVALID_ARG, "kc_local_assm: max_insert %u outside 1 .. %d", p->max_insert, KC_INSERT_MAX);
+  if (p->min_qual > p->hi_qual || p->hi_qual > 93)
+    return fail(KC_ERR_INVALID_ARG, "kc_local_assm: qualities %u %u outside min_qual <= hi_qual <= 93", p->min_qual, p->hi_qual);
+  if (p->min_viable < 1 || p->viable_permille > 1000)
+    return fail(KC_ERR_INVALID_ARG, "kc_local_assm: min_viable %u under 1 or viable_permille %u over 1000", p->min_viable, p->viable_permille);
+  if (p->max_cands < 1 || p->max_cands > KC_LASSM_MAX_CANDS)
+    return fail(KC_ERR_INVALID_ARG, "kc_local_assm: max_cands %u outside 1 .. %u", p->max_cands, KC_LASSM_MAX_CANDS);
+  if (p->flags) return fail(KC_ERR_INVALID_ARG, "kc_local_assm: unknown flags 0x%x", p->flags);
+  if (nreads & 1)
+    return fail(KC_ERR_INVALID_ARG, "kc_local_assm: %llu reads are no pairs (reads 2p and 2p + 1 are mates)", (unsigned long long)nreads);
   if (!c || (nreads && (!offsets || !pairs)) || (n_alns && !alns)) return KC_ERR_INVALID_ARG;
   if (on_device && (((uintptr_t)alns | (uintptr_t)pairs | (uintptr_t)ctgs | (uintptr_t)ends) & 15)) return misaligned_records("kc_local_assm");
-  if (on_device && (((uintptr_t)offsets | (uintptr_t)offsets_out) & 7)) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_local_assm: device offsets are 8-byte aligned");
-    return KC_ERR_INVALID_ARG;
-  }
+  if (on_device && (((uintptr_t)offsets | (uintptr_t)offsets_out) & 7))
+    return fail(KC_ERR_INVALID_ARG, "kc_local_assm: device offsets are 8-byte aligned");
   if (!c->ai_ready) return no_ctg_index("kc_local_assm");
-  if (nreads >= (1ull << 30) || n_alns > 0xFFFFFFFFull) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_local_assm: %llu reads, %llu records: an entry holds a read in 30 bits, a pair an index in 32",
-             (unsigned long long)nreads, (unsigned long long)n_alns);
-    return KC_ERR_CAPACITY;
-  }
+  if (nreads >= (1ull << 30) || n_alns > 0xFFFFFFFFull)
+    return fail(KC_ERR_CAPACITY, "kc_local_assm: %llu reads, %llu records: an entry holds a read in 30 bits, a pair an index in 32",
+                (unsigned long long)nreads, (unsigned long long)n_alns);
   const LassmIo io{bases, quals, offsets, nreads, alns, n_alns, pairs, ctgs, on_device, seqs_out, capacity, offsets_out, ends, nbytes_out, stats};
   return call_with_bufs(c, [&](CallBufs &b) { return lassm_run(c, b, io, *p); });
 }

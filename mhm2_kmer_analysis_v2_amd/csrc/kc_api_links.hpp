@@ -100,11 +100,8 @@ static int links_run(kc_ctx *c, CallBufs &b, const LinkIo &io, const kc_link_par
   }
   KCTRY(read_back(c, h, a.st));
   const uint64_t n_cands = h[LKS_CAND_TOTAL], n = 2 * n_cands;  // every candidate is an item in either direction
-  if (n_cands >= (1ull << 31)) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_ctg_links: %llu candidates, the sort's permutation holds fewer than 2^31",
-             (unsigned long long)n_cands);
-    return KC_ERR_CAPACITY;
-  }
+  if (n_cands >= (1ull << 31))
+    return fail(KC_ERR_CAPACITY, "kc_ctg_links: %llu candidates, the sort's permutation holds fewer than 2^31", (unsigned long long)n_cands);
   const uint64_t ntiles = (n + SORT_TILE - 1) / SORT_TILE, ncnt = ntiles * SORT_DIGITS, nheads = (n + LINK_TILE - 1) / LINK_TILE;
   uint64_t *kbuf[2] = {nullptr, nullptr}, *cnt = nullptr, *tile_heads = nullptr;
   uint32_t *ibuf[2] = {nullptr, nullptr};
@@ -202,11 +199,8 @@ static int links_run(kc_ctx *c, CallBufs &b, const LinkIo &io, const kc_link_par
     st.ends_linked = h[LKS_ENDS];
     *io.stats = st;
   }
-  if (io.links && !fits) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_ctg_links: %llu records, the array holds %llu", (unsigned long long)n_runs,
-             (unsigned long long)io.capacity);
-    return KC_ERR_CAPACITY;
-  }
+  if (io.links && !fits)
+    return fail(KC_ERR_CAPACITY, "kc_ctg_links: %llu records, the array holds %llu", (unsigned long long)n_runs, (unsigned long long)io.capacity);
   return KC_OK;
 }
 
@@ -215,45 +209,25 @@ extern "C" int kc_ctg_links(kc_ctx *c, const uint64_t *offsets, uint64_t nreads,
                             kc_link_stats *stats) {
   // the ranges come before the context so that they can be checked where there is no device
   if (!p || !n_links) return KC_ERR_INVALID_ARG;
-  if (p->end_slack > KC_LINK_MAX_SLACK) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_ctg_links: end_slack %u over %d", p->end_slack, KC_LINK_MAX_SLACK);
-    return KC_ERR_INVALID_ARG;
-  }
-  if (p->max_overlap > KC_LINK_MAX_OVERLAP || p->max_splint_gap > KC_LINK_MAX_SLACK) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_ctg_links: max_overlap %u over %d or max_splint_gap %u over %d", p->max_overlap,
-             KC_LINK_MAX_OVERLAP, p->max_splint_gap, KC_LINK_MAX_SLACK);
-    return KC_ERR_INVALID_ARG;
-  }
-  if (p->insert_avg < 1 || p->insert_avg > p->max_insert || p->max_insert > KC_INSERT_MAX) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_ctg_links: insert_avg %u, max_insert %u outside 1 <= insert_avg <= max_insert <= %d",
-             p->insert_avg, p->max_insert, KC_INSERT_MAX);
-    return KC_ERR_INVALID_ARG;
-  }
-  if (p->max_read_alns < 2 || p->max_read_alns > KC_LINK_MAX_READ_ALNS) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_ctg_links: max_read_alns %u outside 2 .. %d", (unsigned)p->max_read_alns,
-             KC_LINK_MAX_READ_ALNS);
-    return KC_ERR_INVALID_ARG;
-  }
-  if (p->flags) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_ctg_links: unknown flags 0x%x", (unsigned)p->flags);
-    return KC_ERR_INVALID_ARG;
-  }
-  if (nreads & 1) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_ctg_links: %llu reads are no pairs (reads 2p and 2p + 1 are mates)",
-             (unsigned long long)nreads);
-    return KC_ERR_INVALID_ARG;
-  }
+  if (p->end_slack > KC_LINK_MAX_SLACK) return fail(KC_ERR_INVALID_ARG, "kc_ctg_links: end_slack %u over %d", p->end_slack, KC_LINK_MAX_SLACK);
+  if (p->max_overlap > KC_LINK_MAX_OVERLAP || p->max_splint_gap > KC_LINK_MAX_SLACK)
+    return fail(KC_ERR_INVALID_ARG, "kc_ctg_links: max_overlap %u over %d or max_splint_gap %u over %d", p->max_overlap, KC_LINK_MAX_OVERLAP,
+                p->max_splint_gap, KC_LINK_MAX_SLACK);
+  if (p->insert_avg < 1 || p->insert_avg > p->max_insert || p->max_insert > KC_INSERT_MAX)
+    return fail(KC_ERR_INVALID_ARG, "kc_ctg_links: insert_avg %u, max_insert %u outside 1 <= insert_avg <= max_insert <= %d", p->insert_avg,
+                p->max_insert, KC_INSERT_MAX);
+  if (p->max_read_alns < 2 || p->max_read_alns > KC_LINK_MAX_READ_ALNS)
+    return fail(KC_ERR_INVALID_ARG, "kc_ctg_links: max_read_alns %u outside 2 .. %d", (unsigned)p->max_read_alns, KC_LINK_MAX_READ_ALNS);
+  if (p->flags) return fail(KC_ERR_INVALID_ARG, "kc_ctg_links: unknown flags 0x%x", (unsigned)p->flags);
+  if (nreads & 1)
+    return fail(KC_ERR_INVALID_ARG, "kc_ctg_links: %llu reads are no pairs (reads 2p and 2p + 1 are mates)", (unsigned long long)nreads);
   if (!c || (nreads && !offsets) || (n_alns && !alns) || nreads > 0xFFFFFFFFull) return KC_ERR_INVALID_ARG;
   if (on_device && (((uintptr_t)alns | (uintptr_t)pairs | (uintptr_t)links) & 15)) return misaligned_records("kc_ctg_links");
-  if (on_device && (((uintptr_t)offsets | (uintptr_t)end_first) & 7)) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_ctg_links: device offsets and end_first are 8-byte aligned");
-    return KC_ERR_INVALID_ARG;
-  }
+  if (on_device && (((uintptr_t)offsets | (uintptr_t)end_first) & 7))
+    return fail(KC_ERR_INVALID_ARG, "kc_ctg_links: device offsets and end_first are 8-byte aligned");
   if (!c->ai_ready) return no_ctg_index("kc_ctg_links");
-  if (n_alns > 0xFFFFFFFFull) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_ctg_links: %llu records, a pair holds a record's index in 32 bits", (unsigned long long)n_alns);
-    return KC_ERR_CAPACITY;
-  }
+  if (n_alns > 0xFFFFFFFFull)
+    return fail(KC_ERR_CAPACITY, "kc_ctg_links: %llu records, a pair holds a record's index in 32 bits", (unsigned long long)n_alns);
   const LinkIo io{offsets, nreads, alns, n_alns, pairs, on_device, links, capacity, end_first, n_links, stats};
   return call_with_bufs(c, [&](CallBufs &b) { return links_run(c, b, io, *p); });
 }

@@ -7,10 +7,19 @@ struct kc_ctx;
 static hipStream_t ctx_stream(const kc_ctx *c);  // under kc_ctx in kc_api.hip
 static int ctx_device(const kc_ctx *c);
 
+// an error return: the message kc_last_error() hands out, and the status it goes with
+__attribute__((format(printf, 2, 3))) static int fail(int status, const char *fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(g_last_error, sizeof(g_last_error), fmt, ap);
+  va_end(ap);
+  return status;
+}
+
 static int hip_fail(hipError_t e, const char *what, const char *file, int line) {
   const char *base = strrchr(file, '/');
-  snprintf(g_last_error, sizeof(g_last_error), "%s failed at %s:%d: %s", what, base ? base + 1 : file, line, hipGetErrorString(e));
-  return e == hipErrorOutOfMemory ? KC_ERR_OUT_OF_MEMORY : KC_ERR_HIP;
+  return fail(e == hipErrorOutOfMemory ? KC_ERR_OUT_OF_MEMORY : KC_ERR_HIP, "%s failed at %s:%d: %s", what, base ? base + 1 : file, line,
+              hipGetErrorString(e));
 }
 
 #define HIP_FAIL(e, what) hip_fail(e, what, __FILE__, __LINE__)

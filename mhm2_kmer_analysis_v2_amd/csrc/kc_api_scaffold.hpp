@@ -79,10 +79,8 @@ static int scaffold_run(kc_ctx *c, CallBufs &b, const ScafIo &io, const kc_scaf_
   KCTRY(read_back(c, h, st));
   // every path is counted with its twin: half the tails are scaffolds, half the bytes theirs
   const uint64_t total = h[SCS_BYTES2] / 2 + h[SCS_TAILS] / 2;
-  if (total >= (1ull << 31)) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_scaffold: the scaffolds are %llu bytes, a block holds fewer than 2^31", (unsigned long long)total);
-    return KC_ERR_CAPACITY;
-  }
+  if (total >= (1ull << 31))
+    return fail(KC_ERR_CAPACITY, "kc_scaffold: the scaffolds are %llu bytes, a block holds fewer than 2^31", (unsigned long long)total);
   int rk = 0;
   for (int r = 0; r < rounds; r++, rk ^= 1) {
     KCTRY(launch_timed(c, KT_SCAF_RANK_JUMP, kc_unitig_rank_jump_kernel, per_node, tpb, 0, (const uint2 *)rank[rk], rank[rk ^ 1], nn));
@@ -94,11 +92,9 @@ static int scaffold_run(kc_ctx *c, CallBufs &b, const ScafIo &io, const kc_scaf_
   KCTRY(launch_timed(c, KT_SCAF_SCAN, kc_scan_kernel<1>, dim3(1), dim3(SCAN_TPB), 0, ScanArrays<1>{{mcnt}}, (uint64_t)n, st + SCS_MTOTAL));
   KCTRY(read_back(c, h, st));
   const uint64_t n_scaf = h[SCS_TOTALS + 1];
-  if (h[SCS_TOTALS] != total || h[SCS_MTOTAL] != n) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_scaffold: the walk gives %llu bytes and %llu members, the sums %llu and %u",
-             (unsigned long long)h[SCS_TOTALS], (unsigned long long)h[SCS_MTOTAL], (unsigned long long)total, n);
-    return KC_ERR_STATE;
-  }
+  if (h[SCS_TOTALS] != total || h[SCS_MTOTAL] != n)
+    return fail(KC_ERR_STATE, "kc_scaffold: the walk gives %llu bytes and %llu members, the sums %llu and %u", (unsigned long long)h[SCS_TOTALS],
+                (unsigned long long)h[SCS_MTOTAL], (unsigned long long)total, n);
   kc_scaf_stats s;
   memset(&s, 0, sizeof(s));
   s.contigs = n;
@@ -158,11 +154,8 @@ static int scaffold_run(kc_ctx *c, CallBufs &b, const ScafIo &io, const kc_scaf_
   *io.n_scaffolds = n_scaf;
   *io.nbytes_out = total;
   if (io.stats) *io.stats = s;
-  if (io.seqs_out && !fits) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_scaffold: %llu bytes, the array holds %llu", (unsigned long long)total,
-             (unsigned long long)io.capacity);
-    return KC_ERR_CAPACITY;
-  }
+  if (io.seqs_out && !fits)
+    return fail(KC_ERR_CAPACITY, "kc_scaffold: %llu bytes, the array holds %llu", (unsigned long long)total, (unsigned long long)io.capacity);
   return KC_OK;
 }
 
@@ -171,33 +164,21 @@ extern "C" int kc_scaffold(kc_ctx *c, const kc_ctg_link *links, uint64_t n_links
                            uint64_t *n_scaffolds, uint64_t *nbytes_out, kc_scaf_stats *stats) {
   // the ranges come before the context so that they can be checked where there is no device
   if (!p || !n_scaffolds || !nbytes_out) return KC_ERR_INVALID_ARG;
-  if (p->min_splints < 1 || p->min_spans < 1) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_scaffold: min_splints %u, min_spans %u below 1", p->min_splints, p->min_spans);
-    return KC_ERR_INVALID_ARG;
-  }
-  if (p->max_second_permille > 1000) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_scaffold: max_second_permille %u over 1000", p->max_second_permille);
-    return KC_ERR_INVALID_ARG;
-  }
-  if (p->overlap_slack > KC_SCAF_MAX_SLACK) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_scaffold: overlap_slack %u over %d", p->overlap_slack, KC_SCAF_MAX_SLACK);
-    return KC_ERR_INVALID_ARG;
-  }
-  if (p->flags || p->reserved[0] || p->reserved[1] || p->reserved[2]) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_scaffold: unknown flags 0x%x", (unsigned)(p->flags | p->reserved[0] | p->reserved[1] | p->reserved[2]));
-    return KC_ERR_INVALID_ARG;
-  }
+  if (p->min_splints < 1 || p->min_spans < 1)
+    return fail(KC_ERR_INVALID_ARG, "kc_scaffold: min_splints %u, min_spans %u below 1", p->min_splints, p->min_spans);
+  if (p->max_second_permille > 1000) return fail(KC_ERR_INVALID_ARG, "kc_scaffold: max_second_permille %u over 1000", p->max_second_permille);
+  if (p->overlap_slack > KC_SCAF_MAX_SLACK)
+    return fail(KC_ERR_INVALID_ARG, "kc_scaffold: overlap_slack %u over %d", p->overlap_slack, KC_SCAF_MAX_SLACK);
+  if (p->flags || p->reserved[0] || p->reserved[1] || p->reserved[2])
+    return fail(KC_ERR_INVALID_ARG, "kc_scaffold: unknown flags 0x%x", (unsigned)(p->flags | p->reserved[0] | p->reserved[1] | p->reserved[2]));
   if (!c || (n_links && !links)) return KC_ERR_INVALID_ARG;
   if (on_device && (((uintptr_t)links | (uintptr_t)scaffolds | (uintptr_t)members) & 15)) return misaligned_records("kc_scaffold");
-  if (on_device && ((((uintptr_t)offsets_out) & 7) || (((uintptr_t)ctg_member) & 3))) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_scaffold: device offsets are 8-byte aligned, ctg_member 4-byte");
-    return KC_ERR_INVALID_ARG;
-  }
+  if (on_device && ((((uintptr_t)offsets_out) & 7) || (((uintptr_t)ctg_member) & 3)))
+    return fail(KC_ERR_INVALID_ARG, "kc_scaffold: device offsets are 8-byte aligned, ctg_member 4-byte");
   if (!c->ai_ready) return no_ctg_index("kc_scaffold");
-  if (c->ai.n_ctgs == 0 || c->ai.n_ctgs >= (1u << 31)) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_scaffold: %u contigs, oriented node ids are 32-bit (1 .. 2^31 - 1 contigs)", c->ai.n_ctgs);
-    return c->ai.n_ctgs ? KC_ERR_CAPACITY : KC_ERR_STATE;
-  }
+  if (c->ai.n_ctgs == 0 || c->ai.n_ctgs >= (1u << 31))
+    return fail(c->ai.n_ctgs ? KC_ERR_CAPACITY : KC_ERR_STATE, "kc_scaffold: %u contigs, oriented node ids are 32-bit (1 .. 2^31 - 1 contigs)",
+                c->ai.n_ctgs);
   const ScafIo io{links, n_links, on_device, seqs_out, capacity, offsets_out, scaffolds, members, ctg_member, n_scaffolds, nbytes_out, stats};
   return call_with_bufs(c, [&](CallBufs &b) { return scaffold_run(c, b, io, *p); });
 }

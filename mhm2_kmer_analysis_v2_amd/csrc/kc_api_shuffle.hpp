@@ -83,10 +83,7 @@ static int shuffle_run(kc_ctx *c, CallBufs &b, const ShufIo &io) {
   la.n_alns = n_alns;
   la.nreads = nreads;
   KCTRY(check_pairs(c, la, npairs, KT_SHUF_PAIR_CHECK, "kc_shuffle_reads"));
-  if (last && !io.bases) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_shuffle_reads: bases is NULL and the reads have %llu bytes", (unsigned long long)last);
-    return KC_ERR_INVALID_ARG;
-  }
+  if (last && !io.bases) return fail(KC_ERR_INVALID_ARG, "kc_shuffle_reads: bases is NULL and the reads have %llu bytes", (unsigned long long)last);
   // ---- the reads' bytes, in and out: a host caller's get room now that the lengths are known
   const uint8_t *d_bases = io.bases, *d_quals = io.quals;
   uint8_t *d_bases_out = io.bases_out, *d_quals_out = io.quals_out;
@@ -197,29 +194,19 @@ extern "C" int kc_shuffle_reads(kc_ctx *c, const uint8_t *bases, const uint8_t *
                                 uint8_t *bases_out, uint8_t *quals_out, uint64_t *offsets_out, uint32_t *order, uint32_t *home,
                                 uint64_t *part_starts, kc_gap_aln *alns_out, kc_pair_rec *pairs_out, kc_shuffle_stats *stats) {
   // the arguments come before the context so that they can be checked where there is no device
-  if (nreads & 1) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_shuffle_reads: %llu reads are no pairs (reads 2p and 2p + 1 are mates)",
-             (unsigned long long)nreads);
-    return KC_ERR_INVALID_ARG;
-  }
-  if (parts < 1 || parts > KC_SHUFFLE_MAX_PARTS) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_shuffle_reads: parts %u outside 1 .. %d", parts, KC_SHUFFLE_MAX_PARTS);
-    return KC_ERR_INVALID_ARG;
-  }
+  if (nreads & 1)
+    return fail(KC_ERR_INVALID_ARG, "kc_shuffle_reads: %llu reads are no pairs (reads 2p and 2p + 1 are mates)", (unsigned long long)nreads);
+  if (parts < 1 || parts > KC_SHUFFLE_MAX_PARTS)
+    return fail(KC_ERR_INVALID_ARG, "kc_shuffle_reads: parts %u outside 1 .. %d", parts, KC_SHUFFLE_MAX_PARTS);
   {
     const void *need[] = {bases_out, offsets_out, order, home, part_starts, nreads ? (const void *)pairs : (const void *)&parts};
     const char *name[] = {"bases_out", "offsets_out", "order", "home", "part_starts", "pairs"};
     for (int i = 0; i < 6; i++)
-      if (!need[i]) {
-        snprintf(g_last_error, sizeof(g_last_error), "kc_shuffle_reads: %s is NULL", name[i]);
-        return KC_ERR_INVALID_ARG;
-      }
+      if (!need[i]) return fail(KC_ERR_INVALID_ARG, "kc_shuffle_reads: %s is NULL", name[i]);
   }
-  if ((quals == nullptr) != (quals_out == nullptr)) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_shuffle_reads: quals is %s and quals_out is %s: both or neither", quals ? "given" : "NULL",
-             quals_out ? "given" : "NULL");
-    return KC_ERR_INVALID_ARG;
-  }
+  if ((quals == nullptr) != (quals_out == nullptr))
+    return fail(KC_ERR_INVALID_ARG, "kc_shuffle_reads: quals is %s and quals_out is %s: both or neither", quals ? "given" : "NULL",
+                quals_out ? "given" : "NULL");
   {
     const void *in[] = {bases, quals, offsets, alns, pairs};
     const char *in_name[] = {"bases", "quals", "offsets", "alns", "pairs"};
@@ -227,23 +214,17 @@ extern "C" int kc_shuffle_reads(kc_ctx *c, const uint8_t *bases, const uint8_t *
     const char *out_name[] = {"bases_out", "quals_out", "offsets_out", "order", "home", "part_starts", "alns_out", "pairs_out"};
     for (int o = 0; o < 8; o++)
       for (int i = 0; i < 5; i++)
-        if (out[o] && out[o] == in[i]) {
-          snprintf(g_last_error, sizeof(g_last_error), "kc_shuffle_reads: %s is %s: the call does not work in place", out_name[o], in_name[i]);
-          return KC_ERR_INVALID_ARG;
-        }
+        if (out[o] && out[o] == in[i])
+          return fail(KC_ERR_INVALID_ARG, "kc_shuffle_reads: %s is %s: the call does not work in place", out_name[o], in_name[i]);
   }
   if (!c || (nreads && !offsets) || (n_alns && !alns)) return KC_ERR_INVALID_ARG;
   if (on_device && (((uintptr_t)alns | (uintptr_t)pairs | (uintptr_t)alns_out | (uintptr_t)pairs_out) & 15)) return misaligned_records("kc_shuffle_reads");
-  if (on_device && ((((uintptr_t)offsets | (uintptr_t)offsets_out | (uintptr_t)part_starts) & 7) || (((uintptr_t)order | (uintptr_t)home) & 3))) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_shuffle_reads: device offsets, offsets_out and part_starts are 8-byte aligned, order and home 4-byte");
-    return KC_ERR_INVALID_ARG;
-  }
+  if (on_device && ((((uintptr_t)offsets | (uintptr_t)offsets_out | (uintptr_t)part_starts) & 7) || (((uintptr_t)order | (uintptr_t)home) & 3)))
+    return fail(KC_ERR_INVALID_ARG, "kc_shuffle_reads: device offsets, offsets_out and part_starts are 8-byte aligned, order and home 4-byte");
   if (!c->ai_ready) return no_ctg_index("kc_shuffle_reads");
-  if (nreads > 0xFFFFFFFFull || n_alns > 0xFFFFFFFFull) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_shuffle_reads: %llu reads and %llu records, an index of either takes 32 bits",
-             (unsigned long long)nreads, (unsigned long long)n_alns);
-    return KC_ERR_CAPACITY;
-  }
+  if (nreads > 0xFFFFFFFFull || n_alns > 0xFFFFFFFFull)
+    return fail(KC_ERR_CAPACITY, "kc_shuffle_reads: %llu reads and %llu records, an index of either takes 32 bits", (unsigned long long)nreads,
+                (unsigned long long)n_alns);
   const ShufIo io{bases,     quals, offsets,     nreads, alns, n_alns,      pairs,    on_device, parts,
                   bases_out, quals_out, offsets_out, order,  home, part_starts, alns_out, pairs_out, stats};
   return call_with_bufs(c, [&](CallBufs &b) { return shuffle_run(c, b, io); });

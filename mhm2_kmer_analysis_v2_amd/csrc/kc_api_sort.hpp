@@ -95,11 +95,8 @@ extern "C" int kc_sort_results(kc_ctx *c, kc_result *out) {
   if (!c) return KC_ERR_INVALID_ARG;
   if (!c->finalized) return KC_ERR_STATE;
   if (!c->sorted && c->out_n > 1) {
-    if (c->out_n >= (1ull << 32)) {
-      snprintf(g_last_error, sizeof(g_last_error), "kc_sort_results: %llu results, the permutation is 32-bit (fewer than 2^32)",
-               (unsigned long long)c->out_n);
-      return KC_ERR_CAPACITY;
-    }
+    if (c->out_n >= (1ull << 32))
+      return fail(KC_ERR_CAPACITY, "kc_sort_results: %llu results, the permutation is 32-bit (fewer than 2^32)", (unsigned long long)c->out_n);
     KCTRY(call_with_bufs(c, [&](CallBufs &cb) {
       Sorted b;
       KCTRY(sort_run(c, cb, b));  // had it failed, the unsorted results would be as they were
@@ -125,10 +122,7 @@ extern "C" int kc_dump_text_device(kc_ctx *c, uint64_t first, uint64_t count, ui
   if (first > c->out_n || count > c->out_n - first) return KC_ERR_INVALID_ARG;
   if (!count) return KC_OK;
   const uint64_t ntiles = (count + DUMP_TILE - 1) / DUMP_TILE;
-  if (ntiles > 0x7FFFFFFFull) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_dump_text_device: at most 2^31 - 1 tiles of %d lines a call", DUMP_TILE);
-    return KC_ERR_CAPACITY;
-  }
+  if (ntiles > 0x7FFFFFFFull) return fail(KC_ERR_CAPACITY, "kc_dump_text_device: at most 2^31 - 1 tiles of %d lines a call", DUMP_TILE);
   HIPCHK(hipSetDevice(c->cfg.device));
   KCTRY(c->dump_tiles.reserve((ntiles + 1) * 8));
   uint64_t *tiles = c->dump_tiles.as<uint64_t>(), *total = tiles + ntiles;
@@ -140,11 +134,9 @@ extern "C" int kc_dump_text_device(kc_ctx *c, uint64_t first, uint64_t count, ui
   HIPCHK(hipStreamSynchronize(c->stream));
   *nbytes = tot;
   if (!d_text) return KC_OK;  // a size query
-  if (tot > capacity) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_dump_text_device: %llu lines are %llu bytes, the buffer holds %llu", (unsigned long long)count,
-             (unsigned long long)tot, (unsigned long long)capacity);
-    return KC_ERR_CAPACITY;
-  }
+  if (tot > capacity)
+    return fail(KC_ERR_CAPACITY, "kc_dump_text_device: %llu lines are %llu bytes, the buffer holds %llu", (unsigned long long)count,
+                (unsigned long long)tot, (unsigned long long)capacity);
   const uint64_t *keys = c->nl != c->nl_ext ? c->d_out_keys_ext : c->d_out_keys;
   KCTRY(launch_timed(c, KT_DUMP_WRITE, kc_dump_write_kernel, dim3((unsigned)ntiles), dim3(DUMP_TILE), 0, keys, c->nl_ext,
                      (const uint16_t *)c->d_out_counts, (const uint8_t *)c->d_out_left, (const uint8_t *)c->d_out_right, first, count, c->k,

@@ -59,11 +59,9 @@ static int unitig_run(kc_ctx *c, CallBufs &b, uint8_t *d_seqs, uint64_t capacity
     stats->longest = h[UST_LONGEST];
   }
   if (!d_seqs || !d_offsets) return KC_OK;  // a size query
-  if (total > capacity || nu > unitigs_capacity) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_build_unitigs: %llu unitigs are %llu bytes, the arrays hold %llu and %llu",
-             (unsigned long long)nu, (unsigned long long)total, (unsigned long long)unitigs_capacity, (unsigned long long)capacity);
-    return KC_ERR_CAPACITY;
-  }
+  if (total > capacity || nu > unitigs_capacity)
+    return fail(KC_ERR_CAPACITY, "kc_build_unitigs: %llu unitigs are %llu bytes, the arrays hold %llu and %llu", (unsigned long long)nu,
+                (unsigned long long)total, (unsigned long long)unitigs_capacity, (unsigned long long)capacity);
   uint64_t *sums = d_kmer_sums;
   if (!sums && d_depths) KCTRY(b.alloc(&sums, nu * 8));  // the caller keeps none
   if (sums) HIPCHK(hipMemsetAsync(sums, 0, nu * 8, c->stream));
@@ -84,16 +82,11 @@ extern "C" int kc_build_unitigs(kc_ctx *c, uint8_t *d_seqs, uint64_t capacity, u
   *n_unitigs = *nbytes = 0;
   if (stats) memset(stats, 0, sizeof(*stats));
   if (!c->finalized) return KC_ERR_STATE;
-  if (c->cfg.rank_n > 1) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_build_unitigs: this context is one of %d ranks, and links across shards are not followed",
-             c->cfg.rank_n);
-    return KC_ERR_STATE;
-  }
-  if (c->out_n >= (1ull << 31)) {
-    snprintf(g_last_error, sizeof(g_last_error), "kc_build_unitigs: %llu results, oriented node ids are 32-bit (fewer than 2^31 results)",
-             (unsigned long long)c->out_n);
-    return KC_ERR_CAPACITY;
-  }
+  if (c->cfg.rank_n > 1)
+    return fail(KC_ERR_STATE, "kc_build_unitigs: this context is one of %d ranks, and links across shards are not followed", c->cfg.rank_n);
+  if (c->out_n >= (1ull << 31))
+    return fail(KC_ERR_CAPACITY, "kc_build_unitigs: %llu results, oriented node ids are 32-bit (fewer than 2^31 results)",
+                (unsigned long long)c->out_n);
   if (!c->out_n) {
     HIPCHK(hipSetDevice(c->cfg.device));
     if (d_seqs && d_offsets) {

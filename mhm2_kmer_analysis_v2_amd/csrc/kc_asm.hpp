@@ -73,10 +73,11 @@ struct AsmSelArgs {
   uint32_t *by_len;      // [n_ctgs] the selected contigs by length
 };
 
-__device__ __forceinline__ uint64_t asm_wave_sum(uint64_t v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor((unsigned long long)v, o);
-  return v;
-}
+struct AsmRange {
+  uint32_t hi, lo;
+  __device__ __forceinline__ AsmRange join(const AsmRange &y) const { return AsmRange{y.hi > hi ? y.hi : hi, y.lo < lo ? y.lo : lo}; }
+  __device__ __forceinline__ AsmRange across(int o) const { return AsmRange{__shfl_xor(hi, o), __shfl_xor(lo, o)}; }
+};
 
 __global__ void __launch_bounds__(ASM_TPB) kc_asm_lens_kernel(AsmSelArgs a) {
   const uint32_t u = blockIdx.x * ASM_TPB + threadIdx.x;
@@ -87,13 +88,10 @@ __global__ void __launch_bounds__(ASM_TPB) kc_asm_lens_kernel(AsmSelArgs a) {
   const bool first = (threadIdx.x & 63) == 0;
   const uint32_t nsel = wave_count(sel);
   if (!nsel) return;  // the whole wave: nothing of it counts
-  const uint64_t bases = asm_wave_sum(sel ? len : 0u);
-  uint32_t hi = sel ? len : 0u, lo = sel ? len : 0xFFFFFFFFu;
-  for (int o = 32; o > 0; o >>= 1) {
-    const uint32_t t = __shfl_xor(hi, o), s = __shfl_xor(lo, o);
-    hi = t > hi ? t : hi;
-    lo = s < lo ? s : lo;
-  }
+  const uint64_t bases = wave_sum<uint64_t>(sel ? len : 0u);
+  // the longest and the shortest in one butterfly (wave_max and wave_min one after the other take two registers more)
+  const AsmRange r = wave_join(AsmRange{sel ? len : 0u, sel ? len : 0xFFFFFFFFu});
+  const uint32_t hi = r.hi, lo = r.lo;
   if (first) {
     atomicAdd((unsigned long long *)&a.st[AS_SELECTED], (unsigned long long)nsel);
     if (bases) atomicAdd((unsigned long long *)&a.st[AS_SEL_BASES], (unsigned long long)bases);
@@ -106,7 +104,7 @@ __global__ void __launch_bounds__(ASM_TPB) kc_asm_lens_kernel(AsmSelArgs a) {
     const bool ge = sel && len >= cls[j];
     const uint32_t n = wave_count(ge);
     if (!n) break;  // the classes are nested: none of the next either
-    const uint64_t s = asm_wave_sum(ge ? len : 0u);
+    const uint64_t s = wave_sum<uint64_t>(ge ? len : 0u);
     if (first) {
       atomicAdd((unsigned long long *)&a.st[AS_GE_COUNT + j], (unsigned long long)n);
       atomicAdd((unsigned long long *)&a.st[AS_GE_BASES + j], (unsigned long long)s);
@@ -150,22 +148,10 @@ __global__ void __launch_bounds__(ASM_TPB) kc_asm_nx_kernel(AsmSelArgs a) {
   }
 }
 
-// the greatest j in [lo, hi] with starts[j] <= x (starts[lo] <= x)
-__device__ __forceinline__ uint64_t asm_find(const uint64_t *starts, uint64_t lo, uint64_t hi, uint64_t x) {
-  while (lo < hi) {
-    const uint64_t mid = lo + ((hi - lo + 1) >> 1);
-    if (starts[mid] <= x)
-      lo = mid;
-    else
-      hi = mid - 1;
-  }
-  return lo;
-}
-
 // tab[w] = the item of starts[0, n) that holds byte base + 4096 w: n >= 1, starts[0] <= base, the starts increase strictly
 __global__ void __launch_bounds__(ASM_TPB) kc_asm_spans_kernel(const uint64_t *starts, uint64_t n, uint64_t base, uint64_t nspans, uint32_t *tab) {
   const uint64_t w = (uint64_t)blockIdx.x * ASM_TPB + threadIdx.x;
-  if (w < nspans) tab[w] = (uint32_t)asm_find(starts, 0, n - 1, base + (w << ASM_SPAN_SHIFT));
+  if (w < nspans) tab[w] = (uint32_t)find_le(starts, (uint64_t)0, n - 1, base + (w << ASM_SPAN_SHIFT));
 }
 
 // 0x80 in every byte of w that equals ch
@@ -194,7 +180,7 @@ __global__ void __launch_bounds__(ASM_TPB) kc_asm_comp_kernel(const uint8_t *seq
       const uint64_t lo = tab[wg_first >> ASM_SPAN_SHIFT];
       const uint64_t hi = (w1 << ASM_SPAN_SHIFT) < nbytes ? (uint64_t)tab[w1] : n_ctgs - 1;
       const uint64_t from = p0 < 0 ? 0ull : (uint64_t)p0, to = (uint64_t)(p0 + 16) < nbytes ? (uint64_t)(p0 + 16) : nbytes;
-      uint64_t u = asm_find(offs, lo, hi, from);
+      uint64_t u = find_le(offs, lo, hi, from);
       uint64_t sep = offs[u + 1] - 1;  // the contig's separator
       bool sel = sep - offs[u] >= min_len;
       if (sel || to > sep) {
@@ -253,7 +239,7 @@ __global__ void __launch_bounds__(ASM_TPB) kc_asm_comp_kernel(const uint8_t *seq
     }
   }
   const int k[6] = {AS_A, AS_C, AS_G, AS_T, AS_N, AS_N_RUNS};
-  link_stats<6>(st, k, cnt);
+  wg_stats<6>(st, k, cnt);
 }
 
 // ---- the text --------------------------------------------------------------------------------------------------------
@@ -274,11 +260,6 @@ struct AsmTextArgs {
   uint8_t *text;
   uint64_t *st;
 };
-
-__device__ __forceinline__ uint32_t asm_id_digits(uint32_t u) {
-  return u < 10u ? 1u : u < 100u ? 2u : u < 1000u ? 3u : u < 10000u ? 4u : u < 100000u ? 5u : u < 1000000u ? 6u : u < 10000000u ? 7u
-       : u < 100000000u ? 8u : u < 1000000000u ? 9u : 10u;
-}
 
 // Every offset is compared with nbytes before the byte in front of it is read.
 __global__ void __launch_bounds__(ASM_TPB) kc_asm_text_check_kernel(AsmTextArgs a) {
@@ -306,7 +287,7 @@ __global__ void __launch_bounds__(ASM_TPB) kc_asm_sizes_kernel(AsmTextArgs a) {
   const uint32_t u = a.order ? a.order[j] : (uint32_t)j;
   const uint64_t len = a.offs[u + 1] - 1 - a.offs[u];
   const uint64_t lines = a.lwp1 != 0xFFFFFFFFu && len ? (len + a.lw - 1) / a.lw : 1;
-  a.rs[j] = 2 + a.prefix_len + asm_id_digits(u) + len + lines;
+  a.rs[j] = 2 + a.prefix_len + dec_digits<10>(u) + len + lines;
 }
 
 // a.rs, a.rbase: scanned; a.st[AT_TOTAL] the total
@@ -328,20 +309,8 @@ __device__ __forceinline__ AsmRec asm_rec(const AsmTextArgs &a, uint64_t j) {
   r.len = (uint32_t)(a.offs[r.u + 1] - 1 - r.src);
   r.start = a.rs[j];
   r.end = a.rs[j + 1];
-  r.hdr = 2u + a.prefix_len + asm_id_digits(r.u);
+  r.hdr = 2u + a.prefix_len + dec_digits<10>(r.u);
   return r;
-}
-
-// the id's decimal digits, four bits each, the last digit lowest
-__device__ __forceinline__ uint64_t asm_bcd(uint32_t u) {
-  uint64_t bcd = 0;
-  int s = 0;
-  do {
-    bcd |= (uint64_t)(u % 10u) << s;
-    u /= 10u;
-    s += 4;
-  } while (u);
-  return bcd;
 }
 
 // Thread t owns text[16 t - mis, 16 t - mis + 16) cut to [0, written): mis = text's address & 15, so every whole chunk is
@@ -360,7 +329,7 @@ __global__ void __launch_bounds__(ASM_TPB) kc_asm_write_kernel(AsmTextArgs a) {
   const int64_t p0 = (int64_t)((t0 + tid) * 16) - (int64_t)mis;
   if (p0 >= (int64_t)a.written) return;
   const uint64_t from = p0 < 0 ? 0ull : (uint64_t)p0, to = (uint64_t)(p0 + 16) < a.written ? (uint64_t)(p0 + 16) : a.written;
-  uint64_t j = asm_find(a.rs, lo, hi, a.first_byte + from);
+  uint64_t j = find_le(a.rs, lo, hi, a.first_byte + from);
   AsmRec r = asm_rec(a, j);
   const uint64_t q0 = a.first_byte + from - r.start;  // the first byte's place in its record
   uint32_t w[4] = {0u, 0u, 0u, 0u};
@@ -395,7 +364,7 @@ __global__ void __launch_bounds__(ASM_TPB) kc_asm_write_kernel(AsmTextArgs a) {
   }
   if (!done) {  // a header, a record's end, an end of the window, lines under sixteen bases, loads that would leave the block
     w[0] = w[1] = w[2] = w[3] = 0u;
-    uint64_t bcd = asm_bcd(r.u);
+    uint64_t bcd = dec_bcd(r.u);
 #pragma unroll
     for (int k = 0; k < 16; k++) {
       const int64_t p = p0 + k;
@@ -405,7 +374,7 @@ __global__ void __launch_bounds__(ASM_TPB) kc_asm_write_kernel(AsmTextArgs a) {
         while (g >= r.end) {  // ends: rs[n_order] = the total > g
           j++;
           r = asm_rec(a, j);
-          bcd = asm_bcd(r.u);
+          bcd = dec_bcd(r.u);
         }
         const uint64_t q = g - r.start;
         if (q < r.hdr) {

@@ -71,25 +71,6 @@ struct CloseArgs {
   uint64_t *st;
 };
 
-// NK counters of a workgroup, as kc_links.hpp's link_stats: wave sums into LDS, then one global atomic a workgroup and
-// counter.  Every thread of the workgroup calls it.
-template <int NK>
-__device__ __forceinline__ void close_stats(uint64_t *st, const int (&k)[NK], const uint32_t (&mine)[NK]) {
-  __shared__ uint32_t sums[NK];
-  if ((int)threadIdx.x < NK) sums[threadIdx.x] = 0u;
-  __syncthreads();
-#pragma unroll
-  for (int j = 0; j < NK; j++) {
-    uint32_t v = mine[j];
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    if ((threadIdx.x & 63) == 0 && v) atomicAdd(&sums[j], v);
-  }
-  __syncthreads();
-#pragma unroll
-  for (int j = 0; j < NK; j++)
-    if ((int)threadIdx.x == j && sums[j]) atomicAdd((unsigned long long *)&st[k[j]], (unsigned long long)sums[j]);
-}
-
 __device__ __forceinline__ uint32_t close_len(const uint32_t *offs, uint32_t u) { return offs[u + 1] - 1u - offs[u]; }
 
 // scaf: kc_scaffold_rec as two uint4 {first_member, n_members, len, n_bases} {overlap_bases, flags, 0, 0}; ishead: zeroed
@@ -198,7 +179,7 @@ __global__ void __launch_bounds__(LINK_STAT_TPB) kc_close_cands_kernel(CloseArgs
   if (!WRITE) {
     const int k[3] = {CLS_CANDS, CLS_OFF_JOIN, CLS_OVER_CAP};
     const uint32_t mine[3] = {on + off, off, over};
-    close_stats<3>(a.st, k, mine);
+    wg_stats<3>(a.st, k, mine);
   }
 }
 
@@ -229,10 +210,7 @@ __global__ void __launch_bounds__(CLOSE_TPB) kc_close_decide_kernel(const uint4 
       const uint64_t w = ((uint64_t)v << 32) | (uint32_t)~(g + 0x80000000u);
       best = w > best ? w : best;
     }
-    for (int o = 32; o; o >>= 1) {
-      const uint64_t t = __shfl_xor(best, o);
-      best = t > best ? t : best;
-    }
+    best = wave_max(best);
     status = CLOSE_NO_READS;
     if (k) {
       const uint32_t v = (uint32_t)(best >> 32);
@@ -307,16 +285,10 @@ __global__ void __launch_bounds__(LINK_STAT_TPB) kc_close_place_kernel(const uin
       closures[2 * m + 1] = make_uint4(at, 0u, d.y, 0u);
     }
     if (acc && (n_left || skip)) {
-      uint64_t lo = 0, hi = n_scaf;  // the first scaffold that starts behind m: the one before it holds m
-      while (lo < hi) {
-        const uint64_t mid = lo + ((hi - lo) >> 1);
-        if (scaf_in[2 * mid].x <= (uint32_t)m)
-          lo = mid + 1;
-        else
-          hi = mid;
-      }
-      if (n_left) atomicAdd(&acc[2 * (lo - 1)], n_left);
-      if (skip) atomicAdd(&acc[2 * (lo - 1) + 1], skip);
+      // the scaffold that holds m: the first one's first member is 0
+      const uint64_t s = find_le((uint64_t)0, n_scaf - 1, (uint32_t)m, [scaf_in](uint64_t mid) { return scaf_in[2 * mid].x; });
+      if (n_left) atomicAdd(&acc[2 * s], n_left);
+      if (skip) atomicAdd(&acc[2 * s + 1], skip);
     }
   }
   // the call's statistics: one atomic a workgroup and counter (a wave of every gap join adding to one address took half
@@ -325,13 +297,7 @@ __global__ void __launch_bounds__(LINK_STAT_TPB) kc_close_place_kernel(const uin
   const uint32_t mine[9] = {status >= CLOSE_NO_READS ? 1u : 0u, status == CLOSE_NO_READS ? 1u : 0u, status == CLOSE_WEAK ? 1u : 0u,
                             status == CLOSE_FILLED ? 1u : 0u, status == CLOSE_ABUT ? 1u : 0u, status == CLOSE_OVERLAP ? 1u : 0u,
                             status == CLOSE_OVERLAP_REJECTED ? 1u : 0u, filled_bases, n_left};
-  close_stats<9>(st, k, mine);
-}
-
-// the index of a voting byte, A C G T in either case, or 4
-__device__ __forceinline__ uint32_t close_code(uint32_t c) {
-  c &= 0xDFu;  // a letter's upper case; no other byte becomes one of the four
-  return c == 'A' ? 0u : c == 'C' ? 1u : c == 'G' ? 2u : c == 'T' ? 3u : 4u;
+  wg_stats<9>(st, k, mine);
 }
 
 // members_w, fill: as the place kernel wrote them; buf: the fill buffer; closures: may be null
@@ -353,7 +319,7 @@ __global__ void __launch_bounds__(LINK_STAT_TPB) kc_close_vote_kernel(const uint
         if (s.z != g) continue;
         if (c < g) {
           const uint8_t *p = bases + (s.x | ((uint64_t)s.y << 32));
-          uint32_t code = close_code(s.w ? p[g - 1u - c] : p[c]);
+          uint32_t code = base_code4(s.w ? p[g - 1u - c] : p[c]);  // the index of a voting byte, or 4
           if (s.w && code < 4u) code = 3u - code;  // the complement
           n0 += code == 0u;
           n1 += code == 1u;
@@ -373,7 +339,7 @@ __global__ void __launch_bounds__(LINK_STAT_TPB) kc_close_vote_kernel(const uint
   // one atomic a workgroup of sixteen joins, not one a disputed join: every lane of a wave holds the wave's count
   const int k1[1] = {CLS_DISPUTED};
   const uint32_t mine[1] = {lane == 0 ? disputed : 0u};
-  close_stats<1>(st, k1, mine);
+  wg_stats<1>(st, k1, mine);
 }
 
 // scaffolds, offsets: may be null
@@ -393,64 +359,12 @@ __global__ void __launch_bounds__(CLOSE_TPB) kc_close_records_kernel(const uint4
   }
 }
 
-// the member a writer thread is in
-struct CloseSeg {
-  uint32_t s1;  // where the next segment starts
-  uint32_t s0, nrun, skip, len, base, fill;
-  bool rev;
-};
-__device__ __forceinline__ CloseSeg close_seg_load(const uint4 *members, const uint32_t *seg, const uint32_t *fill, const uint32_t *offs, uint32_t i) {
-  const uint4 m = members[i];
-  const int32_t j = (int32_t)m.y;
-  const uint32_t base = offs[m.x];
-  return CloseSeg{seg[i + 1], seg[i], j > 0 ? (uint32_t)j : 0u, j < 0 ? (uint32_t)-j : 0u, offs[m.x + 1] - 1u - base, base, fill[i], m.w != 0u};
-}
-
-// thread t owns out[16 t - mis, 16 t - mis + 16) cut to [0, total): mis = out's address & 15, so every whole chunk is an
-// aligned 16-byte store.  n members, seg[0] = 0, seg[n] = total, seg ascending.
+// kc_scaffold.hpp's writer, with a filled member's run taken from buf
+static_assert(CLOSE_TPB == SCAF_TPB && CLOSE_NONE == SCAF_NONE, "scaf_write_body's workgroup and its mark of a run without fill");
 __global__ void __launch_bounds__(CLOSE_TPB) kc_close_write_kernel(const uint4 *members, const uint32_t *seg, const uint32_t *fill, uint32_t n,
                                                                    const uint8_t *src, const uint32_t *offs, const uint8_t *buf, uint32_t mis,
                                                                    uint32_t total, uint8_t *out) {
-  const uint64_t t = (uint64_t)blockIdx.x * CLOSE_TPB + threadIdx.x;
-  const int64_t p0 = (int64_t)t * 16 - (int64_t)mis;
-  if (p0 >= (int64_t)total) return;
-  const uint32_t from = p0 < 0 ? 0u : (uint32_t)p0, to = p0 + 16 < (int64_t)total ? (uint32_t)(p0 + 16) : total;
-  uint32_t lo = 0, hi = n;  // the first segment that starts behind `from`: the one before it holds `from`
-  while (lo < hi) {
-    const uint32_t mid = lo + ((hi - lo) >> 1);
-    if (seg[mid] <= from)
-      lo = mid + 1;
-    else
-      hi = mid;
-  }
-  uint32_t i = lo - 1u;  // seg[0] = 0 <= from: lo is at least 1
-  CloseSeg m = close_seg_load(members, seg, fill, offs, i);
-  uint32_t w[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-  for (int j = 0; j < 16; j++) {
-    const int64_t p = p0 + j;
-    uint32_t c = 0;
-    if (p >= (int64_t)from && p < (int64_t)to) {
-      while ((uint32_t)p >= m.s1) m = close_seg_load(members, seg, fill, offs, ++i);  // ends: seg[n] = total > p
-      const uint32_t q = (uint32_t)p - m.s0;
-      if (q < m.nrun)
-        c = m.fill != CLOSE_NONE ? (uint32_t)buf[m.fill + q] : (uint32_t)'N';
-      else {
-        const uint32_t b = q - m.nrun + m.skip;
-        c = b < m.len ? scaf_text(src + m.base, m.len, m.rev, b) : (uint32_t)'_';
-      }
-    }
-    w[j >> 2] |= c << (8 * (j & 3));
-  }
-  if (to - from == 16u)
-    *(uint4 *)(out + p0) = make_uint4(w[0], w[1], w[2], w[3]);
-  else {
-#pragma unroll
-    for (int j = 0; j < 16; j++) {
-      const int64_t p = p0 + j;
-      if (p >= (int64_t)from && p < (int64_t)to) out[p] = (uint8_t)(w[j >> 2] >> (8 * (j & 3)));
-    }
-  }
+  scaf_write_body<true>(members, seg, fill, n, src, offs, buf, mis, total, out);
 }
 
 }  // namespace kc

@@ -104,11 +104,6 @@ __device__ __forceinline__ bool depth_passes(const DepthArgs &a, const DepthRec 
 
 __device__ __forceinline__ uint64_t depth_best_word(uint32_t score, uint64_t i) { return ((uint64_t)score << 32) | (0xFFFFFFFFull - i); }
 
-__device__ __forceinline__ uint64_t wave_sum64(uint64_t v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
 // use_reads: read < nreads is part of validity; with a.offsets also rstop <= the read's length
 __global__ void kc_depth_check_kernel(DepthArgs a, int use_reads) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -184,46 +179,32 @@ __global__ void __launch_bounds__(DEPTH_TPB) kc_depth_tile_sums_kernel(DepthArgs
   __shared__ uint32_t ws[DEPTH_TPB / 64];
   const int tid = threadIdx.x;
   uint32_t d[DEPTH_ITEMS];
-  uint32_t s = depth_load8(a.diff, blockIdx.x * DEPTH_TILE + (uint32_t)tid * DEPTH_ITEMS, d);
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  const uint32_t s = wave_sum(depth_load8(a.diff, blockIdx.x * DEPTH_TILE + (uint32_t)tid * DEPTH_ITEMS, d));
   if ((tid & 63) == 0) ws[tid >> 6] = s;
   __syncthreads();
   if (tid == 0) a.tile_sums[blockIdx.x] = (uint64_t)(ws[0] + ws[1] + ws[2] + ws[3]);  // modulo 2^32, like every depth
 }
 static_assert(DEPTH_TPB == 256, "four waves a workgroup");
 
-// the greatest u in [lo, hi] with offs[u] <= j (the starts increase strictly: every contig has its separator)
-__device__ __forceinline__ uint32_t depth_find_ctg(const uint32_t *offs, uint32_t lo, uint32_t hi, uint32_t j) {
-  while (lo < hi) {
-    const uint32_t mid = lo + ((hi - lo + 1u) >> 1);
-    if (offs[mid] <= j)
-      lo = mid;
-    else
-      hi = mid - 1u;
-  }
-  return lo;
-}
-
-// the tile's first and last contig into range[0], range[1] (thread 0 and thread 64: two waves); the caller synchronises
+// the tile's first and last contig into range[0], range[1] (thread 0 and thread 64: two waves); the caller synchronises.
+// A byte's contig is the greatest u with offs[u] <= the byte (the starts increase strictly: every contig has its separator).
 __device__ __forceinline__ void depth_tile_range(const DepthArgs &a, uint32_t tile0, uint32_t *range) {
-  if (threadIdx.x == 0) range[0] = depth_find_ctg(a.offs, 0u, a.n_ctgs - 1u, tile0);
+  if (threadIdx.x == 0) range[0] = find_le(a.offs, 0u, a.n_ctgs - 1u, tile0);
   if (threadIdx.x == 64) {
     const uint32_t last = tile0 + DEPTH_TILE - 1u;
-    range[1] = depth_find_ctg(a.offs, 0u, a.n_ctgs - 1u, last < a.nbytes ? last : a.nbytes - 1u);
+    range[1] = find_le(a.offs, 0u, a.n_ctgs - 1u, last < a.nbytes ? last : a.nbytes - 1u);
   }
 }
 
 struct DepthSeg {
   uint64_t sum;
   uint32_t cov, mn, mx;
+  __device__ __forceinline__ DepthSeg join(const DepthSeg &y) const {
+    return DepthSeg{sum + y.sum, cov + y.cov, mn < y.mn ? mn : y.mn, mx > y.mx ? mx : y.mx};
+  }
+  __device__ __forceinline__ DepthSeg up(int o) const { return DepthSeg{__shfl_up(sum, o), __shfl_up(cov, o), __shfl_up(mn, o), __shfl_up(mx, o)}; }
 };
 __device__ __forceinline__ DepthSeg depth_seg_none() { return DepthSeg{0ull, 0u, 0xFFFFFFFFu, 0u}; }
-__device__ __forceinline__ DepthSeg depth_seg_join(const DepthSeg &x, const DepthSeg &y) {
-  return DepthSeg{x.sum + y.sum, x.cov + y.cov, x.mn < y.mn ? x.mn : y.mn, x.mx > y.mx ? x.mx : y.mx};
-}
-__device__ __forceinline__ DepthSeg depth_seg_up(const DepthSeg &x, int o) {
-  return DepthSeg{__shfl_up(x.sum, o), __shfl_up(x.cov, o), __shfl_up(x.mn, o), __shfl_up(x.mx, o)};
-}
 __device__ __forceinline__ void depth_seg_flush(const DepthArgs &a, uint32_t u, const DepthSeg &s) {
   if (u >= a.n_ctgs) return;
   if (s.sum) atomicAdd((unsigned long long *)&a.csum[u], (unsigned long long)s.sum);
@@ -275,7 +256,7 @@ __global__ void __launch_bounds__(DEPTH_TPB) kc_depth_rescan_kernel(DepthArgs a,
   uint32_t head_u = a.n_ctgs, u = a.n_ctgs, sep = 0xFFFFFFFFu, n_cov = 0, n_sat = 0;
   uint64_t dsum = 0;
   if (j0 < a.nbytes) {
-    u = depth_find_ctg(a.offs, range[0], range[1], j0);
+    u = find_le(a.offs, range[0], range[1], j0);
     sep = a.offs[u + 1] - 1u;
   }
   uint32_t v[DEPTH_ITEMS];
@@ -308,21 +289,13 @@ __global__ void __launch_bounds__(DEPTH_TPB) kc_depth_rescan_kernel(DepthArgs a,
   if (write) depth_store8(a.depths, j0, a.nbytes, v);
   // segmented inclusive scan of the open segments: a lane that holds a separator starts one
   DepthSeg s = cur;
-  bool f = sep_seen;
-  for (int o = 1; o < 64; o <<= 1) {
-    const DepthSeg t = depth_seg_up(s, o);
-    const bool tf = __shfl_up((int)f, o) != 0;
-    if (lane >= o) {
-      if (!f) s = depth_seg_join(t, s);
-      f = f || tf;
-    }
-  }
-  DepthSeg carry = depth_seg_up(s, 1);
+  wave_seg_scan(s, sep_seen, lane);
+  DepthSeg carry = s.up(1);
   if (lane == 0) carry = depth_seg_none();
-  if (sep_seen) depth_seg_flush(a, head_u, depth_seg_join(carry, head));
+  if (sep_seen) depth_seg_flush(a, head_u, carry.join(head));
   if (lane == 63) depth_seg_flush(a, u, s);
-  dsum = wave_sum64(dsum);
-  const uint64_t cs = wave_sum64(((uint64_t)n_sat << 32) | n_cov);  // at most 512 each
+  dsum = wave_sum(dsum);
+  const uint64_t cs = wave_sum(((uint64_t)n_sat << 32) | n_cov);  // at most 512 each
   if (lane == 0) {
     if (dsum) atomicAdd((unsigned long long *)&a.st[DPS_DEPTH_SUM], (unsigned long long)dsum);
     if ((uint32_t)cs) atomicAdd((unsigned long long *)&a.st[DPS_COVERED], (unsigned long long)(uint32_t)cs);
@@ -363,7 +336,7 @@ __global__ void __launch_bounds__(DEPTH_TPB) kc_depth_fill_kernel(DepthArgs a) {
   depth_tile_range(a, tile0, range);
   __syncthreads();
   if (j0 >= a.nbytes) return;
-  uint32_t u = depth_find_ctg(a.offs, range[0], range[1], j0);
+  uint32_t u = find_le(a.offs, range[0], range[1], j0);
   uint32_t sep = a.offs[u + 1] - 1u, mean = a.cmean[u];
   uint32_t v[DEPTH_ITEMS];
 #pragma unroll
@@ -445,8 +418,8 @@ __global__ void __launch_bounds__(PAIR_TPB) kc_pair_classify_kernel(DepthArgs a,
     for (int k = 0; k < PAIR_CLASSES; k++) n_cls[k] += wave_count(cls == k);
     with_best += wave_count(i0 != 0xFFFFFFFFu) + wave_count(i1 != 0xFFFFFFFFu);
   }
-  isum = wave_sum64(isum);
-  isq = wave_sum64(isq);
+  isum = wave_sum(isum);
+  isq = wave_sum(isq);
   if (lane == 0) {
 #pragma unroll
     for (int k = 0; k < PAIR_CLASSES; k++)

@@ -83,21 +83,6 @@ struct FaArgs {
 __device__ __forceinline__ uint64_t fa_begin(const FaArgs &a, uint64_t i) { return i ? a.ends[i - 1] + 1 : 0; }
 __device__ __forceinline__ uint64_t fa_end(const FaArgs &a, uint64_t i) { return i < a.nnl ? a.ends[i] : a.len; }
 
-__device__ __forceinline__ uint64_t fa_wave_max(uint64_t v) {
-  for (int o = 32; o > 0; o >>= 1) {
-    const uint64_t t = __shfl_xor((unsigned long long)v, o);
-    v = t > v ? t : v;
-  }
-  return v;
-}
-__device__ __forceinline__ uint64_t fa_wave_min(uint64_t v) {
-  for (int o = 32; o > 0; o >>= 1) {
-    const uint64_t t = __shfl_xor((unsigned long long)v, o);
-    v = t < v ? t : v;
-  }
-  return v;
-}
-
 // a.len, a.nnl, a.nl: those of the whole text
 __global__ void __launch_bounds__(FA_TPB) kc_fa_lines_kernel(FaArgs a, int partial) {
   const uint64_t i = (uint64_t)blockIdx.x * FA_TPB + threadIdx.x;
@@ -112,7 +97,7 @@ __global__ void __launch_bounds__(FA_TPB) kc_fa_lines_kernel(FaArgs a, int parti
     last = hdr ? i + 1 : 0;
   }
   if (partial) {
-    last = fa_wave_max(last);
+    last = wave_max(last);
     if ((threadIdx.x & 63) == 0 && last) atomicMax((unsigned long long *)&a.st[FAS_LAST], (unsigned long long)last);
   }
 }
@@ -139,15 +124,9 @@ __global__ void __launch_bounds__(FA_TPB) kc_fa_starts_kernel(FaArgs a) {
 }
 
 // the greatest i in [lo, hi] whose line starts at or before byte x of the text (lo's does)
-__device__ __forceinline__ uint64_t fa_find_line(const FaArgs &a, uint64_t lo, uint64_t hi, uint64_t x) {
-  while (lo < hi) {
-    const uint64_t mid = lo + ((hi - lo + 1) >> 1);
-    if (a.ends[mid - 1] + 1 <= x)
-      lo = mid;
-    else
-      hi = mid - 1;
-  }
-  return lo;
+__device__ __forceinline__ uint64_t fa_line_of(const FaArgs &a, uint64_t lo, uint64_t hi, uint64_t x) {
+  const uint64_t *ends = a.ends;
+  return find_le(lo, hi, x, [ends](uint64_t mid) { return ends[mid - 1] + 1; });  // mid > lo >= 0
 }
 
 // by_block 0: tab[w] = the line that holds byte 4096 w of the text (nl >= 1); 1: the line i of [0, nl] with
@@ -156,7 +135,7 @@ __global__ void __launch_bounds__(FA_TPB) kc_fa_spans_kernel(FaArgs a, int by_bl
   const uint64_t w = (uint64_t)blockIdx.x * FA_TPB + threadIdx.x;
   if (w >= nspans) return;
   const uint64_t x = w << FA_SPAN_SHIFT;
-  tab[w] = by_block ? asm_find(a.v, 0, a.nl, x + 1) : fa_find_line(a, 0, a.nl - 1, x);
+  tab[w] = by_block ? find_le(a.v, (uint64_t)0, a.nl, x + 1) : fa_line_of(a, 0, a.nl - 1, x);
 }
 
 // a line as the check walks it
@@ -201,7 +180,7 @@ __global__ void __launch_bounds__(FA_TPB) kc_fa_check_kernel(FaArgs a) {
     const uint64_t lo = a.tab[wg_first >> FA_SPAN_SHIFT];
     const uint64_t hi = (w1 << FA_SPAN_SHIFT) < a.len ? a.tab[w1] : a.nl - 1;
     const uint64_t from = p0 < 0 ? 0ull : (uint64_t)p0, to = (uint64_t)(p0 + 16) < a.len ? (uint64_t)(p0 + 16) : a.len;
-    uint64_t i = fa_find_line(a, lo, hi, from);
+    uint64_t i = fa_line_of(a, lo, hi, from);
     FaLine l = fa_line(a, i);
     uint32_t w[4] = {0u, 0u, 0u, 0u};
     const bool whole = to - from == 16;
@@ -266,10 +245,10 @@ __global__ void __launch_bounds__(FA_TPB) kc_fa_check_kernel(FaArgs a) {
       fa_flag(a, l.rec, f);
     }
   }
-  key = fa_wave_min(key);
+  key = wave_min(key);
   if ((tid & 63) == 0 && key != FQ_NONE) atomicMin((unsigned long long *)&a.st[FAS_KEY], (unsigned long long)key);
   const int k[2] = {FAS_LOWERED, FAS_RECODED};
-  link_stats<2>(a.st, k, cnt);
+  wg_stats<2>(a.st, k, cnt);
 }
 
 // one thread: the line, the column and the byte of the winning position
@@ -277,7 +256,7 @@ __global__ void __launch_bounds__(64) kc_fa_detail_kernel(FaArgs a) {
   if (threadIdx.x) return;
   const uint64_t key = a.st[FAS_KEY];
   if (key == FQ_NONE) return;
-  const uint64_t p = key >> 1, i = fa_find_line(a, 0, a.nl - 1, p);
+  const uint64_t p = key >> 1, i = fa_line_of(a, 0, a.nl - 1, p);
   a.st[FAS_ERR_LINE] = i + 1;
   a.st[FAS_ERR_COL] = p - fa_begin(a, i) + 1;
   a.st[FAS_ERR_BYTE] = a.text[p];
@@ -347,10 +326,10 @@ __global__ void __launch_bounds__(FA_TPB) kc_fa_recs_kernel(FaArgs a) {
     cnt[1] = (rec.flags & FA_HAS_ID) != 0;
     cnt[2] = (rec.flags & FA_HAS_DEPTH) != 0;
   }
-  len = fa_wave_max(len);
+  len = wave_max(len);
   if ((threadIdx.x & 63) == 0 && len) atomicMax((unsigned long long *)&a.st[FAS_LONGEST], (unsigned long long)len);
   const int k[3] = {FAS_EMPTY_RECS, FAS_WITH_ID, FAS_WITH_DEPTH};
-  link_stats<3>(a.st, k, cnt);
+  wg_stats<3>(a.st, k, cnt);
 }
 
 // a line as the writer walks it: block bytes [v0 - 1, v1 - 1) are its
@@ -399,7 +378,7 @@ __global__ void __launch_bounds__(FA_TPB) kc_fa_write_kernel(FaArgs a) {
   const int64_t p0 = (int64_t)((t0 + tid) * 16) - (int64_t)mis;
   if (p0 >= (int64_t)a.nbytes) return;
   const uint64_t from = p0 < 0 ? 0ull : (uint64_t)p0, to = (uint64_t)(p0 + 16) < a.nbytes ? (uint64_t)(p0 + 16) : a.nbytes;
-  uint64_t i = asm_find(a.v, lo, hi, from + 1);
+  uint64_t i = find_le(a.v, lo, hi, from + 1);
   FaSrc s = fa_src(a, i);
   uint32_t w[4] = {0u, 0u, 0u, 0u}, d[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
   const bool whole = to - from == 16;

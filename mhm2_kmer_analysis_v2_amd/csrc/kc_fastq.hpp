@@ -35,6 +35,7 @@
 #include <stdint.h>
 
 #include "kc_common.hpp"
+#include "kc_kit.hpp"
 #include "kc_merge.hpp"
 
 namespace kc {
@@ -130,7 +131,7 @@ __global__ void __launch_bounds__(FQ_TPB) kc_fq_count_kernel(FqFile f) {
     const uint64_t t0 = tile * FQ_TILE + (uint64_t)tid * FQ_VEC;
     uint32_t n = 0;
     for (int s = 0; s < FQ_STEPS; s++) n += __popc(fq_nl_mask(f, t0 + (uint64_t)s * FQ_TPB * FQ_VEC));
-    for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o);
+    n = wave_sum(n);
     if (lane == 0) wsum[wv] = n;
     __syncthreads();
     if (tid == 0) {
@@ -280,7 +281,7 @@ __global__ void __launch_bounds__(FQ_TPB) kc_fq_sums_kernel(FqFile f0, FqFile f1
   for (uint64_t blk = blockIdx.x; blk * FQ_TPB < nout; blk += gridDim.x) {
     const uint64_t g = blk * FQ_TPB + tid;
     uint64_t v = g < nout ? fq_len_at(f0, f1, two, g) : 0;
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    v = wave_sum(v);
     if (lane == 0) wsum[wv] = v;
     __syncthreads();
     if (tid == 0) {

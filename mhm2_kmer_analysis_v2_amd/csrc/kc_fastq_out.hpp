@@ -76,12 +76,6 @@ __device__ __forceinline__ uint64_t rtext_number(const RtextArgs &a, uint32_t i)
   return a.first_id > RTEXT_MAX_NUMBER ? ~0ull : a.first_id + (a.paired ? i & ~1u : i);
 }
 
-__device__ __forceinline__ uint32_t rtext_digits(uint64_t v) {
-  uint32_t d = 1;
-  for (uint64_t p = 10; d < 16 && v >= p; p *= 10) d++;
-  return d;
-}
-
 // Every offset is compared with its neighbour only; no byte of the reads is touched.
 __global__ void __launch_bounds__(RTEXT_TPB) kc_rtext_check_kernel(RtextArgs a) {
   const uint64_t t = (uint64_t)blockIdx.x * RTEXT_TPB + threadIdx.x;
@@ -139,7 +133,7 @@ __global__ void __launch_bounds__(RTEXT_TPB) kc_rtext_bytes_kernel(RtextArgs a) 
   }
   if (!bad) return;
   // the reads of the bad bytes: a search for the first, steps from there (empty reads are stepped over)
-  uint64_t r = asm_find(a.offs, 0, a.nreads - 1, (uint64_t)(p0 + (int64_t)__builtin_ctz(bad)));
+  uint64_t r = find_le(a.offs, (uint64_t)0, a.nreads - 1, (uint64_t)(p0 + (int64_t)__builtin_ctz(bad)));
   uint64_t best = ~0ull;
   while (bad) {
     const uint64_t p = (uint64_t)(p0 + (int64_t)__builtin_ctz(bad));
@@ -181,7 +175,7 @@ __global__ void __launch_bounds__(RTEXT_TPB) kc_rtext_sizes_kernel(RtextArgs a) 
   if (j >= a.n_order) return;
   const uint32_t i = rtext_read_of(a, j);
   const uint64_t len = a.offs[i + 1] - a.offs[i];
-  a.rs[j] = 6 + a.prefix_len + rtext_digits(rtext_number(a, i)) + 2 * a.paired + 2 * len;
+  a.rs[j] = 6 + a.prefix_len + dec_digits<16>(rtext_number(a, i)) + 2 * a.paired + 2 * len;
 }
 
 // a.rs, a.rbase: scanned; a.st[RT_TOTAL] the total
@@ -210,18 +204,6 @@ __device__ __forceinline__ RtextRec rtext_rec(const RtextArgs &a, uint64_t j) {
   r.mid = r.hdr + len;
   r.last = r.mid + 3 + len;
   return r;
-}
-
-// the number's decimal digits, four bits each, the last digit lowest (at most sixteen)
-__device__ __forceinline__ uint64_t rtext_bcd(uint64_t v) {
-  uint64_t bcd = 0;
-  int s = 0;
-  do {
-    bcd |= (v % 10u) << s;
-    v /= 10u;
-    s += 4;
-  } while (v);
-  return bcd;
 }
 
 // four packed bytes as their letters: the code picks one of eight bytes, "ACGT" and four times 'N'
@@ -259,7 +241,7 @@ __global__ void __launch_bounds__(RTEXT_TPB) kc_rtext_write_kernel(RtextArgs a) 
   const int64_t p0 = (int64_t)((t0 + tid) * 16) - (int64_t)mis;
   if (p0 >= (int64_t)a.written) return;
   const uint64_t from = p0 < 0 ? 0ull : (uint64_t)p0, to = (uint64_t)(p0 + 16) < a.written ? (uint64_t)(p0 + 16) : a.written;
-  uint64_t j = asm_find(a.rs, lo, hi, a.first_byte + from);
+  uint64_t j = find_le(a.rs, lo, hi, a.first_byte + from);
   RtextRec r = rtext_rec(a, j);
   const uint64_t q0 = a.first_byte + from - r.start;  // the first byte's place in its record
   uint32_t w[4] = {0u, 0u, 0u, 0u};
@@ -293,7 +275,7 @@ __global__ void __launch_bounds__(RTEXT_TPB) kc_rtext_write_kernel(RtextArgs a) 
       const int s0 = rtext_clip(d), s1 = rtext_clip(d + (int64_t)r.hdr), s2 = rtext_clip(d_mid), s3 = rtext_clip(d_mid + 3), s4 = rtext_clip(d_last),
                 s5 = rtext_clip(d_last + 1);
       if (s1 > s0) {
-        const uint64_t bcd = rtext_bcd(rtext_number(a, r.i));
+        const uint64_t bcd = dec_bcd(rtext_number(a, r.i));
         const uint32_t sfx = 2u * a.paired;
 #pragma unroll
         for (int k = 0; k < 16; k++) {

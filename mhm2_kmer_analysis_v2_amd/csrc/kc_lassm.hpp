@@ -86,11 +86,6 @@ struct LassmArgs {
   uint64_t *newoff;  // [n_ctgs + 1]
 };
 
-__device__ __forceinline__ uint32_t lassm_code(uint32_t ch) {
-  const uint32_t c = ch & 0xDFu;  // either case
-  return c == 'A' ? 0u : c == 'C' ? 1u : c == 'G' ? 2u : c == 'T' ? 3u : 4u;
-}
-
 __device__ __forceinline__ uint32_t lassm_class(const LassmArgs &a, uint64_t at) {
   if (!a.quals) return LASSM_CLS_HI;
   const int q = (int)a.quals[at];
@@ -179,8 +174,8 @@ __global__ void kc_lassm_cands_kernel(LassmArgs a) {
     }
   }
   if (!WRITE) {
-    const uint64_t both = wave_sum64(((uint64_t)n_mate << 32) | n_over);  // at most 128 each
-    n_bases = wave_sum64(n_bases);
+    const uint64_t both = wave_sum(((uint64_t)n_mate << 32) | n_over);  // at most 128 each
+    n_bases = wave_sum(n_bases);
     if ((threadIdx.x & 63) == 0) {
       if ((uint32_t)both) atomicAdd((unsigned long long *)&a.st[LS_OVERHANG], (unsigned long long)(uint32_t)both);
       if (both >> 32) atomicAdd((unsigned long long *)&a.st[LS_MATE], (unsigned long long)(both >> 32));
@@ -209,7 +204,7 @@ __global__ void kc_lassm_text_kernel(LassmArgs a, uint64_t n_ent) {
   uint64_t h = 0;
   for (uint32_t j = 0; j < L; j++) {
     const uint64_t at = r0 + (rc ? L - 1u - j : j);
-    uint32_t c = lassm_code(a.bases[at]);
+    uint32_t c = base_code4(a.bases[at]);
     if (rc && c < 4u) c = 3u - c;
     a.tph[base + j] = h;
     a.tcode[base + j] = (uint8_t)(c | (lassm_class(a, at) << 3));
@@ -220,7 +215,7 @@ __global__ void kc_lassm_text_kernel(LassmArgs a, uint64_t n_ent) {
   a.tnb[base + L] = 0;
   uint32_t run = 0;
   for (uint32_t j = L; j-- > 0;) {
-    const uint32_t c = lassm_code(a.bases[r0 + (rc ? L - 1u - j : j)]);  // a base's complement is a base
+    const uint32_t c = base_code4(a.bases[r0 + (rc ? L - 1u - j : j)]);  // a base's complement is a base
     run = c < 4u ? (run < 255u ? run + 1u : 255u) : 0u;
     a.tnb[base + j] = (uint8_t)run;
   }
@@ -254,7 +249,7 @@ __global__ void __launch_bounds__(64) kc_lassm_walk_kernel(LassmArgs a, uint32_t
     const uint32_t j = j0 + lane;
     uint32_t c = 0;
     if (j < tail) {
-      c = lassm_code(right ? a.seqs[o + len - tail + j] : a.seqs[o + tail - 1u - j]);
+      c = base_code4(right ? a.seqs[o + len - tail + j] : a.seqs[o + tail - 1u - j]);
       if (!right && c < 4u) c = 3u - c;
       ring[j] = (uint8_t)c;
     }
@@ -358,7 +353,7 @@ __global__ void __launch_bounds__(64) kc_lassm_walk_kernel(LassmArgs a, uint32_t
         __syncthreads();  // every lane has read the ring
         if (lane == 0) {
           ring[s_len & 127u] = (uint8_t)vb;
-          ext[ext_len] = (uint8_t)(0x54474341u >> (8u * vb));  // "ACGT"
+          ext[ext_len] = (uint8_t)code_letter(vb);
         }
         __syncthreads();
         h = h * LASSM_HASH_BASE + (vb + 1u) - (uint64_t)(old + 1u) * bm;
@@ -400,8 +395,8 @@ __global__ void kc_lassm_lens_kernel(LassmArgs a) {
     const uint32_t n = wave_count(s0 == k) + wave_count(s1 == k);
     if ((threadIdx.x & 63) == 0 && n) atomicAdd((unsigned long long *)&a.st[LS_STATUS + k], (unsigned long long)n);
   }
-  iters = wave_sum64(iters);
-  ext = wave_sum64(ext);
+  iters = wave_sum(iters);
+  ext = wave_sum(ext);
   const uint32_t n_ext = wave_count(extended != 0u);
   if ((threadIdx.x & 63) == 0) {
     if (iters) atomicAdd((unsigned long long *)&a.st[LS_ITERS], (unsigned long long)iters);
@@ -424,15 +419,7 @@ __global__ void kc_lassm_ends_kernel(LassmArgs a, uint4 *ends) {
 __global__ void kc_lassm_write_kernel(LassmArgs a, uint8_t *out, uint64_t total) {
   const uint64_t j0 = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * 16;
   if (j0 >= total) return;
-  uint32_t lo = 0, hi = a.n_ctgs - 1u;  // the greatest u with newoff[u] <= j0 (the starts increase strictly)
-  while (lo < hi) {
-    const uint32_t mid = lo + ((hi - lo + 1u) >> 1);
-    if (a.newoff[mid] <= j0)
-      lo = mid;
-    else
-      hi = mid - 1u;
-  }
-  uint32_t u = lo;
+  uint32_t u = find_le(a.newoff, 0u, a.n_ctgs - 1u, j0);  // the starts increase strictly
   uint64_t start = 0, sep = 0;
   uint32_t xl = 0, len = 0, o = 0;
   auto load = [&]() {
@@ -452,10 +439,9 @@ __global__ void kc_lassm_write_kernel(LassmArgs a, uint8_t *out, uint64_t total)
       const uint64_t t = j - start;
       if (j == sep)
         ch = '_';
-      else if (t < xl) {  // the left extension, reversed and complemented
-        const uint32_t x = a.ext[2 * (uint64_t)u * a.max_walk + (xl - 1u - (uint32_t)t)];
-        ch = x == 'A' ? 'T' : x == 'C' ? 'G' : x == 'G' ? 'C' : 'A';
-      } else if (t < (uint64_t)xl + len)
+      else if (t < xl)  // the left extension, reversed and complemented: the walk wrote one of the four letters there
+        ch = base_comp(a.ext[2 * (uint64_t)u * a.max_walk + (xl - 1u - (uint32_t)t)]);
+      else if (t < (uint64_t)xl + len)
         ch = a.seqs[o + (uint32_t)(t - xl)];
       else
         ch = a.ext[(2 * (uint64_t)u + 1) * a.max_walk + (uint32_t)(t - xl - len)];

@@ -83,6 +83,16 @@ struct LinkSeg {
   uint64_t cnt;  // splints | spans << 32
   int64_t ssum, psum;
   int32_t smin, smax, pmin, pmax;
+  __device__ __forceinline__ LinkSeg join(const LinkSeg &y) const {
+    return LinkSeg{cnt + y.cnt,           ssum + y.ssum,
+                   psum + y.psum,         smin < y.smin ? smin : y.smin,
+                   smax > y.smax ? smax : y.smax, pmin < y.pmin ? pmin : y.pmin,
+                   pmax > y.pmax ? pmax : y.pmax};
+  }
+  __device__ __forceinline__ LinkSeg up(int o) const {
+    return LinkSeg{__shfl_up(cnt, o),  __shfl_up(ssum, o), __shfl_up(psum, o), __shfl_up(smin, o),
+                   __shfl_up(smax, o), __shfl_up(pmin, o), __shfl_up(pmax, o)};
+  }
 };
 constexpr int32_t LINK_MIN_INIT = 0x7F7F7F7F, LINK_MAX_INIT = (int32_t)0x80808080u;  // what a memset gives
 
@@ -94,37 +104,7 @@ struct LinkAcc {
   int32_t *smax, *pmax;   // [runs] LINK_MAX_INIT
 };
 
-__device__ __forceinline__ LinkSeg link_seg_join(const LinkSeg &x, const LinkSeg &y) {
-  return LinkSeg{x.cnt + y.cnt,           x.ssum + y.ssum,
-                 x.psum + y.psum,         x.smin < y.smin ? x.smin : y.smin,
-                 x.smax > y.smax ? x.smax : y.smax, x.pmin < y.pmin ? x.pmin : y.pmin,
-                 x.pmax > y.pmax ? x.pmax : y.pmax};
-}
-__device__ __forceinline__ LinkSeg link_seg_up(const LinkSeg &x, int o) {
-  return LinkSeg{__shfl_up(x.cnt, o),  __shfl_up(x.ssum, o), __shfl_up(x.psum, o), __shfl_up(x.smin, o),
-                 __shfl_up(x.smax, o), __shfl_up(x.pmin, o), __shfl_up(x.pmax, o)};
-}
-
-// NK counters of a workgroup: wave sums into LDS, then one global atomic a workgroup and counter.  Every wave of the call
-// adding to one address is what a counter costs (0.15 ms for 15 000 waves); the statistics kernels run 1024 threads a
-// workgroup for the same reason.  Every thread of the workgroup calls it.
-template <int NK>
-__device__ __forceinline__ void link_stats(uint64_t *st, const int (&k)[NK], const uint32_t (&mine)[NK]) {
-  __shared__ uint32_t sums[NK];
-  if ((int)threadIdx.x < NK) sums[threadIdx.x] = 0u;
-  __syncthreads();
-#pragma unroll
-  for (int j = 0; j < NK; j++) {
-    uint32_t v = mine[j];
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    if ((threadIdx.x & 63) == 0 && v) atomicAdd(&sums[j], v);
-  }
-  __syncthreads();
-#pragma unroll
-  for (int j = 0; j < NK; j++)
-    if ((int)threadIdx.x == j && sums[j]) atomicAdd((unsigned long long *)&st[k[j]], (unsigned long long)sums[j]);
-}
-constexpr int LINK_STAT_TPB = 1024;  // threads a workgroup of the kernels that count statistics
+constexpr int LINK_STAT_TPB = 1024;  // threads a workgroup of the kernels that count statistics (wg_stats, kc_kit.hpp)
 
 template <bool WRITE>
 __global__ void __launch_bounds__(LINK_STAT_TPB) kc_link_group_kernel(LinkArgs a) {
@@ -155,7 +135,7 @@ __global__ void __launch_bounds__(LINK_STAT_TPB) kc_link_group_kernel(LinkArgs a
   if (!WRITE) {
     const int k[3] = {LKS_NONE, LKS_FILTERED, LKS_PASSED};
     const uint32_t mine[3] = {cls == LKS_NONE ? 1u : 0u, cls == LKS_FILTERED ? 1u : 0u, cls == LKS_PASSED ? 1u : 0u};
-    link_stats<3>(a.st, k, mine);
+    wg_stats<3>(a.st, k, mine);
   }
 }
 
@@ -227,7 +207,7 @@ __global__ void __launch_bounds__(LINK_STAT_TPB) kc_link_cands_kernel(LinkArgs a
     if (t < units) a.ufirst[t] = n;
     const int k[5] = {LKS_SPLINT_CANDS, LKS_GAP_OUT, LKS_OVER_CAP, LKS_SPAN_CANDS, LKS_TOO_FAR};
     const uint32_t mine[5] = {n - n_span, gap_out, over, n_span, too_far};
-    link_stats<5>(a.st, k, mine);
+    wg_stats<5>(a.st, k, mine);
   }
 }
 
@@ -297,15 +277,7 @@ __global__ void __launch_bounds__(LINK_TILE) kc_link_reduce_kernel(const uint64_
   }
   // segmented inclusive scan: a head starts a segment, and so does lane 0 (its run may have begun in another wave) and
   // every lane past the end
-  bool f = head || lane == 0 || !valid;
-  for (int o = 1; o < 64; o <<= 1) {
-    const LinkSeg t = link_seg_up(s, o);
-    const bool tf = __shfl_up((int)f, o) != 0;
-    if (lane >= o) {
-      if (!f) s = link_seg_join(t, s);
-      f = f || tf;
-    }
-  }
+  wave_seg_scan(s, head || lane == 0 || !valid, lane);
   const bool next_live = lane < 63 && ((live >> (lane + 1)) & 1ull), next_head = lane < 63 && ((heads >> (lane + 1)) & 1ull);
   if (valid && (!next_live || next_head)) {  // the last lane of its segment
     atomicAdd((unsigned long long *)&acc.cnt[run], (unsigned long long)s.cnt);
@@ -344,7 +316,7 @@ __global__ void __launch_bounds__(LINK_STAT_TPB) kc_link_emit_kernel(LinkAcc acc
   const int k[5] = {LKS_LINKS, LKS_SPLINT_ONLY, LKS_SPAN_ONLY, LKS_BOTH, LKS_ENDS};
   const uint32_t mine[5] = {cls >= 0 ? 1u : 0u, cls == LKS_SPLINT_ONLY ? 1u : 0u, cls == LKS_SPAN_ONLY ? 1u : 0u, cls == LKS_BOTH ? 1u : 0u,
                             first ? 1u : 0u};
-  link_stats<5>(st, k, mine);
+  wg_stats<5>(st, k, mine);
 }
 
 // end_first[e], e in [0, n_ends]: the first run whose `from` is at least e; n_runs for e = n_ends

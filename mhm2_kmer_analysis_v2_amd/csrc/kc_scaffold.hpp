@@ -55,11 +55,6 @@ enum { SCS_CIRCULAR = 0, SCS_BAD, SCS_QUALIFYING, SCS_ENDS_BEST, SCS_AMBIGUOUS, 
        SCS_JOINED, SCS_SINGLE, SCS_LONGEST, SCS_N2, SCS_OV2, SCS_BYTES2, SCS_TAILS, SCS_TOTALS, SCS_MTOTAL = SCS_TOTALS + 2, SCS_COUNT };
 static_assert(SCS_CIRCULAR == UST_CIRCULAR, "kc_unitig_cut_kernel counts there");
 
-__device__ __forceinline__ void scaf_wave_add(uint64_t *st, int k, unsigned long long v) {
-  for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
-  if ((threadIdx.x & 63) == 0 && v) atomicAdd((unsigned long long *)&st[k], v);
-}
-
 __device__ __forceinline__ bool scaf_kind_ok(uint32_t c, int32_t lo, int32_t hi, int64_t sum) {
   if (c == 0) return lo == 0 && hi == 0 && sum == 0;
   if (!(lo >= -(int32_t)LINK_MAX_OVERLAP && lo <= hi && hi <= 65535)) return false;
@@ -108,6 +103,19 @@ __device__ __forceinline__ int64_t scaf_floor_mean(int64_t sum, int64_t c) {
   return q;
 }
 
+// An end's best record so far and the support of its second.  The order: (support, splints, smaller `to`) as (hi, lo); a
+// qualifying record's support is at least 1, so hi = 0 is none.
+struct ScafBest {
+  uint64_t hi, lo, idx, second;
+  __device__ __forceinline__ ScafBest join(const ScafBest &y) const {
+    if (y.hi > hi || (y.hi == hi && y.lo > lo)) return ScafBest{y.hi, y.lo, y.idx, y.second > hi ? y.second : hi};
+    return ScafBest{hi, lo, idx, y.hi > second ? y.hi : second};
+  }
+  __device__ __forceinline__ ScafBest across(int o) const {
+    return ScafBest{__shfl_xor(hi, o), __shfl_xor(lo, o), __shfl_xor(idx, o), __shfl_xor(second, o)};
+  }
+};
+
 // pick[e] = {best(e).to or SCAF_NONE, its gap, e is ambiguous, 0}
 __global__ void __launch_bounds__(SCAF_TPB) kc_scaf_choose_kernel(const uint4 *links, const uint64_t *end_first, uint64_t n_ends,
                                                                   uint32_t min_splints, uint32_t min_spans, uint32_t permille, uint4 *pick,
@@ -116,34 +124,18 @@ __global__ void __launch_bounds__(SCAF_TPB) kc_scaf_choose_kernel(const uint4 *l
   const uint64_t e = (uint64_t)blockIdx.x * (SCAF_TPB / 64) + (threadIdx.x >> 6);
   if (e >= n_ends) return;  // the whole wave
   const uint64_t first = end_first[e], last = end_first[e + 1];
-  // the order: (support, splints, smaller `to`) as (hi, lo); a qualifying record's support is at least 1, so hi = 0 is none
-  uint64_t bhi = 0, blo = 0, bidx = 0, second = 0;
+  ScafBest b{0, 0, 0, 0};
   uint32_t q = 0;
   for (uint64_t r = first + lane; r < last; r += 64) {
     const uint4 a = links[3 * r];
     if (a.z < min_splints && a.w < min_spans) continue;
     q++;
-    const uint64_t hi = (uint64_t)a.z + a.w, lo = ((uint64_t)a.z << 32) | (uint32_t)~a.y;
-    if (hi > bhi || (hi == bhi && lo > blo)) {
-      second = bhi;  // never below the second so far
-      bhi = hi;
-      blo = lo;
-      bidx = r;
-    } else if (hi > second)
-      second = hi;
+    b = b.join(ScafBest{(uint64_t)a.z + a.w, ((uint64_t)a.z << 32) | (uint32_t)~a.y, r, 0});
   }
-  for (int o = 32; o; o >>= 1) {
-    const uint64_t ohi = __shfl_xor(bhi, o), olo = __shfl_xor(blo, o), oidx = __shfl_xor(bidx, o), osec = __shfl_xor(second, o);
-    if (ohi > bhi || (ohi == bhi && olo > blo)) {
-      second = osec > bhi ? osec : bhi;
-      bhi = ohi;
-      blo = olo;
-      bidx = oidx;
-    } else if (ohi > second)
-      second = ohi;
-  }
-  scaf_wave_add(st, SCS_QUALIFYING, q);
+  b = wave_join(b);
+  wave_add(st, SCS_QUALIFYING, q);
   if (lane) return;
+  const uint64_t bhi = b.hi, bidx = b.idx, second = b.second;
   uint4 out = make_uint4(SCAF_NONE, 0u, 0u, 0u);
   if (bhi) {
     const uint4 a = links[3 * bidx], s = links[3 * bidx + 2];
@@ -157,11 +149,9 @@ __global__ void __launch_bounds__(SCAF_TPB) kc_scaf_choose_kernel(const uint4 *l
   pick[e] = out;
 }
 
-__device__ __forceinline__ uint32_t scaf_comp(uint32_t c) { return c == 'A' ? 'T' : c == 'C' ? 'G' : c == 'G' ? 'C' : c == 'T' ? 'A' : c; }
-
 // byte j of a node's text: the contig at src[0, len), as it stands or reverse-complemented
 __device__ __forceinline__ uint32_t scaf_text(const uint8_t *src, uint32_t len, bool rev, uint32_t j) {
-  return rev ? scaf_comp(src[len - 1u - j]) : (uint32_t)src[j];
+  return rev ? base_comp(src[len - 1u - j]) : (uint32_t)src[j];
 }
 
 // link[e] = {the partner of end e or SCAF_NONE, the join}
@@ -264,10 +254,10 @@ __global__ void __launch_bounds__(SCAF_TPB) kc_scaf_weight_kernel(const uint4 *r
     }
     pos4[u] = make_uint4(r.x, w[0], r.z, w[1]);
   }
-  scaf_wave_add(st, SCS_N2, nb);
-  scaf_wave_add(st, SCS_OV2, ob);
-  scaf_wave_add(st, SCS_BYTES2, bytes);
-  scaf_wave_add(st, SCS_TAILS, tails);
+  wave_add(st, SCS_N2, nb);
+  wave_add(st, SCS_OV2, ob);
+  wave_add(st, SCS_BYTES2, bytes);
+  wave_add(st, SCS_TAILS, tails);
 }
 
 // rank, pos: {head, members before} and {head, text start} of every node; cyc: the cycle search's last buffer.  size, num,
@@ -291,11 +281,8 @@ __global__ void __launch_bounds__(SCAF_TPB) kc_scaf_select_kernel(const uint2 *r
       longest = bases;
     }
   }
-  scaf_wave_add(st, SCS_SINGLE, single);
-  for (int o = 32; o; o >>= 1) {
-    const unsigned long long t = __shfl_xor(longest, o);
-    longest = t > longest ? t : longest;
-  }
+  wave_add(st, SCS_SINGLE, single);
+  longest = wave_max(longest);
   if ((threadIdx.x & 63) == 0 && longest) atomicMax((unsigned long long *)&st[SCS_LONGEST], longest);
 }
 
@@ -342,45 +329,42 @@ __global__ void __launch_bounds__(SCAF_TPB) kc_scaf_records_kernel(const uint4 *
 
 // the member a writer thread is in
 struct ScafSeg {
-  uint32_t s1;         // where the next segment starts
-  uint32_t s0, nrun, skip, len, base;
+  uint32_t s1;  // where the next segment starts
+  uint32_t s0, nrun, skip, len, base, fill;
   bool rev;
 };
-__device__ __forceinline__ ScafSeg scaf_seg_load(const uint4 *members, const uint32_t *seg, const uint32_t *offs, uint32_t i) {
+// FILL: fill[i] is where the bytes of member i's run lie in the fill buffer, SCAF_NONE for a run of N (kc_close.hpp)
+template <bool FILL>
+__device__ __forceinline__ ScafSeg scaf_seg_load(const uint4 *members, const uint32_t *seg, const uint32_t *fill, const uint32_t *offs, uint32_t i) {
   const uint4 m = members[i];
   const int32_t j = (int32_t)m.y;
   const uint32_t base = offs[m.x];
-  return ScafSeg{seg[i + 1], seg[i], j > 0 ? (uint32_t)j : 0u, j < 0 ? (uint32_t)-j : 0u, offs[m.x + 1] - 1u - base, base, m.w != 0u};
+  return ScafSeg{seg[i + 1], seg[i], j > 0 ? (uint32_t)j : 0u, j < 0 ? (uint32_t)-j : 0u, offs[m.x + 1] - 1u - base, base,
+                 FILL ? fill[i] : SCAF_NONE, m.w != 0u};
 }
 
-// thread t owns out[16 t - mis, 16 t - mis + 16) cut to [0, total): mis = out's address & 15, so every whole chunk is an
-// aligned 16-byte store.  n members, seg[0] = 0, seg[n] = total, seg ascending.
-__global__ void __launch_bounds__(SCAF_TPB) kc_scaf_write_kernel(const uint4 *members, const uint32_t *seg, uint32_t n, const uint8_t *src,
-                                                                 const uint32_t *offs, uint32_t mis, uint32_t total, uint8_t *out) {
+// The body of kc_scaf_write_kernel and kc_close_write_kernel.  Thread t owns out[16 t - mis, 16 t - mis + 16) cut to
+// [0, total): mis = out's address & 15, so every whole chunk is an aligned 16-byte store.  n members, seg[0] = 0,
+// seg[n] = total, seg ascending.
+template <bool FILL>
+__device__ __forceinline__ void scaf_write_body(const uint4 *members, const uint32_t *seg, const uint32_t *fill, uint32_t n, const uint8_t *src,
+                                                const uint32_t *offs, const uint8_t *buf, uint32_t mis, uint32_t total, uint8_t *out) {
   const uint64_t t = (uint64_t)blockIdx.x * SCAF_TPB + threadIdx.x;
   const int64_t p0 = (int64_t)t * 16 - (int64_t)mis;
   if (p0 >= (int64_t)total) return;
   const uint32_t from = p0 < 0 ? 0u : (uint32_t)p0, to = p0 + 16 < (int64_t)total ? (uint32_t)(p0 + 16) : total;
-  uint32_t lo = 0, hi = n;  // the first segment that starts behind `from`: the one before it holds `from`
-  while (lo < hi) {
-    const uint32_t mid = lo + ((hi - lo) >> 1);
-    if (seg[mid] <= from)
-      lo = mid + 1;
-    else
-      hi = mid;
-  }
-  uint32_t i = lo - 1u;  // seg[0] = 0 <= from: lo is at least 1
-  ScafSeg m = scaf_seg_load(members, seg, offs, i);
+  uint32_t i = find_le(seg, 0u, n - 1u, from);  // the segment that holds `from`: seg[0] = 0 <= from
+  ScafSeg m = scaf_seg_load<FILL>(members, seg, fill, offs, i);
   uint32_t w[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
   for (int j = 0; j < 16; j++) {
     const int64_t p = p0 + j;
     uint32_t c = 0;
     if (p >= (int64_t)from && p < (int64_t)to) {
-      while ((uint32_t)p >= m.s1) m = scaf_seg_load(members, seg, offs, ++i);  // ends: seg[n] = total > p
+      while ((uint32_t)p >= m.s1) m = scaf_seg_load<FILL>(members, seg, fill, offs, ++i);  // ends: seg[n] = total > p
       const uint32_t q = (uint32_t)p - m.s0;
       if (q < m.nrun)
-        c = 'N';
+        c = FILL && m.fill != SCAF_NONE ? (uint32_t)buf[m.fill + q] : (uint32_t)'N';
       else {
         const uint32_t b = q - m.nrun + m.skip;
         c = b < m.len ? scaf_text(src + m.base, m.len, m.rev, b) : (uint32_t)'_';
@@ -397,6 +381,11 @@ __global__ void __launch_bounds__(SCAF_TPB) kc_scaf_write_kernel(const uint4 *me
       if (p >= (int64_t)from && p < (int64_t)to) out[p] = (uint8_t)(w[j >> 2] >> (8 * (j & 3)));
     }
   }
+}
+
+__global__ void __launch_bounds__(SCAF_TPB) kc_scaf_write_kernel(const uint4 *members, const uint32_t *seg, uint32_t n, const uint8_t *src,
+                                                                 const uint32_t *offs, uint32_t mis, uint32_t total, uint8_t *out) {
+  scaf_write_body<false>(members, seg, nullptr, n, src, offs, nullptr, mis, total, out);
 }
 
 }  // namespace kc

@@ -82,11 +82,7 @@ struct ShufCopy {
 
 __global__ void __launch_bounds__(SHUF_TPB) kc_shuf_longest_kernel(const uint32_t *offs, uint32_t n_ctgs, uint64_t *st) {
   const uint32_t u = blockIdx.x * SHUF_TPB + threadIdx.x;
-  uint32_t len = u < n_ctgs ? offs[u + 1] - 1u - offs[u] : 0u;
-  for (int o = 32; o > 0; o >>= 1) {
-    const uint32_t t = __shfl_xor(len, o);
-    len = t > len ? t : len;
-  }
+  const uint32_t len = wave_max(u < n_ctgs ? offs[u + 1] - 1u - offs[u] : 0u);
   if ((threadIdx.x & 63) == 0 && len) atomicMax((unsigned long long *)&st[SHS_LONGEST], (unsigned long long)len);
 }
 
@@ -112,7 +108,7 @@ __global__ void __launch_bounds__(LINK_STAT_TPB) kc_shuf_key_kernel(ShufArgs a) 
   }
   const int k[4] = {SHS_HOMED, SHS_ONE_MATE, SHS_TWO_SAME, SHS_TWO_DIFF};
   const uint32_t mine[4] = {cls >= 0 ? 1u : 0u, cls == SHS_ONE_MATE ? 1u : 0u, cls == SHS_TWO_SAME ? 1u : 0u, cls == SHS_TWO_DIFF ? 1u : 0u};
-  link_stats<4>(a.st, k, mine);
+  wg_stats<4>(a.st, k, mine);
 }
 
 // the part of rank r of a segment of n pairs dealt over `parts`: floor(((r + 1) * parts - 1) / n), below 2^47
@@ -160,10 +156,7 @@ __global__ void __launch_bounds__(SHUF_TPB) kc_shuf_place_kernel(ShufArgs a) {
     *(ulonglong2 *)(a.lens + 2 * q) = l;
   }
   const uint32_t nheads = wave_count(head);
-  for (int o = 32; o > 0; o >>= 1) {
-    const uint32_t t = __shfl_xor(run, o);
-    run = t > run ? t : run;
-  }
+  run = wave_max(run);
   if ((tid & 63) == 0) {
     heads[tid >> 6] = nheads;
     longest[tid >> 6] = run;
@@ -192,18 +185,6 @@ __global__ void __launch_bounds__(SHUF_TPB) kc_shuf_offsets_kernel(ShufArgs a) {
     const uint64_t w = (s + ((1ull << SHUF_BLOCK_SHIFT) - 1)) >> SHUF_BLOCK_SHIFT;
     if ((w << SHUF_BLOCK_SHIFT) < e) a.blk[w] = (uint32_t)(i >> 1);
   }
-}
-
-// the greatest q in [lo, hi] whose pair starts at or before byte x of the new block (noff[0] = 0 <= x)
-__device__ __forceinline__ uint64_t shuf_find_pair(const uint64_t *noff, uint64_t lo, uint64_t hi, uint64_t x) {
-  while (lo < hi) {
-    const uint64_t mid = lo + ((hi - lo + 1) >> 1);
-    if (noff[2 * mid] <= x)
-      lo = mid;
-    else
-      hi = mid - 1;
-  }
-  return lo;
 }
 
 // The sixteen bytes at address sa as four dwords: two aligned 16-byte loads (one where sa is aligned) and a funnel shift by
@@ -240,7 +221,9 @@ __global__ void __launch_bounds__(SHUF_TPB) kc_shuf_gather_kernel(ShufCopy a) {
   const int64_t p0 = (int64_t)((t0 + tid) * 16) - (int64_t)mis;
   if (p0 >= (int64_t)a.total) return;
   const uint64_t from = p0 < 0 ? 0ull : (uint64_t)p0, to = (uint64_t)(p0 + 16) < a.total ? (uint64_t)(p0 + 16) : a.total;
-  uint64_t q = shuf_find_pair(a.noff, lo, hi, from);
+  // the greatest q whose pair starts at or before `from` (noff[0] = 0)
+  const uint64_t *noff = a.noff;
+  uint64_t q = find_le(lo, hi, from, [noff](uint64_t mid) { return noff[2 * mid]; });
   uint64_t pstart = a.noff[2 * q], pend = a.noff[2 * q + 2], sp = a.psrc[q];
   uint32_t w[4] = {0u, 0u, 0u, 0u};
   const bool whole = to - from == 16;

@@ -36,6 +36,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "kc_kit.hpp"
+
 namespace kc {
 
 constexpr int SORT_TILE = 4096;  // items per workgroup and pass
@@ -181,16 +183,13 @@ __global__ void __launch_bounds__(256) kc_sort_gather_kernel(const uint32_t *per
 }
 
 // ---- the dump text ---------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t dump_count_digits(uint32_t c) { return c < 10 ? 1u : c < 100 ? 2u : c < 1000 ? 3u : c < 10000 ? 4u : 5u; }
-
 // bytes of the lines of entries [first + tile * DUMP_TILE, ...) of [first, first + count)
 __global__ void __launch_bounds__(DUMP_TILE) kc_dump_sizes_kernel(const uint16_t *counts, uint64_t first, uint64_t count, int k,
                                                                   uint64_t *tile_bytes) {
   __shared__ uint32_t ws[DUMP_TILE / 64];
   const int tid = threadIdx.x;
   const uint64_t e = (uint64_t)blockIdx.x * DUMP_TILE + tid;
-  uint32_t len = e < count ? (uint32_t)k + 6u + dump_count_digits(counts[first + e]) : 0u;
-  for (int o = 32; o; o >>= 1) len += __shfl_xor(len, o);
+  const uint32_t len = wave_sum(e < count ? (uint32_t)k + 6u + dec_digits<5>((uint32_t)counts[first + e]) : 0u);
   if ((tid & 63) == 0) ws[tid >> 6] = len;
   __syncthreads();
   if (tid == 0) {
@@ -210,7 +209,7 @@ __global__ void __launch_bounds__(DUMP_TILE) kc_dump_write_kernel(const uint64_t
   const uint64_t e = (uint64_t)blockIdx.x * DUMP_TILE + tid;
   const bool in = e < count;
   const uint32_t c = in ? counts[first + e] : 0u;
-  const uint32_t nd = dump_count_digits(c);
+  const uint32_t nd = dec_digits<5>(c);
   const uint32_t len = in ? (uint32_t)k + 6u + nd : 0u;
   uint32_t inc = len;
   for (int o = 1; o < 64; o <<= 1) {
@@ -234,7 +233,7 @@ __global__ void __launch_bounds__(DUMP_TILE) kc_dump_write_kernel(const uint64_t
       if ((i & 31) == 0) word = kw[i >> 5];
       const uint32_t code = (uint32_t)(word >> 62);
       word <<= 2;
-      p[i] = (uint8_t)(0x54474341u >> (8 * code));  // "ACGT"
+      p[i] = (uint8_t)code_letter(code);
     }
     p += k;
     *p++ = ' ';

@@ -39,6 +39,7 @@
 #include <stdint.h>
 
 #include "kc_kernels.hpp"
+#include "kc_kit.hpp"
 
 namespace kc {
 
@@ -47,18 +48,11 @@ constexpr int UNITIG_TPB = 256;
 // device statistics of a call (uint64_t each)
 enum { UST_CIRCULAR = 0, UST_SINGLETONS, UST_LONGEST, UST_TOTALS, UST_COUNT = UST_TOTALS + 2 };  // totals: bytes, unitigs
 
-__device__ __forceinline__ uint32_t unitig_letter(uint32_t code) { return (0x54474341u >> (8 * code)) & 0xFFu; }  // "ACGT"
-
 // the thread's item, and whether it has one: the last workgroup of 2^32 - 2 nodes reaches past 32 bits
 __device__ __forceinline__ bool unitig_thread(uint32_t items, uint32_t &t) {
   const uint64_t g = (uint64_t)blockIdx.x * UNITIG_TPB + threadIdx.x;
   t = (uint32_t)g;
   return g < items;
-}
-
-__device__ __forceinline__ uint32_t unitig_wave_sum(uint32_t v) {
-  for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
-  return v;
 }
 
 // The node that the node with sequence sq (x, or its reverse complement) and right extension `code` links to.
@@ -88,7 +82,7 @@ __device__ __forceinline__ uint32_t unitig_successor(const uint64_t (&sq)[NL], u
   // both sides agree: extL(y,+) = left(y), extL(y,-) = comp(right(y)) must be the first base of sq
   const uint32_t first = (uint32_t)(sq[0] >> 62);
   const uint32_t have = fwd ? left[e - 1] : right[e - 1];
-  if (have != unitig_letter(fwd ? first : 3u - first)) return UNITIG_NONE;
+  if (have != code_letter(fwd ? first : 3u - first)) return UNITIG_NONE;
   return 2u * (e - 1u) + (fwd ? 0u : 1u);
 }
 
@@ -144,7 +138,7 @@ __global__ void __launch_bounds__(UNITIG_TPB) kc_unitig_cut_kernel(const uint4 *
     rank4[i] = make_uint4(nx.y != UNITIG_NONE ? nx.y ^ 1u : 2u * i, nx.y != UNITIG_NONE, nx.x != UNITIG_NONE ? nx.x ^ 1u : 2u * i + 1u,
                           nx.x != UNITIG_NONE);
   }
-  circ = unitig_wave_sum(circ);
+  circ = wave_sum(circ);
   if ((threadIdx.x & 63) == 0 && circ) atomicAdd((unsigned long long *)&st[UST_CIRCULAR], (unsigned long long)circ);
 }
 
@@ -172,11 +166,8 @@ __global__ void __launch_bounds__(UNITIG_TPB) kc_unitig_select_kernel(const uint
       len = (unsigned long long)k + e.y;
     }
   }
-  single = unitig_wave_sum(single);
-  for (int o = 32; o; o >>= 1) {
-    const unsigned long long t = __shfl_xor(len, o);
-    len = t > len ? t : len;
-  }
+  single = wave_sum(single);
+  len = wave_max(len);
   if ((threadIdx.x & 63) == 0) {
     if (single) atomicAdd((unsigned long long *)&st[UST_SINGLETONS], (unsigned long long)single);
     if (len) atomicMax((unsigned long long *)&st[UST_LONGEST], len);
@@ -209,12 +200,12 @@ __global__ void __launch_bounds__(UNITIG_TPB) kc_unitig_write_kernel(const uint2
         word = kw[have];
       }
       const uint32_t code = (uint32_t)(word >> (62 - 2 * (src & 31))) & 3u;
-      if (at + j < total) seqs[at + j] = (uint8_t)unitig_letter(rev ? 3u - code : code);
+      if (at + j < total) seqs[at + j] = (uint8_t)code_letter(rev ? 3u - code : code);
     }
   } else {  // the last base of seq(v)
     const uint32_t code = rev ? 3u - (uint32_t)(kw[0] >> 62) : (uint32_t)(kw[(k - 1) >> 5] >> (62 - 2 * ((k - 1) & 31))) & 3u;
     const uint64_t p = at + (uint64_t)k - 1u + e.y;
-    if (p < total) seqs[p] = (uint8_t)unitig_letter(code);
+    if (p < total) seqs[p] = (uint8_t)code_letter(code);
   }
   if (next[v] == UNITIG_NONE) {
     const uint64_t p = at + (uint64_t)k + e.y;
