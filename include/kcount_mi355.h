@@ -1433,6 +1433,89 @@ int kc_fastq_text(kc_ctx *ctx, const uint8_t *bases, const uint8_t *quals, const
                   const uint32_t *order, uint64_t n_order, const uint64_t *ids, int on_device,
                   const kc_fastq_out_params *params, uint64_t first_byte, uint8_t *text, uint64_t capacity,
                   uint64_t *written, uint64_t *total);
+/* Duplicate and contained contigs of a seq block, removed on the device.  kc_local_assm grows neighbouring contigs towards
+ * each other and over the short contigs between them, load_contigs and a second round bring their own copies, and the seed
+ * index (kc_ctg_index_build) throws away exactly the k-mers two copies share: reads stop aligning to both.  The reference
+ * holds no contig code, so the rules below are this project's own definition (tests/dedup_model.py); no
+ * parity with MetaHipMer is claimed.  All quantities are integers; every output is one exact byte string for a given input.
+ *
+ * Input: a seq block exactly as kc_ctg_index_build takes it (seqs / nbytes / offsets / n_ctgs, every contig followed by '_',
+ * upper-case A C G T N, empty contigs allowed, 2^31 bytes or more: KC_ERR_CAPACITY) and, optionally, depths: one uint16 per
+ * byte of the block, as kc_submit_ctg_block takes them.  k is the context's kmer_len.
+ *
+ * Contigs and order.  T_u is contig u's text, L_u its length, rc(T) the reverse complement, N staying N.  v OUTRANKS u iff
+ * L_v > L_u, or L_v == L_u and v < u: a strict total order, so the top contig is never removed.
+ * Anchor.  a_u is the smallest p for which T_u[p, p + k) is all A C G T.  A contig without one (shorter than k, or dense in
+ * N) is UNANCHORED: it is always kept.  It has no window either, so no candidate names it as v: it contains nothing.
+ * Window.  A window of v is a position w for which T_v[w, w + k) is all A C G T; it never crosses a '_'.
+ * Candidate (u, v, w, o): u is anchored; v != u and v outranks u; w is a window of v; o is 0 or 1 and v's window text equals
+ * u's anchor text (o = 0) or its reverse complement (o = 1), a palindromic anchor giving both; and with j = w - a_u (o = 0)
+ * or j = w - (L_u - k - a_u) (o = 1) the contig fits: 0 <= j and j + L_u <= L_v.  With KC_DEDUP_DUPLICATES_ONLY L_v == L_u
+ * is required as well.
+ * Mismatches of a candidate: the positions i in [0, L_u) at which (o ? rc(T_u) : T_u)[i] and T_v[j + i] differ as bytes; N
+ * equals N.  A candidate is VERIFIED iff its mismatches <= max_mismatches.  u is REDUNDANT iff it has a verified candidate.
+ * The record names one verified candidate: the one with the greatest v under the order above, then the smallest j, then the
+ * smallest o.  status: KC_DEDUP_KEPT when u is not redundant, KC_DEDUP_DUPLICATE when the named v has L_v == L_u,
+ * KC_DEDUP_CONTAINED otherwise.
+ * Output block: the kept contigs in input order, each followed by '_'; depths_out is gathered the same way.  It is a block
+ * that kc_ctg_index_build, kc_submit_ctg_block, kc_ctg_select and kc_fasta_text take as it is.
+ *
+ * Properties (tests/test_dedup_model.py holds the model to them).  With max_mismatches = 0 an anchored u is redundant exactly
+ * when T_u or rc(T_u) is a substring of some T_v that outranks u, and the named container is itself kept.  With
+ * max_mismatches > 0 the anchor must still match exactly -- a copy whose first all-ACGT window carries a difference is not
+ * found -- and the named container may itself be redundant (containment within a distance is not transitive).
+ *
+ * kc_dedup_rec, one per input contig (recs may be NULL): status; container, pos = j, mismatches and orient = o of the named
+ * candidate (container 0xFFFFFFFF, the others 0 when kept); new_index, the contig's index in the output block (0xFFFFFFFF
+ * when removed); len = L_u; absorbed, the redundant contigs whose record names this one; flags KC_DEDUP_UNANCHORED.
+ * Statistics: contigs, bases (the block without separators); anchored, unanchored; windows (of the whole block);
+ * window_hits, the windows whose key is some contig's anchor key; candidates, verified; duplicates, contained, kept (contigs);
+ * kept_bases, removed_bases, longest_removed.
+ *
+ * Protocol, kc_scaffold's.  Unknown flags, non-zero reserved words and NULL params / n_out / nbytes_out are KC_ERR_INVALID_ARG
+ * in front of ctx, kc_last_error naming the value.  on_device applies to all arrays alike (params is the host's); device
+ * records are 16-byte aligned, offsets 8-byte, depths 2-byte, seqs any.  seqs_out == NULL is a size query: *n_out (kept
+ * contigs), *nbytes_out (their block's bytes) and *stats (may be NULL) are written and nothing else.  A capacity (bytes of
+ * seqs_out; offsets_out has room for n_ctgs + 1 entries, depths_out for capacity) below *nbytes_out: KC_ERR_CAPACITY with the
+ * same three written.  offsets_out and depths_out may be NULL; depths == NULL: depths_out is not written.  The block is
+ * checked as kc_ctg_index_build checks it, with the same verdicts, before anything is stored.  More candidates than
+ * max_candidates (0: 2^26) is KC_ERR_CAPACITY, kc_last_error naming both numbers, nothing written: the defined answer to
+ * pathological repeats (n poly-A contigs give n x windows candidates), never a truncation.  n_ctgs == 0: KC_OK, an empty
+ * block.  The call needs neither index, table nor results, works before or after kc_finalize and with rank_n > 1, runs on
+ * the context's stream, returns when its work is done, keeps no state and frees its scratch: at most 84 bytes a
+ * contig (the table included) and 8 for every word of its key, 16 bytes a candidate, 8 a kept contig, a byte for every 1024
+ * of the block, beside the copies of host arrays.
+ */
+#define KC_DEDUP_DUPLICATES_ONLY 1u
+#define KC_DEDUP_KEPT 0u
+#define KC_DEDUP_DUPLICATE 1u
+#define KC_DEDUP_CONTAINED 2u
+#define KC_DEDUP_UNANCHORED 1u
+typedef struct kc_dedup_params { /* 32 bytes */
+  uint32_t max_mismatches;
+  uint32_t flags;
+  uint64_t max_candidates; /* 0: 2^26 */
+  uint32_t reserved[4];    /* zero */
+} kc_dedup_params;
+typedef struct kc_dedup_rec { /* 32 bytes */
+  uint32_t status;
+  uint32_t container, pos, mismatches;
+  uint32_t new_index, len, absorbed;
+  uint8_t orient, flags;
+  uint8_t reserved[2];
+} kc_dedup_rec;
+typedef struct kc_dedup_stats { /* 128 bytes */
+  uint64_t contigs, bases;
+  uint64_t anchored, unanchored;
+  uint64_t windows, window_hits;
+  uint64_t candidates, verified;
+  uint64_t duplicates, contained;
+  uint64_t kept, kept_bases, removed_bases, longest_removed;
+  uint64_t reserved[2]; /* zero */
+} kc_dedup_stats;
+int kc_ctg_dedup(kc_ctx *ctx, const uint8_t *seqs, uint64_t nbytes, const uint64_t *offsets, uint64_t n_ctgs, const uint16_t *depths,
+                 int on_device, const kc_dedup_params *params, kc_dedup_rec *recs, uint8_t *seqs_out, uint64_t capacity,
+                 uint64_t *offsets_out, uint16_t *depths_out, uint64_t *n_out, uint64_t *nbytes_out, kc_dedup_stats *stats);
 /* KmerDHT::kmer_exists / get_kmer_count / get_local_kmer_counts (src/kcount/kmer_dht.cpp:198-245) in bulk, against the
  * results kept in HBM: nq k-mers of num_longs words each, in either orientation; counts[i] = 0 (and left/right = 0)
  * when the k-mer did not survive.  The index over the results is built on the first call after kc_finalize.

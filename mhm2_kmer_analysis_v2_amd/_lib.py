@@ -280,6 +280,27 @@ KC_FASTQ_OUT_PAIRED = 2
 KC_FASTQ_OUT_CHECK = 4
 KC_FASTQ_OUT_MAX_PREFIX = 32
 
+
+class kc_dedup_params(C.Structure):
+    _fields_ = [("max_mismatches", C.c_uint32), ("flags", C.c_uint32), ("max_candidates", C.c_uint64), ("reserved", C.c_uint32 * 4)]
+
+
+class kc_dedup_rec(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("status", "container", "pos", "mismatches", "new_index", "len", "absorbed")] + [
+        ("orient", C.c_uint8), ("flags", C.c_uint8), ("reserved", C.c_uint8 * 2)]
+
+
+class kc_dedup_stats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("contigs", "bases", "anchored", "unanchored", "windows", "window_hits", "candidates", "verified",
+                                          "duplicates", "contained", "kept", "kept_bases", "removed_bases", "longest_removed")] + [
+        ("reserved", C.c_uint64 * 2)]
+
+
+KC_DEDUP_DUPLICATES_ONLY = 1
+KC_DEDUP_KEPT, KC_DEDUP_DUPLICATE, KC_DEDUP_CONTAINED = range(3)
+KC_DEDUP_UNANCHORED = 1
+KC_DEDUP_NONE = 0xFFFFFFFF
+
 # every symbol include/kcount_mi355.h declares: (restype, argtypes)
 SYMBOLS = {
     "kc_abi_version": (C.c_int, []),
@@ -376,6 +397,9 @@ SYMBOLS = {
                                     C.POINTER(kc_fasta_in_stats)]),
     "kc_fastq_text": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int,
                                 C.POINTER(kc_fastq_out_params), C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "kc_ctg_dedup": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int, C.POINTER(kc_dedup_params), C.c_void_p,
+                               C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                               C.POINTER(kc_dedup_stats)]),
     "kc_lookup": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "kc_dump_table": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
     "kc_get_stats": (C.c_int, [C.c_void_p, C.POINTER(kc_stats)]),

@@ -3,7 +3,7 @@
 //
 // Several kinds are one kernel launched by different callers or in different passes; the name in angle brackets says
 // which (kc_align_lengths_kernel<close> is kc_close_gaps' launch of kc_align_lengths_kernel,
-// <assembly> kc_ctg_select's, <fasta> kc_fasta_text's, <fasta in> kc_fasta_to_block's, <fastq out> kc_fastq_text's).  The *_scan_kernel names are
+// <assembly> kc_ctg_select's, <fasta> kc_fasta_text's, <fasta in> kc_fasta_to_block's, <fastq out> kc_fastq_text's, <dedup> kc_ctg_dedup's).  The *_scan_kernel names are
 // the uses of the one shared kc_scan_kernel (kc_scan.hpp) and keep the names they were first reported under.
 #pragma once
 
@@ -200,7 +200,22 @@
   X(KT_RTEXT_SCAN,         "kc_asm_scan_kernel<fastq out>") \
   X(KT_RTEXT_STARTS,       "kc_rtext_starts_kernel") \
   X(KT_RTEXT_SPANS,        "kc_asm_spans_kernel<fastq out>") \
-  X(KT_RTEXT_WRITE,        "kc_rtext_write_kernel")
+  X(KT_RTEXT_WRITE,        "kc_rtext_write_kernel") \
+  X(KT_DEDUP_CHECK,        "kc_align_check_kernel<dedup>") \
+  X(KT_DEDUP_ANCHOR,       "kc_dedup_anchor_kernel") \
+  X(KT_DEDUP_LINK,         "kc_dedup_link_kernel") \
+  X(KT_DEDUP_COUNT,        "kc_dedup_windows_kernel<count>") \
+  X(KT_DEDUP_WRITE,        "kc_dedup_windows_kernel<write>") \
+  X(KT_DEDUP_VERIFY,       "kc_dedup_verify_kernel") \
+  X(KT_DEDUP_VERIFY_LONG,  "kc_dedup_verify_kernel<long>") \
+  X(KT_DEDUP_BEST,         "kc_dedup_best_kernel") \
+  X(KT_DEDUP_PICK,         "kc_dedup_pick_kernel") \
+  X(KT_DEDUP_STATUS,       "kc_dedup_status_kernel") \
+  X(KT_DEDUP_TILE_SCAN,    "kc_link_tile_scan_kernel<dedup>") \
+  X(KT_DEDUP_SCAN,         "kc_dedup_scan_kernel") \
+  X(KT_DEDUP_RECORDS,      "kc_dedup_records_kernel") \
+  X(KT_DEDUP_GATHER,       "kc_dedup_gather_kernel") \
+  X(KT_DEDUP_GATHER_DEPTHS, "kc_dedup_gather_kernel<depths>")
 
 enum {
 #define X(kind, name) kind,

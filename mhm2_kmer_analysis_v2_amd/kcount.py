@@ -16,6 +16,7 @@
                                                       .sort_results()          kc_sort_results
                                                       .dump_text(...)          kc_dump_text_device
   (traverse_debruijn_graph: commented out there)      .unitigs()               kc_build_unitigs
+  (no counterpart: duplicate / contained contigs)     .dedup_contigs(...)      kc_ctg_dedup
   (ctgs.print_stats: commented out there)             .select_contigs(...)     kc_ctg_select
   (ctgs.dump_contigs: commented out there)            .write_fasta(...)        kc_fasta_text
   (options.ctgs_fname / --checkpoint: likewise)       .load_contigs(...)       kc_fasta_to_block
@@ -971,6 +972,39 @@ class KmerCounter:
         check(lib().kc_ctg_select(self._h, ps, nbytes, po, n, 1 if dev else 0, C.byref(prm), order.ptr, C.byref(nsel), C.byref(st)), "kc_ctg_select")
         return order.first(int(nsel.value)), _stats_dict(st)
 
+    def dedup_contigs(self, seqs, offsets, depths=None, max_mismatches=0, duplicates_only=False, max_candidates=0):
+        """A seq block without its duplicate and contained contigs (kc_ctg_dedup): a contig is removed
+        iff its text or its reverse complement lies, with at most max_mismatches differing bytes, inside a contig that is
+        longer, or as long and of smaller index (duplicates_only: as long).  seqs / offsets: numpy arrays or device tensors,
+        as index_contigs takes them; depths: one uint16 per byte of the block, or None; max_candidates: the call's limit (0:
+        2^26), KC_ERR_CAPACITY beyond it.  Returns (seqs, offsets, depths or None, records, stats): the block index_contigs,
+        submit_ctg_block, select_contigs and fasta_text take as it is, one DEDUP_DTYPE record per input contig and
+        kc_dedup_stats as a dict.  Host arrays in give numpy arrays out; device tensors in give device tensors out (offsets
+        int64, depths int16, records a uint8 tensor of 32-byte records).  The block is allocated at the input's size, which
+        the output never exceeds."""
+        nd = 0 if depths is None else (depths.numel() if _ptr(depths)[1] else len(depths))
+        ps, nbytes, po, n, dev = self._block(seqs, offsets, depths=(_ptr(depths)[1], nd))
+        if depths is not None and nd != nbytes:
+            raise ValueError("depths: one uint16 per byte of the block")
+        prm = _lib.kc_dedup_params(max_mismatches, _lib.KC_DEDUP_DUPLICATES_ONLY if duplicates_only else 0, max_candidates)
+        st, nk, nb = _lib.kc_dedup_stats(), C.c_uint64(0), C.c_uint64(0)
+        recs, offs_out = self._out(dev, n, DEDUP_DTYPE, pad=True), self._out(dev, n + 1, np.uint64)
+
+        def call(capacity):
+            out = self._out(dev, capacity, np.uint8, pad=True), (None if depths is None else self._out(dev, capacity, np.uint16, pad=True))
+            self._hand_over(dev)
+            rc = lib().kc_ctg_dedup(self._h, ps, nbytes, po, n, _ptr(depths)[0], 1 if dev else 0, C.byref(prm), recs.ptr, out[0].ptr, capacity,
+                                    offs_out.ptr, out[1] and out[1].ptr, C.byref(nk), C.byref(nb), C.byref(st))
+            return rc, int(nb.value), out
+
+        rc, told, (seqs_out, depths_out) = _retry_on_capacity(nbytes, call, below=1 << 31)
+        check(rc, "kc_ctg_dedup")
+        return seqs_out.first(told), offs_out.first(int(nk.value) + 1), depths_out and depths_out.first(told), recs.first(), _stats_dict(st)
+
+    def dedup_strings(self, seqs, offsets, **kw):
+        """The kept contigs' texts as Python strings (for tests and small inputs): dedup_contigs() without its records."""
+        return _block_strings(*self.dedup_contigs(seqs, offsets, **kw)[:2])
+
     def _fasta_call(self, seqs, offsets, order, prefix, line_width):
         """what the windows of one text share: call(first_byte, address, capacity) -> (written, total), and the side"""
         p_order, dev_o = _ptr(order)
@@ -1268,6 +1302,9 @@ CLOSURE_DTYPE = np.dtype([("cands", "<u4"), ("reads", "<u4"), ("old_join", "<i4"
                           ("status", "u1"), ("pad", "u1", (3,)), ("reserved", "<u4")])
 # kc_fasta_to_block's record of a contig (kc_fasta_rec, 32 bytes)
 FASTA_REC_DTYPE = np.dtype([("hdr_pos", "<u8"), ("hdr_len", "<u4"), ("seq_lines", "<u4"), ("id", "<u8"), ("depth", "<u4"), ("flags", "<u4")])
+# kc_ctg_dedup's record of an input contig (kc_dedup_rec, 32 bytes)
+DEDUP_DTYPE = np.dtype([("status", "<u4"), ("container", "<u4"), ("pos", "<u4"), ("mismatches", "<u4"), ("new_index", "<u4"), ("len", "<u4"),
+                        ("absorbed", "<u4"), ("orient", "u1"), ("flags", "u1"), ("pad", "u1", (2,))])
 BLASTN_ALN_SCORES = (2, 3, 5, 2, 1)
 ALTERNATE_ALN_SCORES = (1, 1, 1, 1, 1)
 
