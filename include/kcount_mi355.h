@@ -123,6 +123,13 @@ int kc_abi_version(void);
 const char *kc_error_string(int status);
 const char *kc_last_error(void); /* text of the last failing HIP call on this thread */
 int kc_device_count(void);       /* 0 without a GPU; never aborts */
+/* KC_DEBUG_FILL=<byte> in the environment (decimal or 0x.., 0..255; read at every allocation): every device or pinned
+ * allocation the library makes is filled with that byte before anything uses it, so that a result which depends on memory
+ * the library has not written differs from its expectation instead of passing on what the allocator handed out (DESIGN.md,
+ * "Poisoned scratch").  A block the library keeps is not filled again.  Unset or unparsable: nothing is filled.  This is
+ * the number of bytes filled since the library was loaded: 0 without the variable; a test that sets it checks that the
+ * figure rose, and so that its calls allocated at all. */
+uint64_t kc_debug_filled_bytes(void);
 
 /* Kmer<MAX_K>::N_LONGS for the MAX_K the reference would pick: k/32+1 (src/main.cpp:169-190, src/kmer.hpp:64). */
 int kc_num_longs(int kmer_len);

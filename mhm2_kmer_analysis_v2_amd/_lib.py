@@ -306,6 +306,7 @@ SYMBOLS = {
     "kc_abi_version": (C.c_int, []),
     "kc_error_string": (C.c_char_p, [C.c_int]),
     "kc_last_error": (C.c_char_p, []),
+    "kc_debug_filled_bytes": (C.c_uint64, []),
     "kc_device_count": (C.c_int, []),
     "kc_num_longs": (C.c_int, [C.c_int]),
     "kc_record_longs": (C.c_int, [C.c_int]),

@@ -14,6 +14,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <atomic>
 #include <new>
 #include <thread>
 #include <string>
@@ -23,6 +24,7 @@
 
 #include "../../include/kcount_mi355.h"
 #include "kc_kinds.hpp"
+#include "kc_debug_fill.hpp"
 #include "kc_bucketed.hpp"
 #include "kc_shard.hpp"
 #include "kc_wire6.hpp"
@@ -392,6 +394,8 @@ extern "C" const char *kc_error_string(int s) {
 
 extern "C" const char *kc_last_error(void) { return g_last_error; }
 
+extern "C" uint64_t kc_debug_filled_bytes(void) { return g_debug_filled.load(); }
+
 extern "C" int kc_device_count(void) {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -733,6 +737,7 @@ static int pick_fast_arena(kc_ctx *c, uint64_t **arena, size_t bytes, uint32_t G
       break;
     }
     ncand = i + 2;
+    if (debug_fill(cand[i + 1], bytes, false) != KC_OK) rc = KC_ERR_HIP;  // KC_DEBUG_FILL: like Mem::reserve's
   }
   int best_i = -1;
   for (int i = 0; i < ncand; i++)

@@ -36,6 +36,26 @@ static int hip_fail(hipError_t e, const char *what, const char *file, int line) 
     if (rc_) return rc_;      \
   } while (0)
 
+// ---- KC_DEBUG_FILL (kc_debug_fill.hpp) ---------------------------------------------------------------------------------
+// A fresh allocation filled with the variable's byte: whatever the library reads before it has written it is then that
+// byte, on every box and at every size, not what the allocator happened to hand out.  Unset: the getenv and nothing else.
+// A device fill is complete on the device when this returns (the null stream is waited for), so that it is ordered
+// ahead of any stream's work on the block.  Only reserve() below and the arena probe call it, on what they have just made.
+static std::atomic<uint64_t> g_debug_filled{0};
+
+static int debug_fill(void *p, size_t bytes, bool pinned) {
+  const int fill = debug_fill_byte();
+  if (fill < 0 || !p || !bytes) return KC_OK;
+  if (pinned) {
+    memset(p, fill, bytes);
+  } else {
+    HIPCHK(hipMemset(p, fill, bytes));
+    HIPCHK(hipStreamSynchronize(nullptr));
+  }
+  g_debug_filled += bytes;
+  return KC_OK;
+}
+
 static dim3 blocks_for(uint64_t n, unsigned tpb = 256) { return dim3((unsigned)((n + tpb - 1) / tpb)); }
 
 // ---- owners ------------------------------------------------------------------------------------------------------------
@@ -68,7 +88,7 @@ template <bool PINNED> struct Mem {
     HIPCHK(release());
     HIPCHK(PINNED ? hipHostMalloc((void **)&p, bytes, hipHostMallocDefault) : hipMalloc((void **)&p, bytes));
     cap = bytes;
-    return KC_OK;
+    return debug_fill(p, bytes, PINNED);
   }
   void swap(Mem &o) {
     std::swap(p, o.p);

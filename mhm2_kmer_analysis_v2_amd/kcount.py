@@ -22,6 +22,7 @@
   (options.ctgs_fname / --checkpoint: likewise)       .load_contigs(...)       kc_fasta_to_block
 """
 import ctypes as C
+import os
 
 import numpy as np
 
@@ -88,23 +89,42 @@ def _side(ref, dev, **others):
 _TORCH_OF = {"uint8": "uint8", "uint16": "int16", "uint32": "int32", "uint64": "int64"}
 
 
+def _debug_fill():
+    """The byte of KC_DEBUG_FILL as the library reads it (csrc/kc_debug_fill.hpp: decimal or 0x.., 0..255, nothing else), or
+    None: what outputs nobody asked zeroed are made of, so that an element the library did not write shows."""
+    s = os.environ.get("KC_DEBUG_FILL", "")
+    hexa = s[:2] in ("0x", "0X")
+    digits = s[2:] if hexa else s
+    allowed = "0123456789abcdefABCDEF" if hexa else "0123456789"
+    if not digits or any(ch not in allowed for ch in digits):
+        return None
+    v = int(digits, 16 if hexa else 10)
+    return v if v <= 255 else None
+
+
 class _Out:
     """One output array of a call, of n elements of a record dtype or a scalar dtype, and its address (ptr).  device None:
     a numpy array of zeros; else the torch device: an uninitialised tensor (zeroed=True: zeros), records as uint8 bytes of
-    n * itemsize.  pad: room for one element where n is 0, so that the library gets an address; an exact array of no
-    elements has torch's address 0 on the device, which the library reads as NULL -- for the seqs of a call, a size query."""
+    n * itemsize.  With KC_DEBUG_FILL set, either is made of that byte unless zeroed=True asks for zeros.  pad: room for
+    one element where n is 0, so that the library gets an address; an exact array of no elements has torch's address 0 on
+    the device, which the library reads as NULL -- for the seqs of a call, a size query."""
 
     def __init__(self, device, n, dtype, pad=False, zeroed=False):
         dtype = np.dtype(dtype)
         # elements of `a` to one of the n: the bytes of a record on the device, else one
         self.n, self.size = n, dtype.itemsize if dtype.fields and device is not None else 1
         m = max(n, 1) if pad else n
+        fill = None if zeroed else _debug_fill()
         if device is None:
             self.a = np.zeros(m, dtype=dtype)
+            if fill is not None:
+                self.a.view(np.uint8)[...] = fill
         else:
             import torch
             kind = torch.uint8 if dtype.fields else getattr(torch, _TORCH_OF[dtype.name])
             self.a = (torch.zeros if zeroed else torch.empty)(m * self.size, dtype=kind, device=device)
+            if fill is not None:
+                self.a.view(torch.uint8).fill_(fill)
         self.ptr = _ptr(self.a)[0]
 
     def first(self, n=None):
