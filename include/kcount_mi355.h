@@ -1523,6 +1523,69 @@ typedef struct kc_dedup_stats { /* 128 bytes */
 int kc_ctg_dedup(kc_ctx *ctx, const uint8_t *seqs, uint64_t nbytes, const uint64_t *offsets, uint64_t n_ctgs, const uint16_t *depths,
                  int on_device, const kc_dedup_params *params, kc_dedup_rec *recs, uint8_t *seqs_out, uint64_t capacity,
                  uint64_t *offsets_out, uint16_t *depths_out, uint64_t *n_out, uint64_t *nbytes_out, kc_dedup_stats *stats);
+/* ---- k-mer depths of sequences and the count spectrum (tests/kdepth_model.py) ------------------------
+ * Two readers of the finished results.  The reference holds no code for either (it asks the table k-mer by k-mer,
+ * KmerDHT::get_kmer_count, src/kcount/kmer_dht.cpp:198-245, and computes contig depths from such counts), so the rules below
+ * are this project's own.
+ *
+ * kc_seq_kmer_depths: the depth track of sequences.  Sequence i is bytes [offsets[i], offsets[i+1]) of seqs; offsets[0] = 0,
+ * offsets[nseqs] = nbytes, offsets never decrease, empty sequences are allowed.  One form serves reads (bases and offsets as
+ * kc_align_reads takes them) and a seq block with its own offsets, where a contig's trailing '_' is simply its last byte.
+ * A C G T a c g t are bases; every other byte (N, '_', anything) is not a base and is not an error.  With k the context's
+ * kmer_len, position p of sequence i is a window iff p + k <= offsets[i+1] and all k bytes are bases; a window never spans two
+ * sequences.  The window's key is the canonical k-mer of its upper-cased bytes, its count that k-mer's count among the results,
+ * 0 when it is not there: purged as a singleton, below dmin_thres, with a fork or dead-end extension, or another rank's.
+ *
+ * track (nbytes values, may be NULL): track[p] is the window's count at a window start and 0 on every other byte.  With
+ * KC_KDEPTH_FILL_MEAN track[p] is instead the sequence's mean on every base byte and 0 on every non-base byte: what
+ * kc_submit_ctg_block takes, and what kc_build_unitigs writes as d_depths.  recs (one per sequence, may be NULL): sum of the
+ * windows' counts; windows; present, those with a count above 0; solid, those with a count >= max(min_count, 1); min_count and
+ * max_count over the present windows, 0 and 0 without one; mean = windows ? min(65535, (2 * sum + windows) / (2 * windows)) : 0.
+ * stats (may be NULL): seqs, bytes, the totals of windows, present, solid and sum, and longest, the longest sequence in bytes.
+ *
+ * KC_ERR_STATE before kc_finalize.  rank_n > 1: own k-mers only; every k-mer lives on exactly one rank, so the ranks' tracks
+ * (without KC_KDEPTH_FILL_MEAN), sums, present and solid add up to the single-rank answer.  The call uses the lookup index of
+ * kc_lookup and builds it if absent; the results are not sorted, moved or touched, and earlier kc_result pointers stay valid.
+ * KC_ERR_INVALID_ARG, before any device call: NULL ctx / params / offsets, NULL seqs with nbytes > 0, unknown flags, non-zero
+ * reserved words, min_count > 65535, misaligned device arrays (offsets 8 bytes, track 2, recs 16); from the device check:
+ * offsets that go backwards, offsets[0] != 0, offsets[nseqs] != nbytes.  KC_ERR_CAPACITY: a sequence of 2^32 bytes or more,
+ * 2^32 sequences or more.  kc_last_error names the value.  On any error nothing is written.  nseqs == 0 or nbytes == 0: KC_OK
+ * without a look at the offsets, zero stats, zero records, a zero track.  Positions are 64-bit, since a block of reads passes
+ * 2^32 bytes; no test reaches that size.  The call runs on the context's stream and returns when its work there is done; its
+ * scratch (32 bytes a sequence where records or means are asked for, the copies of host arrays) lives for the call.
+ * on_device != 0: seqs, offsets, track and recs are device pointers.
+ *
+ * kc_count_spectrum: hist[c] (KC_SPECTRUM_BINS values) is the number of results whose count is c.  hist or stats may be NULL,
+ * not both (KC_ERR_INVALID_ARG).  KC_ERR_STATE before kc_finalize.  With rank_n > 1 the ranks' histograms add.  on_device != 0:
+ * hist is a device pointer (8-byte aligned); stats is always the host's.
+ */
+#define KC_KDEPTH_FILL_MEAN 1u
+typedef struct kc_kdepth_params { /* 32 bytes */
+  uint32_t min_count;             /* a window is "solid" when its count >= max(min_count, 1); at most 65535 */
+  uint32_t flags;                 /* KC_KDEPTH_FILL_MEAN */
+  uint32_t reserved[6];           /* zero */
+} kc_kdepth_params;
+typedef struct kc_kdepth_rec { /* 32 bytes, one per sequence */
+  uint64_t sum;                /* sum of the windows' counts */
+  uint32_t windows, present, solid;
+  uint16_t min_count, max_count; /* over the present windows; 0 and 0 when there is none */
+  uint16_t mean;                 /* windows ? min(65535, (2*sum + windows) / (2*windows)) : 0 */
+  uint16_t reserved[3];          /* zero */
+} kc_kdepth_rec;
+typedef struct kc_kdepth_stats { /* 64 bytes */
+  uint64_t seqs, bytes, windows, present, solid, sum, longest, reserved;
+} kc_kdepth_stats;
+int kc_seq_kmer_depths(kc_ctx *ctx, const uint8_t *seqs, uint64_t nbytes, const uint64_t *offsets, uint64_t nseqs, int on_device,
+                       const kc_kdepth_params *params, uint16_t *track, kc_kdepth_rec *recs, kc_kdepth_stats *stats);
+#define KC_SPECTRUM_BINS 65536
+typedef struct kc_spectrum_stats { /* 64 bytes */
+  uint64_t kmers, sum_counts;      /* = kc_stats.total_kmers, kc_stats.sum_counts */
+  uint64_t max_count;              /* greatest count with a k-mer, 0 without results */
+  uint64_t mode_count, mode_kmers; /* the count most k-mers have, the smallest on a tie; how many */
+  uint64_t saturated;              /* hist[65535] */
+  uint64_t reserved[2];
+} kc_spectrum_stats;
+int kc_count_spectrum(kc_ctx *ctx, uint64_t *hist, int on_device, kc_spectrum_stats *stats);
 /* KmerDHT::kmer_exists / get_kmer_count / get_local_kmer_counts (src/kcount/kmer_dht.cpp:198-245) in bulk, against the
  * results kept in HBM: nq k-mers of num_longs words each, in either orientation; counts[i] = 0 (and left/right = 0)
  * when the k-mer did not survive.  The index over the results is built on the first call after kc_finalize.

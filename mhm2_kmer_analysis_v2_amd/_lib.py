@@ -301,6 +301,27 @@ KC_DEDUP_KEPT, KC_DEDUP_DUPLICATE, KC_DEDUP_CONTAINED = range(3)
 KC_DEDUP_UNANCHORED = 1
 KC_DEDUP_NONE = 0xFFFFFFFF
 
+class kc_kdepth_params(C.Structure):
+    _fields_ = [("min_count", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 6)]
+
+
+class kc_kdepth_rec(C.Structure):
+    _fields_ = [("sum", C.c_uint64), ("windows", C.c_uint32), ("present", C.c_uint32), ("solid", C.c_uint32), ("min_count", C.c_uint16),
+                ("max_count", C.c_uint16), ("mean", C.c_uint16), ("reserved", C.c_uint16 * 3)]
+
+
+class kc_kdepth_stats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("seqs", "bytes", "windows", "present", "solid", "sum", "longest", "reserved")]
+
+
+class kc_spectrum_stats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("kmers", "sum_counts", "max_count", "mode_count", "mode_kmers", "saturated")] + [
+        ("reserved", C.c_uint64 * 2)]
+
+
+KC_KDEPTH_FILL_MEAN = 1
+KC_SPECTRUM_BINS = 65536
+
 # every symbol include/kcount_mi355.h declares: (restype, argtypes)
 SYMBOLS = {
     "kc_abi_version": (C.c_int, []),
@@ -401,6 +422,9 @@ SYMBOLS = {
     "kc_ctg_dedup": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int, C.POINTER(kc_dedup_params), C.c_void_p,
                                C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                C.POINTER(kc_dedup_stats)]),
+    "kc_seq_kmer_depths": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.POINTER(kc_kdepth_params), C.c_void_p,
+                                     C.c_void_p, C.POINTER(kc_kdepth_stats)]),
+    "kc_count_spectrum": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(kc_spectrum_stats)]),
     "kc_lookup": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "kc_dump_table": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
     "kc_get_stats": (C.c_int, [C.c_void_p, C.POINTER(kc_stats)]),

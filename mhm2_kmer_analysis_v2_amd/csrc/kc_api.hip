@@ -47,6 +47,7 @@
 #include "kc_fasta_in.hpp"
 #include "kc_fastq_out.hpp"
 #include "kc_dedup.hpp"
+#include "kc_kdepth.hpp"
 
 using namespace kc;
 
@@ -2977,6 +2978,7 @@ extern "C" int kc_lookup(kc_ctx *c, const uint64_t *queries, uint64_t nq, int on
 #include "kc_api_fastq_out.hpp"  // kc_fastq_text
 #include "kc_api_fasta_in.hpp"  // kc_fasta_to_block
 #include "kc_api_dedup.hpp"  // kc_ctg_dedup
+#include "kc_api_kdepth.hpp"  // kc_seq_kmer_depths, kc_count_spectrum
 
 // ---- the contig pass (kc_ctg.hpp) ----------------------------------------------------------------------------------
 extern "C" int kc_begin_ctg_kmers(kc_ctx *c, uint64_t max_ctg_kmers) {

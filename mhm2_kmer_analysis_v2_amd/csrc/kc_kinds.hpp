@@ -215,7 +215,14 @@
   X(KT_DEDUP_SCAN,         "kc_dedup_scan_kernel") \
   X(KT_DEDUP_RECORDS,      "kc_dedup_records_kernel") \
   X(KT_DEDUP_GATHER,       "kc_dedup_gather_kernel") \
-  X(KT_DEDUP_GATHER_DEPTHS, "kc_dedup_gather_kernel<depths>")
+  X(KT_DEDUP_GATHER_DEPTHS, "kc_dedup_gather_kernel<depths>") \
+  X(KT_KTRACK_OFFSETS,     "kc_ktrack_offsets_kernel") \
+  X(KT_KTRACK_WINDOWS,     "kc_ktrack_windows_kernel") \
+  X(KT_KTRACK_WINDOWS_FILL, "kc_ktrack_windows_kernel<fill>") \
+  X(KT_KTRACK_RECORDS,     "kc_ktrack_records_kernel") \
+  X(KT_KTRACK_FILL,        "kc_ktrack_fill_kernel") \
+  X(KT_SPECT_HIST,         "kc_spect_hist_kernel") \
+  X(KT_SPECT_STATS,        "kc_spect_stats_kernel")
 
 enum {
 #define X(kind, name) kind,

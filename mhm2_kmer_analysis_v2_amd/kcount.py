@@ -17,6 +17,8 @@
                                                       .dump_text(...)          kc_dump_text_device
   (traverse_debruijn_graph: commented out there)      .unitigs()               kc_build_unitigs
   (no counterpart: duplicate / contained contigs)     .dedup_contigs(...)      kc_ctg_dedup
+  get_kmer_count over a sequence's k-mers             .kmer_depths(...)        kc_seq_kmer_depths
+  (no counterpart: the histogram of the counts)       .count_spectrum()        kc_count_spectrum
   (ctgs.print_stats: commented out there)             .select_contigs(...)     kc_ctg_select
   (ctgs.dump_contigs: commented out there)            .write_fasta(...)        kc_fasta_text
   (options.ctgs_fname / --checkpoint: likewise)       .load_contigs(...)       kc_fasta_to_block
@@ -1025,6 +1027,38 @@ class KmerCounter:
         """The kept contigs' texts as Python strings (for tests and small inputs): dedup_contigs() without its records."""
         return _block_strings(*self.dedup_contigs(seqs, offsets, **kw)[:2])
 
+    def kmer_depths(self, seqs, offsets, min_count=0, fill_mean=False, with_track=True, with_records=True):
+        """The k-mer depth of sequences in the finished results (kc_seq_kmer_depths).  seqs / offsets:
+        the bases and offsets of reads, or a seq block with its own offsets, numpy arrays or device tensors.  Returns
+        (track, records, stats): track[p] the count of the window that starts at byte p, 0 where none does (fill_mean: the
+        sequence's mean on every base byte, what submit_ctg_block takes), one KDEPTH_DTYPE record per sequence, and
+        kc_kdepth_stats as a dict; a window counts as solid at min_count or more.  with_track / with_records False: None in
+        that place, and the library is not asked for it.  Host arrays in give numpy arrays out; device tensors in give device
+        tensors out (the track int16, records a uint8 tensor of 32-byte records)."""
+        ps, nbytes, po, n, dev = self._block(seqs, offsets)
+        prm = _lib.kc_kdepth_params(min_count, _lib.KC_KDEPTH_FILL_MEAN if fill_mean else 0)
+        st = _lib.kc_kdepth_stats()
+        track = self._out(dev, nbytes, np.uint16, pad=True) if with_track else None
+        recs = self._out(dev, n, KDEPTH_DTYPE, pad=True) if with_records else None
+        self._hand_over(dev)
+        check(lib().kc_seq_kmer_depths(self._h, ps, nbytes, po, n, 1 if dev else 0, C.byref(prm), track and track.ptr, recs and recs.ptr,
+                                       C.byref(st)), "kc_seq_kmer_depths")
+        return track and track.first(), recs and recs.first(), _stats_dict(st)
+
+    def contig_kmer_depths(self, seqs, offsets):
+        """One depth per byte of a seq block, from the k-mer counts of the finished results: every contig's mean window count
+        on its bases, 0 on its separator.  The array submit_ctg_block takes."""
+        return self.kmer_depths(seqs, offsets, fill_mean=True, with_records=False)[0]
+
+    def count_spectrum(self, on_device=False):
+        """The histogram of the results' counts (kc_count_spectrum): (hist, stats), hist[c] the number of results whose count
+        is c, a uint64 numpy array of 65536 values (on_device: an int64 device tensor), and kc_spectrum_stats as a dict."""
+        hist = self._out(on_device, _lib.KC_SPECTRUM_BINS, np.uint64)
+        st = _lib.kc_spectrum_stats()
+        self._hand_over(on_device)
+        check(lib().kc_count_spectrum(self._h, hist.ptr, 1 if on_device else 0, C.byref(st)), "kc_count_spectrum")
+        return hist.first(), _stats_dict(st)
+
     def _fasta_call(self, seqs, offsets, order, prefix, line_width):
         """what the windows of one text share: call(first_byte, address, capacity) -> (written, total), and the side"""
         p_order, dev_o = _ptr(order)
@@ -1325,6 +1359,20 @@ FASTA_REC_DTYPE = np.dtype([("hdr_pos", "<u8"), ("hdr_len", "<u4"), ("seq_lines"
 # kc_ctg_dedup's record of an input contig (kc_dedup_rec, 32 bytes)
 DEDUP_DTYPE = np.dtype([("status", "<u4"), ("container", "<u4"), ("pos", "<u4"), ("mismatches", "<u4"), ("new_index", "<u4"), ("len", "<u4"),
                         ("absorbed", "<u4"), ("orient", "u1"), ("flags", "u1"), ("pad", "u1", (2,))])
+# kc_seq_kmer_depths' record of a sequence (kc_kdepth_rec, 32 bytes)
+KDEPTH_DTYPE = np.dtype([("sum", "<u8"), ("windows", "<u4"), ("present", "<u4"), ("solid", "<u4"), ("min_count", "<u2"), ("max_count", "<u2"),
+                         ("mean", "<u2"), ("pad", "<u2", (3,))])
+
+
+def format_spectrum(hist):
+    """The text of a count spectrum: a line "<count> <kmers>\n" for every bin that is not zero, counts ascending.  hist: what
+    count_spectrum returns, a numpy array or a device tensor."""
+    if not isinstance(hist, np.ndarray):
+        hist = hist.cpu().numpy()
+    hist = np.ascontiguousarray(hist).view(np.uint64)  # a tensor's int64 holds the bits
+    return "".join("%d %d\n" % (c, int(hist[c])) for c in np.flatnonzero(hist))
+
+
 BLASTN_ALN_SCORES = (2, 3, 5, 2, 1)
 ALTERNATE_ALN_SCORES = (1, 1, 1, 1, 1)
 
