@@ -1,4 +1,4 @@
-"""ctypes binding of libkcount_mi355.so (include/kcount_mi355.h).  No fallback of any kind."""
+"""ctypes binding of libkcount_mi355.so (include/kcount_mi355.h, include/kcount_mi355_correct.h).  No fallback of any kind."""
 import ctypes as C
 import os
 
@@ -322,6 +322,29 @@ class kc_spectrum_stats(C.Structure):
 KC_KDEPTH_FILL_MEAN = 1
 KC_SPECTRUM_BINS = 65536
 
+
+class kc_correct_params(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("min_count", "min_gain", "min_windows", "rounds", "max_qual", "flags")] + [("reserved", C.c_uint32 * 2)]
+
+
+class kc_correct_rec(C.Structure):
+    _fields_ = [("weak_before", C.c_uint32), ("weak_after", C.c_uint32), ("corrected", C.c_uint16), ("flags", C.c_uint16), ("reserved", C.c_uint32)]
+
+
+class kc_correct_fix(C.Structure):
+    _fields_ = [("seq", C.c_uint32), ("pos", C.c_uint32), ("old_base", C.c_uint8), ("new_base", C.c_uint8), ("round", C.c_uint8), ("side", C.c_uint8),
+                ("score", C.c_uint16), ("runner_up", C.c_uint16)]
+
+
+class kc_correct_stats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("seqs", "bytes", "windows", "weak_before", "weak_after", "sites", "accepted", "rounds")]
+
+
+(KC_CORRECT_UNANCHORED, KC_CORRECT_SHORT_RUN, KC_CORRECT_THIN, KC_CORRECT_QUAL_GATED, KC_CORRECT_NO_GAIN,
+ KC_CORRECT_AMBIGUOUS) = (1 << i for i in range(6))
+KC_CORRECT_MAX_ROUNDS = 8
+KC_CORRECT_LEFT, KC_CORRECT_RIGHT = 0, 1
+
 # every symbol include/kcount_mi355.h declares: (restype, argtypes)
 SYMBOLS = {
     "kc_abi_version": (C.c_int, []),
@@ -437,6 +460,12 @@ SYMBOLS = {
                                         C.c_void_p]),
 }
 
+# every symbol include/kcount_mi355_correct.h declares, in the same form
+SYMBOLS_CORRECT = {
+    "kc_correct_reads": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.POINTER(kc_correct_params),
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(kc_correct_stats)]),
+}
+
 
 def lib_path():
     # KC_LIB: an alternative build of the same library (tuning experiments only)
@@ -452,7 +481,7 @@ def lib():
             raise ImportError("%s is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                               "(or make -C mhm2_kmer_analysis_v2_amd/csrc); there is no CPU fallback" % p)
         L = C.CDLL(p)
-        for name, (res, args) in SYMBOLS.items():
+        for name, (res, args) in list(SYMBOLS.items()) + list(SYMBOLS_CORRECT.items()):
             f = getattr(L, name)  # AttributeError if the .so does not export a declared symbol
             f.restype = res
             f.argtypes = args

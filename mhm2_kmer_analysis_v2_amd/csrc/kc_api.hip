@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "../../include/kcount_mi355.h"
+#include "../../include/kcount_mi355_correct.h"
 #include "kc_kinds.hpp"
 #include "kc_debug_fill.hpp"
 #include "kc_bucketed.hpp"
@@ -48,6 +49,7 @@
 #include "kc_fastq_out.hpp"
 #include "kc_dedup.hpp"
 #include "kc_kdepth.hpp"
+#include "kc_correct.hpp"
 
 using namespace kc;
 
@@ -2979,6 +2981,7 @@ extern "C" int kc_lookup(kc_ctx *c, const uint64_t *queries, uint64_t nq, int on
 #include "kc_api_fasta_in.hpp"  // kc_fasta_to_block
 #include "kc_api_dedup.hpp"  // kc_ctg_dedup
 #include "kc_api_kdepth.hpp"  // kc_seq_kmer_depths, kc_count_spectrum
+#include "kc_api_correct.hpp"  // kc_correct_reads
 
 // ---- the contig pass (kc_ctg.hpp) ----------------------------------------------------------------------------------
 extern "C" int kc_begin_ctg_kmers(kc_ctx *c, uint64_t max_ctg_kmers) {

@@ -3,7 +3,7 @@
 //
 // Several kinds are one kernel launched by different callers or in different passes; the name in angle brackets says
 // which (kc_align_lengths_kernel<close> is kc_close_gaps' launch of kc_align_lengths_kernel,
-// <assembly> kc_ctg_select's, <fasta> kc_fasta_text's, <fasta in> kc_fasta_to_block's, <fastq out> kc_fastq_text's, <dedup> kc_ctg_dedup's).  The *_scan_kernel names are
+// <assembly> kc_ctg_select's, <fasta> kc_fasta_text's, <fasta in> kc_fasta_to_block's, <fastq out> kc_fastq_text's, <dedup> kc_ctg_dedup's, <correct> kc_correct_reads').  The *_scan_kernel names are
 // the uses of the one shared kc_scan_kernel (kc_scan.hpp) and keep the names they were first reported under.
 #pragma once
 
@@ -222,7 +222,16 @@
   X(KT_KTRACK_RECORDS,     "kc_ktrack_records_kernel") \
   X(KT_KTRACK_FILL,        "kc_ktrack_fill_kernel") \
   X(KT_SPECT_HIST,         "kc_spect_hist_kernel") \
-  X(KT_SPECT_STATS,        "kc_spect_stats_kernel")
+  X(KT_SPECT_STATS,        "kc_spect_stats_kernel") \
+  X(KT_CORRECT_OFFSETS,    "kc_ktrack_offsets_kernel<correct>") \
+  X(KT_CORRECT_TRACK,      "kc_ktrack_windows_kernel<correct>") \
+  X(KT_CORRECT_SITES_COUNT, "kc_correct_sites_kernel<count>") \
+  X(KT_CORRECT_SITES_SCAN, "kc_correct_scan_kernel<sites>") \
+  X(KT_CORRECT_SITES_WRITE, "kc_correct_sites_kernel<write>") \
+  X(KT_CORRECT_EVAL,       "kc_correct_eval_kernel") \
+  X(KT_CORRECT_ACCEPT_SCAN, "kc_correct_scan_kernel<accepted>") \
+  X(KT_CORRECT_APPLY,      "kc_correct_apply_kernel") \
+  X(KT_CORRECT_RECORDS,    "kc_correct_records_kernel")
 
 enum {
 #define X(kind, name) kind,

@@ -1045,6 +1045,41 @@ class KmerCounter:
                                        C.byref(st)), "kc_seq_kmer_depths")
         return track and track.first(), recs and recs.first(), _stats_dict(st)
 
+    def correct_reads(self, bases, offsets, quals=None, min_count=2, min_gain=8, min_windows=2, rounds=3, max_qual=0, with_records=True,
+                      with_fixes=False):
+        """Reads with their substitution errors corrected from the finished results (kc_correct_reads).
+        bases / offsets (and quals, only read with max_qual > 0): numpy arrays or device tensors, as kmer_depths takes them.  A
+        window is solid at max(min_count, 1) or more; a weak run beside a solid window gives a site, the byte the first weak
+        window holds and the anchor does not; a site is corrected to the one base that makes at least min(n, min_gain) leading
+        windows of its range solid and more than either other base.  Returns (out, records, fixes, stats): out the corrected
+        bases, of the same length and offsets; one CORRECT_REC_DTYPE record per sequence (with_records False: None); the
+        CORRECT_FIX_DTYPE entries ordered by (round, seq, pos) (with_fixes False: None; True: room is found; a number: room for
+        that many, KC_ERR_CAPACITY beyond); kc_correct_stats as a dict.  Host arrays in give numpy arrays out, device tensors
+        in give device tensors out (records and fixes as uint8 tensors of 16-byte entries)."""
+        ps, nbytes, po, n, dev = self._block(bases, offsets)
+        pq, dev_q = _ptr(quals)
+        if quals is not None and bool(dev_q) != bool(dev):
+            raise ValueError("quals: a call's arrays are all host arrays or all device tensors")
+        prm = _lib.kc_correct_params(min_count, min_gain, min_windows, rounds, max_qual, 0)
+        out = self._out(dev, nbytes, np.uint8, pad=True)
+        recs = self._out(dev, n, CORRECT_REC_DTYPE, pad=True) if with_records else None
+        self._hand_over(dev)
+
+        def call(capacity):
+            st = _lib.kc_correct_stats()
+            fixes = self._out(dev, capacity, CORRECT_FIX_DTYPE, pad=True) if with_fixes is not False else None
+            self._hand_over(dev and fixes is not None)
+            rc = lib().kc_correct_reads(self._h, ps, pq, nbytes, po, n, 1 if dev else 0, C.byref(prm), out.ptr, recs and recs.ptr,
+                                        fixes and fixes.ptr, capacity, C.byref(st))
+            return rc, fixes, st
+
+        exact = with_fixes is not True and with_fixes is not False
+        rc, fixes, st = call(int(with_fixes) if exact else nbytes // 16 + 1024)
+        if rc == _lib.KC_ERR_CAPACITY and with_fixes is True:
+            rc, fixes, st = call(nbytes * max(rounds, 1))  # a round changes a byte at most once
+        check(rc, "kc_correct_reads")
+        return out.first(), recs and recs.first(), fixes and fixes.first(int(st.accepted)), _stats_dict(st)
+
     def contig_kmer_depths(self, seqs, offsets):
         """One depth per byte of a seq block, from the k-mer counts of the finished results: every contig's mean window count
         on its bases, 0 on its separator.  The array submit_ctg_block takes."""
@@ -1362,6 +1397,11 @@ DEDUP_DTYPE = np.dtype([("status", "<u4"), ("container", "<u4"), ("pos", "<u4"),
 # kc_seq_kmer_depths' record of a sequence (kc_kdepth_rec, 32 bytes)
 KDEPTH_DTYPE = np.dtype([("sum", "<u8"), ("windows", "<u4"), ("present", "<u4"), ("solid", "<u4"), ("min_count", "<u2"), ("max_count", "<u2"),
                          ("mean", "<u2"), ("pad", "<u2", (3,))])
+
+# kc_correct_reads' record of a sequence (kc_correct_rec) and entry of a corrected byte (kc_correct_fix), 16 bytes each
+CORRECT_REC_DTYPE = np.dtype([("weak_before", "<u4"), ("weak_after", "<u4"), ("corrected", "<u2"), ("flags", "<u2"), ("reserved", "<u4")])
+CORRECT_FIX_DTYPE = np.dtype([("seq", "<u4"), ("pos", "<u4"), ("old", "u1"), ("new", "u1"), ("round", "u1"), ("side", "u1"), ("score", "<u2"),
+                              ("runner_up", "<u2")])
 
 
 def format_spectrum(hist):
