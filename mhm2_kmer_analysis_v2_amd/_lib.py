@@ -1,4 +1,4 @@
-"""ctypes binding of libkcount_mi355.so (include/kcount_mi355.h, include/kcount_mi355_correct.h).  No fallback of any kind."""
+"""ctypes binding of libkcount_mi355.so (include/kcount_mi355.h, include/kcount_mi355_correct.h, include/kcount_mi355_polish.h).  No fallback of any kind."""
 import ctypes as C
 import os
 
@@ -345,6 +345,28 @@ class kc_correct_stats(C.Structure):
 KC_CORRECT_MAX_ROUNDS = 8
 KC_CORRECT_LEFT, KC_CORRECT_RIGHT = 0, 1
 
+
+
+class kc_polish_params(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("min_score", "min_len", "edge_clip", "max_mismatches", "min_depth", "min_permille", "min_qual", "flags")]
+
+
+class kc_polish_ctg(C.Structure):
+    _fields_ = [("votes", C.c_uint64)] + [(n, C.c_uint32) for n in ("placed", "changed", "filled", "disputed", "thin", "uncovered")]
+
+
+class kc_polish_fix(C.Structure):
+    _fields_ = [("pos", C.c_uint32), ("ctg", C.c_uint32), ("old_base", C.c_uint8), ("new_base", C.c_uint8), ("top", C.c_uint16), ("tot", C.c_uint16),
+                ("pad", C.c_uint16)]
+
+
+class kc_polish_stats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("records", "none", "filtered", "not_best", "unequal", "divergent", "placed", "votes", "columns", "uncovered",
+                                          "thin", "disputed", "confirmed", "changed", "filled", "sort_passes")]
+
+
+KC_POLISH_BEST_ONLY = 1
+
 # every symbol include/kcount_mi355.h declares: (restype, argtypes)
 SYMBOLS = {
     "kc_abi_version": (C.c_int, []),
@@ -466,6 +488,12 @@ SYMBOLS_CORRECT = {
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(kc_correct_stats)]),
 }
 
+# every symbol include/kcount_mi355_polish.h declares, in the same form
+SYMBOLS_POLISH = {
+    "kc_ctg_polish": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.POINTER(kc_polish_params),
+                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(kc_polish_stats)]),
+}
+
 
 def lib_path():
     # KC_LIB: an alternative build of the same library (tuning experiments only)
@@ -481,7 +509,7 @@ def lib():
             raise ImportError("%s is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                               "(or make -C mhm2_kmer_analysis_v2_amd/csrc); there is no CPU fallback" % p)
         L = C.CDLL(p)
-        for name, (res, args) in list(SYMBOLS.items()) + list(SYMBOLS_CORRECT.items()):
+        for name, (res, args) in list(SYMBOLS.items()) + list(SYMBOLS_CORRECT.items()) + list(SYMBOLS_POLISH.items()):
             f = getattr(L, name)  # AttributeError if the .so does not export a declared symbol
             f.restype = res
             f.argtypes = args

@@ -24,6 +24,7 @@
 
 #include "../../include/kcount_mi355.h"
 #include "../../include/kcount_mi355_correct.h"
+#include "../../include/kcount_mi355_polish.h"
 #include "kc_kinds.hpp"
 #include "kc_debug_fill.hpp"
 #include "kc_bucketed.hpp"
@@ -50,6 +51,7 @@
 #include "kc_dedup.hpp"
 #include "kc_kdepth.hpp"
 #include "kc_correct.hpp"
+#include "kc_polish.hpp"
 
 using namespace kc;
 
@@ -2982,6 +2984,7 @@ extern "C" int kc_lookup(kc_ctx *c, const uint64_t *queries, uint64_t nq, int on
 #include "kc_api_dedup.hpp"  // kc_ctg_dedup
 #include "kc_api_kdepth.hpp"  // kc_seq_kmer_depths, kc_count_spectrum
 #include "kc_api_correct.hpp"  // kc_correct_reads
+#include "kc_api_polish.hpp"  // kc_ctg_polish
 
 // ---- the contig pass (kc_ctg.hpp) ----------------------------------------------------------------------------------
 extern "C" int kc_begin_ctg_kmers(kc_ctx *c, uint64_t max_ctg_kmers) {

@@ -3,7 +3,7 @@
 //
 // Several kinds are one kernel launched by different callers or in different passes; the name in angle brackets says
 // which (kc_align_lengths_kernel<close> is kc_close_gaps' launch of kc_align_lengths_kernel,
-// <assembly> kc_ctg_select's, <fasta> kc_fasta_text's, <fasta in> kc_fasta_to_block's, <fastq out> kc_fastq_text's, <dedup> kc_ctg_dedup's, <correct> kc_correct_reads').  The *_scan_kernel names are
+// <assembly> kc_ctg_select's, <fasta> kc_fasta_text's, <fasta in> kc_fasta_to_block's, <fastq out> kc_fastq_text's, <dedup> kc_ctg_dedup's, <correct> kc_correct_reads', <polish> kc_ctg_polish's).  The *_scan_kernel names are
 // the uses of the one shared kc_scan_kernel (kc_scan.hpp) and keep the names they were first reported under.
 #pragma once
 
@@ -231,7 +231,18 @@
   X(KT_CORRECT_EVAL,       "kc_correct_eval_kernel") \
   X(KT_CORRECT_ACCEPT_SCAN, "kc_correct_scan_kernel<accepted>") \
   X(KT_CORRECT_APPLY,      "kc_correct_apply_kernel") \
-  X(KT_CORRECT_RECORDS,    "kc_correct_records_kernel")
+  X(KT_CORRECT_RECORDS,    "kc_correct_records_kernel") \
+  X(KT_POLISH_LENGTHS,     "kc_align_lengths_kernel<polish>") \
+  X(KT_POLISH_CHECK,       "kc_depth_check_kernel<polish>") \
+  X(KT_POLISH_BEST,        "kc_depth_best_kernel<polish>") \
+  X(KT_POLISH_PLACE,       "kc_polish_place_kernel") \
+  X(KT_POLISH_SORT_HIST,   "kc_sort_hist_kernel<polish>") \
+  X(KT_POLISH_SORT_SCAN,   "kc_sort_scan_kernel<polish>") \
+  X(KT_POLISH_SORT_SCATTER, "kc_sort_scatter_kernel<polish>") \
+  X(KT_POLISH_TILE_COUNT,  "kc_polish_tile_kernel<count>") \
+  X(KT_POLISH_TILE_SCAN,   "kc_link_tile_scan_kernel<polish>") \
+  X(KT_POLISH_SCAN,        "kc_polish_scan_kernel") \
+  X(KT_POLISH_TILE_WRITE,  "kc_polish_tile_kernel<write>")
 
 enum {
 #define X(kind, name) kind,

@@ -1080,6 +1080,49 @@ class KmerCounter:
         check(rc, "kc_correct_reads")
         return out.first(), recs and recs.first(), fixes and fixes.first(int(st.accepted)), _stats_dict(st)
 
+    def polish_contigs(self, bases, offsets, gap_alns, quals=None, min_score=0, min_len=0, edge_clip=0, max_mismatches=8, min_depth=3,
+                       min_permille=700, min_qual=0, best_only=False, with_counts=False, with_records=True, with_fixes=True):
+        """The indexed contigs polished from the pileup of align_gapped's records (kc_ctg_polish).  bases /
+        offsets (and quals, only read with min_qual > 0): the reads the records index, numpy arrays or device tensors.  A record
+        that passes the filter (min_score, min_len; best_only: and is its read's best), lies on one diagonal and differs from
+        the contig in at most max_mismatches columns votes with its bases, edge_clip columns short of an end that is not the
+        contig's; a column with min_depth votes or more whose winner has more votes than any other base and at least
+        min_permille thousandths of them becomes the winner.  Substitutions only: the block keeps its length and offsets.
+        Returns (block, counts, records, fixes, stats): the polished block; with_counts the four counts of every byte as a
+        (nbytes, 4) uint16 array, saturated (else None); one POLISH_CTG_DTYPE record per contig (with_records False: None); the
+        POLISH_FIX_DTYPE entries in ascending position (with_fixes False: None; True: room for every column; a number: room for
+        that many, KC_ERR_CAPACITY beyond); kc_polish_stats as a dict.  Host arrays in give numpy arrays out, device tensors in
+        give device tensors out (records and fixes as uint8 tensors, counts an int16 tensor of nbytes * 4 holding the bits)."""
+        pa, n_alns, dev_a = _records("gap_alns", gap_alns, GAP_ALN_DTYPE)
+        pb, pq, po, nreads, dev_b = _reads(bases, quals, offsets)
+        nb_reads = len(bases)
+        dev = _side("offsets", _ptr(offsets)[1], gap_alns=(dev_a, n_alns), bases=(dev_b, nb_reads), quals=(_ptr(quals)[1], nb_reads and quals is not None))
+        if quals is not None and len(quals) != nb_reads:
+            raise ValueError("quals: as many bytes as bases")
+        nbytes, n_ctgs = self.contig_index_info()
+        prm = _lib.kc_polish_params(min_score, min_len, edge_clip, max_mismatches, min_depth, min_permille, min_qual,
+                                    _lib.KC_POLISH_BEST_ONLY if best_only else 0)
+        st = _lib.kc_polish_stats()
+        exact = with_fixes is not True and with_fixes is not False
+        capacity = int(with_fixes) if exact else nbytes
+        out = self._out(dev, nbytes, np.uint8, pad=True)
+        counts = self._out(dev, nbytes * 4, np.uint16, pad=True) if with_counts else None
+        recs = self._out(dev, n_ctgs, POLISH_CTG_DTYPE, pad=True) if with_records else None
+        fixes = self._out(dev, capacity, POLISH_FIX_DTYPE, pad=True) if with_fixes is not False else None
+        self._hand_over(dev)
+        if not nb_reads:  # no bases at all: the library takes no byte arrays then
+            pb = pq = None
+        check(lib().kc_ctg_polish(self._h, pb, pq, po, nreads, pa, n_alns, 1 if dev else 0, C.byref(prm), out.ptr, counts and counts.ptr,
+                                  recs and recs.ptr, fixes and fixes.ptr, capacity, C.byref(st)), "kc_ctg_polish")
+        c = counts and counts.first()
+        if c is not None and not dev:
+            c = c.reshape(nbytes, 4)
+        return out.first(), c, recs and recs.first(), fixes and fixes.first(int(st.changed)), _stats_dict(st)
+
+    def polish_strings(self, bases, offsets, gap_alns, **kw):
+        """polish_contigs' block as a host list of contig strings: for tests and small inputs."""
+        return polish_strings(self, bases, offsets, gap_alns, **kw)
+
     def contig_kmer_depths(self, seqs, offsets):
         """One depth per byte of a seq block, from the k-mer counts of the finished results: every contig's mean window count
         on its bases, 0 on its separator.  The array submit_ctg_block takes."""
@@ -1402,6 +1445,18 @@ KDEPTH_DTYPE = np.dtype([("sum", "<u8"), ("windows", "<u4"), ("present", "<u4"),
 CORRECT_REC_DTYPE = np.dtype([("weak_before", "<u4"), ("weak_after", "<u4"), ("corrected", "<u2"), ("flags", "<u2"), ("reserved", "<u4")])
 CORRECT_FIX_DTYPE = np.dtype([("seq", "<u4"), ("pos", "<u4"), ("old", "u1"), ("new", "u1"), ("round", "u1"), ("side", "u1"), ("score", "<u2"),
                               ("runner_up", "<u2")])
+
+# kc_ctg_polish's record of a contig (kc_polish_ctg, 32 bytes) and entry of a changed column (kc_polish_fix, 16 bytes)
+POLISH_CTG_DTYPE = np.dtype([("votes", "<u8"), ("placed", "<u4"), ("changed", "<u4"), ("filled", "<u4"), ("disputed", "<u4"), ("thin", "<u4"),
+                             ("uncovered", "<u4")])
+POLISH_FIX_DTYPE = np.dtype([("pos", "<u4"), ("ctg", "<u4"), ("old", "u1"), ("new", "u1"), ("top", "<u2"), ("tot", "<u2"), ("pad", "<u2")])
+
+
+def polish_strings(kc, bases, offsets, gap_alns, **kw):
+    """kc.polish_contigs(...)'s block as a host list of contig strings, in the index's order: for tests and small inputs."""
+    block = kc.polish_contigs(bases, offsets, gap_alns, with_records=False, with_fixes=False, **kw)[0]
+    text = (block if isinstance(block, np.ndarray) else block.cpu().numpy()).tobytes().decode()
+    return text.split("_")[:-1]
 
 
 def format_spectrum(hist):
