@@ -1,4 +1,5 @@
-"""ctypes binding of libkcount_mi355.so (include/kcount_mi355.h, include/kcount_mi355_correct.h, include/kcount_mi355_polish.h).  No fallback of any kind."""
+"""ctypes binding of libkcount_mi355.so (include/kcount_mi355.h, include/kcount_mi355_correct.h, include/kcount_mi355_polish.h,
+include/kcount_mi355_break.h).  No fallback of any kind."""
 import ctypes as C
 import os
 
@@ -367,6 +368,28 @@ class kc_polish_stats(C.Structure):
 
 KC_POLISH_BEST_ONLY = 1
 
+
+class kc_break_params(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("max_insert", "max_span", "min_disc", "margin", "min_run", "flags")] + [("reserved", C.c_uint32 * 2)]
+
+
+class kc_break_piece(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("ctg", "start", "len", "flags")]
+
+
+class kc_break_rec(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("ctg", "pos", "run_start", "run_len", "span", "disc", "piece", "pad")]
+
+
+class kc_break_stats(C.Structure):
+    _fields_ = ([(n, C.c_uint64) for n in ("pairs", "spanning", "discordant_pairs", "one_mate", "none", "disc_mates", "empty_intervals", "span_sum",
+                                           "disc_sum")] +
+                [(n, C.c_uint32) for n in ("columns", "interior", "weak", "runs", "short_runs", "breaks", "broken_contigs", "pieces")] +
+                [("reserved", C.c_uint32 * 6)])
+
+
+KC_BREAK_ONE_MATE = 1
+
 # every symbol include/kcount_mi355.h declares: (restype, argtypes)
 SYMBOLS = {
     "kc_abi_version": (C.c_int, []),
@@ -494,6 +517,13 @@ SYMBOLS_POLISH = {
                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(kc_polish_stats)]),
 }
 
+# every symbol include/kcount_mi355_break.h declares, in the same form
+SYMBOLS_BREAK = {
+    "kc_ctg_break": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(kc_break_params),
+                               C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                               C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(kc_break_stats)]),
+}
+
 
 def lib_path():
     # KC_LIB: an alternative build of the same library (tuning experiments only)
@@ -509,7 +539,7 @@ def lib():
             raise ImportError("%s is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                               "(or make -C mhm2_kmer_analysis_v2_amd/csrc); there is no CPU fallback" % p)
         L = C.CDLL(p)
-        for name, (res, args) in list(SYMBOLS.items()) + list(SYMBOLS_CORRECT.items()) + list(SYMBOLS_POLISH.items()):
+        for name, (res, args) in list(SYMBOLS.items()) + list(SYMBOLS_CORRECT.items()) + list(SYMBOLS_POLISH.items()) + list(SYMBOLS_BREAK.items()):
             f = getattr(L, name)  # AttributeError if the .so does not export a declared symbol
             f.restype = res
             f.argtypes = args

@@ -25,6 +25,7 @@
 #include "../../include/kcount_mi355.h"
 #include "../../include/kcount_mi355_correct.h"
 #include "../../include/kcount_mi355_polish.h"
+#include "../../include/kcount_mi355_break.h"
 #include "kc_kinds.hpp"
 #include "kc_debug_fill.hpp"
 #include "kc_bucketed.hpp"
@@ -52,6 +53,7 @@
 #include "kc_kdepth.hpp"
 #include "kc_correct.hpp"
 #include "kc_polish.hpp"
+#include "kc_break.hpp"
 
 using namespace kc;
 
@@ -2985,6 +2987,7 @@ extern "C" int kc_lookup(kc_ctx *c, const uint64_t *queries, uint64_t nq, int on
 #include "kc_api_kdepth.hpp"  // kc_seq_kmer_depths, kc_count_spectrum
 #include "kc_api_correct.hpp"  // kc_correct_reads
 #include "kc_api_polish.hpp"  // kc_ctg_polish
+#include "kc_api_break.hpp"  // kc_ctg_break
 
 // ---- the contig pass (kc_ctg.hpp) ----------------------------------------------------------------------------------
 extern "C" int kc_begin_ctg_kmers(kc_ctx *c, uint64_t max_ctg_kmers) {

@@ -3,7 +3,7 @@
 //
 // Several kinds are one kernel launched by different callers or in different passes; the name in angle brackets says
 // which (kc_align_lengths_kernel<close> is kc_close_gaps' launch of kc_align_lengths_kernel,
-// <assembly> kc_ctg_select's, <fasta> kc_fasta_text's, <fasta in> kc_fasta_to_block's, <fastq out> kc_fastq_text's, <dedup> kc_ctg_dedup's, <correct> kc_correct_reads', <polish> kc_ctg_polish's).  The *_scan_kernel names are
+// <assembly> kc_ctg_select's, <fasta> kc_fasta_text's, <fasta in> kc_fasta_to_block's, <fastq out> kc_fastq_text's, <dedup> kc_ctg_dedup's, <correct> kc_correct_reads', <polish> kc_ctg_polish's, <break> kc_ctg_break's).  The *_scan_kernel names are
 // the uses of the one shared kc_scan_kernel (kc_scan.hpp) and keep the names they were first reported under.
 #pragma once
 
@@ -242,7 +242,22 @@
   X(KT_POLISH_TILE_COUNT,  "kc_polish_tile_kernel<count>") \
   X(KT_POLISH_TILE_SCAN,   "kc_link_tile_scan_kernel<polish>") \
   X(KT_POLISH_SCAN,        "kc_polish_scan_kernel") \
-  X(KT_POLISH_TILE_WRITE,  "kc_polish_tile_kernel<write>")
+  X(KT_POLISH_TILE_WRITE,  "kc_polish_tile_kernel<write>") \
+  X(KT_BREAK_LENGTHS,      "kc_align_lengths_kernel<break>") \
+  X(KT_BREAK_CHECK,        "kc_depth_check_kernel<break>") \
+  X(KT_BREAK_PAIR_CHECK,   "kc_lassm_pair_check_kernel<break>") \
+  X(KT_BREAK_MARK,         "kc_break_mark_kernel") \
+  X(KT_BREAK_TILE_SUMS,    "kc_break_tile_sums_kernel") \
+  X(KT_BREAK_SCAN,         "kc_break_scan_kernel") \
+  X(KT_BREAK_RESCAN,       "kc_break_rescan_kernel") \
+  X(KT_BREAK_TILE_MAX,     "kc_break_tile_max_kernel") \
+  X(KT_BREAK_RUNS_COUNT,   "kc_break_runs_kernel<count>") \
+  X(KT_BREAK_RUNS_SCAN,    "kc_break_scan_kernel<runs>") \
+  X(KT_BREAK_RUNS_WRITE,   "kc_break_runs_kernel<write>") \
+  X(KT_BREAK_RECORDS,      "kc_break_records_kernel") \
+  X(KT_BREAK_GATHER,       "kc_break_gather_kernel") \
+  X(KT_BREAK_GATHER_DEPTHS, "kc_break_gather_kernel<depths>") \
+  X(KT_BREAK_TRACKS,       "kc_break_tracks_kernel")
 
 enum {
 #define X(kind, name) kind,

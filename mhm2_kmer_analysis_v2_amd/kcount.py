@@ -1123,6 +1123,54 @@ class KmerCounter:
         """polish_contigs' block as a host list of contig strings: for tests and small inputs."""
         return polish_strings(self, bases, offsets, gap_alns, **kw)
 
+    def break_contigs(self, offsets, gap_alns, pairs, depths=None, max_insert=1000, max_span=0, min_disc=3, margin=None, min_run=1, one_mate=False,
+                      tracks=False):
+        """The indexed contigs cut where no read pair spans them and the mates that should have landed elsewhere (kc_ctg_break;
+        DESIGN.md section 34).  offsets: the reads' starts (no bases are needed; reads 2p and 2p + 1 are mates); gap_alns
+        align_gapped's records, pairs pair_inserts' records (their classes are not read: every pair is classified again);
+        depths: one uint16 per byte of the indexed block, or None.  A pair on one contig, its mates facing each other at most
+        max_insert apart, spans the columns between its outer ends; every other aligned mate is discordant over the max_insert
+        columns in which its partner should have been (one_mate: also a mate whose partner has no record).  A column at least
+        margin (None: max_insert) from both ends of its contig with at most max_span spanning pairs and at least min_disc
+        discordant mates is weak; a run of min_run or more weak columns is cut in its middle.  Returns (seqs, offsets, depths
+        or None, pieces, breaks, stats, tracks): the block index_contigs, submit_ctg_block, dedup_contigs, select_contigs and
+        fasta_text take as it is, one BREAK_PIECE_DTYPE record per output contig, one BREAK_DTYPE record per break,
+        kc_break_stats as a dict, and with tracks the pair (span, disc) of saturated uint16 counts over the input block (else
+        None).  Host arrays in give numpy arrays out; device tensors in give device tensors out (offsets int64, depths and
+        tracks int16, records uint8 tensors).  A size query comes first, so every array is exact."""
+        pa, n_alns, dev_a = _records("gap_alns", gap_alns, GAP_ALN_DTYPE)
+        pp, n_pairs, dev_p = _records("pairs", pairs, PAIR_DTYPE)
+        po, dev_o = _ptr(offsets)
+        nreads = len(offsets) - 1
+        nbytes, n_ctgs = self.contig_index_info()
+        nd = 0 if depths is None else (depths.numel() if _ptr(depths)[1] else len(depths))
+        dev = _side("offsets", dev_o, gap_alns=(dev_a, n_alns), pairs=(dev_p, n_pairs), depths=(_ptr(depths)[1], nd))
+        if n_pairs != nreads // 2:
+            raise ValueError("pairs: one record per pair of reads")
+        if depths is not None and nd != nbytes:
+            raise ValueError("depths: one uint16 per byte of the indexed block")
+        prm = _lib.kc_break_params(max_insert, max_span, min_disc, max_insert if margin is None else margin, min_run,
+                                   _lib.KC_BREAK_ONE_MATE if one_mate else 0)
+        st, no, nb = _lib.kc_break_stats(), C.c_uint64(0), C.c_uint64(0)
+        head = (self._h, po, nreads, pa, n_alns, pp, _ptr(depths)[0], 1 if dev else 0, C.byref(prm))
+        tail = (C.byref(no), C.byref(nb), C.byref(st))
+        self._hand_over(dev)
+        check(lib().kc_ctg_break(*head, None, 0, None, None, None, None, 0, None, None, *tail), "kc_ctg_break")
+        n_out, total, n_brk = int(no.value), int(nb.value), int(st.breaks)
+        seqs, offs_out = self._out(dev, total, np.uint8, pad=True), self._out(dev, n_out + 1, np.uint64)
+        depths_out = None if depths is None else self._out(dev, total, np.uint16, pad=True)
+        pieces, recs = self._out(dev, n_out, BREAK_PIECE_DTYPE, pad=True), self._out(dev, n_brk, BREAK_DTYPE, pad=True)
+        tr = (self._out(dev, nbytes, np.uint16, pad=True), self._out(dev, nbytes, np.uint16, pad=True)) if tracks else None
+        self._hand_over(dev)  # fresh arrays
+        check(lib().kc_ctg_break(*head, seqs.ptr, total, offs_out.ptr, depths_out and depths_out.ptr, pieces.ptr, recs.ptr, n_brk,
+                                 tr and tr[0].ptr, tr and tr[1].ptr, *tail), "kc_ctg_break")
+        return (seqs.first(), offs_out.first(), depths_out and depths_out.first(), pieces.first(), recs.first(), _stats_dict(st),
+                tr and (tr[0].first(), tr[1].first()))
+
+    def break_strings(self, offsets, gap_alns, pairs, **kw):
+        """break_contigs' block as a host list of contig strings: for tests and small inputs."""
+        return break_strings(self, offsets, gap_alns, pairs, **kw)
+
     def contig_kmer_depths(self, seqs, offsets):
         """One depth per byte of a seq block, from the k-mer counts of the finished results: every contig's mean window count
         on its bases, 0 on its separator.  The array submit_ctg_block takes."""
@@ -1457,6 +1505,17 @@ def polish_strings(kc, bases, offsets, gap_alns, **kw):
     block = kc.polish_contigs(bases, offsets, gap_alns, with_records=False, with_fixes=False, **kw)[0]
     text = (block if isinstance(block, np.ndarray) else block.cpu().numpy()).tobytes().decode()
     return text.split("_")[:-1]
+
+
+# kc_ctg_break's record of an output contig (kc_break_piece, 16 bytes) and of a break (kc_break_rec, 32 bytes)
+BREAK_PIECE_DTYPE = np.dtype([("ctg", "<u4"), ("start", "<u4"), ("len", "<u4"), ("flags", "<u4")])
+BREAK_DTYPE = np.dtype([("ctg", "<u4"), ("pos", "<u4"), ("run_start", "<u4"), ("run_len", "<u4"), ("span", "<u4"), ("disc", "<u4"), ("piece", "<u4"),
+                        ("pad", "<u4")])
+
+
+def break_strings(kc, offsets, gap_alns, pairs, **kw):
+    """kc.break_contigs(...)'s block as a host list of contig strings, in block order: for tests and small inputs."""
+    return _block_strings(*kc.break_contigs(offsets, gap_alns, pairs, **kw)[:2])
 
 
 def format_spectrum(hist):
